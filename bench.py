@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- influence-matrix build throughput (BASELINE.json metric) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline alone: it sets up, runs W warm-up steps, times ONE block of exactly K steps, writes the
+outputs of the last timed step when ``--dump-outputs DIR`` is given (DIR/influence_matrix.npy, float64) and prints the
+result line (``value``, ``ms_per_step`` = milliseconds of one timed step).  ``--full`` adds everything else the line used to
+carry -- the in-run PMC passes, the device-resident figure, per-kernel tables and rooflines, the drop-in API leg, the other
+modes and workloads, the SpMM legs, the strong-scaling workloads, the CPU baseline and the parity gate -- and times the
+headline as ``--blocks`` blocks of K steps (see Timing below).
 
 N = 1 runs in this process.  N > 1: when the torchrun environment (RANK / WORLD_SIZE) is present this process is one rank
 of N (``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``); otherwise ``python bench.py --gpus N``
@@ -16,19 +23,19 @@ every probe and the n_test x n_test influence norms, plus -- for N > 1 -- the si
 graph) is fixed, so this is STRONG scaling, as the BASELINE.json metric ("n_test=500 at 1/2/4/8 GPU") is.  Inputs are
 synthetic (no dataset on the box) and resident in HBM before timing.
 
-Timing: W warm-up steps, then ``--blocks`` (default 5) timed blocks of EXACTLY K steps each, every block bracketed by a
-barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks; ``value`` / ``ms_per_step`` are the
-MEDIAN block ("median of >= 5"), all block times are in the line.
+Timing: W warm-up steps, then ONE timed block of EXACTLY K steps (``--full``: ``--blocks``, default 5, such blocks), every
+block bracketed by a barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks; ``value`` /
+``ms_per_step`` are the MEDIAN block ("median of >= 5"), all block times are in the line.
 
-Next to ``value`` the line carries ``api_wall``: the drop-in API itself -- ``Attacker.influence_matrix()`` on the same workload
+With ``--full``, next to ``value`` the line carries ``api_wall``: the drop-in API itself -- ``Attacker.influence_matrix()`` on the same workload
 (the same region plus the Python surface: state_dict walk, cached node lists) -- ``value_host``, ``d2h_us``,
 ``ms_per_step_export_launch`` (round 5's host path: an export launch behind the step).
 
 ``value`` is measured in ``--mode delta`` (default): the mode whose scores, AUC and AP meet north_star's 1e-4 against the
 reference.  `full` (every probe a full perturbed forward, the reference's fp32 finite difference)
-and `sparse` (bit-identical to it) are reported next to it under ``other_modes`` and never substituted for it; the line
-carries a ``parity`` object (GPU rows against the CPU reference path run in fp32 and fp64 in this same process) and the
-process exits non-zero when that check fails.
+and `sparse` (bit-identical to it) are reported next to it under ``other_modes`` (``--full``) and never substituted for it;
+the ``--full`` line carries a ``parity`` object (GPU rows against the CPU reference path run in fp32 and fp64 in this same
+process) and the process exits non-zero when that check fails.
 """
 import argparse
 import ctypes as C
@@ -134,7 +141,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=5)
-    p.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps; the median block is reported")
+    p.add_argument("--blocks", type=int, default=5, help="--full: timed blocks of --steps steps; the median block is reported "
+                                                          "(a plain run times one block)")
+    p.add_argument("--full", action="store_true", help="measure and check everything else as well (the --no-* options below "
+                                                       "select among those legs); default: the headline alone")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned to its caller as DIR/<name>.npy")
     p.add_argument("--workload", default="twitch-RU", choices=["twitch-RU", "twitch-ES"])
     p.add_argument("--n-test", type=int, default=500)
     p.add_argument("--hidden", type=int, default=256)
@@ -269,6 +281,23 @@ def spmm_bytes(n, nnz, h, elem=4):
     return nnz * 8 + (n + 1) * 4 + 2 * n * h * elem
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, m_host):
+    """--dump-outputs: what the timed path hands its caller in the last timed step -- influence_val, [n_test, n_test] float64 on
+    the host -- as DIR/influence_matrix.npy.  Above 64 MB a fixed, seeded sample of its rows is written instead, their indices
+    (as float64) in DIR/influence_matrix_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    m = np.asarray(m_host, dtype=np.float64)
+    if m.nbytes > DUMP_CAP_BYTES:
+        k = DUMP_CAP_BYTES // (m.shape[1] * 8 + 8)
+        rows = np.sort(np.random.RandomState(0).choice(m.shape[0], k, replace=False))
+        np.save(os.path.join(dirname, "influence_matrix_rows.npy"), rows.astype(np.float64))
+        m = m[rows]
+    np.save(os.path.join(dirname, "influence_matrix.npy"), m)
+
+
 def main():
     a = parse()
     if "RANK" not in os.environ and a.gpus > 1 and not a.pmc_child:
@@ -283,7 +312,7 @@ def main():
     # HBM traffic of the kernels this line prices, measured now (rank 0 of a 1-GPU run; child processes, so that this
     # process has not touched the GPU when they start)
     pmc, pmc_note = (None, "N > 1: not collected")
-    if world == 1 and not a.pmc_child and not a.only_spmm and os.environ.get("LT_FORCE_COLLECTIVES") != "1":
+    if a.full and world == 1 and not a.pmc_child and not a.only_spmm and os.environ.get("LT_FORCE_COLLECTIVES") != "1":
         pmc, pmc_note = pmc_inrun(a)
 
     import torch
@@ -452,7 +481,7 @@ def main():
                        "by_gathers_in_flight": {str(u): round(v, 3) for u, v in g_ms.items()},
                        "kernel_ms": round(sec * 1e3, 3),
                        "kernel_reaches_of_gather_ceiling": round(best / (sec * 1e3), 4),
-                       "kernel_reaches_of_gather_plus_store_ceiling": round(best_s / (sec * 1e3), 4),
+                       "kernel_reaches_of_gather_and_store_ceiling": round(best_s / (sec * 1e3), 4),
                        "ceiling_as_frac_of_hbm_roofline": round(byts / (best * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                        "note": "k_rows_tiled with its val stream, fmaf chains and result rows removed (XOR-folded loads): what the memory "
                                "system needs for THIS index stream at THIS hit distribution -- no row-gather SpMM issuing these gathers runs "
@@ -659,6 +688,70 @@ def main():
         torch.cuda.synchronize()
         if a.spmm_scale:
             spmm_rmat_leg(a.spmm_scale, h)
+        return
+
+    def line_head(block_h):
+        """The headline part of the result line (all a plain run prints): `value` / `ms_per_step` of the median block of
+        host-landed steps, and what was measured."""
+        elapsed_ = float(np.median(block_h))
+        shard_note = ("single GPU" if not multi else
+                      (("fp64" if a.mode == "delta" else "fp32") + " X*W1 sharded over ranks + all-gather" if baseline_sharded else
+                       ("feature-difference fp64 product on every rank (one pass over X)" if (a.mode == "delta" and fp64_route == 1)
+                        else "replicated on every rank")))
+        hp = (h + 3) // 4 * 4
+        coll = 0
+        if multi:
+            coll = world * per * a.n_test * 4 if probe_sharded else 0
+            if baseline_sharded:
+                coll += world * lt_dist.shard_bounds(n, rank, world)[2] * hp * (8 if a.mode == "delta" else 4)
+        return {
+            "metric": "influence-matrix node-pairs/sec", "value": round(a.n_test * a.n_test * a.steps / elapsed_, 1), "unit": "node-pairs/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed_ / a.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "value_note": "a step ends with influence_val on the HOST as float64 -- the region the reference times (attacker.py:213 -> 231, "
+                          "SURVEY 8(d)); inputs (graph, features, weights, node lists) resident in HBM.  ONE library call per step "
+                          "(lt_influence_rows_f64): half of the matrix's rows are zero-filled over PCIe by a few waves riding in the "
+                          "product rows' and the pre-activation's launches and their probes' blocks send the touched positions only; the "
+                          "other rows are widened whole by their blocks (round 6: 0.106 -> 0.094 ms; profiles/r06_host_landed_lab.txt)",
+            "dtype": "f64" if a.mode == "delta" else "f32",
+            "data": "synthetic",
+            "config": {"workload": f"n_test={a.n_test} {a.workload}-shaped {'PL' if a.powerlaw else 'ER'} N={n} E={adj.nnz // 2} F={f} H={h} C={c} "
+                                   f"influence=1e-4 (BASELINE configs[1])",
+                       "graph": f"{'power-law' if a.powerlaw else 'Erdos-Renyi'}, nnz(A_hat)={nnz}, 2-layer GCN, FirstOrderGCN",
+                       "features": "standardised 0/1 indicators, Bernoulli(0.006) (two values per column, as the reference's twitch loader "
+                                   "produces: utils/load.py:53-59 + StandardScaler)",
+                       "mode": a.mode, "probes_per_rank": n_probe_local, "baseline_XW1": shard_note,
+                       "probe_sharding": probe_choice if multi else "one rank",
+                       "fp64_product_route": {1: "feature rows as differences to a reference row (k_s1d_feature_rows)",
+                                              2: "aggregate-first on the rows the probes reach (k_rows_tiled_xf64 + k_gemm_f64_rows)",
+                                              0: "f64 matrix cores (k_gemm_f64acc_128)", -1: "not used"}[fp64_route],
+                       "collective_bytes_per_step": coll,
+                       "step": "baseline forward of the mode + all probes + norms" + (" + all-gather" if multi else "") +
+                               " + the matrix as float64 on the host",
+                       "host_path": ("lt_influence_rows_f64: the probes' blocks write their rows into pinned host memory (no export launch)"
+                                     if (not multi and a.mode == "delta") else "lt_export_rows_f64 behind the last kernel")},
+            "timing": {"blocks": len(block_h), "steps_per_block": a.steps, "reported": "median block",
+                       "block_ms": [round(b * 1e3, 3) for b in block_h]},
+        }
+
+    def finish(out):
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+            flush_c_stdio()
+        if rank == 0:
+            print(json.dumps(out))
+            sys.stdout.flush()
+
+    if not a.full:
+        # ---------------- a plain run: the headline alone -- W warm-up steps, ONE timed block of exactly K steps ----------------
+        block_h, m_host = timed_host(a.mode, a.steps, a.warmup)
+        out = None
+        if rank == 0:
+            out = line_head(block_h)
+            if a.dump_outputs:
+                dump_outputs(a.dump_outputs, m_host)
+        finish(out)
         return
 
     # ---------------- the timed region ----------------
@@ -1219,52 +1312,19 @@ def main():
             parity["ok"] = bool(parity["ok"] and ok)
         cpu["max_abs_diff_vs_gpu_rows"] = float(np.abs(cpu32 - full[:done].cpu().numpy().astype(np.float64)).max())
 
+    out = None
     if rank == 0:
-        shard_note = ("single GPU" if not multi else
-                      (("fp64" if a.mode == "delta" else "fp32") + " X*W1 sharded over ranks + all-gather" if baseline_sharded else
-                       ("feature-difference fp64 product on every rank (one pass over X)" if (a.mode == "delta" and fp64_route == 1)
-                        else "replicated on every rank")))
-        hp = (h + 3) // 4 * 4
-        coll = 0
-        if multi:
-            coll = world * per * a.n_test * 4 if probe_sharded else 0
-            if baseline_sharded:
-                coll += world * lt_dist.shard_bounds(n, rank, world)[2] * hp * (8 if a.mode == "delta" else 4)
-        out = {
-            "metric": "influence-matrix node-pairs/sec", "value": round(value, 1), "unit": "node-pairs/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "value_note": "a step ends with influence_val on the HOST as float64 -- the region the reference times (attacker.py:213 -> 231, "
-                          "SURVEY 8(d)); inputs (graph, features, weights, node lists) resident in HBM.  ONE library call per step "
-                          "(lt_influence_rows_f64): half of the matrix's rows are zero-filled over PCIe by a few waves riding in the "
-                          "product rows' and the pre-activation's launches and their probes' blocks send the touched positions only; the "
-                          "other rows are widened whole by their blocks (round 6: 0.106 -> 0.094 ms; profiles/r06_host_landed_lab.txt)",
+        out = line_head(block_h)
+        out.update({
             "value_device": round(value_dev, 1), "ms_per_step_device": round(ms_per_step_dev, 4),
             "value_device_note": "the same K steps ending with the fp32 matrix in HBM (what `value` was up to round 5)",
-            "host_matrix_equals_device_matrix": host_equals_device,
-            "dtype": "f64" if a.mode == "delta" else "f32",
-            "data": "synthetic",
-            "config": {"workload": f"n_test={a.n_test} {a.workload}-shaped {'PL' if a.powerlaw else 'ER'} N={n} E={adj.nnz // 2} F={f} H={h} C={c} "
-                                   f"influence=1e-4 (BASELINE configs[1])",
-                       "graph": f"{'power-law' if a.powerlaw else 'Erdos-Renyi'}, nnz(A_hat)={nnz}, 2-layer GCN, FirstOrderGCN",
-                       "features": "standardised 0/1 indicators, Bernoulli(0.006) (two values per column, as the reference's twitch loader "
-                                   "produces: utils/load.py:53-59 + StandardScaler)",
-                       "mode": a.mode, "probes_per_rank": n_probe_local, "baseline_XW1": shard_note,
-                       "probe_sharding": probe_choice if multi else "one rank",
-                       "fp64_product_route": {1: "feature rows as differences to a reference row (k_s1d_feature_rows)",
-                                              2: "aggregate-first on the rows the probes reach (k_rows_tiled_xf64 + k_gemm_f64_rows)",
-                                              0: "f64 matrix cores (k_gemm_f64acc_128)", -1: "not used"}[fp64_route],
-                       "collective_bytes_per_step": coll,
-                       "step": "baseline forward of the mode + all probes + norms" + (" + all-gather" if multi else "") +
-                               " + the matrix as float64 on the host",
-                       "host_path": ("lt_influence_rows_f64: the probes' blocks write their rows into pinned host memory (no export launch)"
-                                     if (not multi and a.mode == "delta") else "lt_export_rows_f64 behind the last kernel")},
-            "timing": {"blocks": len(block_h), "steps_per_block": a.steps, "reported": "median block",
-                       "block_ms": [round(b * 1e3, 3) for b in block_h],
-                       "device_block_ms": [round(b * 1e3, 3) for b in block_s],
-                       "event_pair_overhead_us": event_pair_us,
-                       "event_pair_note": "an EMPTY hipEventRecord pair on the kernels' stream reads this much: the per-class avg_launch_us "
-                                          "figures (HIP events) sit that far above the rocprofv3 kernel durations in profiles/"},
+            "host_matrix_equals_device_matrix": host_equals_device})
+        out["timing"].update({
+            "device_block_ms": [round(b * 1e3, 3) for b in block_s],
+            "event_pair_overhead_us": event_pair_us,
+            "event_pair_note": "an EMPTY hipEventRecord pair on the kernels' stream reads this much: the per-class avg_launch_us "
+                               "figures (HIP events) sit that far above the rocprofv3 kernel durations in profiles/"})
+        out.update({
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "kernels": per_kernel,
             "kernels_note": f"dominant class ({dom_name}) timed by HIP events inside the device-resident timed region (`value_device`; every "
                             f"{PROFILE_EVERY}th step: an event pair costs ~5 us of stream time); the other rows from an "
@@ -1273,8 +1333,7 @@ def main():
             "kernels_host_note": "the same classes over an instrumented repeat of the HOST-landed steps (`value`): the product rows' launch "
                                  "carries 35 % of the float64 matrix's zeros and the pre-activation's 15 % (a few waves each, over PCIe); "
                                  "item_stageB (k_delta_probe_finish) holds the transfer of the rest -- the link, not the kernel's "
-                                 "arithmetic, is what it waits for",
-        }
+                                 "arithmetic, is what it waits for"})
         if a.mode != "delta":
             out["parity_note"] = ("this mode is the reference's fp32 finite difference: its raw AUC can move by 1 / n_edges when a low-score "
                                   "edge quantises to 0 (DESIGN.md section 3); `delta` is the mode that meets north_star's 1e-4")
@@ -1285,15 +1344,11 @@ def main():
         if scaling is not None:
             out["scaling_workloads"] = scaling
         out["collectives"] = rccl_info()
-        if os.environ.get("LT_BENCH_DUMP"):          # test hook: the matrix of the last timed step
+        if os.environ.get("LT_BENCH_DUMP"):          # test hook: the matrix of the last device-resident timed step
             np.save(os.environ["LT_BENCH_DUMP"], full.cpu().numpy())
-    if multi:
-        dist.barrier()
-        dist.destroy_process_group()
-        flush_c_stdio()
-    if rank == 0:
-        print(json.dumps(out))
-        sys.stdout.flush()
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, m_host)
+    finish(out)
     if rank == 0 and parity is not None and not parity["ok"]:
         sys.exit(3)
 

@@ -79,7 +79,7 @@ def test_bench_two_ranks_through_its_own_launcher(gpu, tmp_path, mode, extra):
     n_gpus == 2, a non-zero collective, and the matrix of the last step equal to the one-rank run's bit for bit -- with the
     loop-invariant product replicated, sharded (fp32 X W1 for `full`; the fp64 product for `delta` on dense-feature
     routing), or served by the feature-difference route."""
-    common = ["--steps", "3", "--warmup", "1", "--blocks", "2", "--no-cpu-baseline", "--no-extras", "--no-pmc", "--mode", mode,
+    common = ["--full", "--steps", "3", "--warmup", "1", "--blocks", "2", "--no-cpu-baseline", "--no-extras", "--no-pmc", "--mode", mode,
               "--n-test", "120"]
     one = _bench(common, {"LT_BENCH_DUMP": str(tmp_path / "one.npy"), **extra})
     two = _bench(common + ["--gpus", "2"], {"LT_BENCH_BACKEND": "gloo", "LT_BENCH_DEVICE": "0", "LT_SHARD_PROBES": "1",

@@ -69,7 +69,7 @@ def test_bench_collectives_execute_under_rccl_at_world_size_1(gpu, tmp_path, mod
     timing all-reduce, barriers -- on device tensors, so RCCL itself runs them.  The process must have librccl mapped, the
     line must carry the three strong-scaling workloads with an event-timed collective, and the matrix of the last step
     must equal the plain one-process run bit for bit."""
-    common = ["--steps", "3", "--warmup", "1", "--blocks", "2", "--no-cpu-baseline", "--no-extras", "--no-pmc", "--mode", mode,
+    common = ["--full", "--steps", "3", "--warmup", "1", "--blocks", "2", "--no-cpu-baseline", "--no-extras", "--no-pmc", "--mode", mode,
               "--n-test", "120", "--spmm-scale", "14"]
     plain = _bench(common, {"LT_BENCH_DUMP": str(tmp_path / "plain.npy"), **extra})
     # (LT_SHARD_PROBES=1: the all-gather of row slabs on every step -- under the default `auto` a one-rank "group" would find

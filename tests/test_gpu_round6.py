@@ -186,7 +186,7 @@ def test_probe_sharding_auto_never_slower_than_one_gpu(gpu, tmp_path):
     build -- whose step is its loop-invariant baseline -- that is the local build, the line says so, and the matrix equals the
     plain run's bit for bit."""
     from test_gpu_round4 import _bench
-    common = ["--steps", "5", "--warmup", "1", "--blocks", "3", "--no-cpu-baseline", "--no-extras", "--no-pmc", "--no-scaling-workloads",
+    common = ["--full", "--steps", "5", "--warmup", "1", "--blocks", "3", "--no-cpu-baseline", "--no-extras", "--no-pmc", "--no-scaling-workloads",
               "--no-api-wall", "--mode", "delta", "--n-test", "200"]
     plain = _bench(common, {"LT_BENCH_DUMP": str(tmp_path / "plain.npy")})
     auto = _bench(common, {"LT_FORCE_COLLECTIVES": "1", "LT_BENCH_DUMP": str(tmp_path / "auto.npy")})

@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-rm -rf /tmp/tr; LT_FEATURE_DELTA=0 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr -- python3 $R/bench.py --steps 20 --no-extras --no-api-wall --no-pmc --no-cpu-baseline --blocks 1 > /dev/null 2>&1
+rm -rf /tmp/tr; LT_FEATURE_DELTA=0 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr -- python3 $R/bench.py --full --steps 20 --no-extras --no-api-wall --no-pmc --no-cpu-baseline --blocks 1 > /dev/null 2>&1
 python3 - <<PY
 import csv,glob
 f=glob.glob('/tmp/tr/**/*kernel_stats.csv',recursive=True)[0]

@@ -1,7 +1,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 for f in 1; do
-  rm -rf /tmp/tr; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr -- python3 $R/bench.py --steps 20 --no-extras --powerlaw > /dev/null 2>&1
+  rm -rf /tmp/tr; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr -- python3 $R/bench.py --full --steps 20 --no-extras --powerlaw > /dev/null 2>&1
   echo "== power-law step"
   python3 - <<PY
 import csv,glob

@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT
 for cfg in "1 1" "1 0" "0 1" "0 0" "1 1" "1 0"; do
   set -- $cfg
-  LT_OVERLAP=$1 LT_LONG_PAR=$2 python bench.py --no-cpu-baseline --no-extras --powerlaw --steps 30 | python -c "
+  LT_OVERLAP=$1 LT_LONG_PAR=$2 python bench.py --full --no-cpu-baseline --no-extras --powerlaw --steps 30 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('PL full overlap=$1 long_par=$2', d['ms_per_step'], {k:v['avg_us'] for k,v in d['kernels'].items()})"
 done

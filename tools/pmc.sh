@@ -1,11 +1,11 @@
 #!/bin/bash
-# usage: tools/pmc.sh <tag> "<counters>" -- collects PMC counters for bench.py kernels (separate pass per call)
-tag=$1; ctrs=$2
+# usage: tools/pmc.sh <tag> "<counters>" <out dir> -- collects PMC counters for bench.py kernels (separate pass per call)
+tag=$1; ctrs=$2; R=$(cd "$(dirname "$0")/.." && pwd); O=$(realpath -m "${3:?usage: tools/pmc.sh <tag> \"<counters>\" <out dir>}")/pmc_$tag; mkdir -p "${O%/*}"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $ctrs --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/pmc_$tag -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras --no-pmc --steps 3 --warmup 1 > $GRAFT_REPO_ROOT/gpurun_out/pmc_$tag.log 2>&1
+rocprofv3 --pmc $ctrs --output-format csv -d $O -- python3 $R/bench.py --full --no-cpu-baseline --no-extras --no-pmc --steps 3 --warmup 1 > $O.log 2>&1
 python3 - <<PY
 import csv, glob, collections
-f = glob.glob("$GRAFT_REPO_ROOT/gpurun_out/pmc_$tag/*/*counter_collection.csv")
+f = glob.glob("$O/*/*counter_collection.csv")
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
 for fn in f:
     for r in csv.DictReader(open(fn)):

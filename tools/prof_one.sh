@@ -1,9 +1,9 @@
 #!/bin/bash
 # usage: tools/prof_one.sh <tag> <bench args...>   -- rocprofv3 kernel stats of one bench configuration (GPU box)
-tag=$1; shift
+tag=$1; shift; R=$(cd "$(dirname "$0")/.." && pwd)
 O=$GRAFT_REPO_ROOT/gpurun_out/prof_$tag
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras --no-pmc --steps 20 --warmup 3 "$@" > $O.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 $R/bench.py --full --no-cpu-baseline --no-extras --no-pmc --steps 20 --warmup 3 "$@" > $O.log 2>&1
 python3 - <<PY
 import csv,glob
 f=glob.glob("$O/*/*kernel_stats.csv")[0]

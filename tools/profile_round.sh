@@ -3,7 +3,7 @@
 # (default = --mode delta; the dense-feature route of delta; full; sparse; power-law delta and full; the R-MAT SpMM leg)
 tag=$1; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_$tag; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="--no-cpu-baseline --no-extras --no-pmc --steps 20 --warmup 3 --blocks 1"
+B="--full --no-cpu-baseline --no-extras --no-pmc --steps 20 --warmup 3 --blocks 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/step -- python3 $R/bench.py $B > $O/step.log 2>&1
 LT_FEATURE_DELTA=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/step_dense -- python3 $R/bench.py $B > $O/step_dense.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/step_full -- python3 $R/bench.py $B --mode full > $O/step_full.log 2>&1

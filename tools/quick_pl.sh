@@ -1,7 +1,7 @@
 #!/bin/bash
 # quick perf check: ER + power-law, all modes (GPU box)
 cd $GRAFT_REPO_ROOT
-python bench.py --no-cpu-baseline --spmm-scale 0 --steps 30 > /tmp/quick_pl.json
+python bench.py --full --no-cpu-baseline --spmm-scale 0 --steps 30 > /tmp/quick_pl.json
 python - <<'PY'
 import json
 d = json.loads(open('/tmp/quick_pl.json').read().strip().splitlines()[-1])
