@@ -34,7 +34,8 @@ extern "C" {
                             point is unchanged.  4: lt_export_rows_f64 (the matrix leaves the device once, as float64), node ids checked on the device
                             (LT_ERR_INDEX, lt_node_check), lt_profile_calls; every version-3 entry point is unchanged.  2: lt_baseline_refresh launches nothing (lazy recomputation on the first reader's stream); fp64 shard entry points;
                             profile classes 9-11.  3: lt_influence_rows_vec + lt_wide_combine (layers wider than one pass of the fused
-                            kernels), lt_spmm_gather_ceiling (measurement support); every version-2 entry point is unchanged */
+                            kernels), lt_spmm_gather_ceiling (measurement support); every version-2 entry point is unchanged.
+                            Additive within 5: training of the 2-layer GCN (lt_gcn2_trainer_*) and lt_adam_step; no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -392,6 +393,43 @@ int lt_influence3_rows_mode(const lt_baseline3 *b, const int32_t *probe_nodes, i
  * asserts) returns LT_ERR_UNSUPPORTED. */
 int lt_lapgraph_select(int32_t n, const int32_t *lower_rowptr, const int32_t *lower_col, double *cells, int64_t n_keep,
                        int64_t *out_idx, void *work, size_t work_bytes, double *threshold_out, void *stream);
+
+/* ---- training of the 2-layer GCN (reference gcn_trainer.py:144-170 train_one_epoch + optim.Adam) ----
+ * lt_gcn2_trainer_create borrows the graph, X [n, ldx], labels (int32 [n], device, each in [0, C)) and the four parameter
+ * tensors (W1 [F, H], b1 [H], W2 [H, C], b2 [C], dense fp32 device buffers), which every epoch updates IN PLACE; it owns
+ * the Adam moments and every intermediate.  H <= 256 and C <= 8 (the fused forward's limits), dropout in [0, 1]; anything
+ * else is LT_ERR_INVALID.  One epoch, with e = the epochs run since creation:
+ *   S1 = X W1; Z1 = A S1 + b1; H1d = dropout_p(relu(Z1)); S2 = H1d W2; Z2 = A S2 + b2  (the launches of lt_gcn2_forward:
+ *        with dropout 0 the first epoch's Z2 equals lt_gcn2_forward's logits bit for bit)
+ *   loss = mean_r CE(Z2[r], y[r]); dZ2 = (softmax(Z2) - onehot(y)) / n; dS2 = A^T dZ2 (the CSC: A need not be symmetric)
+ *   dW2 = H1d^T dS2, db2 = sum_r dZ2, dZ1 = [H1d > 0] (dS2 W2^T) / (1 - p), db1 = sum_r dZ1, dS1 = A^T dZ1, dW1 = X^T dS1
+ *   one Adam step (torch.optim.Adam: betas (0.9, 0.999), eps 1e-8, weight decay added to the gradient), step = e + 1
+ * Dropout: element (r, h) has i = r * H + h; it is kept iff word (i & 3) of Philox4x32-10 with counter
+ * (q & 0xffffffff, q >> 32, e, 0), q = i >> 2, and key (seed & 0xffffffff, seed >> 32) is >= floor(p * 2^32); kept
+ * elements are scaled by (float)(1 / (1 - p)).  p = 0 draws nothing; p = 1 keeps nothing.
+ * lt_gcn2_trainer_run enqueues n_epochs epochs on `stream`, no host synchronisation; record (device, [n_epochs, 2] fp32):
+ * per epoch the mean training loss and the number of rows whose first argmax equals the label.  Every reduction has a
+ * fixed order: the same inputs and seed give the same bits, and run(40) equals four run(10).
+ * lt_gcn2_trainer_grads / _logits: the LAST epoch's gradients (before weight decay) and its train-mode logits Z2 (before
+ * that epoch's update) -- for tests, as lt_spmm_gather_ceiling is for measurement.  lt_gcn2_trainer_epoch: epochs run. */
+typedef struct lt_gcn2_trainer lt_gcn2_trainer;
+int lt_gcn2_trainer_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const int32_t *labels, int32_t H,
+                           int32_t C, float *W1, float *b1, float *W2, float *b2, double lr, double weight_decay,
+                           double dropout, uint64_t seed, void *stream, lt_gcn2_trainer **out);
+int lt_gcn2_trainer_run(lt_gcn2_trainer *t, int32_t n_epochs, float *record, void *stream);
+int lt_gcn2_trainer_grads(const lt_gcn2_trainer *t, float *dW1, float *db1, float *dW2, float *db2, void *stream);
+int lt_gcn2_trainer_logits(const lt_gcn2_trainer *t, float *Z2, int64_t ldz, void *stream);
+int lt_gcn2_trainer_epoch(const lt_gcn2_trainer *t, int64_t *epoch);
+int lt_gcn2_trainer_destroy(lt_gcn2_trainer *t);
+/* One Adam step over n fp32 elements in place (the trainer's update, exported so it is tested on its own):
+ * torch/optim/adam.py _single_tensor_adam op by op in fp32 with correctly rounded sqrt and division, and fused multiply-adds
+ * where torch's CPU kernels fuse (the weight-decay add, lerp_, addcmul_) --
+ *   g' = fma(p, wd, g); m = fma(w1, g' - m, m) (lerp_, w1 = 1 - beta1); v = v beta2; v = fma(w2 g', g', v) (w2 = 1 - beta2);
+ *   p = p + (-lr / bc1 * m) / (sqrt(v) / sqrt(bc2) + eps),  bc1 = 1 - beta1^step, bc2 = 1 - beta2^step
+ * -- the scalars formed in double and rounded once to float, as torch does with Python scalars.  step >= 1 is the step
+ * count after this update. */
+int lt_adam_step(int64_t n, float *p, const float *g, float *m, float *v, int64_t step, double lr, double beta1,
+                 double beta2, double eps, double weight_decay, void *stream);
 
 /* ---- per-kernel timing (used by bench.py for the roofline object) --------------------------
  * lt_profile_enable(mask): bit k of mask set = launches of kernel class k are bracketed by a pair of

@@ -90,6 +90,16 @@ SIGNATURES = {
     "lt_node_check": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lt_export_rows_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "lt_profile_calls": (C.c_int, [C.POINTER(C.c_int64)]),
+    "lt_gcn2_trainer_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                         C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lt_gcn2_trainer_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lt_gcn2_trainer_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_gcn2_trainer_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "lt_gcn2_trainer_epoch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "lt_gcn2_trainer_destroy": (C.c_int, [C.c_void_p]),
+    "lt_adam_step": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
+                               C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "lt_profile_enable": (C.c_int, [C.c_int]),
     "lt_profile_reset": (C.c_int, []),
     "lt_profile_summary": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -536,6 +536,16 @@ __global__ void k_sum_slabs(const float *__restrict__ slabs, long slab_stride, i
     C[(long)r * ldc + c] = acc;
 }
 
+int lt_launch_sum_slabs(const float *slabs, long slab_stride, int splits, int M, int N, long ld, float *C, long ldc,
+                        hipStream_t st) {
+    const long tot = (long)M * N;
+    if (tot == 0) return LT_OK;
+    hipLaunchKernelGGL(k_sum_slabs, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, slabs, slab_stride, splits, M, N,
+                       ld, C, ldc);
+    LT_CHECK_LAUNCH();
+    return LT_OK;
+}
+
 // Slice length for the big (128x128-tile) split-K product: pick the slice count whose workgroups fill the
 // 256 CUs in whole rounds (a 2.2-blocks-per-CU grid runs as long as a 3-per-CU one), charging each extra
 // slab ~2 tile-steps of write + re-read.  Deterministic in (M, N, K); multiples of 16.

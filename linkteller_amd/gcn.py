@@ -4,9 +4,9 @@ Same class names, constructor arguments, parameter names/shapes (``gc1.weight [F
 ``gc1.bias [H]``, ``gc2.weight [H,C]``, ``gc2.bias [C]``) and init law, so a ``state_dict``
 trained with the reference loads unchanged (gcn_trainer.py:102-105).  ``forward(x, adj)`` accepts
 what the reference passes (a dense float tensor and a torch sparse COO adjacency) or a
-``HipGraph``; inference runs through liblinkteller_hip.  Training (autograd through these layers)
-is outside the hot path ("OUT OF SCOPE GCNTrainer.train") and is refused
-rather than silently served by another backend.
+``HipGraph``; inference runs through liblinkteller_hip.  Autograd through these layers is refused
+rather than silently served by another backend; the 2-layer GCN is trained by the fused HIP trainer
+(``engine.GCN2Trainer``, ``GCNTrainer.train``, ``main --train``).
 """
 from __future__ import annotations
 
@@ -22,7 +22,7 @@ def _refuse_training(module):
     if module.training and torch.is_grad_enabled():
         raise NotImplementedError(
             "linkteller_amd implements the inference/attack hot path only; call model.eval() and/or "
-            "torch.no_grad().  Train with the reference implementation and load its state_dict.")
+            "torch.no_grad().  Train with engine.GCN2Trainer (main --train) or load a state_dict.")
 
 
 class GraphConvolution(nn.Module):

@@ -4,8 +4,14 @@
         --norm FirstOrderGCN --test --model-path model.pt --attack --attack-mode efficient \
         --sample-type unbalanced --n-test 500 [--influence-mode {full,sparse,delta}]
 
-Every flag of the reference is accepted with its default; only ``--test`` (inference + attack on a
-reference-trained ``state_dict``) is implemented -- training stays with the reference.
+Every flag of the reference is accepted with its default.  ``--test`` runs inference + attack on a saved ``state_dict``;
+``--train`` (an addition) trains the 2-layer GCN on the GPU as the reference does without ``--test``, saves
+``model_<dataset>/<subdir>/model.pt``, then tests it and attacks it with ``--attack``:
+
+    python -m linkteller_amd.main --train --mode vanilla --eps 5 --dataset twitch/ES/RU --hidden 256 \
+        --norm FirstOrderGCN --attack --sample-type unbalanced --n-test 500
+
+Without either switch the run is refused (a default run does not start a 500-epoch job by itself).
 """
 from __future__ import annotations
 
@@ -40,7 +46,9 @@ _OPTIONS = {
     "influence-mode": (str, "delta", ["full", "sparse", "delta"]), "data-root": (str, "./data"),
 }
 _SWITCHES = ["no-cuda", "fastmode", "approx", "attack", "test", "break-down", "display", "same-size",
-             "eval-degree", "trainable", "early", "fnormalize"]
+             "eval-degree", "trainable", "early", "fnormalize",
+             # addition: train (as the reference does without --test), then test, and attack with --attack
+             "train"]
 
 
 def build_parser():
@@ -96,6 +104,12 @@ def init_distributed():
 
 def main(argv=None):
     args = get_arguments(argv)
+    import os
+    if args.train and not args.test:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise NotImplementedError("--train runs on one GPU: launch it without torchrun / WORLD_SIZE > 1")
+        if args.n_layer != 2:
+            raise NotImplementedError("--train: training is implemented for the 2-layer GCN only (--n-layer 2)")
     owns_group = init_distributed()
     try:
         _run(args)
@@ -119,6 +133,9 @@ def _run(args):
     torch.manual_seed(args.seed)
     if torch.cuda.is_available():
         torch.cuda.manual_seed(args.seed)
+    if not args.test and args.train:
+        _train(args)
+        return
     if not args.test:
         raise NotImplementedError("only --test (inference + attack on a saved state_dict) is implemented; "
                                   "train with the reference")
@@ -128,6 +145,47 @@ def _run(args):
     trainer = GCNTrainer(args, worker=worker)
     trainer.init_model(model_path=args.model_path)
     trainer.test(args.eval_degree)
+
+
+
+def init_logger(log_path, log_file, level=logging.INFO):
+    """utils/logging.py with print_log=False: INFO records go to ``<log_path>/<log_file>.log`` in the reference's format.
+    The handler is added to the root logger (``logging.basicConfig`` would do nothing where a handler is installed already)."""
+    import os
+    os.makedirs(log_path, exist_ok=True)
+    handler = logging.FileHandler("{0}/{1}.log".format(log_path, log_file))
+    handler.setFormatter(logging.Formatter(
+        "%(asctime)s [%(process)d] [%(threadName)-12.12s] [%(levelname)-5.5s]  %(message)s"))
+    root = logging.getLogger()
+    root.addHandler(handler)
+    root.setLevel(level)
+    return handler
+
+
+def _train(args):
+    """main.py:114-162 for the modes with a GCN (vanilla-clean, vanilla): subdir, log file, Worker, train, test."""
+    import datetime
+    cur_time = datetime.datetime.now().strftime("%m-%d-%H:%M:%S.%f")
+    if args.mode == "vanilla-clean":
+        subdir = "mode-{}_hidden-{}_lr-{}_decay-{}_dropout-{}_norm-{}_{}".format(
+            args.mode, args.hidden, args.lr, args.weight_decay, args.dropout, args.norm, cur_time)
+    elif args.mode == "vanilla":
+        subdir = "mode-global_perturb-{}_eps-{}_{}".format(args.perturb_type, args.epsilon, cur_time)
+    else:
+        raise NotImplementedError("mode = {}: --train is implemented for vanilla-clean and vanilla".format(args.mode))
+    print("subdir = {}".format(subdir))
+    handler = init_logger("./logs_{}".format(args.dataset), subdir)
+    try:
+        from .trainer import GCNTrainer
+        from .worker import Worker
+        worker = Worker(args, dataset=args.dataset, mode=args.mode, data_root=args.data_root)
+        trainer = GCNTrainer(args, subdir=subdir, worker=worker)
+        trainer.init_model()
+        trainer.train()
+        trainer.test(args.eval_degree)
+    finally:
+        logging.getLogger().removeHandler(handler)
+        handler.close()
 
 
 if __name__ == "__main__":

@@ -1,9 +1,14 @@
-"""The slice of ``GCNTrainer`` the attack goes through (reference gcn_trainer.py:55-110, 113-141,
-262-284, 320-406): build the model, load a reference-trained ``state_dict``, one clean forward for
-the utility metrics, dispatch to ``Attacker``.  Training is outside the hot path."""
+"""``GCNTrainer`` (reference gcn_trainer.py:23-110, 113-243, 262-284, 320-406): build the model, either load a
+``state_dict`` or train the 2-layer GCN on the GPU (``engine.GCN2Trainer``: forward, cross-entropy, backward and Adam as HIP
+kernels), one clean forward for the utility metrics, dispatch to ``Attacker``.
+
+Training differs from the reference in two documented ways: dropout draws a Philox4x32-10 mask keyed by ``--seed`` and the
+epoch (include/linkteller_hip.h), not torch's generator; and no TensorBoard logs are written (``tensorboard`` is not a
+dependency of this package) -- the per-epoch lines go to the log file as the reference writes them."""
 from __future__ import annotations
 
 import logging
+import os
 import time
 
 import torch
@@ -21,6 +26,10 @@ class GCNTrainer:
         self.mode = worker.mode
         self.dataset = worker.dataset
         self.subdir = subdir
+        self.gpu_trainer = None
+        if subdir:                                             # gcn_trainer.py:37-52 (without the SummaryWriter)
+            self.model_path = os.path.join("model_{}".format(self.dataset), subdir)
+            os.makedirs(self.model_path, exist_ok=True)
 
     def init_model(self, model_path=""):
         a, w = self.args, self.worker
@@ -33,14 +42,50 @@ class GCNTrainer:
                               dropout=a.dropout)
         else:
             raise NotImplementedError(f"n_layer = {a.n_layer} not implemented!")
-        if not model_path:
-            raise NotImplementedError("training is out of scope: pass --model-path to a state_dict trained "
-                                      "with the reference (gcn_trainer.py:240)")
-        self.model.load_state_dict(torch.load(model_path, map_location="cpu"))
-        print("load model from {} done!".format(model_path))
-        self.model_path = model_path
+        if model_path:
+            self.model.load_state_dict(torch.load(model_path, map_location="cpu"))
+            print("load model from {} done!".format(model_path))
+            self.model_path = model_path
+        elif a.n_layer != 2:
+            raise NotImplementedError("training is implemented for the 2-layer GCN only (--n-layer 2)")
         if torch.cuda.is_available():
             self.model.cuda()
+        if not model_path:
+            # the optimizer state of gcn_trainer.py:106-108: Adam's moments live in the GPU trainer, which updates the
+            # model's parameters in place
+            from .engine import GCN2Trainer
+            if not w.transfer:
+                raise NotImplementedError(f"dataset = {self.dataset}: training is implemented for transfer datasets")
+            g1, g2 = self.model.gc1, self.model.gc2
+            self.gpu_trainer = GCN2Trainer(w.adj_1, w.features_1, w.labels_1, g1.weight.detach(), g1.bias.detach(),
+                                           g2.weight.detach(), g2.bias.detach(), lr=a.lr, weight_decay=a.weight_decay,
+                                           dropout=a.dropout, seed=a.seed)
+
+    def train(self):
+        """gcn_trainer.py:200-243 on a transfer dataset: ``num_epochs`` epochs on (features_1, adj_1, labels_1), the
+        per-epoch log line of train_one_epoch, ``model.pt`` under ``model_<dataset>/<subdir>``.  The epochs run back to back
+        on the device and the per-epoch record is read once at the end, so the ``time`` of an epoch's line is the run's wall
+        time divided by the number of epochs."""
+        if self.gpu_trainer is None:
+            raise RuntimeError("init_model() without a model path first")
+        a = self.args
+        t_total = time.time()
+        self.model.train()
+        n_epochs = int(a.num_epochs)
+        loss, correct = self.gpu_trainer.run(n_epochs)
+        per_epoch = (time.time() - t_total) / max(n_epochs, 1)
+        n = self.gpu_trainer.n
+        for epoch in range(n_epochs):
+            logging.info("[epoch {}]".format(epoch))
+            output_info = "Epoch: {:04d}".format(epoch + 1), \
+                "loss_train: {:.4f}".format(float(loss[epoch])), \
+                "acc_train: {:.4f}".format(int(correct[epoch]) / n), \
+                "time: {:.4f}s".format(per_epoch)
+            logging.info(output_info)
+        self.model.eval()
+        torch.save(self.model.state_dict(), os.path.join(self.model_path, "model.pt"))
+        print("Optimization Finished!")
+        print("Total time elapsed: {:.4f}s".format(time.time() - t_total))
 
     def forward(self, mode="train"):
         w = self.worker
