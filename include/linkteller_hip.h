@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LT_ABI_VERSION 5   /* 5: lt_influence_rows_f64 (the probes' blocks write the float64 matrix themselves), the on-demand pre-activation by
+#define LT_ABI_VERSION 5   /* 5: lt_influence_rows_f64 (the probes' blocks write the float64 matrix themselves), lt_influence_matrix_host (the same, synchronous, packed), the on-demand pre-activation by
                             row list (lt_baseline_form / gather / scatter_rows_fp64: hub rows shared between ranks); every version-4 entry
                             point is unchanged.  4: lt_export_rows_f64 (the matrix leaves the device once, as float64), node ids checked on the device
                             (LT_ERR_INDEX, lt_node_check), lt_profile_calls; every version-3 entry point is unchanged.  2: lt_baseline_refresh launches nothing (lazy recomputation on the first reader's stream); fp64 shard entry points;
@@ -130,6 +130,10 @@ int lt_device_count(int *count);
  *   "export_zero_blocks"  waves that zero-fill in each of the two launches (default 16; 1 .. 4096: more of them, or more stores in
  *                         flight, and the writes queued for the link hold up the loads of the kernels beside them)
  *   "export_zero_inflight"   1-KiB stores each such wave keeps in flight (default 4; 1 .. 64)
+ *   "export_compact"      lt_influence_matrix_host on the fused LT_MODE_DELTA route: 1 = the probes' blocks send their touched values
+ *                         as packed 8-byte entries (fp32 value, index into dst) into pinned staging while the host zero-fills dst, and
+ *                         the host places them after the stream wait, when the graph's mean touched share of a row is below 0.25
+ *                         (default), 0 = never (the route of lt_influence_rows_f64), 2 = always.  Bit-identical
  *   "feature_stagger"     feature-difference route, one wave per row: the row blocks start in (value & 255) groups, (value >> 8) x 10 ns
  *                         apart, so that a group walks its lists while the next one's rows arrive; 0 = all together.  Bit-identical
  *   "xf64_blocks"         aggregate-first route: blocks per XCD that walk the compacted work items of the rows a call reaches (default 96;
@@ -316,6 +320,18 @@ int lt_influence_rows_f64(const lt_baseline *b, const int32_t *probe_nodes, int3
                           const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode,
                           float *out, int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
                           void *stream);
+
+/* lt_influence_rows_f64 into PINNED host memory, and the wait: returns once dst[i * ldd + j] holds the float64 matrix (the
+ * reference's influence_val, attacker.py:213 -> 231); columns n_obs .. ldd - 1 are left as they are.  Same arguments, checks and
+ * LT_ERR_INDEX behaviour as lt_influence_rows_f64; out is written as by lt_influence_rows.  On the fused LT_MODE_DELTA route
+ * ("export_compact") the matrix's zeros do not cross PCIe: the probes' blocks send their touched values packed into a pinned
+ * staging block the baseline owns (allocated on first use, worst-case size, freed by lt_baseline_destroy), the host zero-fills
+ * dst while the GPU computes and places the values after the stream wait.  Every other call is lt_influence_rows_f64 followed
+ * by the wait.  Same values, bit for bit.  Like every call on a baseline handle, not thread-safe. */
+int lt_influence_matrix_host(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
+                             const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode,
+                             float *out, int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
+                             void *stream);
 
 /* ---- measurement support: the gather ceiling of the tiled SpMM ------------------------------------------------------
  * The tiled (column-sliced work-item) kernel of lt_spmm_csr_f32 with everything but its gathers removed: the same work

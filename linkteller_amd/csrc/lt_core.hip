@@ -66,6 +66,7 @@ static lt_tuning tuning_defaults() {
     t.export_zero_inflight = (int)std::min<long long>(64, std::max<long long>(1, env_ll("LT_EXPORT_ZERO_INFLIGHT", 4)));
     t.export_zero_share2 = (int)std::min<long long>(100, std::max<long long>(0, env_ll("LT_EXPORT_ZERO_SHARE2", 15)));
     t.export_zero_share = (int)std::min<long long>(100, std::max<long long>(0, env_ll("LT_EXPORT_ZERO_SHARE", 35)));
+    t.export_compact = (int)std::min<long long>(2, std::max<long long>(0, env_ll("LT_EXPORT_COMPACT", 1)));
     t.feature_stagger = (int)env_ll("LT_FEATURE_STAGGER", 0);
     const long long xb = env_ll("LT_XF64_BLOCKS", 96);
     t.xf64_blocks = xb > 0 && xb <= 4096 ? (int)xb : 96;
@@ -120,6 +121,10 @@ extern "C" int lt_set_tuning(const char *key, long long value) {
     else if (!strcmp(key, "export_zero_share2")) t.export_zero_share2 = reset ? d.export_zero_share2 : (int)std::min<long long>(100, std::max<long long>(0, value));
     else if (!strcmp(key, "export_zero_share")) t.export_zero_share = reset ? d.export_zero_share : (int)std::min<long long>(100, std::max<long long>(0, value));
     else if (!strcmp(key, "export_zero_inflight")) t.export_zero_inflight = reset ? d.export_zero_inflight : (int)std::min<long long>(64, std::max<long long>(1, value));
+    else if (!strcmp(key, "export_compact")) {
+        LT_REQUIRE(reset || (value >= 0 && value <= 2), "lt_set_tuning: export_compact must be 0, 1 or 2");
+        t.export_compact = reset ? d.export_compact : (int)value;
+    }
     else if (!strcmp(key, "export_zero_blocks")) t.export_zero_blocks = reset ? d.export_zero_blocks : (int)std::min<long long>(4096, std::max<long long>(1, value));
     else if (!strcmp(key, "feature_stagger")) {
         LT_REQUIRE(reset || (value >= 0 && value < (1 << 24)), "lt_set_tuning: feature_stagger out of range");
@@ -578,6 +583,9 @@ extern "C" int lt_graph_create(int32_t n, int64_t nnz, const int32_t *rowptr, co
                 if (e == hipSuccess) {
                     g->dl_max_t = dl.max_t;
                     g->dl_max_tu = dl.max_tu;
+                    double touched = 0.0;
+                    for (int32_t v = 0; v < n; ++v) touched += dl.meta[(size_t)v * 4 + 2];
+                    g->dl_touch_frac = touched / ((double)n * n);
                 } else {
                     (void)hipGetLastError();
                     (void)hipFree(g->dl_meta); (void)hipFree(g->dl_rec);
@@ -758,7 +766,7 @@ static __global__ __launch_bounds__(256) void k_export_rows_f64(const float *__r
 
 // dst may be host memory: only pinned (device-mapped) memory can be written by a kernel -- resolve its device-side alias and
 // refuse pageable pointers instead of faulting
-int lt_export_resolve(double *dst, double **dev, const char *who) {
+int lt_export_resolve(double *dst, double **dev, const char *who, bool *is_host) {
     hipPointerAttribute_t at;
     hipError_t e = hipPointerGetAttributes(&at, dst);
     if (e != hipSuccess) {
@@ -766,6 +774,7 @@ int lt_export_resolve(double *dst, double **dev, const char *who) {
         return lt_set_error(LT_ERR_INVALID, "%s: dst is neither device memory nor pinned host memory (%s)", who, hipGetErrorString(e));
     }
     *dev = dst;
+    if (is_host) *is_host = at.type == hipMemoryTypeHost;
     if (at.type == hipMemoryTypeHost) {
         LT_REQUIRE(at.devicePointer != nullptr, "%s: pinned dst has no device-side alias", who);
         *dev = (double *)at.devicePointer;

@@ -408,6 +408,8 @@ static void free_baseline(lt_baseline *b) {
     if (b->side) { (void)hipStreamSynchronize(b->side); (void)hipStreamDestroy(b->side); }
     if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
     if (b->ev_join) (void)hipEventDestroy(b->ev_join);
+    if (b->stage_host) (void)hipHostFree(b->stage_host);
+    (void)hipFree(b->stage_cur);
     delete b;
 }
 

@@ -18,7 +18,9 @@
 //          A_hat[u,r] * dS2[r] over r in R_v.  Free of the fp32 cancellation noise of the
 //          finite difference: agrees with an fp64 run of the reference.
 #include <stdlib.h>
+#include <string.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "lt_rows.hip.h"
@@ -1524,7 +1526,9 @@ __global__ __launch_bounds__(LT_BLOCK) void k_delta_probe_finish(
     const double *__restrict__ crefv, const double *__restrict__ S1qs, const float *__restrict__ Z1x, int Hp,
     const float *__restrict__ W2p, int C, const int32_t *__restrict__ rec, int rec_words, int maxc,
     const int32_t *__restrict__ dl_src, int n_obs, float delta, float *__restrict__ out, long ldo,
-    double *__restrict__ out64 = nullptr, long ld64 = 0, int out64_sparse = 0) {      // (rows [0, out64_sparse) of out64 hold zeros already)
+    double *__restrict__ out64 = nullptr, long ld64 = 0, int out64_sparse = 0,      // (rows [0, out64_sparse) of out64 hold zeros already)
+    uint2 *__restrict__ cent = nullptr, int32_t *__restrict__ ccnt = nullptr, int *__restrict__ ccur = nullptr,
+    int *__restrict__ ccur_next = nullptr, long crow0 = 0, long cld = 0, long ccap = 0) {
     extern __shared__ __attribute__((aligned(16))) unsigned char df_smem[];
     float *sS2 = reinterpret_cast<float *>(df_smem);             // [maxc][C] the items' layer-2 differences
     // (launched with 256, 128 or 64 threads: a call of more probes than the chip holds 4-wave blocks for -- ~ 90 VGPRs, 5 waves per
@@ -1550,11 +1554,25 @@ __global__ __launch_bounds__(LT_BLOCK) void k_delta_probe_finish(
     // rows [0, out64_sparse) of out64 were zero-filled over PCIe by blocks of the launch that formed the product rows: their
     // probes' blocks write the touched positions only -- 7 % of the row at twitch size
     double *const srow = (out64 && b < out64_sparse) ? out64 + (long)b * ld64 : (double *)nullptr;
-    auto put = [&](int pos, float v) __attribute__((always_inline)) {
+    // cent != NULL (lt_influence_matrix_host): the touched positions' values leave as packed entries (fp32 bits, index into the host
+    // matrix) in ONE dense run of the pinned staging block -- the block claims its stretch off a cursor, its entry k is the k-th
+    // position of its table row (the short ones k = x, the long ones k = n_short + s: neighbouring lanes, neighbouring entries) --
+    // the host zero-fills the matrix meanwhile and reads the run front to back after the stream wait.  Which stretch a block gets
+    // varies from run to run, where its values land does not.  The other cursor is cleared for the next call
+    __shared__ int s_cbase;
+    const bool packed = cent != nullptr;
+    auto put = [&](int pos, int k, float v) __attribute__((always_inline)) {
         orow[pos] = v;
         if (srow) srow[pos] = (double)v;
+        if (packed && s_cbase + k < ccap) cent[s_cbase + k] = make_uint2(__float_as_uint(v), (unsigned)((crow0 + b) * cld + pos));
     };
     const int cnt = hdr.x, n_short = hdr.y & 0xffff, n_long = (int)((unsigned)hdr.y >> 16), v = hdr.z;
+    int cbase = 0;
+    if (packed && tid == 0) {
+        cbase = atomicAdd(ccur, n_short + n_long);      // (the barrier ahead of the first put publishes it)
+        ccnt[b] = n_short + n_long;
+        if (b == 0) *ccur_next = 0;
+    }
     const lt_df_inc *ent = reinterpret_cast<const lt_df_inc *>(dl_src + hdr.w);
     // per touched position: up to 4 entries by one thread (a select per (entry, chain) pair, nothing but registers)
     auto short_answer = [&](const lt_df_inc (&e)[4], const int c_) -> float {
@@ -1594,7 +1612,7 @@ __global__ __launch_bounds__(LT_BLOCK) void k_delta_probe_finish(
         const int st = lt_.y & 0xffff, c_ = lt_.y >> 16;
         return ent[st + min(y0 + lane, c_ - 1)];
     };
-    auto long_answer = [&](const int2 lt_, lt_df_inc mine) {
+    auto long_answer = [&](const int2 lt_, const int k_, lt_df_inc mine) {
         const int st = lt_.y & 0xffff, c_ = lt_.y >> 16;
         const int qq = lane & (LT_L2_LANES - 1), cl = lane >> 3;
         float acc = 0.f;
@@ -1634,7 +1652,7 @@ __global__ __launch_bounds__(LT_BLOCK) void k_delta_probe_finish(
             const float dd = oc / delta;
             ss = fmaf(dd, dd, ss);
         }
-        if (lane == 0) put(lt_.x, sqrtf(ss));
+        if (lane == 0) put(lt_.x, k_, sqrtf(ss));
     };
     lt_df_inc te[TPR][4];
     lt_df_inc lmine = {0.f, 0};
@@ -1761,14 +1779,15 @@ __global__ __launch_bounds__(LT_BLOCK) void k_delta_probe_finish(
         } while (base < cnt);
     }
     DF_STAMP(1);
+    if (packed && tid == 0) s_cbase = cbase;
     __syncthreads();
     DF_STAMP(2);
     // ---- the touched positions ----
 #pragma unroll
     for (int h = 0; h < TPR; ++h)
-        if (tid + h * NT < n_short) put(tp[h].x, short_answer(te[h], tp[h].y >> 16));
+        if (tid + h * NT < n_short) put(tp[h].x, tid + h * NT, short_answer(te[h], tp[h].y >> 16));
     DF_STAMP(3);
-    if (wid < n_long) long_answer(ltp, lmine);
+    if (wid < n_long) long_answer(ltp, n_short + wid, lmine);
     DF_STAMP(4);
     // (beyond the registers: a trip of their own each)
     for (int x = tid + TPR * NT; x < n_short; x += NT) {
@@ -1777,7 +1796,7 @@ __global__ __launch_bounds__(LT_BLOCK) void k_delta_probe_finish(
         lt_df_inc e[4];
 #pragma unroll
         for (int y = 0; y < 4; ++y) e[y] = ent[st + min(y, c_ - 1)];
-        put(t_.x, short_answer(e, c_));
+        put(t_.x, x, short_answer(e, c_));
     }
     // The long positions beyond each wave's first (a clique of k nodes among the probes is k of them per member): 8 lanes per
     // position, 8 positions per wave side by side.  Lane q of a group holds entries q, q + 8, ... of a 64-entry stretch and the
@@ -1830,7 +1849,7 @@ __global__ __launch_bounds__(LT_BLOCK) void k_delta_probe_finish(
                     ss = fmaf(dd, dd, ss);
                 }
             }
-            if (have && q == 0) put(t_.x, sqrtf(ss));
+            if (have && q == 0) put(t_.x, n_short + s_, sqrtf(ss));
         }
     }
     DF_STAMP(5);
@@ -2426,10 +2445,21 @@ extern "C" size_t lt_influence_workspace_bytes(const lt_baseline *b, int32_t n_p
     return carve_infl(nullptr, b, n_probe, n_obs, mode).bytes;
 }
 
+// lt_influence_matrix_host's packed form of the fused DELTA route: the staging run (device-side alias of the baseline's pinned
+// block), the call's cursor and whether the call took it
+struct lt_compact_out {
+    uint2 *ent;         // [n_probe * n_obs at most] (fp32 bits of the value, i * ldd + j), in no particular order
+    int32_t *cnt;       // [n_probe] entries of each row
+    int *cur, *cur_next;   // device: this call's cursor (0 on entry) and the next call's (cleared by this call's launches)
+    long ld;            // ldd
+    long cap;           // entries the run holds (n_probe * n_obs: every pair touched)
+    bool taken;
+};
 static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
                                const int32_t *observe_nodes, int32_t n_obs, float delta,
                                int32_t mode, float *out, int64_t ldo, void *workspace,
-                               size_t workspace_bytes, void *stream, float *vec, double *dst64 = nullptr, int64_t ldd = 0);
+                               size_t workspace_bytes, void *stream, float *vec, double *dst64 = nullptr, int64_t ldd = 0,
+                               lt_compact_out *cmp = nullptr);
 
 // lt_influence_rows + the finished rows as float64 in dst (device memory, or pinned host memory: the reference's influence_val,
 // attacker.py:216-229): the fused DELTA route's blocks write their own rows there, every other route ends with the launch of
@@ -2446,6 +2476,98 @@ extern "C" int lt_influence_rows_f64(const lt_baseline *b, const int32_t *probe_
     }
     return influence_rows_impl(b, probe_nodes, n_probe, observe_nodes, n_obs, delta, mode, out, ldo, workspace, workspace_bytes,
                                stream, nullptr, dev, ldd);
+}
+
+// lt_influence_rows_f64 into pinned host memory, returning once the matrix is there (include/linkteller_hip.h).  On the fused DELTA
+// route of a graph whose probes touch a small share of a row (twitch-RU: 7 %), the matrix's zeros never cross PCIe: the probes'
+// blocks send the touched values as packed entries (8 bytes each, one dense run, instead of 8 bytes per position), the host
+// zero-fills dst while the GPU computes and places them after the stream wait.  Ordering is program order and that wait alone.
+// Every other call: lt_influence_rows_f64 and the wait.
+#define LT_COMPACT_MAX_FRAC 0.25              // mean touched share of a row up to which "export_compact" = 1 packs (see NOTES.md)
+#define LT_COMPACT_MAX_BYTES ((size_t)256 << 20)   // pinned staging beyond this: whole rows
+extern "C" int lt_influence_matrix_host(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
+                                        const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode, float *out,
+                                        int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
+                                        void *stream) {
+    LT_REQUIRE(b != nullptr, "lt_influence_matrix_host: baseline is NULL");
+    LT_REQUIRE(dst != nullptr || n_probe == 0 || n_obs == 0, "lt_influence_matrix_host: dst is NULL");
+    LT_REQUIRE(ldd >= n_obs, "lt_influence_matrix_host: ldd smaller than the row");
+    hipStream_t st = (hipStream_t)stream;
+    double *dev = nullptr;
+    bool host_dst = false;
+    if (n_probe > 0 && n_obs > 0) {
+        const int rc = lt_export_resolve(dst, &dev, "lt_influence_matrix_host", &host_dst);
+        if (rc) return rc;
+    }
+    const int ec = lt_tune().export_compact;
+    const size_t cells = (size_t)(n_probe > 0 ? n_probe : 0) * (size_t)(n_obs > 0 ? n_obs : 0);
+    const size_t ent_bytes = lt_align_up(cells * sizeof(uint2), 256);
+    const size_t need = ent_bytes + (size_t)(n_probe > 0 ? n_probe : 0) * sizeof(int32_t);
+    bool want = host_dst && mode == LT_MODE_DELTA && b->g->dl_meta != nullptr && n_obs <= 65534 && need <= LT_COMPACT_MAX_BYTES &&
+                (uint64_t)n_probe * (uint64_t)ldd <= 0xffffffffull &&
+                (ec == 2 || (ec == 1 && b->g->dl_touch_frac < LT_COMPACT_MAX_FRAC));
+    if (want && !b->stage_cur) {     // the two cursors, zero
+        if (hipMalloc((void **)&b->stage_cur, 2 * sizeof(int)) != hipSuccess ||
+            hipMemset(b->stage_cur, 0, 2 * sizeof(int)) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(b->stage_cur);
+            b->stage_cur = nullptr;
+            want = false;
+        }
+        b->stage_parity = 0;
+    }
+    if (want && b->stage_bytes < need) {
+        // (worst case: every pair touched; this call is synchronous, so nothing of an earlier one still writes the old block)
+        if (b->stage_host) (void)hipHostFree(b->stage_host);
+        b->stage_host = nullptr;
+        b->stage_bytes = 0;
+        if (hipHostMalloc(&b->stage_host, need, hipHostMallocDefault) == hipSuccess) b->stage_bytes = need;
+        else { (void)hipGetLastError(); b->stage_host = nullptr; want = false; }
+    }
+    lt_compact_out cmp = {};
+    if (want) {
+        char *d = nullptr;
+        if (hipHostGetDevicePointer((void **)&d, b->stage_host, 0) != hipSuccess) { (void)hipGetLastError(); want = false; }
+        else {
+            cmp.ent = reinterpret_cast<uint2 *>(d);
+            cmp.cnt = reinterpret_cast<int32_t *>(d + ent_bytes);
+            cmp.cur = b->stage_cur + b->stage_parity;
+            cmp.cur_next = b->stage_cur + (b->stage_parity ^ 1);
+            cmp.ld = (long)ldd;
+            cmp.cap = (long)cells;
+        }
+    }
+    const int rc = influence_rows_impl(b, probe_nodes, n_probe, observe_nodes, n_obs, delta, mode, out, ldo, workspace,
+                                       workspace_bytes, stream, nullptr, dev, ldd, want ? &cmp : nullptr);
+    if (cmp.taken) b->stage_parity ^= 1;     // (the launches that used this cursor cleared the other one)
+    if (rc) {
+        if (cmp.taken) {       // (launches already queued may still write the staging block; either cursor may be left dirty)
+            (void)hipStreamSynchronize(st);
+            (void)hipMemset(b->stage_cur, 0, 2 * sizeof(int));
+        }
+        return rc;
+    }
+    if (cmp.taken) {        // np.zeros (attacker.py:216), here, while the GPU computes; the padding columns stay as they are
+        if (ldd == n_obs) memset(dst, 0, cells * sizeof(double));
+        else
+            for (int32_t i = 0; i < n_probe; ++i) memset(dst + (size_t)i * ldd, 0, (size_t)n_obs * sizeof(double));
+    }
+    LT_HIP(hipStreamSynchronize(st));
+    if (cmp.taken) {        // the run front to back: the values' own stores are the only scattered accesses
+        const char *h = static_cast<const char *>(b->stage_host);
+        const uint2 *ent = reinterpret_cast<const uint2 *>(h);
+        const int32_t *cnt = reinterpret_cast<const int32_t *>(h + ent_bytes);
+        size_t total = 0;
+        for (int32_t i = 0; i < n_probe; ++i) total += (size_t)std::min(std::max(cnt[i], 0), n_obs);
+        const uint64_t lim = (uint64_t)n_probe * (uint64_t)ldd;
+        for (size_t e = 0; e < total && e < cells; ++e) {
+            const uint2 x = ent[e];
+            float v;
+            memcpy(&v, &x.x, sizeof(float));
+            if (x.y < lim) dst[x.y] = (double)v;
+        }
+    }
+    return LT_OK;
 }
 
 extern "C" int lt_influence_rows(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
@@ -2473,7 +2595,8 @@ extern "C" int lt_influence_rows_vec(const lt_baseline *b, const int32_t *probe_
 static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
                                const int32_t *observe_nodes, int32_t n_obs, float delta,
                                int32_t mode, float *out, int64_t ldo, void *workspace,
-                               size_t workspace_bytes, void *stream, float *vec, double *dst64, int64_t ldd) {
+                               size_t workspace_bytes, void *stream, float *vec, double *dst64, int64_t ldd,
+                               lt_compact_out *cmp) {
     lt_prof_call prof_call_;
     int32_t exported_rows = 0;      // (dst64) rows the fused route's blocks wrote themselves: the chunks are in probe order
     LT_REQUIRE(b != nullptr, "lt_influence_rows: baseline is NULL");
@@ -2510,6 +2633,12 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
     const df_geom dg = df_geometry(g, C, n_obs);
     const bool fused = delta64 && vec == nullptr && lt_tune().delta_fused != 0 && dg.ok && w.dl_rec != nullptr &&
                        !lt_fp64_agg_active(b) && !lt_fp64_on_demand(b, n_probe);
+    // (lt_influence_matrix_host, packed form: the blocks never write dst64 -- no zero-filling waves, no widened rows, no export)
+    const bool compact = fused && cmp != nullptr && cmp->ent != nullptr;
+    if (compact) {
+        dst64 = nullptr;
+        cmp->taken = true;
+    }
     const bool use_marks = !fused && mode != LT_MODE_FULL && w.pm_cnt != nullptr &&
                            (w.bits == nullptr || (long long)(n_probe < w.chunk ? n_probe : w.chunk) * n_obs >= lt_tune().pair_marks);
     // observed hubs (stageB_long_block): members found from the short side, or every entry tested against every probe.
@@ -2766,7 +2895,10 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
         if (dg.finish_smem > (size_t)64 * 1024) { const int rc_ = df_allow_big_lds<LPR_, CP_, SX_, ZF_>(); if (rc_) return rc_; }    \
         hipLaunchKernelGGL((k_delta_probe_finish<LPR_, CP_, SX_, ZF_>), dim3((unsigned)nb), dim3(df_threads), dg.finish_smem, st,      \
                            b->Z1d, b->S1d, sxp, crp, b->S1qs, zxp, Hp, b->W2p, C, w.dl_rec, dg.rec_words, dg.maxc, g->dl_rec,        \
-                           n_obs, delta, orow, (long)ldo, drow64, (long)ldd, sparse_rows - p0)))
+                           n_obs, delta, orow, (long)ldo, drow64, (long)ldd, sparse_rows - p0,                                     \
+                           compact ? cmp->ent : (uint2 *)nullptr, compact ? cmp->cnt + p0 : (int32_t *)nullptr,                    \
+                           compact ? cmp->cur : (int *)nullptr, compact ? cmp->cur_next : (int *)nullptr, (long)p0,                 \
+                           compact ? cmp->ld : 0L, compact ? cmp->cap : 0L)))
                     double *const drow64 = (dst64 && exported_rows == p0) ? dst64 + (int64_t)p0 * ldd : (double *)nullptr;
                     if (drow64) exported_rows = p0 + nb;
                     if (sxp && zxp) { LT_DF_LAUNCH(true, true); }

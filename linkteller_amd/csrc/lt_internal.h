@@ -33,6 +33,7 @@ struct lt_graph {
     int4 *dl_meta = nullptr;      // [n] (offset into dl_rec in words, items, touched nodes, incidences)
     int32_t *dl_rec = nullptr;
     int32_t dl_max_t = 0, dl_max_tu = 0;   // largest incidence / touched-node count of a node
+    double dl_touch_frac = 1.0;   // mean over the nodes of (touched nodes / n): the share of a probe's row the fused route writes
     // Long rows (hubs).  A row of more than LT_ROW_SEG entries is summed segment by segment in EVERY kernel
     // (lt_rows.hip.h row_dot: 128-entry fmaf chains, their sums added in segment order), which lets any kernel hand
     // the segments of a hub row to separate waves and still produce the same bits: the SpMM / layer-1 segment
@@ -137,6 +138,11 @@ struct lt_baseline {
     // kernel (fork after the probe-row GEMM, join before stage B).  Created on first use.
     mutable hipStream_t side = nullptr;
     mutable hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // lt_influence_matrix_host, packed form: pinned staging of the touched values (lt_influence.hip), allocated on first use
+    mutable void *stage_host = nullptr;
+    mutable size_t stage_bytes = 0;
+    mutable int *stage_cur = nullptr;   // device: the two cursors of the packed run (one per call, alternating; the other is cleared)
+    mutable int stage_parity = 0;
 };
 
 int lt_set_error(int code, const char *fmt, ...);
@@ -196,6 +202,8 @@ struct lt_tuning {
     int export_zero_share2;      // the next so many % of the rows, by blocks of the pre-activation's launch (LT_EXPORT_ZERO_SHARE2)
     int export_zero_blocks;      // waves that zero-fill (LT_EXPORT_ZERO_BLOCKS)
     int export_zero_inflight;    // stores each of them keeps in flight (LT_EXPORT_ZERO_INFLIGHT)
+    int export_compact;          // lt_influence_matrix_host, fused route: 1 packed touched values when the graph is sparse enough,
+                                 // 0 never, 2 always (LT_EXPORT_COMPACT)
     int feature_stagger;         // the row-per-wave kernel's blocks start in (value & 255) groups, (value >> 8) ticks of 10 ns apart; 0 = together
                                  // (LT_FEATURE_STAGGER)
     int feature_ring_min_rows;   // (LT_FEATURE_RING_MIN_ROWS, default 1024: below it the CUs' waves have no row each)
@@ -204,7 +212,7 @@ struct lt_tuning {
 };
 lt_tuning &lt_tune();
 // the float64 export (lt_core.hip): a dst pointer's device-side alias (pinned host memory) / itself (device memory); the launch
-int lt_export_resolve(double *dst, double **dev, const char *who);
+int lt_export_resolve(double *dst, double **dev, const char *who, bool *is_host = nullptr);
 int lt_export_rows_dev(const float *src, int64_t lds, int32_t rows, int32_t cols, double *dst_dev, int64_t ldd, hipStream_t stream);
 
 #define LT_HIP(call)                                                                       \

@@ -244,9 +244,11 @@ class Baseline:
         _lib.check(_lib.lib().lt_baseline_logits(self._h, out.data_ptr(), _stream()), "lt_baseline_logits")
         return out
 
-    def influence_rows(self, probe_nodes, observe_nodes, delta: float, mode="full", out=None, host=None) -> torch.Tensor:
+    def influence_rows(self, probe_nodes, observe_nodes, delta: float, mode="full", out=None, host=None,
+                       wait=False) -> torch.Tensor:
         """[n_probe, n_obs] fp32 on the device: ||(f(X + delta e_v x_v^T) - f(X))[u]||_2 / delta.  ``host``: a pinned (or
-        device) float64 [n_probe, n_obs] tensor that receives the same matrix widened (valid once the stream has drained).
+        device) float64 [n_probe, n_obs] tensor that receives the same matrix widened (valid once the stream has drained;
+        with ``wait``, a PINNED HOST tensor that holds it when the call returns: lt_influence_matrix_host).
         Node lists given as int32 CUDA tensors are checked on the device: call ``engine.node_check()`` after synchronising
         (see ``_as_nodes``)."""
         dev = self.x.device
@@ -267,6 +269,13 @@ class Baseline:
         if ws is None or ws.numel() < need:
             ws = _workspace(need, dev)
             self._ws = {key: ws}   # keep only the latest: sizes repeat across steps
+        if host is not None and wait:
+            # lt_influence_matrix_host: the same call, and the stream wait; on the fused `delta` route the matrix's zeros are
+            # written here on the host while the GPU computes, and only the touched values cross PCIe
+            _lib.check(_lib.lib().lt_influence_matrix_host(self._h, probes.data_ptr(), npb, obs.data_ptr(), nob, float(delta),
+                                                           m, out.data_ptr(), nob, host.data_ptr(), max(nob, 1), ws.data_ptr(),
+                                                           ws.numel(), _stream()), "lt_influence_matrix_host")
+            return out
         if host is not None:
             # lt_influence_rows_f64: the float64 matrix is written as part of the same call (the fused `delta` route's blocks
             # export their own rows; other routes end with the export launch)
@@ -280,12 +289,12 @@ class Baseline:
         return out
 
     def influence_matrix_host(self, probe_nodes, observe_nodes, delta: float, mode="delta", refresh=False):
-        """[n_probe, n_obs] float64 on the HOST (the reference's ``influence_val``, attacker.py:216-229) by ONE library call:
-        the rows are formed and land in pinned host memory (a block of torch's pinned-memory cache, owned by the returned
-        array) without an export launch of their own where the route allows; one stream wait; then the device-side node-id
-        check (IndexError, as the reference raises).  ``refresh``: mark the loop-invariant baseline stale first (``refresh(mode)``)
-        -- the call then recomputes it, and on the fused `delta` route the matrix's zeros cross PCIe under the launch that forms
-        the product rows while the probes' blocks send the touched positions only."""
+        """[n_probe, n_obs] float64 on the HOST (the reference's ``influence_val``, attacker.py:216-229) by ONE library call
+        that returns with the matrix in pinned host memory (a block of torch's pinned-memory cache, owned by the returned
+        array; lt_influence_matrix_host), then the device-side node-id check (IndexError, as the reference raises).  On the
+        fused `delta` route the host zero-fills the matrix while the GPU computes and only the touched values cross PCIe,
+        packed; other routes write whole rows without an export launch of their own where the route allows.  ``refresh``:
+        mark the loop-invariant baseline stale first (``refresh(mode)``) -- the call then recomputes it."""
         dev = self.x.device
         probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
         obs = _as_nodes(observe_nodes, self.n, dev, "observe_nodes")
@@ -299,8 +308,7 @@ class Baseline:
         if refresh:
             self.refresh(mode)
         if npb and nob:
-            self.influence_rows(probes, obs, delta, mode, out=out, host=host)
-            torch.cuda.current_stream(dev).synchronize()
+            self.influence_rows(probes, obs, delta, mode, out=out, host=host, wait=True)
             node_check()
         return host.numpy()
 
