@@ -130,10 +130,16 @@ int lt_device_count(int *count);
  *   "export_zero_blocks"  waves that zero-fill in each of the two launches (default 16; 1 .. 4096: more of them, or more stores in
  *                         flight, and the writes queued for the link hold up the loads of the kernels beside them)
  *   "export_zero_inflight"   1-KiB stores each such wave keeps in flight (default 4; 1 .. 64)
- *   "export_compact"      lt_influence_matrix_host on the fused LT_MODE_DELTA route: 1 = the probes' blocks send their touched values
- *                         as packed 8-byte entries (fp32 value, index into dst) into pinned staging while the host zero-fills dst, and
- *                         the host places them after the stream wait, when the graph's mean touched share of a row is below 0.25
- *                         (default), 0 = never (the route of lt_influence_rows_f64), 2 = always.  Bit-identical
+ *   "export_compact"      lt_influence_matrix_host on the fused LT_MODE_DELTA route: 1 = the touched values travel packed into pinned
+ *                         staging (their indices into dst from the probes' record blocks, early in the step; their fp32 values from the
+ *                         probes' blocks) while the host zero-fills dst, and the host places them after the stream wait, when the
+ *                         graph's mean touched share of a row is below 0.25 (default), 0 = never (the route of
+ *                         lt_influence_rows_f64), 2 = always.  Bit-identical
+ *   "export_early"        ... packed calls of one probe chunk: 1 = after zero-filling dst the host looks (bounded by hipStreamQuery,
+ *                         never waiting) for the index run the GPU publishes early in the step and, if it is there, walks it and asks
+ *                         for the destination lines before the stream wait, 0 = everything after the wait (default: the look
+ *                         shortens the section behind the wait by 1.6 us and costs the twitch-RU step 2.4), 2 = as 1, and the
+ *                         indices the early look saw are compared with the finished run (lt_host_landing_stats).  Bit-identical
  *   "feature_stagger"     feature-difference route, one wave per row: the row blocks start in (value & 255) groups, (value >> 8) x 10 ns
  *                         apart, so that a group walks its lists while the next one's rows arrive; 0 = all together.  Bit-identical
  *   "xf64_blocks"         aggregate-first route: blocks per XCD that walk the compacted work items of the rows a call reaches (default 96;
@@ -324,14 +330,22 @@ int lt_influence_rows_f64(const lt_baseline *b, const int32_t *probe_nodes, int3
 /* lt_influence_rows_f64 into PINNED host memory, and the wait: returns once dst[i * ldd + j] holds the float64 matrix (the
  * reference's influence_val, attacker.py:213 -> 231); columns n_obs .. ldd - 1 are left as they are.  Same arguments, checks and
  * LT_ERR_INDEX behaviour as lt_influence_rows_f64; out is written as by lt_influence_rows.  On the fused LT_MODE_DELTA route
- * ("export_compact") the matrix's zeros do not cross PCIe: the probes' blocks send their touched values packed into a pinned
- * staging block the baseline owns (allocated on first use, worst-case size, freed by lt_baseline_destroy), the host zero-fills
- * dst while the GPU computes and places the values after the stream wait.  Every other call is lt_influence_rows_f64 followed
- * by the wait.  Same values, bit for bit.  Like every call on a baseline handle, not thread-safe. */
+ * ("export_compact") the matrix's zeros do not cross PCIe: the touched values travel packed into a pinned staging block the
+ * baseline owns (allocated on first use, worst-case size, freed by lt_baseline_destroy) -- 4 bytes of index per value early in
+ * the step, as soon as the probes' records are matched, 4 bytes of value from the probes' blocks at its end -- the host zero-fills
+ * dst while the GPU computes, may walk the index run before the stream wait ("export_early") and places the values after it.
+ * Every other call is lt_influence_rows_f64 followed by the wait.  Same values, bit for bit.  Like every call on a baseline
+ * handle, not thread-safe. */
 int lt_influence_matrix_host(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
                              const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode,
                              float *out, int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
                              void *stream);
+
+/* The packed calls of lt_influence_matrix_host on this baseline so far: out4[0] = calls whose index run the host consumed before
+ * the stream wait, [1] = calls that did everything after it, [2] = nanoseconds spent between the wait's return and the matrix
+ * being complete, summed over both, [3] = ("export_early" = 2) index words the early look saw differently from the finished
+ * run -- anything but 0 means the publication is broken.  Additive in ABI 5. */
+int lt_host_landing_stats(const lt_baseline *b, int64_t *out4);
 
 /* ---- measurement support: the gather ceiling of the tiled SpMM ------------------------------------------------------
  * The tiled (column-sliced work-item) kernel of lt_spmm_csr_f32 with everything but its gathers removed: the same work

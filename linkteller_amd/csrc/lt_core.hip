@@ -67,6 +67,7 @@ static lt_tuning tuning_defaults() {
     t.export_zero_share2 = (int)std::min<long long>(100, std::max<long long>(0, env_ll("LT_EXPORT_ZERO_SHARE2", 15)));
     t.export_zero_share = (int)std::min<long long>(100, std::max<long long>(0, env_ll("LT_EXPORT_ZERO_SHARE", 35)));
     t.export_compact = (int)std::min<long long>(2, std::max<long long>(0, env_ll("LT_EXPORT_COMPACT", 1)));
+    t.export_early = (int)std::min<long long>(2, std::max<long long>(0, env_ll("LT_EXPORT_EARLY", 0)));
     t.feature_stagger = (int)env_ll("LT_FEATURE_STAGGER", 0);
     const long long xb = env_ll("LT_XF64_BLOCKS", 96);
     t.xf64_blocks = xb > 0 && xb <= 4096 ? (int)xb : 96;
@@ -124,6 +125,10 @@ extern "C" int lt_set_tuning(const char *key, long long value) {
     else if (!strcmp(key, "export_compact")) {
         LT_REQUIRE(reset || (value >= 0 && value <= 2), "lt_set_tuning: export_compact must be 0, 1 or 2");
         t.export_compact = reset ? d.export_compact : (int)value;
+    }
+    else if (!strcmp(key, "export_early")) {
+        LT_REQUIRE(reset || (value >= 0 && value <= 2), "lt_set_tuning: export_early must be 0, 1 or 2");
+        t.export_early = reset ? d.export_early : (int)value;
     }
     else if (!strcmp(key, "export_zero_blocks")) t.export_zero_blocks = reset ? d.export_zero_blocks : (int)std::min<long long>(4096, std::max<long long>(1, value));
     else if (!strcmp(key, "feature_stagger")) {

@@ -410,6 +410,7 @@ static void free_baseline(lt_baseline *b) {
     if (b->ev_join) (void)hipEventDestroy(b->ev_join);
     if (b->stage_host) (void)hipHostFree(b->stage_host);
     (void)hipFree(b->stage_cur);
+    free(b->stage_copy);
     delete b;
 }
 

@@ -1590,14 +1590,16 @@ static int form_z1d(lt_baseline *b, int32_t *state, hipStream_t st, const lt_bit
     const unsigned gj = (jb.nblocks > 0 ? (unsigned)jb.nblocks : 0u);
     if (job_done) *job_done = gj + gz > 0;
     const size_t jsm = gj > 0 ? (size_t)jb.smem_bytes : 0;
+    // (the index blocks of a packed host landing go FIRST: the host waits for what they publish, and they are gone long before the rows)
+    const int job_first = (gj > 0 && jb.csend) ? -1 : (int)(g2 + gs);
     if (b->s1_f32) {
         LT_DISPATCH_LPR(lpr, hipLaunchKernelGGL((k_spmm_f64<LPR_, float>), dim3(g2 + gs + gj + gz), dim3(256), jsm, st, n, g->rowptr,
                                                 g->col, g->val, b->S1x, Hp, b->b1p, b->Z1d, (int)gs, g->q_n_seg, g->q_seg_begin,
-                                                g->q_seg_long, g->q_long_row, b->seg_d, state, b->fd_rs, crefv, jb, (int)(g2 + gs), zf, b->S1qs));
+                                                g->q_seg_long, g->q_long_row, b->seg_d, state, b->fd_rs, crefv, jb, job_first, zf, b->S1qs));
     } else {
         LT_DISPATCH_LPR(lpr, hipLaunchKernelGGL((k_spmm_f64<LPR_, double>), dim3(g2 + gs + gj + gz), dim3(256), jsm, st, n, g->rowptr,
                                                 g->col, g->val, b->S1d, Hp, b->b1p, b->Z1d, (int)gs, g->q_n_seg, g->q_seg_begin,
-                                                g->q_seg_long, g->q_long_row, b->seg_d, state, b->fd_rs, crefv, jb, (int)(g2 + gs), zf));
+                                                g->q_seg_long, g->q_long_row, b->seg_d, state, b->fd_rs, crefv, jb, job_first, zf));
     }
     LT_CHECK_LAUNCH();
     if (have_long) {

@@ -17,6 +17,7 @@
 //          evaluated piecewise-linearly (no subtraction of nearly equal numbers); layer 2 sums
 //          A_hat[u,r] * dS2[r] over r in R_v.  Free of the fp32 cancellation noise of the
 //          finite difference: agrees with an fp64 run of the reference.
+#include <time.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -1527,8 +1528,7 @@ __global__ __launch_bounds__(LT_BLOCK) void k_delta_probe_finish(
     const float *__restrict__ W2p, int C, const int32_t *__restrict__ rec, int rec_words, int maxc,
     const int32_t *__restrict__ dl_src, int n_obs, float delta, float *__restrict__ out, long ldo,
     double *__restrict__ out64 = nullptr, long ld64 = 0, int out64_sparse = 0,      // (rows [0, out64_sparse) of out64 hold zeros already)
-    uint2 *__restrict__ cent = nullptr, int32_t *__restrict__ ccnt = nullptr, int *__restrict__ ccur = nullptr,
-    int *__restrict__ ccur_next = nullptr, long crow0 = 0, long cld = 0, long ccap = 0) {
+    float *__restrict__ cval = nullptr, long ccap = 0) {
     extern __shared__ __attribute__((aligned(16))) unsigned char df_smem[];
     float *sS2 = reinterpret_cast<float *>(df_smem);             // [maxc][C] the items' layer-2 differences
     // (launched with 256, 128 or 64 threads: a call of more probes than the chip holds 4-wave blocks for -- ~ 90 VGPRs, 5 waves per
@@ -1554,25 +1554,18 @@ __global__ __launch_bounds__(LT_BLOCK) void k_delta_probe_finish(
     // rows [0, out64_sparse) of out64 were zero-filled over PCIe by blocks of the launch that formed the product rows: their
     // probes' blocks write the touched positions only -- 7 % of the row at twitch size
     double *const srow = (out64 && b < out64_sparse) ? out64 + (long)b * ld64 : (double *)nullptr;
-    // cent != NULL (lt_influence_matrix_host): the touched positions' values leave as packed entries (fp32 bits, index into the host
-    // matrix) in ONE dense run of the pinned staging block -- the block claims its stretch off a cursor, its entry k is the k-th
-    // position of its table row (the short ones k = x, the long ones k = n_short + s: neighbouring lanes, neighbouring entries) --
-    // the host zero-fills the matrix meanwhile and reads the run front to back after the stream wait.  Which stretch a block gets
-    // varies from run to run, where its values land does not.  The other cursor is cleared for the next call
-    __shared__ int s_cbase;
-    const bool packed = cent != nullptr;
+    // cval != NULL (lt_influence_matrix_host): the touched positions' values leave as fp32 words in ONE dense run of the pinned
+    // staging block -- entry k of the block's stretch is the k-th position of its table row (the short ones k = x, the long ones
+    // k = n_short + s: neighbouring lanes, neighbouring words).  The stretch was claimed, and the entries' indices into the host
+    // matrix sent, by the probe's record block (lt_items.hip.h), whose header names the base: 4 bytes per touched value cross the
+    // link behind the probes.  Which stretch a block gets varies from run to run, where its values land does not.
+    const long cbase = hdr.z;
     auto put = [&](int pos, int k, float v) __attribute__((always_inline)) {
         orow[pos] = v;
         if (srow) srow[pos] = (double)v;
-        if (packed && s_cbase + k < ccap) cent[s_cbase + k] = make_uint2(__float_as_uint(v), (unsigned)((crow0 + b) * cld + pos));
+        if (cval && cbase + k < ccap) cval[cbase + k] = v;
     };
-    const int cnt = hdr.x, n_short = hdr.y & 0xffff, n_long = (int)((unsigned)hdr.y >> 16), v = hdr.z;
-    int cbase = 0;
-    if (packed && tid == 0) {
-        cbase = atomicAdd(ccur, n_short + n_long);      // (the barrier ahead of the first put publishes it)
-        ccnt[b] = n_short + n_long;
-        if (b == 0) *ccur_next = 0;
-    }
+    const int cnt = hdr.x & 0xffff, n_short = hdr.y & 0xffff, n_long = (int)((unsigned)hdr.y >> 16), v = (int)((unsigned)hdr.x >> 16);
     const lt_df_inc *ent = reinterpret_cast<const lt_df_inc *>(dl_src + hdr.w);
     // per touched position: up to 4 entries by one thread (a select per (entry, chain) pair, nothing but registers)
     auto short_answer = [&](const lt_df_inc (&e)[4], const int c_) -> float {
@@ -1779,7 +1772,6 @@ __global__ __launch_bounds__(LT_BLOCK) void k_delta_probe_finish(
         } while (base < cnt);
     }
     DF_STAMP(1);
-    if (packed && tid == 0) s_cbase = cbase;
     __syncthreads();
     DF_STAMP(2);
     // ---- the touched positions ----
@@ -2448,13 +2440,20 @@ extern "C" size_t lt_influence_workspace_bytes(const lt_baseline *b, int32_t n_p
 // lt_influence_matrix_host's packed form of the fused DELTA route: the staging run (device-side alias of the baseline's pinned
 // block), the call's cursor and whether the call took it
 struct lt_compact_out {
-    uint2 *ent;         // [n_probe * n_obs at most] (fp32 bits of the value, i * ldd + j), in no particular order
-    int32_t *cnt;       // [n_probe] entries of each row
+    uint32_t *idx;      // [n_probe * n_obs at most] i * ldd + j of every touched position, in no particular order (the record blocks)
+    float *val;         // ... and its value, same numbering (the finish kernel)
+    unsigned *ready;    // [0] entries of the run + 1 once every index of a chunk is in host memory (0 before), [1] the entries
     int *cur, *cur_next;   // device: this call's cursor (0 on entry) and the next call's (cleared by this call's launches)
+    int *tick;          // device: the record blocks' ticket (0 between launches)
     long ld;            // ldd
     long cap;           // entries the run holds (n_probe * n_obs: every pair touched)
     bool taken;
+    int chunks;         // probe chunks of the call (taken only)
 };
+static void lt_compact_job(lt_bits_job &j, const lt_compact_out &c, long row0) {
+    j.cidx = c.idx; j.ccur = c.cur; j.ccur_next = c.cur_next; j.ctick = c.tick; j.cready = c.ready;
+    j.crow0 = row0; j.cld = c.ld; j.ccap = c.cap;
+}
 static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
                                const int32_t *observe_nodes, int32_t n_obs, float delta,
                                int32_t mode, float *out, int64_t ldo, void *workspace,
@@ -2479,12 +2478,35 @@ extern "C" int lt_influence_rows_f64(const lt_baseline *b, const int32_t *probe_
 }
 
 // lt_influence_rows_f64 into pinned host memory, returning once the matrix is there (include/linkteller_hip.h).  On the fused DELTA
-// route of a graph whose probes touch a small share of a row (twitch-RU: 7 %), the matrix's zeros never cross PCIe: the probes'
-// blocks send the touched values as packed entries (8 bytes each, one dense run, instead of 8 bytes per position), the host
-// zero-fills dst while the GPU computes and places them after the stream wait.  Ordering is program order and that wait alone.
-// Every other call: lt_influence_rows_f64 and the wait.
+// route of a graph whose probes touch a small share of a row (twitch-RU: 7 %), the matrix's zeros never cross PCIe: the touched
+// values travel as one dense run in the baseline's pinned staging block, in two halves of the same numbering -- the indices into
+// dst, which depend on the graph and the lists alone, early in the step (lt_items.hip.h: delta_index_group in the pre-activation's
+// launch when the records rode behind the product rows, else the record blocks' own tail), the fp32 values from the finish kernel
+// -- next to one 64-byte line with the ready word.  The host zero-fills dst while the GPU computes and places the values behind
+// the stream wait.  With "export_early" a single-chunk call looks in between, without ever waiting for it, whether the index run
+// has been published and if so walks it once -- the indices are then in this core's cache, the destination lines asked for.  What
+// orders that look is the ready word (delta_index_publish); everything else is program order and the wait.  (Off by default: it
+// shortens the section behind the wait and costs the step more, profiles/host_early_ab.txt.)  Every other call:
+// lt_influence_rows_f64 and the wait.
 #define LT_COMPACT_MAX_FRAC 0.25              // mean touched share of a row up to which "export_compact" = 1 packs (see NOTES.md)
 #define LT_COMPACT_MAX_BYTES ((size_t)256 << 20)   // pinned staging beyond this: whole rows
+#define LT_EARLY_QUERY_EVERY 256              // looks at the ready word between two hipStreamQuery calls
+static inline int64_t lt_now_ns() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (int64_t)ts.tv_sec * 1000000000ll + ts.tv_nsec;
+}
+#ifdef LT_HOST_LAB
+#include <vector>
+static volatile uint32_t g_host_lab_sink;
+static int lt_host_lab_env(const char *name) { const char *e = getenv(name); return (e && *e) ? atoi(e) : 0; }
+#endif
+extern "C" int lt_host_landing_stats(const lt_baseline *b, int64_t *out4) {
+    LT_REQUIRE(b != nullptr, "lt_host_landing_stats: baseline is NULL");
+    LT_REQUIRE(out4 != nullptr, "lt_host_landing_stats: out is NULL");
+    out4[0] = b->stage_early; out4[1] = b->stage_late; out4[2] = b->stage_post_ns; out4[3] = b->stage_mismatch;
+    return LT_OK;
+}
 extern "C" int lt_influence_matrix_host(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
                                         const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode, float *out,
                                         int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
@@ -2499,16 +2521,16 @@ extern "C" int lt_influence_matrix_host(const lt_baseline *b, const int32_t *pro
         const int rc = lt_export_resolve(dst, &dev, "lt_influence_matrix_host", &host_dst);
         if (rc) return rc;
     }
-    const int ec = lt_tune().export_compact;
+    const int ec = lt_tune().export_compact, early = lt_tune().export_early;
     const size_t cells = (size_t)(n_probe > 0 ? n_probe : 0) * (size_t)(n_obs > 0 ? n_obs : 0);
-    const size_t ent_bytes = lt_align_up(cells * sizeof(uint2), 256);
-    const size_t need = ent_bytes + (size_t)(n_probe > 0 ? n_probe : 0) * sizeof(int32_t);
+    const size_t run_bytes = lt_align_up(cells * sizeof(uint32_t), 256);      // index run | value run | the ready word's line
+    const size_t need = 2 * run_bytes + 64;
     bool want = host_dst && mode == LT_MODE_DELTA && b->g->dl_meta != nullptr && n_obs <= 65534 && need <= LT_COMPACT_MAX_BYTES &&
                 (uint64_t)n_probe * (uint64_t)ldd <= 0xffffffffull &&
                 (ec == 2 || (ec == 1 && b->g->dl_touch_frac < LT_COMPACT_MAX_FRAC));
-    if (want && !b->stage_cur) {     // the two cursors, zero
-        if (hipMalloc((void **)&b->stage_cur, 2 * sizeof(int)) != hipSuccess ||
-            hipMemset(b->stage_cur, 0, 2 * sizeof(int)) != hipSuccess) {
+    if (want && !b->stage_cur) {     // the two cursors and the ticket, zero
+        if (hipMalloc((void **)&b->stage_cur, 4 * sizeof(int)) != hipSuccess ||
+            hipMemset(b->stage_cur, 0, 4 * sizeof(int)) != hipSuccess) {
             (void)hipGetLastError();
             (void)hipFree(b->stage_cur);
             b->stage_cur = nullptr;
@@ -2517,56 +2539,145 @@ extern "C" int lt_influence_matrix_host(const lt_baseline *b, const int32_t *pro
         b->stage_parity = 0;
     }
     if (want && b->stage_bytes < need) {
-        // (worst case: every pair touched; this call is synchronous, so nothing of an earlier one still writes the old block)
+        // (worst case: every pair touched; this call is synchronous, so nothing of an earlier one still writes the old block.)
+        // Coherent, said explicitly: the host reads the block while a kernel may still be running, and what the default means for
+        // that depends on the environment.  The device-side alias is asked once, here.
         if (b->stage_host) (void)hipHostFree(b->stage_host);
         b->stage_host = nullptr;
+        b->stage_dev = nullptr;
         b->stage_bytes = 0;
-        if (hipHostMalloc(&b->stage_host, need, hipHostMallocDefault) == hipSuccess) b->stage_bytes = need;
-        else { (void)hipGetLastError(); b->stage_host = nullptr; want = false; }
+        if (hipHostMalloc(&b->stage_host, need, hipHostMallocCoherent) == hipSuccess &&
+            hipHostGetDevicePointer(&b->stage_dev, b->stage_host, 0) == hipSuccess) b->stage_bytes = need;
+        else {
+            (void)hipGetLastError();
+            if (b->stage_host) (void)hipHostFree(b->stage_host);
+            b->stage_host = nullptr; b->stage_dev = nullptr; want = false;
+        }
     }
+    // (the block may be larger than this call needs: the ready word's line is its last one, wherever the runs end)
+    const size_t ready_off = b->stage_bytes >= 64 ? b->stage_bytes - 64 : 0;
+    char *const hs = static_cast<char *>(b->stage_host);
+    unsigned *const h_ready = want ? reinterpret_cast<unsigned *>(hs + ready_off) : nullptr;
     lt_compact_out cmp = {};
     if (want) {
-        char *d = nullptr;
-        if (hipHostGetDevicePointer((void **)&d, b->stage_host, 0) != hipSuccess) { (void)hipGetLastError(); want = false; }
-        else {
-            cmp.ent = reinterpret_cast<uint2 *>(d);
-            cmp.cnt = reinterpret_cast<int32_t *>(d + ent_bytes);
-            cmp.cur = b->stage_cur + b->stage_parity;
-            cmp.cur_next = b->stage_cur + (b->stage_parity ^ 1);
-            cmp.ld = (long)ldd;
-            cmp.cap = (long)cells;
-        }
+        char *d = static_cast<char *>(b->stage_dev);
+        cmp.idx = reinterpret_cast<uint32_t *>(d);
+        cmp.val = reinterpret_cast<float *>(d + run_bytes);
+        cmp.ready = reinterpret_cast<unsigned *>(d + ready_off);
+        cmp.cur = b->stage_cur + b->stage_parity;
+        cmp.cur_next = b->stage_cur + (b->stage_parity ^ 1);
+        cmp.tick = b->stage_cur + 2;
+        cmp.ld = (long)ldd;
+        cmp.cap = (long)cells;
+        // (nothing of an earlier call is in flight: a stale ready word cannot be taken for this call's)
+        __atomic_store_n(h_ready + 1, 0u, __ATOMIC_RELAXED);
+        __atomic_store_n(h_ready, 0u, __ATOMIC_RELEASE);
     }
     const int rc = influence_rows_impl(b, probe_nodes, n_probe, observe_nodes, n_obs, delta, mode, out, ldo, workspace,
                                        workspace_bytes, stream, nullptr, dev, ldd, want ? &cmp : nullptr);
     if (cmp.taken) b->stage_parity ^= 1;     // (the launches that used this cursor cleared the other one)
     if (rc) {
-        if (cmp.taken) {       // (launches already queued may still write the staging block; either cursor may be left dirty)
+        if (cmp.taken) {       // (launches already queued may still write the staging block; cursors and ticket may be left dirty)
             (void)hipStreamSynchronize(st);
-            (void)hipMemset(b->stage_cur, 0, 2 * sizeof(int));
+            (void)hipMemset(b->stage_cur, 0, 4 * sizeof(int));
         }
         return rc;
     }
-    if (cmp.taken) {        // np.zeros (attacker.py:216), here, while the GPU computes; the padding columns stay as they are
-        if (ldd == n_obs) memset(dst, 0, cells * sizeof(double));
-        else
-            for (int32_t i = 0; i < n_probe; ++i) memset(dst + (size_t)i * ldd, 0, (size_t)n_obs * sizeof(double));
+    if (!cmp.taken) {
+        LT_HIP(hipStreamSynchronize(st));
+        return LT_OK;
     }
-    LT_HIP(hipStreamSynchronize(st));
-    if (cmp.taken) {        // the run front to back: the values' own stores are the only scattered accesses
-        const char *h = static_cast<const char *>(b->stage_host);
-        const uint2 *ent = reinterpret_cast<const uint2 *>(h);
-        const int32_t *cnt = reinterpret_cast<const int32_t *>(h + ent_bytes);
-        size_t total = 0;
-        for (int32_t i = 0; i < n_probe; ++i) total += (size_t)std::min(std::max(cnt[i], 0), n_obs);
-        const uint64_t lim = (uint64_t)n_probe * (uint64_t)ldd;
-        for (size_t e = 0; e < total && e < cells; ++e) {
-            const uint2 x = ent[e];
-            float v;
-            memcpy(&v, &x.x, sizeof(float));
-            if (x.y < lim) dst[x.y] = (double)v;
+    // np.zeros (attacker.py:216), here, while the GPU computes; the padding columns stay as they are
+    if (ldd == n_obs) memset(dst, 0, cells * sizeof(double));
+    else
+        for (int32_t i = 0; i < n_probe; ++i) memset(dst + (size_t)i * ldd, 0, (size_t)n_obs * sizeof(double));
+    const uint32_t *idx = reinterpret_cast<const uint32_t *>(hs);
+    const float *val = reinterpret_cast<const float *>(hs + run_bytes);
+    const uint64_t lim = (uint64_t)n_probe * (uint64_t)ldd;
+    // The opportunistic look: bounded by the stream -- it leaves when the word is there OR the stream is no longer busy (done or
+    // failed), and never waits on GPU-written memory alone.  Not seen: nothing early happens, the call is the late form.
+    size_t seen = 0;        // entries of the run the early look walked
+    if (early >= 1 && cmp.chunks == 1) {
+        unsigned r = 0;
+        bool queried = false;
+        for (unsigned it = 1;; ++it) {
+            r = __atomic_load_n(h_ready, __ATOMIC_ACQUIRE);
+            if (r != 0u) break;
+            if ((it % LT_EARLY_QUERY_EVERY) == 0u) {
+                queried = true;
+                if (hipStreamQuery(st) != hipErrorNotReady) break;
+            }
+        }
+        if (queried) (void)hipGetLastError();      // (hipErrorNotReady is an answer, not an error to be found by a later check)
+        if (r != 0u && (size_t)(r - 1u) <= cells) {
+            seen = (size_t)(r - 1u);
+            if (early == 2) {
+                if (b->stage_copy_words < seen) {
+                    free(b->stage_copy);
+                    b->stage_copy = static_cast<uint32_t *>(malloc(std::max<size_t>(seen, 1) * sizeof(uint32_t)));
+                    b->stage_copy_words = b->stage_copy ? seen : 0;
+                }
+                if (b->stage_copy_words >= seen) memcpy(b->stage_copy, idx, seen * sizeof(uint32_t));
+            }
+            // one pass over the run: its lines come into this core's cache, and each destination line is asked for, for writing
+#ifdef LT_HOST_LAB
+            if (lt_host_lab_env("LT_HOST_LAB_NOPF")) {
+                uint32_t acc = 0;
+                for (size_t e = 0; e < seen; ++e) acc += idx[e];
+                g_host_lab_sink = acc;
+            } else
+#endif
+            for (size_t e = 0; e < seen; ++e) {
+                const uint32_t x = idx[e];
+                if (x < lim) __builtin_prefetch(dst + x, 1, 3);
+            }
         }
     }
+    LT_HIP(hipStreamSynchronize(st));
+#ifdef LT_HOST_LAB      // tools/host_lab/early_ab.py --forms: where the post-wait section's time goes (forms 1 and 2 are not the product)
+    {
+        const int form = lt_host_lab_env("LT_HOST_LAB_FORM");
+        const size_t tot = std::min<size_t>((size_t)__atomic_load_n(h_ready + 1, __ATOMIC_ACQUIRE), cells);
+        if (form == 1) {            // reading the run only: the sum of its words, no stores
+            const int64_t t1 = lt_now_ns();
+            uint32_t acc = 0;
+            for (size_t e = 0; e < tot; ++e) { uint32_t vb; memcpy(&vb, val + e, 4); acc += idx[e] + vb; }
+            g_host_lab_sink = acc;
+            b->stage_post_ns += lt_now_ns() - t1;
+            ++b->stage_late;
+            return LT_OK;
+        }
+        if (form == 2) {            // placing from a copy the host made itself: warm reads, the same stores
+            static std::vector<uint32_t> ci;
+            static std::vector<float> cv;
+            ci.assign(idx, idx + tot);
+            cv.assign(val, val + tot);
+            const int64_t t1 = lt_now_ns();
+            for (size_t e = 0; e < tot; ++e)
+                if (ci[e] < lim) dst[ci[e]] = (double)cv[e];
+            b->stage_post_ns += lt_now_ns() - t1;
+            ++b->stage_late;
+            return LT_OK;
+        }
+    }
+#endif
+    const int64_t t0 = lt_now_ns();
+    const unsigned r_end = __atomic_load_n(h_ready, __ATOMIC_ACQUIRE);
+    if (r_end == 0u) return lt_set_error(LT_ERR_HIP, "lt_influence_matrix_host: the packed run was not published");
+    const size_t total = std::min<size_t>((size_t)__atomic_load_n(h_ready + 1, __ATOMIC_RELAXED), cells);
+    for (size_t e = 0; e < total; ++e) {
+        const uint32_t x = idx[e];
+        if (x < lim) dst[x] = (double)val[e];
+    }
+    b->stage_post_ns += lt_now_ns() - t0;
+    if (seen > 0) {
+        ++b->stage_early;
+        if (early == 2) {       // the early look against the finished run: a word that differs was consumed before it was there
+            if (seen != total || b->stage_copy_words < seen) ++b->stage_mismatch;
+            else
+                for (size_t e = 0; e < seen; ++e) b->stage_mismatch += b->stage_copy[e] != idx[e];
+        }
+    } else ++b->stage_late;
     return LT_OK;
 }
 
@@ -2634,10 +2745,11 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
     const bool fused = delta64 && vec == nullptr && lt_tune().delta_fused != 0 && dg.ok && w.dl_rec != nullptr &&
                        !lt_fp64_agg_active(b) && !lt_fp64_on_demand(b, n_probe);
     // (lt_influence_matrix_host, packed form: the blocks never write dst64 -- no zero-filling waves, no widened rows, no export)
-    const bool compact = fused && cmp != nullptr && cmp->ent != nullptr;
+    const bool compact = fused && cmp != nullptr && cmp->idx != nullptr;
     if (compact) {
         dst64 = nullptr;
         cmp->taken = true;
+        cmp->chunks = (n_probe + w.chunk - 1) / w.chunk;
     }
     const bool use_marks = !fused && mode != LT_MODE_FULL && w.pm_cnt != nullptr &&
                            (w.bits == nullptr || (long long)(n_probe < w.chunk ? n_probe : w.chunk) * n_obs >= lt_tune().pair_marks);
@@ -2856,6 +2968,7 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
                         cj.dl_maxc = dg.maxc; cj.dl_rec_words = dg.rec_words; cj.observe = observe_nodes; cj.n_obs = n_obs;
                         cj.n = n; cj.err = node_err;
                         cj.smem_bytes = (unsigned)dg.record_smem;
+                        if (compact) lt_compact_job(cj, *cmp, p0);
                         bool rode = p0 == 0 && recs_rode;      // (chunk 0's records went along with the product rows' launch)
                         if (p0 == 0 && recs_rode) {
                             // (the next rows of lt_influence_rows_f64's matrix are zero-filled under this launch)
@@ -2867,10 +2980,22 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
                                 zj.zero_rows = (int)std::min<long long>(want, n_probe - cj0.zero_rows);
                                 zj.zero_blocks = cj0.zero_blocks; zj.zero_inflight = cj0.zero_inflight;
                             }
-                            int rc = lt_fp64_prepare_rows(b, nullptr, 0, nullptr, n_probe, st, zj.zero_blocks > 0 ? &zj : nullptr,
-                                                          zj.zero_blocks > 0 ? &z_rode : nullptr);
+                            // (packed host landing: the records rode WITHOUT their index half -- the blocks that carried them start
+                            // late in that launch, into the slots its rows leave, and every round trip added to them was added to
+                            // the launch: +6.8 us.  The index half goes first in this one.)
+                            if (compact) {
+                                zj.probes = probes; zj.nb = nb; zj.nblocks = (nb + LT_IDX_GROUP - 1) / LT_IDX_GROUP; zj.dl_rec = w.dl_rec; zj.dl_maxc = dg.maxc;
+                                zj.dl_rec_words = dg.rec_words; zj.n_obs = n_obs; zj.csend = 1;
+                                lt_compact_job(zj, *cmp, p0);
+                            }
+                            const bool zjob = zj.zero_blocks > 0 || zj.csend != 0;
+                            int rc = lt_fp64_prepare_rows(b, nullptr, 0, nullptr, n_probe, st, zjob ? &zj : nullptr, zjob ? &z_rode : nullptr);
                             if (rc) return rc;
                             if (z_rode) sparse_rows += zj.zero_rows;
+                            if (zj.csend != 0 && !z_rode) {      // (no launch to ride in: one of their own)
+                                hipLaunchKernelGGL(k_delta_records, dim3((unsigned)zj.nblocks), dim3(256), 0, st, zj);
+                                LT_CHECK_LAUNCH();
+                            }
                         } else if (p0 == 0) {
                             // (a launch's dynamic LDS is given to ALL its blocks: beyond 16 KB of node list the records get a launch
                             // of their own rather than cost the row blocks their occupancy)
@@ -2896,9 +3021,7 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
         hipLaunchKernelGGL((k_delta_probe_finish<LPR_, CP_, SX_, ZF_>), dim3((unsigned)nb), dim3(df_threads), dg.finish_smem, st,      \
                            b->Z1d, b->S1d, sxp, crp, b->S1qs, zxp, Hp, b->W2p, C, w.dl_rec, dg.rec_words, dg.maxc, g->dl_rec,        \
                            n_obs, delta, orow, (long)ldo, drow64, (long)ldd, sparse_rows - p0,                                     \
-                           compact ? cmp->ent : (uint2 *)nullptr, compact ? cmp->cnt + p0 : (int32_t *)nullptr,                    \
-                           compact ? cmp->cur : (int *)nullptr, compact ? cmp->cur_next : (int *)nullptr, (long)p0,                 \
-                           compact ? cmp->ld : 0L, compact ? cmp->cap : 0L)))
+                           compact ? cmp->val : (float *)nullptr, compact ? cmp->cap : 0L)))
                     double *const drow64 = (dst64 && exported_rows == p0) ? dst64 + (int64_t)p0 * ldd : (double *)nullptr;
                     if (drow64) exported_rows = p0 + nb;
                     if (sxp && zxp) { LT_DF_LAUNCH(true, true); }

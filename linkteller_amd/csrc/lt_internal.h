@@ -141,8 +141,15 @@ struct lt_baseline {
     // lt_influence_matrix_host, packed form: pinned staging of the touched values (lt_influence.hip), allocated on first use
     mutable void *stage_host = nullptr;
     mutable size_t stage_bytes = 0;
+    mutable void *stage_dev = nullptr;  // its device-side alias (asked once, when the block is allocated)
     mutable int *stage_cur = nullptr;   // device: the two cursors of the packed run (one per call, alternating; the other is cleared)
+                                        // and, in [2], the record blocks' ticket (0 between launches)
     mutable int stage_parity = 0;
+    // lt_host_landing_stats: packed calls that consumed the index run before the stream wait / after it, the nanoseconds spent
+    // behind the wait, and ("export_early" = 2) index words that differed between the early look and the finished run
+    mutable int64_t stage_early = 0, stage_late = 0, stage_post_ns = 0, stage_mismatch = 0;
+    mutable uint32_t *stage_copy = nullptr;   // "export_early" = 2: the indices as the early look saw them
+    mutable size_t stage_copy_words = 0;
 };
 
 int lt_set_error(int code, const char *fmt, ...);
@@ -204,6 +211,10 @@ struct lt_tuning {
     int export_zero_inflight;    // stores each of them keeps in flight (LT_EXPORT_ZERO_INFLIGHT)
     int export_compact;          // lt_influence_matrix_host, fused route: 1 packed touched values when the graph is sparse enough,
                                  // 0 never, 2 always (LT_EXPORT_COMPACT)
+    int export_early;            // ... packed, single-chunk calls: 1 the host looks for the index run the GPU publishes early and warms it
+                                 // before the stream wait, 0 everything after the wait (default: the look costs the step more than it
+                                 // saves behind the wait, profiles/host_early_ab.txt), 2 as 1 and the early look is compared with the
+                                 // finished run (LT_EXPORT_EARLY)
     int feature_stagger;         // the row-per-wave kernel's blocks start in (value & 255) groups, (value >> 8) ticks of 10 ns apart; 0 = together
                                  // (LT_FEATURE_STAGGER)
     int feature_ring_min_rows;   // (LT_FEATURE_RING_MIN_ROWS, default 1024: below it the CUs' waves have no row each)
@@ -329,6 +340,18 @@ struct lt_bits_job {
     long zero_ld;
     int zero_row0, zero_rows, zero_cols, zero_blocks, zero_inflight;
     unsigned smem_bytes;    // dynamic LDS the job's blocks need (the launch that carries them must be given it)
+    // cidx != NULL (lt_influence_matrix_host, packed form; record jobs only): each block claims its stretch of the call's run off
+    // *ccur, leaves the base in its table row's header and sends the indices (crow0 + b) * cld + j of its touched positions to
+    // cidx[base ...] (pinned host memory, ccap words); block 0 clears *ccur_next; the block that draws the last of the job's nblocks
+    // tickets (*ctick) stores the run's length so far to cready[1] and that + 1 to cready[0] (pinned), and clears the ticket
+    // csend: the table rows are there already (the record blocks rode in an earlier launch of the step): the job's blocks do the
+    // claiming and sending alone, a wave per LT_IDX_GROUP probes (delta_index_group; uses dl_rec / dl_rec_words / dl_maxc / n_obs / nb;
+    // nblocks = the groups)
+    uint32_t *cidx;
+    int csend;
+    int *ccur, *ccur_next, *ctick;
+    unsigned *cready;
+    long crow0, cld, ccap;
 };
 // job != NULL: *job_done says whether the job went along (it does when every row is formed by one plain launch; the on-demand
 // form needs the tables BEFORE, the caller then launches k_item_bits itself and calls again without a job)

@@ -169,12 +169,73 @@ static __global__ __launch_bounds__(256) void k_item_bits(const int32_t *__restr
 // node among the probe's touched nodes (a binary search in LDS), and where are its entries -- and writes what the finish
 // kernel needs as one small table row (probes -> meta -> record -> search: dependent round trips and LDS passes the finish
 // kernel then does not make; a kernel starts with cold caches, a trip is ~ 2 us):
-//     [0] items  [1] short | long << 16 touched POSITIONS  [2] v  [3] offset of the node's entries in dl_rec
+//     [0] items | v << 16  [1] short | long << 16 touched POSITIONS  [2] base of the probe's stretch of the packed run (lt_influence_matrix_host;
+//     else 0)  [3] offset of the node's entries in dl_rec
 //     | items [maxc, the unused slots repeat the first] | touched positions (j, start | count << 16) [n_obs]: those of up to 4 entries from
 //     the front, the longer ones (row v itself holds ALL of R_v) from the back, in no particular order
 // Nothing here reads a layer, so these blocks ride in the launch that forms the pre-activation (k_spmm_f64), which hides them.
 struct lt_df_inc { float a; int ik; };      // A_hat[u, r] and (item << 16 | entry position in row u)
 static inline __host__ __device__ int lt_dl_rec_words(int maxc, int n_obs) { return (4 + 2 * maxc + 2 * n_obs + 3) & ~3; }
+// Publication of the index run: the ticket hand-off of fd_slab_block (lt_fp64.hip), towards the host.  Called by ONE thread of a job
+// block once every wave of the block has drained its index stores.  Fences of the HIP memory model at system scope are not an
+// option in a launch that streams rows through the L2: each writes the whole L2 back (the product rows' launch went from 22 to
+// 76 us with them; profiles/host_early_ab.txt).
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "this hand-off is written against gfx950's memory system (sc0 sc1 write-through stores, vmcnt counting stores): on another target fence at system scope around the ticket and give the ready word __ATOMIC_RELEASE"
+#endif
+// Memory-order argument (as fd_slab_block's, first table row of MI355X_MICROARCH.md "Valid forms"; the reader is the host):
+//  (1) every index is stored `sc0 sc1` (a system-scope atomic store) into fine-grained host memory: written through, no L2 copy
+//      left behind that the word could overtake;
+//  (2) each storing wave drains ITS stores (s_waitcnt vmcnt(0): acknowledged by the memory system, not just gone from the wave);
+//  (3) a block of several waves puts a workgroup barrier between every wave's drain and the ticket; the claim on the cursor had
+//      returned before the indices were stored;
+//  (4) the ticket is an agent-scope atomic whose RETURNED value names the job's last block: every other block's indices and claims
+//      were complete before its own ticket, hence before this one;
+//  (5) that block reads the run's length off the cursor (past the L2: an agent-scope load), stores it, drains, and only then
+//      stores the ready word, `sc0 sc1` again.  The host loads the word with acquire semantics and reads the indices behind it.
+// The ticket goes back to 0 for the next launch (stream order separates the launches).
+static __device__ __forceinline__ void delta_index_publish(const lt_bits_job &J) {
+    if (__hip_atomic_fetch_add(J.ctick, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != J.nblocks - 1) return;
+    const int total = __hip_atomic_load(J.ccur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(J.ctick, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(J.cready + 1, (unsigned)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store(J.cready, (unsigned)total + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// ---- lt_influence_matrix_host, packed form: the INDEX half of a probe's entries ---------------------------------------------------
+// An entry of the packed run is (index into the host matrix, fp32 value).  The index of entry k of probe b is known as soon as its
+// table row is: entry k is the k-th touched position of the row in the finish kernel's numbering (the short ones from the front,
+// long position s at k = n_short + s from the back).  So whoever has the row -- the record block itself, here (it still owes the row
+// its header: hxw = words 0 and 3), or a wave of a later launch (delta_index_group, below) -- claims the probe's stretch of the
+// call's run off the cursor (one returning add, in a launch where nothing waits for it), leaves the base in header word 2, where
+// the finish kernel's first round trip finds it, and sends the indices to the pinned run while the link carries nothing else; the
+// finish kernel sends 4 bytes per value.  Block 0 clears the other cursor for the next call.
+static __device__ __forceinline__ void delta_index_send(const int b, const lt_bits_job &J, int32_t *R, const int n_short, const int n_long,
+                                                        const int2 hxw) {
+    __shared__ int s_cbase;
+    constexpr int NT = 256;
+    const int tid = threadIdx.x, n_touched = n_short + n_long;
+    const int2 *gtp = reinterpret_cast<const int2 *>(R + 4 + 2 * J.dl_maxc);
+    auto pos_of = [&](int k) { return k < n_short ? gtp[k].x : gtp[J.n_obs - 1 - (k - n_short)].x; };
+    // (the first positions are asked for while thread 0's add is under way: one round trip for both)
+    const int j_first = tid < n_touched ? pos_of(tid) : 0;
+    if (tid == 0) {
+        const int cbase = atomicAdd(J.ccur, n_touched);
+        if (b == 0) *J.ccur_next = 0;
+        s_cbase = cbase;
+        *reinterpret_cast<int4 *>(R) = make_int4(hxw.x, n_short | (n_long << 16), cbase, hxw.y);
+    }
+    __syncthreads();
+    const long cbase = s_cbase;
+    const unsigned row_idx = (unsigned)((J.crow0 + b) * J.cld);
+    for (int k = tid; k < n_touched; k += NT) {
+        const int j = k == tid ? j_first : pos_of(k);
+        if (cbase + k < J.ccap) __hip_atomic_store(J.cidx + cbase + k, row_idx + (unsigned)j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (2)
+    __syncthreads();                                        // (3)
+    if (tid == 0) delta_index_publish(J);
+}
 static __device__ __forceinline__ void delta_record_block(const int b, const lt_bits_job &J, unsigned char *smem) {
     int2 *sL = reinterpret_cast<int2 *>(smem);                  // [lcap] the probe's touched nodes (u, start | count << 16), u ascending
     __shared__ int32_t s_ntp, s_nlp;
@@ -224,11 +285,78 @@ static __device__ __forceinline__ void delta_record_block(const int b, const lt_
         }
     }
     __syncthreads();
-    if (tid == 0) *reinterpret_cast<int4 *>(R) = make_int4(cnt, s_ntp | (s_nlp << 16), v, m.x + 2 * (cnt + Tu));
+    const int n_short = s_ntp, n_long = s_nlp;
+    if (J.cidx == nullptr) {
+        if (tid == 0) *reinterpret_cast<int4 *>(R) = make_int4(cnt | (int)((unsigned)v << 16), n_short | (n_long << 16), 0, m.x + 2 * (cnt + Tu));
+        return;
+    }
+    delta_index_send(b, J, R, n_short, n_long, make_int2(cnt | (int)((unsigned)v << 16), m.x + 2 * (cnt + Tu)));
+}
+// The index half alone, for table rows that are already there (lt_bits_job::csend: the record blocks rode in an earlier launch
+// of the step, whose tail they would have lengthened).  ONE wave per LT_IDX_GROUP probes, the block's other waves leave at once:
+// host writes queued for the link hold up the loads of the kernels beside them (see zero_rows_wave), and a block per probe -- 500
+// bursts at once -- cost the carrying launch 8 us wherever it sat.  Here a wave claims the stretches of its probes with one add
+// (a scan over their lengths), has the first 64 positions of all of them in flight together, and keeps a bounded number of stores
+// in flight.
+#define LT_IDX_GROUP 16
+static __device__ __forceinline__ void delta_index_group(const int g, const lt_bits_job &J) {
+    constexpr int G = LT_IDX_GROUP;
+    if (threadIdx.x >= 64) return;
+    const int lane = threadIdx.x;
+    const int p_l = g * G + (lane & (G - 1));
+    const bool own = lane < G && p_l < J.nb;
+    const int hy = p_l < J.nb ? J.dl_rec[(size_t)p_l * J.dl_rec_words + 1] : 0;
+    const int n_l = own ? (hy & 0xffff) + (int)((unsigned)hy >> 16) : 0;
+    int incl = n_l;
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) {
+        const int t = __shfl_up(incl, m, 64);
+        if (lane >= m) incl += t;
+    }
+    const int tot = __shfl(incl, G - 1, 64);
+    int gbase = 0;
+    if (lane == 0) {
+        gbase = atomicAdd(J.ccur, tot);
+        if (g == 0) *J.ccur_next = 0;
+    }
+    gbase = __shfl(gbase, 0, 64);
+    const int base_l = gbase + incl - n_l;
+    if (own) J.dl_rec[(size_t)p_l * J.dl_rec_words + 2] = base_l;       // (header word 2: the finish kernel's first round trip)
+    int jv[G];
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+        const int p = min(g * G + q, J.nb - 1);
+        const int hq = __shfl(hy, q, 64);
+        const int ns = hq & 0xffff, nt = g * G + q < J.nb ? ns + (int)((unsigned)hq >> 16) : 0;
+        const int2 *gtp = reinterpret_cast<const int2 *>(J.dl_rec + (size_t)p * J.dl_rec_words + 4 + 2 * J.dl_maxc);
+        jv[q] = lane < nt ? (lane < ns ? gtp[lane].x : gtp[J.n_obs - 1 - (lane - ns)].x) : 0;
+    }
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+        const int p = g * G + q;
+        const int hq = __shfl(hy, q, 64);
+        const long bq = __shfl(base_l, q, 64);
+        const int ns = hq & 0xffff, nt = p < J.nb ? ns + (int)((unsigned)hq >> 16) : 0;
+        const unsigned row_idx = (unsigned)((J.crow0 + p) * J.cld);
+        if (lane < nt && bq + lane < J.ccap)
+            __hip_atomic_store(J.cidx + bq + lane, row_idx + (unsigned)jv[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        asm volatile("s_waitcnt vmcnt(3)" ::: "memory");          // (at most 4 stores of this wave on their way)
+        if (nt > 64) {       // (wave-uniform; a probe that touches more than 64 positions: the rest, a trip each)
+            const int2 *gtp = reinterpret_cast<const int2 *>(J.dl_rec + (size_t)p * J.dl_rec_words + 4 + 2 * J.dl_maxc);
+            for (int k = lane + 64; k < nt; k += 64) {
+                const int j = k < ns ? gtp[k].x : gtp[J.n_obs - 1 - (k - ns)].x;
+                if (bq + k < J.ccap) __hip_atomic_store(J.cidx + bq + k, row_idx + (unsigned)j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (2) of delta_index_publish's argument; one wave: no barrier
+    if (lane == 0) delta_index_publish(J);
 }
 static __global__ __launch_bounds__(256) void k_delta_records(const lt_bits_job job) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dr_smem[];
-    delta_record_block((int)blockIdx.x, job, dr_smem);
+    if (job.csend) delta_index_group((int)blockIdx.x, job);
+    else delta_record_block((int)blockIdx.x, job, dr_smem);
 }
 // the same block as part of another launch (256 threads per block)
 // lt_bits_job::zero_*: wave `w` of zero_blocks fills rows zero_row0 + w, + zero_blocks, ... of the caller's float64 matrix (pinned
@@ -254,7 +382,8 @@ static __device__ __forceinline__ void zero_rows_wave(const lt_bits_job &j, cons
 
 static __device__ __forceinline__ void item_bits_block(const int bid, const lt_bits_job &j, unsigned char *smem = nullptr) {
     if (j.dl_rec != nullptr) {      // (`smem`: the launch's dynamic LDS, j.smem_bytes)
-        delta_record_block(bid, j, smem);
+        if (j.csend) delta_index_group(bid, j);
+        else delta_record_block(bid, j, smem);
         return;
     }
     item_bits_block(bid, j.tptr, j.trow, j.probes, j.nb, j.words, j.bits, j.off, j.item_pr, j.big_bits, j.big_slot, j.big_count, j.rowptr,

@@ -312,6 +312,13 @@ class Baseline:
             node_check()
         return host.numpy()
 
+    def host_landing_stats(self) -> dict:
+        """The packed ``influence_matrix_host`` calls on this baseline so far (lt_host_landing_stats): how many consumed the
+        index run before the stream wait (``early``) / after it (``late``), the nanoseconds spent behind the wait
+        (``post_ns``), and the index words an ``export_early`` = 2 look saw differently from the finished run (``mismatch``)."""
+        o = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().lt_host_landing_stats(self._h, o), "lt_host_landing_stats")
+        return {"early": int(o[0]), "late": int(o[1]), "post_ns": int(o[2]), "mismatch": int(o[3])}
 
     def influence_rows_vec(self, probes: torch.Tensor, obs: torch.Tensor, delta: float, m: int, out: torch.Tensor,
                            vec: torch.Tensor) -> torch.Tensor:
