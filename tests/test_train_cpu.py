@@ -35,6 +35,102 @@ def test_dropout_mask_counter_layout(h):
     assert not T.dropout_keep(n, h, epoch, seed, 1.0).any()
 
 
+def _autograd(adj, x, y, params, keep, scale, dtype):
+    """The form of test_train_gpu._autograd, with the forward values returned as well."""
+    import torch.nn.functional as F
+    coo = adj.tocoo()
+    a = torch.sparse_coo_tensor(np.vstack([coo.row, coo.col]), coo.data.astype(np.float64), adj.shape).to(dtype).coalesce()
+    ps = [torch.from_numpy(np.asarray(p, dtype=np.float64)).to(dtype).requires_grad_() for p in params]
+    w1, b1, w2, b2 = ps
+    xt = torch.from_numpy(x).to(dtype)
+    z1 = torch.sparse.mm(a, xt @ w1) + b1
+    h = torch.relu(z1) * torch.from_numpy(keep.astype(np.float64) * float(scale)).to(dtype)
+    z = torch.sparse.mm(a, h @ w2) + b2
+    loss = F.cross_entropy(z, torch.from_numpy(y))
+    loss.backward()
+    return dict(Z1=z1.detach().numpy(), Z2=z.detach().numpy(), loss=float(loss.detach()),
+                **{k: p.grad.numpy() for k, p in zip(("dW1", "db1", "dW2", "db2"), ps)})
+
+
+@pytest.mark.parametrize("name", ["B", "D"])
+def test_epoch_reference_against_autograd(name):
+    """The written-out fp64 epoch (train_restate.epoch_reference) against torch's fp64 autograd: 1e-12 of each tensor's
+    largest magnitude.  B has dropout, three classes and a symmetric graph; D a directed weighted graph with empty rows and
+    columns, where A^T is not A."""
+    import train_cases as K
+    torch.set_num_threads(1)
+    case = K.make(name)
+    keep = T.dropout_keep(case["n"], case["H"], 0, K.SEED, case["p"])
+    scale = T.dropout_scale(case["p"])
+    got = T.epoch_reference(case["adj"], case["x"], case["y"], case["params"], keep, scale, np.float64)
+    ref = _autograd(case["adj"], case["x"], case["y"], case["params"], keep, scale, torch.float64)
+    for k in ("Z1", "Z2", "dW1", "db1", "dW2", "db2"):
+        err, top = np.abs(got[k] - ref[k]).max(), np.abs(ref[k]).max()
+        assert got[k].dtype == np.float64 and top > 0 and err <= 1e-12 * top, (k, err, top)
+    assert abs(got["loss"] - ref["loss"]) <= 1e-12 * abs(ref["loss"])
+    assert np.array_equal(got["argmax"], ref["Z2"].argmax(axis=1))
+    if name == "D":
+        a = case["adj"]
+        assert (np.diff(a.indptr) == 0).any() and (np.diff(a.tocsc().indptr) == 0).any() and (a != a.T).nnz > 0
+
+
+def test_epoch_reference_relu_argument_and_extremes():
+    """relu_on reaches dW1 and db1 only, and only the columns it changes; a single class gives a zero loss and zero
+    gradients; p = 1 gives zero dW1, db1, dW2 and logits equal to b2."""
+    import train_cases as K
+    case = K.make("F")
+    keep = T.dropout_keep(case["n"], case["H"], 0, K.SEED, case["p"])
+    args = (case["adj"], case["x"], case["y"], case["params"], keep, T.dropout_scale(case["p"]), np.float64)
+    base = T.epoch_reference(*args)
+    on = base["Z1"] > 0
+    flip = on.copy()
+    r, h = np.argwhere(keep)[0]
+    flip[r, h] = ~flip[r, h]
+    other = T.epoch_reference(*args, relu_on=flip)
+    for k in ("Z1", "Z2", "dW2", "db2"):
+        assert np.array_equal(base[k], other[k])
+    cols = np.arange(case["H"]) != h
+    assert np.array_equal(base["dW1"][:, cols], other["dW1"][:, cols]) and np.array_equal(base["db1"][cols], other["db1"][cols])
+    assert base["db1"][h] != other["db1"][h] and not np.array_equal(base["dW1"][:, h], other["dW1"][:, h])
+    assert np.array_equal(T.epoch_reference(*args, relu_on=on)["dW1"], base["dW1"])
+    c = K.make("C")
+    keep = T.dropout_keep(c["n"], c["H"], 0, K.SEED, c["p"])
+    one = T.epoch_reference(c["adj"], c["x"], c["y"], c["params"], keep, T.dropout_scale(c["p"]), np.float64)
+    assert one["loss"] == 0 and all(not one[k].any() for k in K.NAMES) and np.abs(one["Z2"]).max() > 0
+    e = K.make("E")
+    none = T.epoch_reference(e["adj"], e["x"], e["y"], e["params"], np.zeros((e["n"], e["H"]), bool), T.dropout_scale(1.0),
+                             np.float64)
+    assert all(not none[k].any() for k in ("dW1", "db1", "dW2")) and np.abs(none["db2"]).max() > 0
+    assert np.array_equal(none["Z2"], np.broadcast_to(e["params"][3].astype(np.float64), none["Z2"].shape))
+
+
+@pytest.mark.parametrize("name", ["A", "B", "C", "D", "E", "F", "T"])
+def test_backward_case_conditions(name):
+    """What test_train_backward_gpu.py relies on, at the initial parameters: hidden columns with near-kink elements (kept
+    pre-activations within tau = 8 max|Z1_fp32 - Z1_fp64| of 0) are at most 1/8 of H, rows with a top-2 logit margin below
+    1e-4 at most 1 % of n; and what each case is there to reach is really in it."""
+    import train_cases as K
+    from linkteller_amd import graph
+    case = K.make(name)
+    n, f, h, c, p, _ = K.SHAPES[name]
+    assert case["x"].shape == (n, f) and case["params"][0].shape == (f, h) and case["params"][2].shape == (h, c)
+    assert int(case["y"].max()) == c - 1 and p == case["p"]
+    an = K.analyse(case, case["params"], 0)
+    K.check_conditions(case, an)
+    assert an["r32"]["Z1"].dtype == np.float32 and an["r32"]["dW1"].dtype == np.float32
+    assert an["tau"] > 0 or p == 1.0
+    rows = np.diff(case["adj"].indptr)
+    if name == "A":
+        assert rows.max() > 128 and np.diff(case["adj"].tocsc().indptr).max() > 128     # hub rows and hub columns
+    if name == "D":
+        assert rows.min() == 0 and np.diff(case["adj"].tocsc().indptr).min() == 0
+    if name in ("B", "E"):
+        assert h % 4 and f % 4 == 1
+    if name in ("A", "B", "T"):
+        assert np.array_equal(graph.csr_arrays(case["adj"])[3], case["adj"].data)       # the reference reads the device's values
+        assert not np.array_equal(an["keep"], T.dropout_keep(n, h, 1, K.SEED, p))
+
+
 def _ulps(a, b):
     ia = np.asarray(a, dtype=np.float32).view(np.int32).astype(np.int64)
     ib = np.asarray(b, dtype=np.float32).view(np.int32).astype(np.int64)

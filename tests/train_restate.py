@@ -1,5 +1,6 @@
 """numpy restatements of the training kernels' bit-level contracts (include/linkteller_hip.h, lt_train.hip): the
-Philox4x32-10 dropout mask and the fp32 Adam op order.  Shared by test_train_cpu.py and test_train_gpu.py."""
+Philox4x32-10 dropout mask and the fp32 Adam op order; and one whole epoch written out in numpy / scipy (epoch_reference), the
+high-precision reference of test_train_backward_gpu.py.  Shared by test_train_cpu.py and the GPU training tests."""
 import numpy as np
 
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
@@ -35,6 +36,58 @@ def dropout_keep(n, h, epoch, seed, p):
 
 def dropout_scale(p):
     return np.float32(1.0 / (1.0 - p)) if p < 1 else np.float32(0)
+
+
+def epoch_reference(adj, x, y, params, keep, scale, dtype=np.float64, relu_on=None):
+    """One epoch of the trainer's contract (include/linkteller_hip.h) up to the gradients, written out in numpy / scipy
+    in ``dtype`` with no autograd:
+        S1 = X W1; Z1 = A S1 + b1; H1d = keep * scale * relu(Z1); Z2 = A (H1d W2) + b2
+        loss = mean_r (logsumexp(Z2[r]) - Z2[r, y[r]]); dZ2 = (softmax(Z2) - onehot(y)) / n; dS2 = A^T dZ2
+        dW2 = H1d^T dS2; db2 = sum_r dZ2; dZ1 = relu_on * keep * scale * (dS2 W2^T); db1 = sum_r dZ1; dW1 = X^T (A^T dZ1)
+    ``keep`` is the dropout mask (bool [n, H]), ``scale`` its 1 / (1 - p).  ``relu_on`` (bool [n, H]) is the derivative of the
+    ReLU; None takes Z1 > 0 in ``dtype``.  Passing it lets a caller evaluate the gradients with chosen elements switched
+    off or on (the forward values do not depend on it).  Returns a dict: Z1, Z2, loss (a Python float), argmax (first
+    maximum of each row), dW1, db1, dW2, db2 -- arrays in ``dtype``."""
+    a = adj.tocsr().astype(dtype)
+    at = a.T.tocsr()
+    x = np.asarray(x).astype(dtype)
+    w1, b1, w2, b2 = (np.asarray(p).astype(dtype) for p in params)
+    y = np.asarray(y).astype(np.int64).reshape(-1)
+    n = x.shape[0]
+    rows = np.arange(n)
+    z1 = a @ (x @ w1) + b1
+    drop = np.asarray(keep).astype(dtype) * dtype(scale)
+    h1d = np.maximum(z1, dtype(0)) * drop
+    z2 = a @ (h1d @ w2) + b2
+    mx = z2.max(axis=1, keepdims=True)
+    e = np.exp(z2 - mx)
+    s = e.sum(axis=1, keepdims=True)
+    loss = ((mx[:, 0] + np.log(s[:, 0])) - z2[rows, y]).sum(dtype=dtype) / dtype(n)
+    dz2 = e / s
+    dz2[rows, y] -= dtype(1)
+    dz2 = dz2 / dtype(n)
+    ds2 = at @ dz2
+    on = (z1 > 0) if relu_on is None else np.asarray(relu_on, dtype=bool)
+    dz1 = (ds2 @ w2.T) * drop * on.astype(dtype)
+    return dict(Z1=z1, Z2=z2, loss=float(loss), argmax=z2.argmax(axis=1), dW1=x.T @ (at @ dz1), db1=dz1.sum(axis=0),
+                dW2=h1d.T @ ds2, db2=dz2.sum(axis=0))
+
+
+def near_kink(z1_64, z1_32, keep):
+    """(tau, bool [n, H]): the kept pre-activations within tau = 8 max|Z1_fp32 - Z1_fp64| of the ReLU's kink.  An fp32
+    evaluation whose error is within twice the fp32 reference's may put such an element on the other side (a flip needs an
+    error of at least |z|; 8 is a 4x margin over that), and then its derivative legitimately differs from the fp64 one."""
+    tau = 8.0 * float(np.abs(np.asarray(z1_32, dtype=np.float64) - z1_64).max())
+    return tau, np.asarray(keep, dtype=bool) & (np.abs(z1_64) <= tau)
+
+
+def fragile_rows(z2, tiny=1e-4):
+    """Rows whose top-2 logit margin is below ``tiny``: their argmax may differ between two roundings (the convention of
+    golden/generate_train.py).  A single class has no second logit and no fragile row."""
+    if z2.shape[1] < 2:
+        return 0
+    top = np.sort(z2, axis=1)
+    return int((np.abs(top[:, -1] - top[:, -2]) < tiny).sum())
 
 
 def fma32(a, b, c):
