@@ -305,6 +305,31 @@ int lt_influence_rows(const lt_baseline *b, const int32_t *probe_nodes, int32_t 
  *   - by the next lt_influence_rows / _vec / lt_influence3_rows* call that finds it set: LT_ERR_INDEX, nothing enqueued. */
 int lt_node_check(int32_t *bad_probe, int32_t *bad_observe);
 
+/* ---- the probe primitive over a LIST of pairs -------------------------------------------------------------------------
+ * Stands in for Attacker.get_gradient_eps + the loops of link_prediction_attack (attacker.py:89-97, 143-163) and for the
+ * per-node partner lists of link_prediction_attack_efficient_balanced (attacker.py:250-284): callers that read a few dozen
+ * pairs per probe, not a rectangle.  Pairs are grouped by probe: probe i = probe_nodes[i] owns
+ * pair_obs[pair_ptr[i] .. pair_ptr[i + 1]), and
+ *   out[k] = || (f(X + delta * e_v x_v^T) - f(X))[u] ||_2 / delta,   v = the probe that owns k, u = pair_obs[k]
+ * -- the value lt_influence_rows writes at (v, u) for the same mode, bit for bit.  A probe may own no pair, probes may
+ * repeat, u == v is allowed, a pair may be listed twice.  probe_nodes / pair_obs / out are device pointers; out holds n_pairs
+ * floats.  pair_ptr is a HOST array of n_probe + 1 offsets: the call reads it while it runs -- it is validated before anything
+ * is launched (pair_ptr[0] == 0, non-decreasing, pair_ptr[n_probe] == n_pairs, not NULL unless n_pairs == 0: LT_ERR_INVALID)
+ * and gives every probe chunk its range of pairs by value -- and sends it to the device with one stream-ordered copy: pageable
+ * memory may be released when the call returns, pinned memory once the stream has passed that copy.
+ * Everything else follows lt_influence_rows: enqueue only; node ids checked on the device (LT_ERR_INDEX / lt_node_check;
+ * bad_observe covers pair_obs); probes chunked by "chunk_budget_bytes".  The workspace holds the item tables of one probe
+ * chunk, the checked lists and the offsets -- nothing of the size of n_probe x (nodes observed) -- and out is sized by the list.
+ * Modes: LT_MODE_DELTA as in lt_influence_rows (the fp64 kink test with lt_baseline_enable_fp64 on); LT_MODE_SPARSE;
+ * LT_MODE_FULL is accepted and EVALUATED AS LT_MODE_SPARSE -- the two are bit-identical (see above), and a pair list has no use
+ * for FULL's all-rows stage A.  n_pairs == 0 or n_probe == 0: LT_OK, nothing launched.  At most 2^31 - 65537 pairs per call.
+ * The 2-layer lt_baseline only (H <= 256, C <= 8). */
+size_t lt_influence_pairs_workspace_bytes(const lt_baseline *b, int32_t n_probe, int64_t n_pairs, int32_t mode);
+int lt_influence_pairs(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
+                       const int64_t *pair_ptr, const int32_t *pair_obs, int64_t n_pairs,
+                       float delta, int32_t mode, float *out, void *workspace, size_t workspace_bytes,
+                       void *stream);
+
 /* ---- the finished rows, once, as float64 ------------------------------------------------------------------------------
  * Stands in for influence_val = np.zeros((n_test, n_test)) (float64, attacker.py:216) and the n_test^2 `.norm().item()` host
  * round trips that fill it (attacker.py:227-229): dst[i * ldd + j] = (double)src[i * lds + j] by one launch.  src: device

@@ -63,6 +63,9 @@ SIGNATURES = {
     "lt_influence_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "lt_influence_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
                                     C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lt_influence_pairs_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32]),
+    "lt_influence_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
+                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "lt_graph_reached_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lt_baseline_form_rows_fp64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "lt_baseline_gather_rows_fp64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -275,6 +275,70 @@ class Attacker:
         out_p = engine.gcn2_forward(base.graph, xp, w1, b1, w2, b2)
         return (out_p - base.logits()) / delta
 
+    def get_gradient_eps(self, u, v):
+        """attacker.py:89-97: row u of ``get_gradient_eps_mat(v)`` (API parity; the naive attack scores its pairs through
+        ``pair_scores``)."""
+        return self.get_gradient_eps_mat(v)[u]
+
+    def pair_scores(self, probe, observed, mode=None, chunk=1024) -> np.ndarray:
+        """||grad_mat(probe[k])[observed[k]]||_2 for a LIST of pairs, float64 [n_pairs] on the host in input order.  A 2-layer
+        model served by ``engine.Baseline`` goes through ``lt_influence_pairs``: the pairs grouped by probe
+        (``engine.group_pairs``), one call, ONE device-to-host copy of n_pairs floats.  Every other model the attacker accepts
+        (GCN3, ``engine.WideBaseline``, generic stacks) takes ``_rows`` on ``chunk`` probes x the distinct observed nodes of
+        their pairs and gathers -- the same values, through a rectangle."""
+        probe = np.asarray(probe, dtype=np.int64).reshape(-1)
+        observed = np.asarray(observed, dtype=np.int64).reshape(-1)
+        if probe.shape != observed.shape:
+            raise ValueError(f"probe and observed differ in length: {probe.size} / {observed.size}")
+        n = int(self.features.shape[0])
+        for ids, what in ((probe, "probe"), (observed, "observed")):      # (features[v] / grad[u] raise it in the reference)
+            if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= n):
+                raise IndexError(f"{what}: node id out of range for {n} nodes")
+        scores = np.empty(probe.size, dtype=np.float64)
+        if probe.size == 0:
+            return scores
+        nodes, ptr, obs, order = engine.group_pairs(probe, observed)
+        kind, sd = self._walk()
+        if kind == "gcn2" and self.features.is_cuda:
+            m = self._mode(mode)
+            base = self.baseline(m, sd)
+            if isinstance(base, engine.Baseline):
+                out = base.influence_pairs(nodes, ptr, obs, float(self.args.influence), m)
+                scores[order] = out.cpu().numpy()
+                engine.node_check()
+                return scores
+        for c0 in range(0, len(nodes), chunk):
+            pc = nodes[c0:c0 + chunk]
+            k0, k1 = int(ptr[c0]), int(ptr[c0 + len(pc)])
+            cols, inv = np.unique(obs[k0:k1], return_inverse=True)
+            rows = self._rows(pc.astype(np.int64), cols.astype(np.int64), mode).cpu().numpy().astype(np.float64)
+            ridx = np.repeat(np.arange(len(pc)), np.diff(ptr[c0:c0 + len(pc) + 1]))
+            scores[order[k0:k1]] = rows[ridx, inv.reshape(-1)]
+        return scores
+
+    def naive_result_filename(self):
+        """attacker.py:181-184: the naive attack's file carries no attack-mode prefix."""
+        a = self.args
+        folder = f"eval_{self.dataset}"
+        if a.mode == "vanilla-clean":
+            return osp.join(folder, f"{a.sample_type}_{a.n_test}_{a.sample_seed}.pt")
+        return osp.join(folder, f"{a.sample_type}_{a.perturb_type}_{a.n_test}_{a.sample_seed}"
+                                f"_eps-{a.epsilon}_seed-{a.noise_seed}.pt")
+
+    def link_prediction_attack(self):
+        """The naive attack (``--attack-mode naive``, attacker.py:143-201): every sampled (u, v) is scored by perturbing v and
+        reading ||grad[u]|| -- the existing pairs, then the non-existing ones, one ``pair_scores`` call each (the reference's
+        two timed loops of two full forwards per pair), its prints and its result file."""
+        t = time.time()
+        ex = np.asarray(self.exist_edges, dtype=np.int64).reshape(-1, 2)
+        norm_exist = list(self.pair_scores(ex[:, 1], ex[:, 0]))
+        print(f"time for predicting existing edges: {time.time() - t}")
+        t = time.time()
+        nex = np.asarray(self.nonexist_edges, dtype=np.int64).reshape(-1, 2)
+        norm_nonexist = list(self.pair_scores(nex[:, 1], nex[:, 0]))
+        print(f"time for predicting non-existing edges: {time.time() - t}")
+        self.compute_and_save(norm_exist, norm_nonexist, filename=self.naive_result_filename(), announce=False)
+
     def influence_matrix(self, mode=None) -> np.ndarray:
         """influence_val[i][j] = ||grad_mat(test_nodes[i])[test_nodes[j]]||_2 (attacker.py:216-229)
         as float64 [n_test, n_test] on the host.  Probes are sharded over ranks when
@@ -348,10 +412,18 @@ class Attacker:
         ex = np.asarray(self.exist_edges, dtype=np.int64).reshape(-1, 2)
         nex = np.asarray(self.nonexist_edges, dtype=np.int64).reshape(-1, 2)
         n = self.worker.n_nodes
-        all_nodes = np.arange(n, dtype=np.int64)
-        starts = np.union1d(ex[:, 0], nex[:, 0])
-        pos = np.full(n, -1, dtype=np.int64)
         s_ex = np.empty(len(ex)); s_nex = np.empty(len(nex))
+        kind, sd = self._walk()
+        if kind == "gcn2" and self.features.is_cuda and isinstance(self.baseline(None, sd), engine.Baseline):
+            # only the listed pairs are formed (lt_influence_pairs: probe = the first node, observed = the second), and only their
+            # scores cross PCIe -- the rows path below forms chunk x N scores to read a few dozen per row; same bits
+            s = self.pair_scores(np.concatenate([ex[:, 0], nex[:, 0]]), np.concatenate([ex[:, 1], nex[:, 1]]))
+            s_ex[:], s_nex[:] = s[:len(ex)], s[len(ex):]
+            starts = np.empty(0, dtype=np.int64)
+        else:
+            starts = np.union1d(ex[:, 0], nex[:, 0])
+        all_nodes = np.arange(n, dtype=np.int64)
+        pos = np.full(n, -1, dtype=np.int64)
         for c0 in range(0, len(starts), chunk):
             probes = starts[c0:c0 + chunk]
             rows = self._rows(probes, all_nodes).cpu().numpy().astype(np.float64)
@@ -425,8 +497,9 @@ class Attacker:
                     f"_eps-{a.epsilon}_seed-{a.noise_seed}.pt")
         return osp.join(folder, name)
 
-    def compute_and_save(self, norm_exist, norm_nonexist):
-        """attacker.py:378-412: sklearn ROC / PR on the host, same prints, same ``.pt`` schema."""
+    def compute_and_save(self, norm_exist, norm_nonexist, filename=None, announce=True):
+        """attacker.py:378-412: sklearn ROC / PR on the host, same prints, same ``.pt`` schema.  ``filename`` / ``announce``:
+        the naive attack writes the same dict under its own name and prints no "saved" line (attacker.py:165-201)."""
         y = [1] * len(norm_exist) + [0] * len(norm_nonexist)
         pred = list(norm_exist) + list(norm_nonexist)
 
@@ -440,11 +513,12 @@ class Attacker:
         rank, _ = lt_dist.world()
         if rank != 0:
             return
-        filename = self.result_filename()
+        filename = filename or self.result_filename()
         os.makedirs(osp.dirname(filename), exist_ok=True)
         torch.save({
             "auc": {"fpr": fpr, "tpr": tpr, "thresholds": thresholds},
             "pr": {"precision": precision, "recall": recall, "thresholds": thresholds_2},
             "result": {"y": y, "pred": pred},
         }, filename)
-        print(f"attack results saved to: {filename}")
+        if announce:
+            print(f"attack results saved to: {filename}")

@@ -2046,6 +2046,37 @@ __global__ __launch_bounds__(LT_BLOCK) void k_item_stageB_list(
                                     delta, out, ldo, bits, words, skip_long, marks, big_bits, big_slot, vec);
 }
 
+// ---- lt_influence_pairs: stage B over the CALLER's list of pairs -----------------------------------------------------------
+// One 8-lane group per listed pair k of the chunk, pair_ptr[c0] <= k < pair_ptr[c1] (the range by value), grid-stride.  The pair's
+// probe is the last b with pair_ptr[b] <= k -- probes without pairs repeat an offset -- found by a binary search in the chunk's
+// slice of the device copy of pair_ptr (10 steps at 1 024 probes, in lines every group of the wave shares; a per-pair index from
+// an expand kernel would cost a launch and 4 bytes per pair to save them).  The pair itself IS item_stageB_pair's: a rectangle of
+// one column (n_obs = 1, ldo = 0) whose observed list and output start at the pair -- the same membership test (the chunk's
+// bitmap row, else find_row), the same row2_dot chains (entry e on chain (e - e0) & 7), the same butterfly and tail, so the
+// bits of lt_influence_rows at (probe, observed).  Observed hub rows take the same walk (skip_long = 0): no hub blocks.
+template <int CP, bool DELTA>
+__global__ __launch_bounds__(LT_BLOCK) void k_pair_stageB(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+    const float *__restrict__ val, const int32_t *__restrict__ tptr,
+    const int32_t *__restrict__ trow, const float *__restrict__ S2, int C,
+    const float *__restrict__ b2, const float *__restrict__ OUT,
+    const int32_t *__restrict__ probes, int nb, const int32_t *__restrict__ off,
+    const float *__restrict__ S2x, const int64_t *__restrict__ pair_ptr, long k0, long k1,
+    const int32_t *__restrict__ pair_obs, float delta, float *__restrict__ out,
+    const uint2 *__restrict__ bits, int words, const uint2 *__restrict__ big_bits, const int32_t *__restrict__ big_slot) {
+    const int q = threadIdx.x & (LT_L2_LANES - 1);
+    const long groups = (long)gridDim.x * (LT_BLOCK / LT_L2_LANES);
+    for (long k = k0 + ((long)blockIdx.x * LT_BLOCK + threadIdx.x) / LT_L2_LANES; k < k1; k += groups) {
+        int lo = 0, hi = nb;      // pair_ptr[lo] <= k < pair_ptr[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (pair_ptr[mid] <= k) lo = mid; else hi = mid;
+        }
+        item_stageB_pair<CP, DELTA>((long)lo, q, rowptr, col, val, tptr, trow, S2, C, b2, OUT, probes, nb, off, S2x, pair_obs + k, 1,
+                                    delta, out + k, 0L, bits, words, 0, (const unsigned *)nullptr, big_bits, big_slot, (float *)nullptr);
+    }
+}
+
 // SPARSE / DELTA stage B, calls with a bitmap row per probe (twitch size): one block per (observed node, slice of the
 // probes) instead of one 8-lane group per pair.  k_item_stageB pays the chain observe[j] -> rowptr[u] -> col[e] -> bitmap
 // for every one of the 250 K pairs of a 500 x 500 call although 93 % of them turn out untouched; here the observed row
@@ -2354,11 +2385,14 @@ struct infl_ws {
     int32_t *big_slot;     // [chunk + 1] slot of each probe (-1: none) + the slot counter
     uint2 *bits;           // SPARSE / DELTA: membership bitmap + positions of R_v per probe [chunk][ceil(n / 32)], or NULL (huge graphs)
     int32_t *probes_s, *obs_s;   // the call's lists with every id checked against [0, n) (lt_items.hip.h checked_node) [n_probe] / [n_obs]
+    int64_t *pair_ptr;     // lt_influence_pairs: the device copy of pair_ptr [n_probe + 1] (obs_s is then [n_pairs])
     size_t bytes;
     int chunk;
 };
 
-static infl_ws carve_infl(void *base, const lt_baseline *b, int n_probe, int n_obs, int mode) {
+// n_pairs >= 0: the carve of lt_influence_pairs (n_obs = 0) -- the checked observed list and the offsets are sized by the pair
+// list, and nothing keyed by an observe list is carved (hub_obs, the fused route's records, pair marks)
+static infl_ws carve_infl(void *base, const lt_baseline *b, int n_probe, int n_obs, int mode, int64_t n_pairs = -1) {
     infl_ws w = {};
     const size_t n = (size_t)b->n, C = (size_t)b->C, Hp = (size_t)b->Hp, F = (size_t)b->F;
     const size_t maxc = (size_t)(b->g->max_col_nnz > 0 ? b->g->max_col_nnz : 1);
@@ -2381,7 +2415,8 @@ static infl_ws carve_infl(void *base, const lt_baseline *b, int n_probe, int n_o
         return q;
     };
     w.probes_s = (int32_t *)take((size_t)(n_probe > 0 ? n_probe : 1) * sizeof(int32_t));
-    w.obs_s = (int32_t *)take((size_t)(n_obs > 0 ? n_obs : 1) * sizeof(int32_t));
+    w.obs_s = (int32_t *)take((size_t)(n_pairs >= 0 ? n_pairs : (int64_t)n_obs) * sizeof(int32_t));
+    if (n_pairs >= 0) w.pair_ptr = (int64_t *)take(((size_t)n_probe + 1) * sizeof(int64_t));
     if (mode == LT_MODE_FULL || mode == LT_MODE_SPARSE) {
         w.Sp = (float *)take(chunk * Hp * sizeof(float));
         w.slabs = (float *)take(lt_gemm_splitk_slab_bytes((int)chunk, b->H, b->F, probe_kslice(b)));
@@ -2395,11 +2430,11 @@ static infl_ws carve_infl(void *base, const lt_baseline *b, int n_probe, int n_o
     if (mode == LT_MODE_DELTA) w.Spd = (double *)take(chunk * Hp * sizeof(double));   // aggregate-first: X[probes] W1 in fp64
     {   // the fused route's records (k_delta_probe_finish), when the graph qualifies and they stay modest
         const df_geom dg = df_geometry(b->g, (int)C, n_obs);
-        if (mode == LT_MODE_DELTA && dg.ok && chunk * (size_t)dg.rec_words * sizeof(int32_t) <= ((size_t)1 << 30))
+        if (mode == LT_MODE_DELTA && n_pairs < 0 && dg.ok && chunk * (size_t)dg.rec_words * sizeof(int32_t) <= ((size_t)1 << 30))
             w.dl_rec = (int32_t *)take(chunk * (size_t)dg.rec_words * sizeof(int32_t));
     }
     if (mode != LT_MODE_FULL) {
-        w.hub_obs = (int32_t *)take(((size_t)n_obs + 1) * sizeof(int32_t));   // the observed nodes that are hub rows (k_item_bits)
+        if (n_pairs < 0) w.hub_obs = (int32_t *)take(((size_t)n_obs + 1) * sizeof(int32_t));   // the observed nodes that are hub rows (k_item_bits)
         w.S2x = (float *)take(chunk * maxc * C * sizeof(float));
         w.off = (int32_t *)take((chunk + 1) * sizeof(int32_t));
         w.item_pr = (int2 *)take(chunk * maxc * sizeof(int2));
@@ -2412,7 +2447,7 @@ static infl_ws carve_infl(void *base, const lt_baseline *b, int n_probe, int n_o
             w.big_bits = (uint2 *)take((size_t)LT_BIG_SLOTS * bw * sizeof(uint2));
             w.big_slot = (int32_t *)take((chunk + 1) * sizeof(int32_t));
         }
-        if (lt_tune().pair_marks >= 0) {
+        if (lt_tune().pair_marks >= 0 && n_pairs < 0) {
             const size_t slots = (size_t)(n_obs > 0 ? n_obs : 1) * LT_ROW_SEG;
             w.pm_cnt = (int32_t *)take((n + 1) * sizeof(int32_t));     // [n] counts + the list cursor
             w.pm_start = (int32_t *)take(n * sizeof(int32_t));
@@ -2450,6 +2485,15 @@ struct lt_compact_out {
     bool taken;
     int chunks;         // probe chunks of the call (taken only)
 };
+// lt_influence_pairs: the caller's pair list.  A call with one has no observe list (observe_nodes = NULL, n_obs = 0): stage A runs as
+// in every other call on the item route -- no fused records, no pair marks, no per-row stage B, no hub blocks, all of which are keyed
+// by an observe list -- and stage B is k_pair_stageB writing out[k].
+#define LT_PAIRS_MAX ((int64_t)2147483647 - 65536)      // the list's check shares a launch (and its int counts) with the probes'
+struct lt_pairs_job {
+    const int64_t *ptr;      // HOST [n_probe + 1], validated by the caller
+    const int32_t *obs;      // device [n_pairs]
+    int64_t n_pairs;
+};
 static void lt_compact_job(lt_bits_job &j, const lt_compact_out &c, long row0) {
     j.cidx = c.idx; j.ccur = c.cur; j.ccur_next = c.cur_next; j.ctick = c.tick; j.cready = c.ready;
     j.crow0 = row0; j.cld = c.ld; j.ccap = c.cap;
@@ -2458,7 +2502,7 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
                                const int32_t *observe_nodes, int32_t n_obs, float delta,
                                int32_t mode, float *out, int64_t ldo, void *workspace,
                                size_t workspace_bytes, void *stream, float *vec, double *dst64 = nullptr, int64_t ldd = 0,
-                               lt_compact_out *cmp = nullptr);
+                               lt_compact_out *cmp = nullptr, const lt_pairs_job *pj = nullptr);
 
 // lt_influence_rows + the finished rows as float64 in dst (device memory, or pinned host memory: the reference's influence_val,
 // attacker.py:216-229): the fused DELTA route's blocks write their own rows there, every other route ends with the launch of
@@ -2689,6 +2733,34 @@ extern "C" int lt_influence_rows(const lt_baseline *b, const int32_t *probe_node
                                stream, nullptr);
 }
 
+// ---- lt_influence_pairs (include/linkteller_hip.h): the scores of a LIST of (probe, observed) pairs, grouped by probe ------------
+extern "C" size_t lt_influence_pairs_workspace_bytes(const lt_baseline *b, int32_t n_probe, int64_t n_pairs, int32_t mode) {
+    if (!b || n_probe < 0 || n_pairs < 0 || n_pairs > LT_PAIRS_MAX || mode < LT_MODE_FULL || mode > LT_MODE_DELTA) return 0;
+    return carve_infl(nullptr, b, n_probe, 0, mode == LT_MODE_FULL ? LT_MODE_SPARSE : mode, n_pairs).bytes;
+}
+extern "C" int lt_influence_pairs(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe, const int64_t *pair_ptr,
+                                  const int32_t *pair_obs, int64_t n_pairs, float delta, int32_t mode, float *out,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+    LT_REQUIRE(b != nullptr, "lt_influence_pairs: baseline is NULL");
+    LT_REQUIRE(n_probe >= 0 && n_pairs >= 0, "lt_influence_pairs: negative count");
+    LT_REQUIRE(n_pairs <= LT_PAIRS_MAX, "lt_influence_pairs: %lld pairs (at most %lld per call)", (long long)n_pairs, (long long)LT_PAIRS_MAX);
+    LT_REQUIRE(mode >= LT_MODE_FULL && mode <= LT_MODE_DELTA, "lt_influence_pairs: unknown mode %d", mode);
+    // the offsets, on the host, before anything is launched
+    LT_REQUIRE(pair_ptr != nullptr || n_pairs == 0, "lt_influence_pairs: pair_ptr is NULL");
+    if (pair_ptr) {
+        LT_REQUIRE(pair_ptr[0] == 0, "lt_influence_pairs: pair_ptr[0] = %lld, not 0", (long long)pair_ptr[0]);
+        for (int32_t i = 0; i < n_probe; ++i)
+            LT_REQUIRE(pair_ptr[i + 1] >= pair_ptr[i], "lt_influence_pairs: pair_ptr decreases at probe %d", i);
+        LT_REQUIRE(pair_ptr[n_probe] == n_pairs, "lt_influence_pairs: pair_ptr[n_probe] = %lld, n_pairs = %lld",
+                   (long long)pair_ptr[n_probe], (long long)n_pairs);
+    }
+    if (n_probe == 0 || n_pairs == 0) return LT_OK;
+    // (FULL names the quantity SPARSE computes, bit for bit: nothing of a pair list needs the all-rows stage A)
+    const lt_pairs_job pj = {pair_ptr, pair_obs, n_pairs};
+    return influence_rows_impl(b, probe_nodes, n_probe, nullptr, 0, delta, mode == LT_MODE_FULL ? LT_MODE_SPARSE : mode, out, 0,
+                               workspace, workspace_bytes, stream, nullptr, nullptr, 0, nullptr, &pj);
+}
+
 // The same call with the pairs' difference VECTORS next to the norms: vec[(i * ldo + j) * C + c], unscaled (see
 // store_diff_vec in lt_items.hip.h).  For models wider than one pass of these kernels the caller runs one such call per slice
 // of the hidden layer (W1[:, s], b1[s], W2[s, t]) and per slice of <= 8 classes and joins them with lt_wide_combine.
@@ -2707,25 +2779,25 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
                                const int32_t *observe_nodes, int32_t n_obs, float delta,
                                int32_t mode, float *out, int64_t ldo, void *workspace,
                                size_t workspace_bytes, void *stream, float *vec, double *dst64, int64_t ldd,
-                               lt_compact_out *cmp) {
+                               lt_compact_out *cmp, const lt_pairs_job *pj) {
     lt_prof_call prof_call_;
     int32_t exported_rows = 0;      // (dst64) rows the fused route's blocks wrote themselves: the chunks are in probe order
     LT_REQUIRE(b != nullptr, "lt_influence_rows: baseline is NULL");
     LT_REQUIRE(n_probe >= 0 && n_obs >= 0, "lt_influence_rows: negative count");
     LT_REQUIRE(mode >= LT_MODE_FULL && mode <= LT_MODE_DELTA, "lt_influence_rows: unknown mode %d", mode);
     LT_REQUIRE(delta != 0.f && delta == delta, "lt_influence_rows: delta must be a non-zero number");
-    if (n_probe == 0 || n_obs == 0) return LT_OK;
-    LT_REQUIRE(probe_nodes && observe_nodes && out, "lt_influence_rows: NULL pointer");
+    if (n_probe == 0 || (pj ? pj->n_pairs == 0 : n_obs == 0)) return LT_OK;
+    LT_REQUIRE(probe_nodes && (pj ? pj->obs : observe_nodes) && out, "lt_influence_rows: NULL pointer");
     LT_REQUIRE(ldo >= n_obs, "lt_influence_rows: ldo=%lld < n_obs=%d", (long long)ldo, n_obs);
     LT_REQUIRE(b->n > 0, "lt_influence_rows: empty graph");
     { const int rc = lt_node_err_pending(); if (rc) return rc; }     // an earlier call's list held an id out of range
-    const size_t need = lt_influence_workspace_bytes(b, n_probe, n_obs, mode);
+    const size_t need = pj ? carve_infl(nullptr, b, n_probe, 0, mode, pj->n_pairs).bytes : lt_influence_workspace_bytes(b, n_probe, n_obs, mode);
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 256))
         return lt_set_error(LT_ERR_WORKSPACE, "lt_influence_rows: workspace needs %zu bytes, 256-byte aligned", need);
 
     hipStream_t st = (hipStream_t)stream;
     const lt_graph *g = b->g;
-    const infl_ws w = carve_infl(workspace, b, n_probe, n_obs, mode);
+    const infl_ws w = carve_infl(workspace, b, n_probe, n_obs, mode, pj ? pj->n_pairs : -1);
     const int lpr = lt_lpr_for(b->Hp), cp = lt_cp_for(b->C), C = b->C, Hp = b->Hp, n = b->n;
     // SPARSE / DELTA read the baseline activations (Z1, S2, OUT; DELTA the fp64 Z1 when enabled); FULL forms
     // what it needs of them itself
@@ -2760,7 +2832,7 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
     // stage B per observed row (k_item_stageB_rows) instead of per pair: calls with a bitmap row per probe and no pair marks
     // ("stageb_rows" = 0 keeps the per-pair kernel; results are bit-identical)
     // (the vector form is written by the per-pair kernel and the hub blocks only)
-    const bool rows_route = mode != LT_MODE_FULL && w.bits != nullptr && !use_marks && lt_tune().stageb_rows != 0 && vec == nullptr;
+    const bool rows_route = mode != LT_MODE_FULL && w.bits != nullptr && !use_marks && lt_tune().stageb_rows != 0 && vec == nullptr && !pj;
     // probes of a chunk split over `psplit` blocks per observed node so that the launch fills the chip
     int psplit = 1;
     {
@@ -2816,15 +2888,17 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
     // every other call -- FULL / SPARSE start with a GEMM that gathers X[probes], pair marks with the observed rows -- by a
     // launch of its own, ~2 us in front of steps of 0.15 ms and more.  Behind the check every kernel reads the checked lists.
     int32_t *const node_err = lt_node_err_dev();
-    const bool inline_check = mode == LT_MODE_DELTA && !use_marks;
+    // (a pair list: always that launch -- the list's only reader is stage B -- and the offsets' copy to the device with it)
+    const bool inline_check = mode == LT_MODE_DELTA && !use_marks && !pj;
     if (!inline_check) {
-        const long tot = (long)n_probe + n_obs;
-        hipLaunchKernelGGL(k_check_nodes, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, probe_nodes, n_probe, observe_nodes,
-                           n_obs, n, w.probes_s, w.obs_s, node_err);
+        const long n_list = pj ? (long)pj->n_pairs : (long)n_obs, tot = (long)n_probe + n_list;
+        hipLaunchKernelGGL(k_check_nodes, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, probe_nodes, n_probe,
+                           pj ? pj->obs : observe_nodes, (int)n_list, n, w.probes_s, w.obs_s, node_err);
         LT_CHECK_LAUNCH();
         probe_nodes = w.probes_s;
         observe_nodes = w.obs_s;
     }
+    if (pj) LT_HIP(hipMemcpyAsync(w.pair_ptr, pj->ptr, ((size_t)n_probe + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     if (use_marks) {
         LT_REQUIRE((long)n_obs * LT_ROW_SEG / 256 + 1 < 2147483647L, "lt_influence_rows: n_obs=%d exceeds the grid limit", n_obs);
         const unsigned gl = (unsigned)(((long)n_obs * LT_ROW_SEG + 255) / 256);
@@ -2840,6 +2914,7 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
     for (int p0 = 0; p0 < n_probe; p0 += w.chunk) {
         const int nb = (n_probe - p0) < w.chunk ? (n_probe - p0) : w.chunk;
         const int32_t *probes = probe_nodes + p0;
+        if (pj && pj->ptr[p0] == pj->ptr[p0 + nb]) continue;      // (a chunk whose probes own no pair)
         float *orow = out + (int64_t)p0 * ldo;
         float *vrow = vec ? vec + (int64_t)p0 * ldo * b->C : (float *)nullptr;
         const long pairs = (long)nb * n_obs;
@@ -3032,6 +3107,16 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
                     continue;
                 }
             }
+            // lt_influence_pairs: stage B of the chunk's pairs, pair_ptr[p0] .. pair_ptr[p0 + nb) (the host copy gives the range)
+#define LT_PAIRS_LAUNCH(DELTA_)                                                                                                       \
+    do {                                                                                                                              \
+        const long k0_ = (long)pj->ptr[p0], k1_ = (long)pj->ptr[p0 + nb];                                                             \
+        const long want_ = ((k1_ - k0_) * LT_L2_LANES + LT_BLOCK - 1) / LT_BLOCK;                                                     \
+        LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_pair_stageB<CP_, DELTA_>), dim3((unsigned)std::min<long>(want_, LT_ITEM_GRID)),      \
+                                               dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val, g->tptr, g->trow, b->S2, C, b->b2,   \
+                                               b->OUT, probes, nb, w.off, w.S2x, w.pair_ptr + p0, k0_, k1_, w.obs_s, delta, out,      \
+                                               w.bits, words, w.big_bits, w.big_slot));                                               \
+    } while (0)
             bool bits_done = false;
             lt_bits_job job = {g->tptr, g->trow, probes, nb, words, w.bits, w.off, w.item_pr, w.big_bits, w.big_slot,
                                w.big_slot ? w.big_slot + w.chunk : (int32_t *)nullptr, g->rowptr, observe_nodes, n_obs,
@@ -3086,6 +3171,11 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
                                        (const float *)nullptr))); }
                 LT_CHECK_LAUNCH();
                 lt_prof_scope prof_(LT_K_ITEM_B, st);
+                if (pj) {
+                    LT_PAIRS_LAUNCH(false);
+                    LT_CHECK_LAUNCH();
+                    continue;
+                }
                 if (long_blocks > 0 && hub_short) {
                     LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_item_stageB_hubs<CP_, false, true>), dim3((unsigned)long_blocks),
                                                            dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
@@ -3165,6 +3255,11 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
                 } }
                 LT_CHECK_LAUNCH();
                 lt_prof_scope prof_(LT_K_ITEM_B, st);
+                if (pj) {
+                    LT_PAIRS_LAUNCH(true);
+                    LT_CHECK_LAUNCH();
+                    continue;
+                }
                 // twitch size (a bitmap row per probe, every probe walks the hub's row): the hub blocks ride in front of the per-row
                 // kernel's launch
                 const bool hubs_ride = long_blocks > 0 && rows_route && !hub_short && w.bits != nullptr && vrow == nullptr;
@@ -3208,6 +3303,7 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
             LT_CHECK_LAUNCH();
         }
     }
+#undef LT_PAIRS_LAUNCH
     if (dst64 && exported_rows < n_probe && n_obs > 0)      // (the rows no block exported itself: one launch behind the last kernel)
         return lt_export_rows_dev(out + (int64_t)exported_rows * ldo, ldo, n_probe - exported_rows, n_obs,
                                   dst64 + (int64_t)exported_rows * ldd, ldd, (hipStream_t)stream);

@@ -288,6 +288,41 @@ class Baseline:
                                                 ws.numel(), _stream()), "lt_influence_rows")
         return out
 
+    def influence_pairs(self, probe_nodes, pair_ptr, pair_obs, delta: float, mode="delta", out=None) -> torch.Tensor:
+        """[n_pairs] fp32 on the device: the scores of a LIST of pairs grouped by probe (lt_influence_pairs).  Probe i =
+        ``probe_nodes[i]`` owns ``pair_obs[pair_ptr[i]:pair_ptr[i + 1]]`` (``group_pairs`` builds the three from two id arrays)
+        and ``out[k]`` is what ``influence_rows`` writes at (that probe, ``pair_obs[k]``) for the same mode, bit for bit --
+        without the rectangle: the output and the workspace are sized by the list.  ``pair_ptr`` is a HOST array of
+        n_probe + 1 int64 offsets (validated by the library before anything is launched); the node lists follow
+        ``influence_rows`` (int32 CUDA tensors are checked on the device: ``engine.node_check()`` after synchronising)."""
+        import numpy as np
+        dev = self.x.device
+        probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
+        obs = _as_nodes(pair_obs, self.n, dev, "pair_obs")
+        if isinstance(pair_ptr, torch.Tensor):
+            pair_ptr = pair_ptr.cpu().numpy()
+        ptr = np.ascontiguousarray(np.asarray(pair_ptr).reshape(-1), dtype=np.int64)
+        npb, npairs = probes.numel(), obs.numel()
+        if ptr.size != npb + 1:
+            raise ValueError(f"pair_ptr must hold n_probe + 1 = {npb + 1} offsets, got {ptr.size}")
+        m = _lib.MODES[mode] if isinstance(mode, str) else int(mode)
+        if m == _lib.MODE_DELTA and not self._fp64:
+            self.enable_fp64()
+        if out is None:
+            out = torch.empty((npairs,), dtype=torch.float32, device=dev)
+        elif out.shape != (npairs,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError("out must be a contiguous float32 [n_pairs] tensor on the baseline's device")
+        key = ("pairs", npb, npairs, m)
+        need = _lib.lib().lt_influence_pairs_workspace_bytes(self._h, npb, npairs, m)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _workspace(need, dev)
+            self._ws = {key: ws}
+        _lib.check(_lib.lib().lt_influence_pairs(self._h, probes.data_ptr(), npb, ptr.ctypes.data, obs.data_ptr(), npairs,
+                                                 float(delta), m, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                   "lt_influence_pairs")
+        return out
+
     def influence_matrix_host(self, probe_nodes, observe_nodes, delta: float, mode="delta", refresh=False):
         """[n_probe, n_obs] float64 on the HOST (the reference's ``influence_val``, attacker.py:216-229) by ONE library call
         that returns with the matrix in pinned host memory (a block of torch's pinned-memory cache, owned by the returned
@@ -644,6 +679,24 @@ class Baseline3:
                                                       out.data_ptr(), nob, ws.data_ptr(), ws.numel(), _stream()),
                    "lt_influence3_rows_mode")
         return out
+
+
+def group_pairs(probe, observed):
+    """Two equal-length id arrays in any order -> ``(probe_nodes, pair_ptr, pair_obs, order)``, the grouped layout of
+    ``Baseline.influence_pairs`` (pure numpy, host only).  ``probe_nodes``: the distinct probes ascending (int32);
+    ``pair_ptr``: int64 [len(probe_nodes) + 1]; ``pair_obs = observed[order]`` (int32), where ``order`` is the STABLE sort of the
+    pairs by probe -- the pairs of one probe keep their input order, duplicates are kept.  Scores come back grouped; in input
+    order they are ``scores = np.empty(len(order)); scores[order] = out``."""
+    import numpy as np
+    probe = np.asarray(probe, dtype=np.int64).reshape(-1)
+    observed = np.asarray(observed, dtype=np.int64).reshape(-1)
+    if probe.shape != observed.shape:
+        raise ValueError(f"probe and observed differ in length: {probe.size} / {observed.size}")
+    order = np.argsort(probe, kind="stable")
+    nodes, counts = np.unique(probe, return_counts=True)
+    pair_ptr = np.zeros(nodes.size + 1, dtype=np.int64)
+    np.cumsum(counts, out=pair_ptr[1:])
+    return nodes.astype(np.int32), pair_ptr, observed[order].astype(np.int32), order
 
 
 def export_rows_f64(rows: torch.Tensor):

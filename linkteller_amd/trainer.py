@@ -123,9 +123,10 @@ class GCNTrainer:
                     self.attacker.baseline_attack_balanced()
                 else:
                     self.attacker.baseline_attack()
+            elif a.attack_mode == "naive":                        # gcn_trainer.py:331-332
+                self.attacker.link_prediction_attack()
             else:
-                raise NotImplementedError(f"attack_mode = {a.attack_mode}: the per-pair naive attack is superseded by "
-                                          "the efficient one (SURVEY.md section 2)")
+                raise NotImplementedError(f"attack_mode = {a.attack_mode} not implemented!")
             print(f"attacks done using {time.time() - t} seconds!")
         labels = self.worker.labels_2
         loss_test = F.cross_entropy(output, labels.squeeze())
