@@ -35,7 +35,8 @@ extern "C" {
                             (LT_ERR_INDEX, lt_node_check), lt_profile_calls; every version-3 entry point is unchanged.  2: lt_baseline_refresh launches nothing (lazy recomputation on the first reader's stream); fp64 shard entry points;
                             profile classes 9-11.  3: lt_influence_rows_vec + lt_wide_combine (layers wider than one pass of the fused
                             kernels), lt_spmm_gather_ceiling (measurement support); every version-2 entry point is unchanged.
-                            Additive within 5: training of the 2-layer GCN (lt_gcn2_trainer_*) and lt_adam_step; no entry point changed */
+                            Additive within 5: training of the 2-layer GCN (lt_gcn2_trainer_*) and lt_adam_step; no entry point changed.
+                            Additive within 5: training of the 3-layer GCN (lt_gcn3_trainer_*); no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -476,6 +477,43 @@ int lt_gcn2_trainer_grads(const lt_gcn2_trainer *t, float *dW1, float *db1, floa
 int lt_gcn2_trainer_logits(const lt_gcn2_trainer *t, float *Z2, int64_t ldz, void *stream);
 int lt_gcn2_trainer_epoch(const lt_gcn2_trainer *t, int64_t *epoch);
 int lt_gcn2_trainer_destroy(lt_gcn2_trainer *t);
+/* ---- training of the 3-layer GCN (reference gcn/models.py:28-46 GCN3 under the same train_one_epoch) ----
+ * Ownership, validation and stream semantics of lt_gcn2_trainer_*: the graph, X [n, ldx], labels and the six parameter tensors
+ * (W1 [F, H1], b1 [H1], W2 [H1, H2], b2 [H2], W3 [H2, C], b3 [C], dense fp32 device buffers) are borrowed and the parameters
+ * are updated IN PLACE; the trainer owns every intermediate and the Adam moments.  H1, H2 <= 256 and C <= 8 (the limits of
+ * lt_baseline3_create), dropout in [0, 1], lr and weight_decay >= 0; anything else is LT_ERR_INVALID.  One epoch, with e =
+ * the epochs run since creation, A the graph as given (not symmetric in general), scale = (float)(1 / (1 - p)):
+ *   S1 = X W1;   Z1 = A S1 + b1; H1d = drop_0(relu(Z1))   [n, H1]
+ *   S2 = H1d W2; Z2 = A S2 + b2; H2d = drop_1(relu(Z2))   [n, H2]
+ *   S3 = H2d W3; Z3 = A S3 + b3                           [n, C]
+ *   loss = mean_r CE(Z3[r], y[r]); dZ3 = (softmax(Z3) - onehot(y)) / n; db3 = sum_r dZ3
+ *   dS3 = A^T dZ3; dW3 = H2d^T dS3; dZ2 = [H2d > 0] scale (dS3 W3^T); db2 = sum_r dZ2
+ *   dS2 = A^T dZ2; dW2 = H1d^T dS2; dZ1 = [H1d > 0] scale (dS2 W2^T); db1 = sum_r dZ1
+ *   dW1 = X^T (A^T dZ1)
+ *   one Adam step (lt_adam_step's op order, weight decay added to the gradient) over W1 | b1 | W2 | b2 | W3 | b3, step = e + 1
+ * Dropout: for hidden layer k in {0, 1}, element (r, h) has i = r * H_{k+1} + h; it is kept iff word (i & 3) of
+ * Philox4x32-10 with counter (q & 0xffffffff, q >> 32, e, k), q = i >> 2, and key (seed & 0xffffffff, seed >> 32) is
+ * >= floor(p * 2^32).  Layer 0 is exactly the 2-layer trainer's mask; the layer word keeps the two masks apart when
+ * H1 = H2.  p = 0 draws nothing; p = 1 keeps nothing.
+ * lt_gcn3_trainer_run enqueues without a host synchronisation; record [n_epochs, 2] = (mean loss, correct count) per epoch.
+ * No float atomics and every reduction in a fixed order: run(a + b) equals run(a); run(b) bit for bit, and two trainers
+ * with the same inputs give the same bits.
+ * lt_gcn3_trainer_grads / _logits / _hidden are test accessors for the LAST epoch: its six gradients (before weight decay),
+ * its train-mode logits Z3 [n, ldz] and its H1d (layer 1, [n, H1]) or H2d (layer 2, [n, H2]) after ReLU and dropout, written
+ * with leading dimension ld. */
+typedef struct lt_gcn3_trainer lt_gcn3_trainer;
+int lt_gcn3_trainer_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const int32_t *labels,
+                           int32_t H1, int32_t H2, int32_t C,
+                           float *W1, float *b1, float *W2, float *b2, float *W3, float *b3,
+                           double lr, double weight_decay, double dropout, uint64_t seed, void *stream,
+                           lt_gcn3_trainer **out);
+int lt_gcn3_trainer_run(lt_gcn3_trainer *t, int32_t n_epochs, float *record, void *stream);
+int lt_gcn3_trainer_grads(const lt_gcn3_trainer *t, float *dW1, float *db1, float *dW2, float *db2,
+                          float *dW3, float *db3, void *stream);
+int lt_gcn3_trainer_logits(const lt_gcn3_trainer *t, float *Z3, int64_t ldz, void *stream);
+int lt_gcn3_trainer_hidden(const lt_gcn3_trainer *t, int32_t layer /* 1 | 2 */, float *dst, int64_t ld, void *stream);
+int lt_gcn3_trainer_epoch(const lt_gcn3_trainer *t, int64_t *epoch);
+int lt_gcn3_trainer_destroy(lt_gcn3_trainer *t);
 /* One Adam step over n fp32 elements in place (the trainer's update, exported so it is tested on its own):
  * torch/optim/adam.py _single_tensor_adam op by op in fp32 with correctly rounded sqrt and division, and fused multiply-adds
  * where torch's CPU kernels fuse (the weight-decay add, lerp_, addcmul_) --

@@ -105,6 +105,16 @@ SIGNATURES = {
     "lt_gcn2_trainer_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lt_gcn2_trainer_epoch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "lt_gcn2_trainer_destroy": (C.c_int, [C.c_void_p]),
+    "lt_gcn3_trainer_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                         C.c_double, C.c_double, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lt_gcn3_trainer_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lt_gcn3_trainer_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "lt_gcn3_trainer_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "lt_gcn3_trainer_hidden": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "lt_gcn3_trainer_epoch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "lt_gcn3_trainer_destroy": (C.c_int, [C.c_void_p]),
     "lt_adam_step": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
                                C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "lt_profile_enable": (C.c_int, [C.c_int]),

@@ -14,6 +14,8 @@
 //   dW1 = X^T dS1               k_gemm_tn_mfma + k_sum_slabs   v_mfma_f32_32x32x2_f32, A^T staged through LDS, split-K
 //   Adam                        k_tr_adam                      one launch over W1 | b1 | W2 | b2
 //
+// The 3-layer GCN's epoch (lt_gcn3_trainer_*) is built from the same kernels further down, with its own launch table.
+//
 // Every reduction has a fixed order (no float atomics): two trainings with the same inputs give the same bits.
 // Built with -ffp-contract=off: the only fused operations are explicit fmaf calls and the MFMAs.
 #include <math.h>
@@ -42,9 +44,9 @@ __device__ __forceinline__ uint4 lt_philox4x32_10(uint4 c, uint2 k) {
     return c;
 }
 
-// word (i & 3) of Philox(counter (q lo, q hi, epoch, 0), key (seed lo, seed hi)), q = i >> 2
-__device__ __forceinline__ uint4 lt_drop_block(uint64_t q, uint32_t epoch, uint64_t seed) {
-    return lt_philox4x32_10(make_uint4((uint32_t)q, (uint32_t)(q >> 32), epoch, 0u),
+// word (i & 3) of Philox(counter (q lo, q hi, epoch, layer), key (seed lo, seed hi)), q = i >> 2
+__device__ __forceinline__ uint4 lt_drop_block(uint64_t q, uint32_t epoch, uint64_t seed, uint32_t layer) {
+    return lt_philox4x32_10(make_uint4((uint32_t)q, (uint32_t)(q >> 32), epoch, layer),
                             make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
 }
 
@@ -54,7 +56,33 @@ struct lt_drop_args {
     float scale;         // 1 / (1 - p), rounded once from double
     uint32_t epoch;
     uint64_t seed;
+    uint32_t layer = 0;  // counter word 3: the hidden layer the mask belongs to (the 2-layer trainer has one: 0)
 };
+
+// columns coff .. coff + 3 of row r of a [n, H] hidden layer (h >= 0 already): kept elements scaled, the others and the
+// pad columns zero
+__device__ __forceinline__ f32x4 lt_drop4(f32x4 h, int r, int coff, int H, const lt_drop_args &d) {
+    const uint64_t i0 = (uint64_t)r * H + coff;
+    uint32_t u[4];
+    if ((H & 3) == 0) {    // the 4 columns are the 4 words of one Philox block
+        const uint4 w = lt_drop_block(i0 >> 2, d.epoch, d.seed, d.layer);
+        u[0] = w.x; u[1] = w.y; u[2] = w.z; u[3] = w.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint64_t i = i0 + j;
+            const uint4 w = lt_drop_block(i >> 2, d.epoch, d.seed, d.layer);
+            const uint32_t sel = (uint32_t)(i & 3);
+            u[j] = sel == 0 ? w.x : sel == 1 ? w.y : sel == 2 ? w.z : w.w;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const bool keep = coff + j < H && (uint64_t)u[j] >= d.thresh;
+        h[j] = keep ? h[j] * d.scale : 0.f;
+    }
+    return h;
+}
 
 // --------------------------------------------------------------------------------------------
 // H1d = dropout(relu(Z1)) and S2 = H1d W2 (lane layout and summation order of k_layer1: with p = 0 these are its S2 bits)
@@ -78,27 +106,7 @@ __global__ __launch_bounds__(TR_BLOCK) void k_tr_dropout(int n, const float *__r
     if (active) {
         const f32x4 z = ld4(Z1 + (size_t)r * Hp + coff);
         f32x4 h = {fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f)};
-        if (d.on) {
-            const uint64_t i0 = (uint64_t)r * H + coff;
-            uint32_t u[4];
-            if ((H & 3) == 0) {    // the 4 columns are the 4 words of one Philox block
-                const uint4 w = lt_drop_block(i0 >> 2, d.epoch, d.seed);
-                u[0] = w.x; u[1] = w.y; u[2] = w.z; u[3] = w.w;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint64_t i = i0 + j;
-                    const uint4 w = lt_drop_block(i >> 2, d.epoch, d.seed);
-                    const uint32_t sel = (uint32_t)(i & 3);
-                    u[j] = sel == 0 ? w.x : sel == 1 ? w.y : sel == 2 ? w.z : w.w;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool keep = coff + j < H && (uint64_t)u[j] >= d.thresh;
-                h[j] = keep ? h[j] * d.scale : 0.f;
-            }
-        }
+        if (d.on) h = lt_drop4(h, r, coff, H, d);
         *reinterpret_cast<f32x4 *>(H1d + (size_t)r * Hp + coff) = h;
         relu_w2_partial<CP>(h, W2p + (size_t)coff * C, C, part);   // h >= 0: the relu is the identity
     }
@@ -720,5 +728,524 @@ extern "C" int lt_gcn2_trainer_logits(const lt_gcn2_trainer *t, float *Z2, int64
     LT_REQUIRE(ldz >= t->C, "lt_gcn2_trainer_logits: ldz=%lld < C=%d", (long long)ldz, t->C);
     LT_HIP(hipMemcpy2DAsync(Z2, (size_t)ldz * sizeof(float), t->Z2, (size_t)t->C * sizeof(float), (size_t)t->C * sizeof(float),
                             (size_t)t->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return LT_OK;
+}
+
+// ============================================================================================
+// Training of the 3-layer GCN (reference gcn/models.py:28-46): the 2-layer epoch one layer up.
+//
+//   S1 = X W1                      lt_launch_gemm(_splitk)        the 2-layer trainer's product
+//   H1d = drop_0(relu(A S1 + b1))  k_tr3_layer1 (+ _long)         row_dot chains from the bias, ReLU and the Philox mask (layer
+//                                                                 word 0) as the epilogue: Z1 never exists in memory
+//   S2 = H1d W2                    lt_launch_gemm
+//   Z2 = A S2 + b2                 lt_launch_layer1 (Z2 stored)
+//   H2d = drop_1(relu(Z2)), S3     k_tr_dropout, layer word 1
+//   Z3 = A S3 + b3                 lt_launch_layer2
+//   loss, dZ3, db3, correct        k_tr_ce, k_tr_ce_reduce
+//   dS3 = A^T dZ3                  k_tr_spmm_t_narrow
+//   dZ2, db2 | dW3                 k_tr_bwd_rows(H2d, dS3, W3p) + k_tr_colsum
+//   dS2 = A^T dZ2                  k_tr_spmm_t_wide
+//   dW2 = H1d^T dS2                k_gemm_tn_mfma + k_sum_slabs
+//   dZ1 = [H1d > 0] scale (dS2 W2^T), db1 slabs     k_tr3_dz_mfma, then k_tr_colsum
+//   dS1 = A^T dZ1; dW1 = X^T dS1   k_tr_spmm_t_wide, k_gemm_tn_mfma + k_sum_slabs
+//   Adam                           k_tr3_adam                     one launch over W1 | b1 | W2 | b2 | W3 | b3 and the padded copies
+// ============================================================================================
+
+// H1d[r] = drop(relu(A[r, :] S + bias)) for every row.  The launch's first seg_blocks blocks take the SEGMENTS of the hub rows
+// (k_layer1's scheme: row_dot's canonical order, the first segment's chain started from the bias); k_tr3_layer1_long adds
+// them in segment order and applies the same epilogue.
+template <int LPR>
+__global__ __launch_bounds__(TR_BLOCK) void k_tr3_layer1(
+    int n, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+    const float *__restrict__ S, int Hp, int H, const float *__restrict__ biasp, lt_drop_args d, float *__restrict__ Hd,
+    int skip_long, int seg_blocks, int n_seg, const int32_t *__restrict__ seg_long, const int32_t *__restrict__ seg_begin,
+    const int32_t *__restrict__ long_row, float *__restrict__ seg_part) {
+    constexpr int RPW = 64 / LPR;
+    const int lane = threadIdx.x & 63;
+    const int gl = lane & (LPR - 1);
+    const int coff = 4 * gl;
+    const bool active = coff < Hp;
+    if ((int)blockIdx.x < seg_blocks) {
+        int sg = ((blockIdx.x * TR_BLOCK + threadIdx.x) >> 6) * RPW + lane / LPR;
+        if (LPR == 64) sg = __builtin_amdgcn_readfirstlane(sg);
+        if (sg >= n_seg) return;
+        const int rs = long_row[seg_long[sg]];
+        const int s0 = seg_begin[sg], s1 = min(rowptr[rs + 1], s0 + LT_ROW_SEG);
+        const f32x4 init = (active && s0 == rowptr[rs]) ? ld4(biasp + coff) : f32x4{0.f, 0.f, 0.f, 0.f};
+        const f32x4 zs = seg_chain<16>(col, val, s0, s1, S, Hp, coff, active, -1, nullptr, init);
+        if (active) *reinterpret_cast<f32x4 *>(seg_part + (size_t)sg * Hp + coff) = zs;
+        return;
+    }
+    const int wave = (((int)blockIdx.x - seg_blocks) * TR_BLOCK + threadIdx.x) >> 6;
+    int r = wave * RPW + lane / LPR;
+    if (LPR == 64) r = __builtin_amdgcn_readfirstlane(r);
+    if (r >= n) return;
+    if (skip_long && rowptr[r + 1] - rowptr[r] > LT_ROW_SEG) return;
+    const f32x4 bv = active ? ld4(biasp + coff) : f32x4{0.f, 0.f, 0.f, 0.f};
+    const f32x4 z = row_dot<8>(col, val, rowptr[r], rowptr[r + 1], S, Hp, coff, active, -1, nullptr, bv);
+    if (active) {
+        f32x4 h = {fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f)};
+        if (d.on) h = lt_drop4(h, r, coff, H, d);
+        *reinterpret_cast<f32x4 *>(Hd + (size_t)r * Hp + coff) = h;
+    }
+}
+
+template <int LPR>
+__global__ __launch_bounds__(TR_BLOCK) void k_tr3_layer1_long(int n_long, const int32_t *__restrict__ long_row,
+                                                              const int32_t *__restrict__ long_segptr,
+                                                              const float *__restrict__ part, int Hp, int H, lt_drop_args d,
+                                                              float *__restrict__ Hd) {
+    constexpr int RPW = 64 / LPR;
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * TR_BLOCK + threadIdx.x) >> 6;
+    const int gl = lane & (LPR - 1);
+    int li = wave * RPW + lane / LPR;
+    if (LPR == 64) li = __builtin_amdgcn_readfirstlane(li);
+    if (li >= n_long) return;
+    const int coff = 4 * gl;
+    if (coff >= Hp) return;
+    const int r = long_row[li];
+    const int s0 = long_segptr[li], s1 = long_segptr[li + 1];
+    f32x4 z = ld4(part + (size_t)s0 * Hp + coff);
+    for (int s = s0 + 1; s < s1; ++s) {
+        const f32x4 t = ld4(part + (size_t)s * Hp + coff);
+        z.x += t.x; z.y += t.y; z.z += t.z; z.w += t.w;
+    }
+    f32x4 h = {fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f)};
+    if (d.on) h = lt_drop4(h, r, coff, H, d);
+    *reinterpret_cast<f32x4 *>(Hd + (size_t)r * Hp + coff) = h;
+}
+
+// --------------------------------------------------------------------------------------------
+// dZ[M, N] = [Hd > 0] * scale * (A W^T) with A = dS2 [M = n, K = H2] and the weight W = W2 [N = H1, K = H2] read as it
+// lies: its 64 x 16 tile is loaded as rows of 4 consecutive k and transposed on its way into LDS (rows of the LDS tile
+// padded to 65 floats).  (A transposed mirror of W2 kept current by the Adam launch and read with the NN tile shape
+// measured the same per epoch and was removed: NOTES.md section 13.)
+// Block / wave structure of k_gemm_f32_mfma: 64 x 64 block tile, four waves of one 32 x 32 v_mfma_f32_32x32x2_f32 tile,
+// 16-deep k-tiles with a register prefetch.  K <= 256: one pass, no split-K.  Epilogue: the mask and the scale, the store,
+// and the block's column sums (a lane's 16 rows in register order, the two half-waves, the two row waves) into slab
+// blockIdx.x of part [gridDim.x, N]: k_tr_colsum adds the slabs in order for db1.
+// --------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_tr3_dz_mfma(const float *__restrict__ A, long lda, const float *__restrict__ B,
+                                                     long ldb, const float *__restrict__ Hd, float *__restrict__ dZ,
+                                                     long ldz, int M, int N, int K, float scale,
+                                                     float *__restrict__ part) {
+    constexpr int LDB = TN_BN + 1;
+    __shared__ __attribute__((aligned(16))) float As[2][TN_BM * TN_LDA];
+    __shared__ __attribute__((aligned(16))) float Bs[2][TN_BK * LDB];
+    __shared__ float red[2][TN_BN];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wid = tid >> 6;
+    const int wr = wid >> 1, wc = wid & 1;
+    const int m0 = blockIdx.x * TN_BM;
+    const int n0 = blockIdx.y * TN_BN;
+    const int a_row = tid >> 2, a_col = (tid & 3) * 4;          // A tile 64 x 16: row tid / 4, 4 consecutive k
+    const bool a_row_ok = (m0 + a_row) < M;
+    const float *a_ptr = A + (long)(m0 + a_row) * lda + a_col;
+    const int b_row = tid >> 2, b_col = (tid & 3) * 4;          // W2 tile 64 x 16: n-row tid / 4, 4 consecutive k
+    const float *b_ptr = B + (long)(n0 + b_row) * ldb + b_col;
+
+    f32x4 ra, rb;
+    auto load_tiles = [&](int k0) {
+        ra = f32x4{0.f, 0.f, 0.f, 0.f};
+        rb = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (a_row_ok) {
+            if (k0 + a_col + 3 < K) {
+                ra = *reinterpret_cast<const f32x4u *>(a_ptr + k0);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (k0 + a_col + j < K) ra[j] = a_ptr[k0 + j];
+            }
+        }
+        if (n0 + b_row < N) {
+            if (k0 + b_col + 3 < K) {
+                rb = *reinterpret_cast<const f32x4u *>(b_ptr + k0);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (k0 + b_col + j < K) rb[j] = b_ptr[k0 + j];
+            }
+        }
+    };
+    auto store_tiles = [&](int buf) {
+        float *as = &As[buf][a_row * TN_LDA + a_col];
+        as[0] = ra.x; as[1] = ra.y; as[2] = ra.z; as[3] = ra.w;
+        float *bs = &Bs[buf][b_col * LDB + b_row];
+        bs[0] = rb.x; bs[LDB] = rb.y; bs[2 * LDB] = rb.z; bs[3 * LDB] = rb.w;
+    };
+
+    f32x16 acc, total;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc[i] = 0.f; total[i] = 0.f; }
+    const int nk = (K + TN_BK - 1) / TN_BK;
+    load_tiles(0);
+    store_tiles(0);
+    __syncthreads();
+    const int a_frag = (wr * 32 + (lane & 31)) * TN_LDA + (lane >> 5);
+    const int b_frag = (lane >> 5) * LDB + wc * 32 + (lane & 31);
+    constexpr int FOLD_TILES = TN_FOLD / TN_BK;
+    for (int kt = 0; kt < nk; ++kt) {
+        const int buf = kt & 1;
+        if (kt + 1 < nk) load_tiles((kt + 1) * TN_BK);
+        const float *as = &As[buf][a_frag];
+        const float *bs = &Bs[buf][b_frag];
+#pragma unroll
+        for (int kk = 0; kk < TN_BK; kk += 2)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[kk], bs[kk * LDB], acc, 0, 0, 0);
+        if ((kt + 1) % FOLD_TILES == 0) {
+            total += acc;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        }
+        if (kt + 1 < nk) store_tiles(buf ^ 1);
+        __syncthreads();
+    }
+    total += acc;
+    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+    const int cn = n0 + wc * 32 + (lane & 31);
+    float cs = 0.f;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int cm = m0 + wr * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+        float dz = 0.f;
+        if (cm < M && cn < N) {
+            dz = Hd[(long)cm * ldz + cn] > 0.f ? total[reg] * scale : 0.f;
+            dZ[(long)cm * ldz + cn] = dz;
+        }
+        cs += dz;
+    }
+    cs += __shfl_xor(cs, 32, 64);
+    if (lane < 32) red[wr][wc * 32 + lane] = cs;
+    __syncthreads();
+    if (tid < TN_BN && n0 + tid < N) part[(size_t)blockIdx.x * N + n0 + tid] = red[0][tid] + red[1][tid];
+}
+
+// The six parameter tensors in one launch: index i of the concatenation W1 | b1 | W2 | b2 | W3 | b3 (o[k] = where tensor
+// k ends).  The copies the row kernels read follow the update: b1p [Hp1], b2p [Hp2], W3p [Hp2, C] (zero-padded).
+struct lt_tr3_tensors {
+    float *p[6];
+    int64_t o[6];
+    float *b1p, *b2p, *W3p;
+};
+
+__global__ void k_tr3_adam(lt_tr3_tensors T, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                           lt_adam_scalars s) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T.o[5]) return;
+    const int k = i < T.o[0] ? 0 : i < T.o[1] ? 1 : i < T.o[2] ? 2 : i < T.o[3] ? 3 : i < T.o[4] ? 4 : 5;
+    const int64_t j = k ? i - T.o[k - 1] : i;
+    float *p;      // a switch over constant indices: T.p[k] with a run-time k would move the argument struct to scratch
+    switch (k) {
+        case 0: p = T.p[0]; break;
+        case 1: p = T.p[1]; break;
+        case 2: p = T.p[2]; break;
+        case 3: p = T.p[3]; break;
+        case 4: p = T.p[4]; break;
+        default: p = T.p[5]; break;
+    }
+    float mi = m[i], vi = v[i];
+    const float np = adam_elem(p[j], g[i], mi, vi, s);
+    p[j] = np;
+    m[i] = mi;
+    v[i] = vi;
+    if (k == 1) T.b1p[j] = np;
+    else if (k == 3) T.b2p[j] = np;
+    else if (k == 4) T.W3p[j] = np;
+}
+
+__global__ void k_tr3_pad(const float *__restrict__ b1, int H1, int Hp1, const float *__restrict__ b2, int H2, int Hp2, const float *__restrict__ W3, int C,
+                          float *__restrict__ b1p, float *__restrict__ b2p, float *__restrict__ W3p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < Hp1) b1p[i] = i < H1 ? b1[i] : 0.f;
+    if (i < Hp2) b2p[i] = i < H2 ? b2[i] : 0.f;
+    if (i < Hp2 * C) W3p[i] = (i / C) < H2 ? W3[i] : 0.f;
+}
+
+struct lt_gcn3_trainer {
+    const lt_graph *g = nullptr;
+    int32_t n = 0, F = 0, H1 = 0, H2 = 0, C = 0, Hp1 = 0, Hp2 = 0;
+    const float *X = nullptr;
+    int64_t ldx = 0;
+    const int32_t *labels = nullptr;
+    float *P[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // W1, b1, W2, b2, W3, b3 (borrowed)
+    int64_t off[6] = {0, 0, 0, 0, 0, 0};                                    // where each ends in grad / m / v
+    double lr = 0, wd = 0, p = 0;
+    uint64_t seed = 0;
+    int64_t epoch = 0;
+    int32_t kslice = 0;                       // split-K slicing of X W1 (the forward's)
+    int32_t tn1_kslice = 0, tn1_splits = 0;   // dW1 = X^T dS1
+    int32_t tn2_kslice = 0, tn2_splits = 0;   // dW2 = H1d^T dS2
+    int32_t n_part = 0;                       // row blocks of k_tr_bwd_rows (layer 2)
+    int32_t n_mblk = 0;                       // row blocks of k_tr3_dz_mfma
+    float *S1 = nullptr, *H1d = nullptr, *dZ1 = nullptr, *dS1 = nullptr;                        // [n, Hp1]
+    float *S2 = nullptr, *Z2 = nullptr, *H2d = nullptr, *dZ2 = nullptr, *dS2 = nullptr;         // [n, Hp2]
+    float *S3 = nullptr, *Z3 = nullptr, *dZ3 = nullptr, *dS3 = nullptr;                         // [n, C]
+    float *loss_r = nullptr;
+    int32_t *corr_r = nullptr;
+    float *b1p = nullptr, *b2p = nullptr, *W3p = nullptr;
+    float *slabs = nullptr, *tn1_slabs = nullptr, *tn2_slabs = nullptr, *part = nullptr, *part1 = nullptr, *seg_part = nullptr;
+    float *grad = nullptr, *m = nullptr, *v = nullptr;
+};
+
+static void free_trainer3(lt_gcn3_trainer *t) {
+    if (!t) return;
+    float *bufs[] = {t->S1, t->H1d, t->dZ1, t->dS1, t->S2, t->Z2, t->H2d, t->dZ2, t->dS2, t->S3, t->Z3, t->dZ3, t->dS3,
+                     t->loss_r, t->b1p, t->b2p, t->W3p, t->slabs, t->tn1_slabs, t->tn2_slabs, t->part, t->part1,
+                     t->seg_part, t->grad, t->m, t->v};
+    for (float *b : bufs) (void)hipFree(b);
+    (void)hipFree(t->corr_r);
+    delete t;
+}
+
+extern "C" int lt_gcn3_trainer_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const int32_t *labels,
+                                      int32_t H1, int32_t H2, int32_t C, float *W1, float *b1, float *W2, float *b2,
+                                      float *W3, float *b3, double lr, double weight_decay, double dropout, uint64_t seed,
+                                      void *stream, lt_gcn3_trainer **out) {
+    LT_REQUIRE(out != nullptr, "lt_gcn3_trainer_create: out is NULL");
+    *out = nullptr;
+    LT_REQUIRE(g != nullptr, "lt_gcn3_trainer_create: graph is NULL");
+    LT_REQUIRE(F > 0 && H1 > 0 && H2 > 0 && C > 0, "lt_gcn3_trainer_create: F=%d H1=%d H2=%d C=%d must be positive", F, H1,
+               H2, C);
+    LT_REQUIRE(H1 <= LT_MAX_H && H2 <= LT_MAX_H && C <= LT_MAX_C,
+               "lt_gcn3_trainer_create: H1=%d H2=%d C=%d (supported: H1, H2 <= %d, C <= %d)", H1, H2, C, LT_MAX_H, LT_MAX_C);
+    LT_REQUIRE(X && labels && W1 && b1 && W2 && b2 && W3 && b3, "lt_gcn3_trainer_create: NULL tensor pointer");
+    LT_REQUIRE(ldx >= F, "lt_gcn3_trainer_create: ldx=%lld < F=%d", (long long)ldx, F);
+    LT_REQUIRE(dropout >= 0.0 && dropout <= 1.0, "lt_gcn3_trainer_create: dropout=%g outside [0, 1]", dropout);
+    LT_REQUIRE(lr >= 0.0 && weight_decay >= 0.0, "lt_gcn3_trainer_create: lr=%g weight_decay=%g", lr, weight_decay);
+    LT_REQUIRE(g->n > 0, "lt_gcn3_trainer_create: empty graph");
+    lt_gcn3_trainer *t = new (std::nothrow) lt_gcn3_trainer();
+    if (!t) return lt_set_error(LT_ERR_NOMEM, "lt_gcn3_trainer_create: out of host memory");
+    const int n = g->n;
+    t->g = g; t->n = n; t->F = F; t->H1 = H1; t->H2 = H2; t->C = C;
+    t->Hp1 = lt_round_up(H1, 4); t->Hp2 = lt_round_up(H2, 4);
+    t->X = X; t->ldx = ldx; t->labels = labels;
+    float *ps[6] = {W1, b1, W2, b2, W3, b3};
+    const int64_t sizes[6] = {(int64_t)F * H1, H1, (int64_t)H1 * H2, H2, (int64_t)H2 * C, C};
+    int64_t end = 0;
+    for (int k = 0; k < 6; ++k) { t->P[k] = ps[k]; end += sizes[k]; t->off[k] = end; }
+    t->lr = lr; t->wd = weight_decay; t->p = dropout; t->seed = seed;
+    t->kslice = lt_gemm_pick_kslice(n, H1, F);
+    t->tn1_splits = tn_pick_splits(F, H1, n);
+    t->tn1_kslice = lt_round_up((n + t->tn1_splits - 1) / t->tn1_splits, TN_BK);
+    t->tn1_splits = (n + t->tn1_kslice - 1) / t->tn1_kslice;
+    t->tn2_splits = tn_pick_splits(H1, H2, n);
+    t->tn2_kslice = lt_round_up((n + t->tn2_splits - 1) / t->tn2_splits, TN_BK);
+    t->tn2_splits = (n + t->tn2_kslice - 1) / t->tn2_kslice;
+    t->n_part = (n + TR_ROWS_PER_BLOCK - 1) / TR_ROWS_PER_BLOCK;
+    t->n_mblk = (n + TN_BM - 1) / TN_BM;
+    const size_t nh1 = (size_t)n * t->Hp1 * sizeof(float), nh2 = (size_t)n * t->Hp2 * sizeof(float);
+    const size_t nc = (size_t)n * C * sizeof(float), np_bytes = (size_t)end * sizeof(float);
+    const int hpm = t->Hp1 > t->Hp2 ? t->Hp1 : t->Hp2;
+    hipStream_t st = (hipStream_t)stream;
+#define T_HIP(call)                                                                         \
+    do {                                                                                    \
+        hipError_t e_ = (call);                                                             \
+        if (e_ != hipSuccess) {                                                             \
+            free_trainer3(t);                                                               \
+            return lt_set_error(LT_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
+        }                                                                                   \
+    } while (0)
+    float **h1bufs[] = {&t->S1, &t->H1d, &t->dZ1, &t->dS1};
+    for (float **b : h1bufs) T_HIP(hipMalloc((void **)b, nh1));
+    float **h2bufs[] = {&t->S2, &t->Z2, &t->H2d, &t->dZ2, &t->dS2};
+    for (float **b : h2bufs) T_HIP(hipMalloc((void **)b, nh2));
+    float **cbufs[] = {&t->S3, &t->Z3, &t->dZ3, &t->dS3};
+    for (float **b : cbufs) T_HIP(hipMalloc((void **)b, nc));
+    T_HIP(hipMalloc((void **)&t->loss_r, (size_t)n * sizeof(float)));
+    T_HIP(hipMalloc((void **)&t->corr_r, (size_t)n * sizeof(int32_t)));
+    T_HIP(hipMalloc((void **)&t->b1p, (size_t)t->Hp1 * sizeof(float)));
+    T_HIP(hipMalloc((void **)&t->b2p, (size_t)t->Hp2 * sizeof(float)));
+    T_HIP(hipMalloc((void **)&t->W3p, (size_t)t->Hp2 * C * sizeof(float)));
+    const size_t sb = lt_gemm_splitk_slab_bytes(n, H1, F, t->kslice);
+    if (sb) T_HIP(hipMalloc((void **)&t->slabs, sb));
+    if (t->tn1_splits > 1) T_HIP(hipMalloc((void **)&t->tn1_slabs, (size_t)t->tn1_splits * F * H1 * sizeof(float)));
+    if (t->tn2_splits > 1) T_HIP(hipMalloc((void **)&t->tn2_slabs, (size_t)t->tn2_splits * H1 * H2 * sizeof(float)));
+    T_HIP(hipMalloc((void **)&t->part, (size_t)t->n_part * ((size_t)H2 + (size_t)H2 * C) * sizeof(float)));
+    T_HIP(hipMalloc((void **)&t->part1, (size_t)t->n_mblk * H1 * sizeof(float)));
+    if (g->p_n_seg > 0) T_HIP(hipMalloc((void **)&t->seg_part, (size_t)g->p_n_seg * hpm * sizeof(float)));
+    float **pbufs[] = {&t->grad, &t->m, &t->v};
+    for (float **b : pbufs) T_HIP(hipMalloc((void **)b, np_bytes));
+    // pad columns of S1 / S2 (the GEMMs write H of them) and of dZ1 (its product writes H1 of them) stay zero
+    T_HIP(hipMemsetAsync(t->S1, 0, nh1, st));
+    T_HIP(hipMemsetAsync(t->S2, 0, nh2, st));
+    T_HIP(hipMemsetAsync(t->dZ1, 0, nh1, st));
+    T_HIP(hipMemsetAsync(t->m, 0, np_bytes, st));
+    T_HIP(hipMemsetAsync(t->v, 0, np_bytes, st));
+#undef T_HIP
+    *out = t;
+    return LT_OK;
+}
+
+extern "C" int lt_gcn3_trainer_destroy(lt_gcn3_trainer *t) {
+    free_trainer3(t);
+    return LT_OK;
+}
+
+extern "C" int lt_gcn3_trainer_epoch(const lt_gcn3_trainer *t, int64_t *epoch) {
+    LT_REQUIRE(t != nullptr && epoch != nullptr, "lt_gcn3_trainer_epoch: NULL argument");
+    *epoch = t->epoch;
+    return LT_OK;
+}
+
+static int launch_tn(const float *A, long lda, const float *B, long ldb, float *C, int M, int N, int K, int kslice, int splits,
+                     float *slabs, hipStream_t st) {
+    const bool split = splits > 1;
+    dim3 grid((unsigned)((M + TN_BM - 1) / TN_BM), (unsigned)((N + TN_BN - 1) / TN_BN), (unsigned)splits);
+    hipLaunchKernelGGL(k_gemm_tn_mfma, grid, dim3(256), 0, st, A, lda, B, ldb, split ? slabs : C, (long)N, M, N, K, kslice,
+                       (long)M * N);
+    LT_CHECK_LAUNCH();
+    if (split) return lt_launch_sum_slabs(slabs, (long)M * N, splits, M, N, (long)N, C, (long)N, st);
+    return LT_OK;
+}
+
+static int run_epoch3(lt_gcn3_trainer *t, float *record, hipStream_t st) {
+    const lt_graph *g = t->g;
+    const int n = t->n, F = t->F, H1 = t->H1, H2 = t->H2, C = t->C, Hp1 = t->Hp1, Hp2 = t->Hp2;
+    const int lpr1 = lt_lpr_for(Hp1), lpr2 = lt_lpr_for(Hp2), cp = lt_cp_for(C);
+    const int rpb1 = (TR_BLOCK / 64) * (64 / lpr1), rpb2 = (TR_BLOCK / 64) * (64 / lpr2);
+    float *W1 = t->P[0], *W2 = t->P[2], *b3 = t->P[5];
+    float *gW1 = t->grad, *gb1 = t->grad + t->off[0], *gW2 = t->grad + t->off[1], *gb2 = t->grad + t->off[2],
+          *gb3 = t->grad + t->off[4];
+    int rc;
+    lt_drop_args d;
+    d.on = t->p > 0.0;
+    d.thresh = (uint64_t)floor(t->p * 4294967296.0);
+    d.scale = t->p < 1.0 ? (float)(1.0 / (1.0 - t->p)) : 0.f;
+    d.epoch = (uint32_t)t->epoch;
+    d.seed = t->seed;
+    const float scale = t->p > 0.0 ? d.scale : 1.f;
+    // layer 1
+    if (t->slabs)
+        rc = lt_launch_gemm_splitk(t->X, t->ldx, W1, H1, t->S1, Hp1, n, H1, F, t->kslice, t->slabs, st);
+    else
+        rc = lt_launch_gemm(t->X, t->ldx, W1, H1, t->S1, Hp1, n, H1, F, st);
+    if (rc) return rc;
+    {
+        const int have_long = g->p_n_long > 0 ? 1 : 0;
+        const unsigned seg_blocks = have_long ? rows_grid(g->p_n_seg, rpb1) : 0u;
+        d.layer = 0;
+        LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k_tr3_layer1<LPR_>), dim3(rows_grid(n, rpb1) + seg_blocks), dim3(TR_BLOCK), 0,
+                                                 st, n, g->rowptr, g->col, g->val, t->S1, Hp1, H1, t->b1p, d, t->H1d, have_long,
+                                                 (int)seg_blocks, g->p_n_seg, g->p_seg_long, g->p_seg_begin, g->p_long_row,
+                                                 t->seg_part));
+        LT_CHECK_LAUNCH();
+        if (have_long) {
+            LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k_tr3_layer1_long<LPR_>), dim3(rows_grid(g->p_n_long, rpb1)),
+                                                     dim3(TR_BLOCK), 0, st, g->p_n_long, g->p_long_row, g->p_long_segptr,
+                                                     t->seg_part, Hp1, H1, d, t->H1d));
+            LT_CHECK_LAUNCH();
+        }
+    }
+    // layers 2 and 3: the 2-layer trainer's chain
+    rc = lt_launch_gemm(t->H1d, Hp1, W2, H2, t->S2, Hp2, n, H2, H1, st);
+    if (rc) return rc;
+    rc = lt_launch_layer1(g, t->S2, Hp2, t->b2p, t->W3p, C, t->Z2, t->S3, st, t->seg_part);
+    if (rc) return rc;
+    d.layer = 1;
+    LT_DISPATCH_LPR(lpr2, LT_DISPATCH_CP(cp,
+        hipLaunchKernelGGL((k_tr_dropout<LPR_, CP_>), dim3(rows_grid(n, rpb2)), dim3(TR_BLOCK), 0, st, n, t->Z2, Hp2, H2, t->W3p,
+                           C, d, t->H2d, t->S3)));
+    LT_CHECK_LAUNCH();
+    rc = lt_launch_layer2(g, t->S3, C, b3, t->Z3, st);
+    if (rc) return rc;
+    // loss head
+    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_ce<CP_>), dim3(rows_grid(n, TR_BLOCK)), dim3(TR_BLOCK), 0, st, n, t->Z3, C,
+                                          t->labels, 1.0f / (float)n, t->loss_r, t->corr_r, t->dZ3));
+    LT_CHECK_LAUNCH();
+    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_ce_reduce<CP_>), dim3(1), dim3(TR_BLOCK), 0, st, n, C, t->loss_r, t->corr_r,
+                                          t->dZ3, record, gb3));
+    LT_CHECK_LAUNCH();
+    // backward through layer 3
+    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_spmm_t_narrow<CP_>), dim3(rows_grid(n, TR_BLOCK / LT_L2_LANES)),
+                                          dim3(TR_BLOCK), 0, st, n, g->tptr, g->trow, g->tval, t->dZ3, C, t->dS3));
+    LT_CHECK_LAUNCH();
+    int W = 1;
+    while (W < Hp2) W <<= 1;
+    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_bwd_rows<CP_>), dim3((unsigned)t->n_part), dim3(TR_BLOCK), 0, st, n, H2, Hp2, W,
+                                          C, t->H2d, t->dS3, t->W3p, scale, t->dZ2, t->part));
+    LT_CHECK_LAUNCH();
+    const int L = H2 + H2 * C;   // db2 | dW3: adjacent in the gradient buffer
+    hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((L + 63) / 64)), dim3(TR_BLOCK), 0, st, t->part, t->n_part, L, gb2);
+    LT_CHECK_LAUNCH();
+    // backward through layer 2
+    LT_DISPATCH_LPR(lpr2, hipLaunchKernelGGL((k_tr_spmm_t_wide<LPR_>), dim3(rows_grid(n, rpb2)), dim3(TR_BLOCK), 0, st, n,
+                                             g->tptr, g->trow, g->tval, t->dZ2, Hp2, t->dS2));
+    LT_CHECK_LAUNCH();
+    rc = launch_tn(t->H1d, (long)Hp1, t->dS2, (long)Hp2, gW2, H1, H2, n, t->tn2_kslice, t->tn2_splits, t->tn2_slabs, st);
+    if (rc) return rc;
+    {
+        dim3 grid((unsigned)t->n_mblk, (unsigned)((H1 + TN_BN - 1) / TN_BN));
+        hipLaunchKernelGGL(k_tr3_dz_mfma, grid, dim3(256), 0, st, t->dS2, (long)Hp2, W2, (long)H2, t->H1d, t->dZ1, (long)Hp1, n,
+                           H1, H2, scale, t->part1);
+        LT_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((H1 + 63) / 64)), dim3(TR_BLOCK), 0, st, t->part1, t->n_mblk, H1, gb1);
+    LT_CHECK_LAUNCH();
+    // backward through layer 1
+    LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k_tr_spmm_t_wide<LPR_>), dim3(rows_grid(n, rpb1)), dim3(TR_BLOCK), 0, st, n,
+                                             g->tptr, g->trow, g->tval, t->dZ1, Hp1, t->dS1));
+    LT_CHECK_LAUNCH();
+    rc = launch_tn(t->X, (long)t->ldx, t->dS1, (long)Hp1, gW1, F, H1, n, t->tn1_kslice, t->tn1_splits, t->tn1_slabs, st);
+    if (rc) return rc;
+    // Adam
+    const int64_t step = t->epoch + 1;
+    lt_tr3_tensors T;
+    for (int k = 0; k < 6; ++k) { T.p[k] = t->P[k]; T.o[k] = t->off[k]; }
+    T.b1p = t->b1p; T.b2p = t->b2p; T.W3p = t->W3p;
+    hipLaunchKernelGGL(k_tr3_adam, dim3((unsigned)((t->off[5] + 255) / 256)), dim3(256), 0, st, T, t->grad, t->m, t->v,
+                       adam_scalars(step, t->lr, 0.9, 0.999, 1e-8, t->wd));
+    LT_CHECK_LAUNCH();
+    t->epoch = step;
+    return LT_OK;
+}
+
+extern "C" int lt_gcn3_trainer_run(lt_gcn3_trainer *t, int32_t n_epochs, float *record, void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_run: trainer is NULL");
+    LT_REQUIRE(n_epochs >= 0, "lt_gcn3_trainer_run: n_epochs=%d", n_epochs);
+    if (n_epochs == 0) return LT_OK;
+    LT_REQUIRE(record != nullptr, "lt_gcn3_trainer_run: record is NULL");
+    LT_REQUIRE(t->epoch + n_epochs <= (int64_t)UINT32_MAX, "lt_gcn3_trainer_run: epoch counter would pass 2^32");
+    hipStream_t st = (hipStream_t)stream;
+    // the borrowed parameters may have changed since the last run: the mirrors from them (Adam keeps them current after that)
+    const int mx = t->Hp1 > t->Hp2 * t->C ? t->Hp1 : t->Hp2 * t->C;
+    hipLaunchKernelGGL(k_tr3_pad, dim3((mx + 255) / 256), dim3(256), 0, st, t->P[1], t->H1, t->Hp1, t->P[3], t->H2, t->Hp2,
+                       t->P[4], t->C, t->b1p, t->b2p, t->W3p);
+    LT_CHECK_LAUNCH();
+    for (int32_t j = 0; j < n_epochs; ++j) {
+        const int rc = run_epoch3(t, record + 2 * (size_t)j, st);
+        if (rc) return rc;
+    }
+    return LT_OK;
+}
+
+extern "C" int lt_gcn3_trainer_grads(const lt_gcn3_trainer *t, float *dW1, float *db1, float *dW2, float *db2, float *dW3,
+                                     float *db3, void *stream) {
+    LT_REQUIRE(t != nullptr && dW1 && db1 && dW2 && db2 && dW3 && db3, "lt_gcn3_trainer_grads: NULL argument");
+    float *dst[6] = {dW1, db1, dW2, db2, dW3, db3};
+    for (int k = 0; k < 6; ++k) {
+        const int64_t b = k ? t->off[k - 1] : 0;
+        LT_HIP(hipMemcpyAsync(dst[k], t->grad + b, (size_t)(t->off[k] - b) * sizeof(float), hipMemcpyDeviceToDevice,
+                              (hipStream_t)stream));
+    }
+    return LT_OK;
+}
+
+extern "C" int lt_gcn3_trainer_logits(const lt_gcn3_trainer *t, float *Z3, int64_t ldz, void *stream) {
+    LT_REQUIRE(t != nullptr && Z3 != nullptr, "lt_gcn3_trainer_logits: NULL argument");
+    LT_REQUIRE(ldz >= t->C, "lt_gcn3_trainer_logits: ldz=%lld < C=%d", (long long)ldz, t->C);
+    LT_HIP(hipMemcpy2DAsync(Z3, (size_t)ldz * sizeof(float), t->Z3, (size_t)t->C * sizeof(float), (size_t)t->C * sizeof(float),
+                            (size_t)t->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return LT_OK;
+}
+
+extern "C" int lt_gcn3_trainer_hidden(const lt_gcn3_trainer *t, int32_t layer, float *dst, int64_t ld, void *stream) {
+    LT_REQUIRE(t != nullptr && dst != nullptr, "lt_gcn3_trainer_hidden: NULL argument");
+    LT_REQUIRE(layer == 1 || layer == 2, "lt_gcn3_trainer_hidden: layer=%d, must be 1 or 2", layer);
+    const int H = layer == 1 ? t->H1 : t->H2, Hp = layer == 1 ? t->Hp1 : t->Hp2;
+    LT_REQUIRE(ld >= H, "lt_gcn3_trainer_hidden: ld=%lld < H%d=%d", (long long)ld, layer, H);
+    LT_HIP(hipMemcpy2DAsync(dst, (size_t)ld * sizeof(float), layer == 1 ? t->H1d : t->H2d, (size_t)Hp * sizeof(float),
+                            (size_t)H * sizeof(float), (size_t)t->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return LT_OK;
 }

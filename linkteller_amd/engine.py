@@ -602,6 +602,92 @@ class GCN2Trainer:
         return out
 
 
+class GCN3Trainer:
+    """Training of the 3-layer GCN3 on the GPU (lt_gcn3_trainer_*): the epoch of ``GCN2Trainer`` one layer up -- two hidden
+    layers with independent Philox masks (the counter's layer word), the backward through the middle layer on the matrix
+    cores, one Adam launch over the six tensors -- as stream-ordered launches on torch's current stream and no host
+    synchronisation.  ``w1 .. b3`` are updated IN PLACE (version counters bumped after every ``run``).  Limits: hidden
+    widths <= 256, classes <= 8."""
+
+    def __init__(self, adj, x, labels, w1, b1, w2, b2, w3, b3, *, lr, weight_decay, dropout, seed):
+        if not 0.0 <= float(dropout) <= 1.0:      # F.dropout's message
+            raise ValueError(f"dropout probability has to be between 0 and 1, but got {dropout}")
+        self.graph: HipGraph = as_hip_graph(adj)
+        self.x = _f32(x, "x")
+        names = ("W1", "b1", "W2", "b2", "W3", "b3")
+        self.params = [_f32(t, n) for t, n in zip((w1, b1, w2, b2, w3, b3), names)]
+        for t, src in zip(self.params, (w1, b1, w2, b2, w3, b3)):
+            if t.data_ptr() != src.data_ptr():
+                raise ValueError("the parameters are updated in place: pass contiguous float32 device tensors")
+        self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = self.params
+        n, f = self.x.shape
+        self.n, self.f, self.h1, self.h2, self.c = n, f, self.w1.shape[1], self.w2.shape[1], self.w3.shape[1]
+        if (n != self.graph.n or self.w1.shape != (f, self.h1) or self.b1.shape != (self.h1,)
+                or self.w2.shape != (self.h1, self.h2) or self.b2.shape != (self.h2,)
+                or self.w3.shape != (self.h2, self.c) or self.b3.shape != (self.c,)):
+            raise ValueError("inconsistent GCN3 shapes")
+        if self.graph.device_index != self.x.device.index:
+            raise ValueError(f"the graph lives on cuda:{self.graph.device_index}, the features on {self.x.device}")
+        _require_finite(features=self.x, **dict(zip(names, self.params)))
+        if not isinstance(labels, torch.Tensor):
+            labels = torch.as_tensor(labels)
+        labels = labels.reshape(-1)
+        if labels.numel() != n:
+            raise ValueError(f"labels: {labels.numel()} entries for {n} nodes")
+        if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= self.c):
+            raise ValueError(f"labels outside [0, {self.c})")
+        self.labels = labels.to(device=self.x.device, dtype=torch.int32).contiguous()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().lt_gcn3_trainer_create(self.graph.handle, self.x.data_ptr(), f, f, self.labels.data_ptr(),
+                                                     self.h1, self.h2, self.c, *[t.data_ptr() for t in self.params],
+                                                     float(lr), float(weight_decay), float(dropout),
+                                                     int(seed) & (2**64 - 1), _stream(), C.byref(h)),
+                   "lt_gcn3_trainer_create")
+        self._h = h
+        self._finalizer = weakref.finalize(self, _lib.lib().lt_gcn3_trainer_destroy, h)
+
+    @property
+    def epoch(self) -> int:
+        e = C.c_int64()
+        _lib.check(_lib.lib().lt_gcn3_trainer_epoch(self._h, C.byref(e)), "lt_gcn3_trainer_epoch")
+        return e.value
+
+    def run_async(self, epochs: int) -> torch.Tensor:
+        """Enqueue ``epochs`` epochs; returns the device record [epochs, 2] (mean loss, correct count) without syncing."""
+        record = torch.empty((max(int(epochs), 0), 2), dtype=torch.float32, device=self.x.device)
+        _lib.check(_lib.lib().lt_gcn3_trainer_run(self._h, int(epochs), record.data_ptr(), _stream()), "lt_gcn3_trainer_run")
+        for p in self.params:
+            torch.autograd.graph.increment_version(p)
+        return record
+
+    def run(self, epochs: int):
+        """Run ``epochs`` epochs; returns (loss [epochs] float32, correct [epochs] int64) as CPU arrays (one read at the end)."""
+        rec = self.run_async(epochs).cpu().numpy()
+        return rec[:, 0].copy(), rec[:, 1].astype("int64")
+
+    def grads(self):
+        """(dW1, db1, dW2, db2, dW3, db3) of the last epoch (before weight decay)."""
+        out = [torch.empty_like(p) for p in self.params]
+        _lib.check(_lib.lib().lt_gcn3_trainer_grads(self._h, *[t.data_ptr() for t in out], _stream()), "lt_gcn3_trainer_grads")
+        return tuple(out)
+
+    def logits(self) -> torch.Tensor:
+        """The last epoch's train-mode logits (both dropouts applied, before that epoch's update)."""
+        out = torch.empty((self.n, self.c), dtype=torch.float32, device=self.x.device)
+        _lib.check(_lib.lib().lt_gcn3_trainer_logits(self._h, out.data_ptr(), self.c, _stream()), "lt_gcn3_trainer_logits")
+        return out
+
+    def hidden(self, layer: int) -> torch.Tensor:
+        """The last epoch's hidden activations after ReLU and dropout: layer 1 -> H1d [n, H1], layer 2 -> H2d [n, H2]."""
+        if layer not in (1, 2):
+            raise ValueError(f"layer must be 1 or 2, got {layer}")
+        width = self.h1 if layer == 1 else self.h2
+        out = torch.empty((self.n, width), dtype=torch.float32, device=self.x.device)
+        _lib.check(_lib.lib().lt_gcn3_trainer_hidden(self._h, int(layer), out.data_ptr(), width, _stream()),
+                   "lt_gcn3_trainer_hidden")
+        return out
+
+
 def fused_shapes(h: int, c: int) -> bool:
     """What lt_baseline_create / lt_influence_rows are built for (one pass of the row kernels, fused layer-2 epilogue)."""
     return h <= 256 and c <= 8

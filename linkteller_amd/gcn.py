@@ -5,8 +5,9 @@ Same class names, constructor arguments, parameter names/shapes (``gc1.weight [F
 trained with the reference loads unchanged (gcn_trainer.py:102-105).  ``forward(x, adj)`` accepts
 what the reference passes (a dense float tensor and a torch sparse COO adjacency) or a
 ``HipGraph``; inference runs through liblinkteller_hip.  Autograd through these layers is refused
-rather than silently served by another backend; the 2-layer GCN is trained by the fused HIP trainer
-(``engine.GCN2Trainer``, ``GCNTrainer.train``, ``main --train``).
+rather than silently served by another backend; the models are trained by the fused HIP trainers: the 2-layer
+GCN by ``engine.GCN2Trainer`` (``GCNTrainer.train``, ``main --train``), the 3-layer GCN3 by ``engine.GCN3Trainer``
+(``GCNTrainer.init_model(); .train()`` with ``--n-layer 3``).
 """
 from __future__ import annotations
 
@@ -22,7 +23,7 @@ def _refuse_training(module):
     if module.training and torch.is_grad_enabled():
         raise NotImplementedError(
             "linkteller_amd implements the inference/attack hot path only; call model.eval() and/or "
-            "torch.no_grad().  Train with engine.GCN2Trainer (main --train) or load a state_dict.")
+            "torch.no_grad().  Train with engine.GCN2Trainer (main --train) or engine.GCN3Trainer (GCNTrainer.train with --n-layer 3), or load a state_dict.")
 
 
 class GraphConvolution(nn.Module):

@@ -1,6 +1,6 @@
 """``GCNTrainer`` (reference gcn_trainer.py:23-110, 113-243, 262-284, 320-406): build the model, either load a
-``state_dict`` or train the 2-layer GCN on the GPU (``engine.GCN2Trainer``: forward, cross-entropy, backward and Adam as HIP
-kernels), one clean forward for the utility metrics, dispatch to ``Attacker``.
+``state_dict`` or train the model on the GPU (``engine.GCN2Trainer`` / ``engine.GCN3Trainer``: forward, cross-entropy,
+backward and Adam as HIP kernels), one clean forward for the utility metrics, dispatch to ``Attacker``.
 
 Training differs from the reference in two documented ways: dropout draws a Philox4x32-10 mask keyed by ``--seed`` and the
 epoch (include/linkteller_hip.h), not torch's generator; and no TensorBoard logs are written (``tensorboard`` is not a
@@ -46,20 +46,19 @@ class GCNTrainer:
             self.model.load_state_dict(torch.load(model_path, map_location="cpu"))
             print("load model from {} done!".format(model_path))
             self.model_path = model_path
-        elif a.n_layer != 2:
-            raise NotImplementedError("training is implemented for the 2-layer GCN only (--n-layer 2)")
         if torch.cuda.is_available():
             self.model.cuda()
         if not model_path:
             # the optimizer state of gcn_trainer.py:106-108: Adam's moments live in the GPU trainer, which updates the
             # model's parameters in place
-            from .engine import GCN2Trainer
+            from .engine import GCN2Trainer, GCN3Trainer
             if not w.transfer:
                 raise NotImplementedError(f"dataset = {self.dataset}: training is implemented for transfer datasets")
-            g1, g2 = self.model.gc1, self.model.gc2
-            self.gpu_trainer = GCN2Trainer(w.adj_1, w.features_1, w.labels_1, g1.weight.detach(), g1.bias.detach(),
-                                           g2.weight.detach(), g2.bias.detach(), lr=a.lr, weight_decay=a.weight_decay,
-                                           dropout=a.dropout, seed=a.seed)
+            layers = [self.model.gc1, self.model.gc2] + ([self.model.gc3] if a.n_layer == 3 else [])
+            params = [t.detach() for g in layers for t in (g.weight, g.bias)]
+            self.gpu_trainer = (GCN3Trainer if a.n_layer == 3 else GCN2Trainer)(
+                w.adj_1, w.features_1, w.labels_1, *params, lr=a.lr, weight_decay=a.weight_decay, dropout=a.dropout,
+                seed=a.seed)
 
     def train(self):
         """gcn_trainer.py:200-243 on a transfer dataset: ``num_epochs`` epochs on (features_1, adj_1, labels_1), the
