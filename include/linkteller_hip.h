@@ -36,7 +36,8 @@ extern "C" {
                             profile classes 9-11.  3: lt_influence_rows_vec + lt_wide_combine (layers wider than one pass of the fused
                             kernels), lt_spmm_gather_ceiling (measurement support); every version-2 entry point is unchanged.
                             Additive within 5: training of the 2-layer GCN (lt_gcn2_trainer_*) and lt_adam_step; no entry point changed.
-                            Additive within 5: training of the 3-layer GCN (lt_gcn3_trainer_*); no entry point changed */
+                            Additive within 5: training of the 3-layer GCN (lt_gcn3_trainer_*); no entry point changed.
+                            Additive within 5: edge recovery (lt_top_pairs_lower, profile classes 12-13); no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -450,6 +451,28 @@ int lt_influence3_rows_mode(const lt_baseline3 *b, const int32_t *probe_nodes, i
 int lt_lapgraph_select(int32_t n, const int32_t *lower_rowptr, const int32_t *lower_col, double *cells, int64_t n_keep,
                        int64_t *out_idx, void *work, size_t work_bytes, double *threshold_out, void *stream);
 
+/* ---- edge recovery: the m highest-scoring pairs of sampled nodes (attack_stats_all.py:106-116: n_pos = ceil(ratio * n_total),
+ * ind = np.argpartition(pred, -n_pos)[-n_pos:] over the saved score list, then precision / recall / F1 of y[ind]) -----------
+ * scores: device [n, lds] fp32, what lt_influence_rows / lt_influence3_rows* wrote for probes == observed == the sampled nodes.
+ * Only the cells (i, j) with j < i are read -- row = perturbed node, column = observed node, the cells the reference scores
+ * its sampled pairs from (attacker.py:235-245); the diagonal, the upper triangle and columns n .. lds - 1 are never read.
+ * The cells are ranked by the total order "value descending, then flat index i * n + j ascending", in which -0.0 counts as
+ * +0.0 (the key is taken of v + 0.0f; negative values and +-inf rank as numbers).  out_idx[0 .. m): the flat indices i * n + j
+ * of the m first cells in that order, written in ASCENDING flat index; out_score[k]: the value at out_idx[k], bit for bit as
+ * stored (a stored -0.0 stays -0.0).  out_info (int64 [4], device): [0] the bit pattern of the m-th value (of v + 0.0f,
+ * zero-extended), [1] the cells strictly above it, [2] the cells tied at it that were taken (the first so many in flat order),
+ * [3] the cells tied at it in total; [1] + [2] == m.  The output is a pure function of the input: two calls give identical
+ * bytes (np.argpartition picks among tied values as its partition happens to leave them).  A matrix holding NaNs gives an
+ * unspecified set; exactly m in-region indices are written all the same.
+ * Enqueue only, no synchronisation, no host round trip: a radix select by four digit histograms (the pick of each digit is the
+ * prologue of the next launch), then count / scan / write launches of an ordered compaction; stream order is the only barrier
+ * between blocks.  LT_ERR_INVALID before anything is enqueued: NULL pointers, n < 2, lds < n, m outside [1, n (n - 1) / 2], a
+ * workspace smaller than lt_top_pairs_workspace_bytes(n, m) or not 8-byte aligned.  The query returns 0 for invalid arguments.
+ * Additive in ABI 5. */
+size_t lt_top_pairs_workspace_bytes(int32_t n, int64_t m);
+int lt_top_pairs_lower(const float *scores, int64_t lds, int32_t n, int64_t m, int64_t *out_idx, float *out_score,
+                       int64_t *out_info, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- training of the 2-layer GCN (reference gcn_trainer.py:144-170 train_one_epoch + optim.Adam) ----
  * lt_gcn2_trainer_create borrows the graph, X [n, ldx], labels (int32 [n], device, each in [0, C)) and the four parameter
  * tensors (W1 [F, H], b1 [H], W2 [H, C], b2 [C], dense fp32 device buffers), which every epoch updates IN PLACE; it owns
@@ -545,7 +568,9 @@ typedef enum lt_kernel_id {
     LT_K_FP64_PRODUCT = 9,/* S1d = X*W1 in fp64: k_s1d_feature_rows (+ the reference row's product), or k_gemm_f64acc_128 + k_sum_slabs_f64 */
     LT_K_FP64_SPMM = 10,  /* Z1d = A_hat*S1d + b1: k_spmm_f64 / k_rows_tiled_f64 (+ long-row combine) */
     LT_K_ITEM_BITS = 11,  /* k_item_bits (+ the pair-mark kernels): item offsets, (probe, row) table, membership bitmap */
-    LT_K_COUNT = 12
+    LT_K_SELECT_HIST = 12,    /* lt_top_pairs_lower: the clear of its workspace header + the four k_sel_hist digit passes */
+    LT_K_SELECT_COLLECT = 13, /* lt_top_pairs_lower: k_sel_count + k_sel_scan + k_sel_write (the ordered compaction) */
+    LT_K_COUNT = 14
 } lt_kernel_id;
 int lt_profile_enable(int mask);
 int lt_profile_reset(void);

@@ -91,6 +91,9 @@ SIGNATURES = {
                                      C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "lt_lapgraph_select": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.POINTER(C.c_double), C.c_void_p]),
+    "lt_top_pairs_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "lt_top_pairs_lower": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_size_t, C.c_void_p]),
     "lt_baseline3_enable_fp64": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lt_influence3_rows_mode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -122,7 +125,8 @@ SIGNATURES = {
     "lt_profile_summary": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
 }
 KERNEL_IDS = {"gemm": 0, "layer1": 1, "layer2": 2, "perturb": 3, "full_stageA": 4, "full_stageB": 5,
-              "item_stageA": 6, "item_stageB": 7, "spmm": 8, "fp64_product": 9, "fp64_spmm": 10, "item_bits": 11}
+              "item_stageA": 6, "item_stageB": 7, "spmm": 8, "fp64_product": 9, "fp64_spmm": 10, "item_bits": 11,
+              "select_hist": 12, "select_collect": 13}
 ABI_VERSION = 5
 
 

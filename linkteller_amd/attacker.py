@@ -438,6 +438,74 @@ class Attacker:
         self.compute_and_save(list(s_ex[oe]), list(s_nex[on]))
 
     # ------------------------------------------------------------------------------------------
+    def recover_edges(self, beliefs=None, mode=None) -> dict:
+        """The attack's edge list (the reference's post-processing script, attack_stats_all.py:44-116): under a belief k about the
+        density of the sampled subgraph, the m = ceil(k n (n - 1) / 2) highest-scoring pairs of sampled nodes are predicted as
+        edges.  ``beliefs=None``: the reference's ladder r/4 .. 4r around the subgraph's true density (``recover.density_ladder``).
+        The n_test x n_test rows are formed on the device (``_rows``: every model kind it serves) and stay there: ONE
+        ``engine.top_pairs_lower`` call selects the largest m of the beliefs from their strict lower triangle -- cell (i, j), j < i,
+        is the pair (test_nodes[j], test_nodes[i]) scored by perturbing test_nodes[i], as ``link_prediction_attack_efficient``
+        reads it -- and m indices and scores cross PCIe instead of the matrix.  The order (score descending, then cell index) is
+        total, so a smaller belief's prediction is a prefix of the ranked list.  Needs ``prepare_test_data()`` with an
+        ``unbalanced*`` sample type.  With several ranks every rank forms all rows itself: no collective of its own to mismatch."""
+        from . import recover
+        st = str(self.args.sample_type)
+        if not st.startswith("unbalanced"):
+            raise NotImplementedError(f"recover_edges: sample_type = {st} has no all-pairs square of sampled nodes "
+                                      f"(unbalanced, unbalanced-lo, unbalanced-hi do)")
+        nodes = np.asarray(self.test_nodes, dtype=np.int64)
+        n = len(nodes)
+        if n < 2:
+            raise ValueError("recover_edges: fewer than two sampled nodes")
+        n_total = n * (n - 1) // 2
+        n_edges = len(self.exist_edges)
+        beliefs = recover.density_ladder(n_edges, n) if beliefs is None else [float(b) for b in beliefs]
+        counts = recover.belief_counts(beliefs, n_total)
+        m = int(counts.max())
+        probes, observed = self._device_nodes(nodes, 0, n)
+        rows = self._rows(probes, observed, mode)
+        idx_d, val_d, info = engine.top_pairs_lower(rows, m)
+        idx, val, raw = idx_d.cpu().numpy(), val_d.cpu().numpy(), info["raw"].cpu().numpy()
+        engine.node_check()
+        order = np.lexsort((idx, -val.astype(np.float64)))      # ascending cell index -> rank order
+        idx, val = idx[order], val[order]
+        ci, cj = idx // n, idx % n
+        import scipy.sparse as sp
+        adj = sp.csr_matrix(self.worker.adj_ori)
+        pattern = sp.csr_matrix((np.ones(adj.indices.shape[0], dtype=np.int8), adj.indices, adj.indptr), shape=adj.shape)
+        u, v = nodes[cj], nodes[ci]
+        present = np.asarray(pattern[u, v]).reshape(-1) != 0     # structural presence of v in row u, as edge_sets_among_nodes reads it
+        stats = recover.recovery_stats(present, n_edges, counts)
+        self.recovered = {
+            "pairs": np.stack([u, v], axis=1).astype(np.int64), "scores": val.astype(np.float64), "is_edge": present,
+            "beliefs": list(beliefs), "counts": counts, "precision": stats["precision"], "recall": stats["recall"],
+            "f1": stats["f1"], "tp": stats["tp"],
+            "threshold": float(np.array([raw[0]], dtype=np.int64).astype(np.uint32).view(np.float32)[0]),
+            "n_edges": n_edges, "n_total": n_total,
+            "above": int(raw[1]), "tied_taken": int(raw[2]), "tied_total": int(raw[3]),
+        }
+        return self.recovered
+
+    def recovered_filename(self):
+        name = self.result_filename()
+        return osp.join(osp.dirname(name), "recover_" + osp.basename(name))
+
+    def save_recovered(self):
+        """The dict of ``recover_edges`` next to the attack's result file (``eval_<dataset>/recover_<result file>``), one printed
+        line per belief.  Rank 0 only."""
+        rank, _ = lt_dist.world()
+        if rank != 0:
+            return
+        r = self.recovered
+        for k, b in enumerate(r["beliefs"]):
+            print(f"belief = {b:.6g}, m = {int(r['counts'][k])}, tp = {int(r['tp'][k])}, precision = {r['precision'][k]:.4f}, "
+                  f"recall = {r['recall'][k]:.4f}, f1 = {r['f1'][k]:.4f}")
+        filename = self.recovered_filename()
+        os.makedirs(osp.dirname(filename), exist_ok=True)
+        torch.save(r, filename)
+        print(f"recovered edges saved to: {filename}")
+
+    # ------------------------------------------------------------------------------------------
     def _baseline_vectors(self):
         """attacker.py:295-303: softmax posteriors (sigmoid for ppi) or the raw features, float32 on host."""
         am = self.args.attack_mode

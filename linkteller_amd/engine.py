@@ -785,6 +785,50 @@ def group_pairs(probe, observed):
     return nodes.astype(np.int32), pair_ptr, observed[order].astype(np.int32), order
 
 
+_select_ws = {}      # top_pairs_lower's workspace: only the latest (device, size) is kept, sizes repeat across calls
+
+
+def top_pairs_lower(scores: torch.Tensor, m: int):
+    """The ``m`` highest-scoring cells (i, j), j < i, of an n x n fp32 score matrix on the device (lt_top_pairs_lower; the
+    reference's ``np.argpartition(pred, -n_pos)[-n_pos:]``, attack_stats_all.py:106-116) -> ``(idx, score, info)``:
+    ``idx`` int64 [m], the flat indices ``i * n + j`` in ascending order; ``score`` fp32 [m], the stored values at them;
+    ``info``: ``threshold_bits`` (bit pattern of the m-th value), ``above``, ``tied_taken``, ``tied_total`` as 0-d int64 device
+    tensors and all four as ``raw`` -- nothing is brought to the host here.  Cells are ranked by value descending, then flat index
+    ascending (-0.0 as +0.0): a tied threshold -- the zeros of an influence matrix -- is cut at the same cells on every call.
+    ``scores`` may be a view with a row stride > n (last-dimension stride 1); nothing outside the strict lower triangle is read."""
+    if not isinstance(scores, torch.Tensor):
+        raise TypeError("scores must be a torch.Tensor")
+    if not scores.is_cuda:
+        raise _lib.LinkTellerHipError(f"scores must live on the GPU (got {scores.device}); there is no CPU path")
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.shape[0] != scores.shape[1]:
+        raise TypeError(f"scores must be a square 2-d float32 tensor, got {scores.dtype} {tuple(scores.shape)}")
+    n = int(scores.shape[0])
+    if n > 1 and scores.stride(1) != 1:
+        raise ValueError("scores must have last-dimension stride 1 (rows may be strided)")
+    m = int(m)
+    total = n * (n - 1) // 2
+    if n < 2 or not 1 <= m <= total:
+        raise ValueError(f"m={m} outside [1, {total}] for n={n}")
+    lds = int(scores.stride(0))
+    if lds < n:
+        raise ValueError(f"row stride {lds} smaller than n={n}")
+    dev = scores.device
+    idx = torch.empty(m, dtype=torch.int64, device=dev)
+    val = torch.empty(m, dtype=torch.float32, device=dev)
+    raw = torch.empty(4, dtype=torch.int64, device=dev)
+    need = _lib.lib().lt_top_pairs_workspace_bytes(n, m)
+    key = (dev, need)
+    ws = _select_ws.get(key)
+    if ws is None:
+        ws = _workspace(need, dev)
+        _select_ws.clear()
+        _select_ws[key] = ws
+    _lib.check(_lib.lib().lt_top_pairs_lower(scores.data_ptr(), lds, n, m, idx.data_ptr(), val.data_ptr(), raw.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), _stream()), "lt_top_pairs_lower")
+    info = {"threshold_bits": raw[0], "above": raw[1], "tied_taken": raw[2], "tied_total": raw[3], "raw": raw}
+    return idx, val, info
+
+
 def export_rows_f64(rows: torch.Tensor):
     """The finished rows as a float64 numpy array on the host (the reference's ``influence_val = np.zeros(...)`` filled by
     n_test**2 ``.item()`` round trips, attacker.py:216-229) -- ONE launch that widens on the device and writes straight into

@@ -44,11 +44,16 @@ _OPTIONS = {
     # (scores / AUC / AP equal the reference evaluated in fp64); 'sparse' is the reference's fp32 finite difference
     # restricted to the rows a probe can change, bit-identical to 'full' (every probe a full forward); where ./data lives
     "influence-mode": (str, "delta", ["full", "sparse", "delta"]), "data-root": (str, "./data"),
+    # addition: with --recover, a single density belief k > 0 instead of the ladder r/4 .. 4r (0 = the ladder)
+    "density-belief": (float, 0.0),
 }
 _SWITCHES = ["no-cuda", "fastmode", "approx", "attack", "test", "break-down", "display", "same-size",
              "eval-degree", "trainable", "early", "fnormalize",
              # addition: train (as the reference does without --test), then test, and attack with --attack
-             "train"]
+             "train",
+             # addition: after the efficient attack on an unbalanced* sample, recover the edge list under a density belief
+             # (Attacker.recover_edges; the reference's attack_stats_all.py) and save it next to the result file
+             "recover"]
 
 
 def build_parser():
@@ -102,8 +107,22 @@ def init_distributed():
     return True
 
 
+def check_recover(args):
+    """``--recover`` is served after ``--attack --attack-mode efficient`` on an ``unbalanced*`` sample only; anything else is
+    refused here, before a Worker is built or the GPU is touched."""
+    if not getattr(args, "recover", False):
+        return
+    if not (args.attack and args.attack_mode == "efficient" and str(args.sample_type).startswith("unbalanced")):
+        raise NotImplementedError("--recover needs --attack --attack-mode efficient and --sample-type unbalanced / unbalanced-lo / "
+                                  f"unbalanced-hi (got attack={args.attack}, attack-mode={args.attack_mode}, "
+                                  f"sample-type={args.sample_type})")
+    if args.density_belief < 0:
+        raise ValueError(f"--density-belief {args.density_belief}: a density belief is > 0 (0 = the ladder around the true density)")
+
+
 def main(argv=None):
     args = get_arguments(argv)
+    check_recover(args)
     import os
     if args.train and not args.test:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:

@@ -109,6 +109,8 @@ class GCNTrainer:
     def eval_output(self, output, mode="clean", eval_degree=False):
         a = self.args
         if a.attack:
+            if getattr(a, "recover", False) and not (a.attack_mode == "efficient" and str(a.sample_type).startswith("unbalanced")):
+                raise NotImplementedError("recover: served after the efficient attack on an unbalanced* sample only")
             self.attacker = Attacker(args=a, model=self.model, worker=self.worker)
             self.attacker.prepare_test_data()
             t = time.time()
@@ -127,6 +129,10 @@ class GCNTrainer:
             else:
                 raise NotImplementedError(f"attack_mode = {a.attack_mode} not implemented!")
             print(f"attacks done using {time.time() - t} seconds!")
+            if getattr(a, "recover", False):                      # addition (main.check_recover: efficient + unbalanced* only)
+                belief = float(getattr(a, "density_belief", 0.0) or 0.0)
+                self.attacker.recover_edges(beliefs=[belief] if belief > 0 else None)
+                self.attacker.save_recovered()
         labels = self.worker.labels_2
         loss_test = F.cross_entropy(output, labels.squeeze())
         acc = self.rare_class_f1(output, labels)
