@@ -105,7 +105,7 @@ int lt_device_count(int *count);
  *                         product rows whenever that launch runs (a refreshed baseline on the feature-difference route: CU slots to
  *                         spare, seven times the duration) (default), 0 = in the pre-activation's launch.  Bit-identical
  *   "feature_ring"        feature-difference route: the product rows by the persistent LDS-ring kernel (two workgroups per CU, a row in
- *                         flight by LDS-DMA ahead of the row a wave works on, rows claimed from counters; rows 8-byte aligned,
+ *                         flight by LDS-DMA ahead of the row a wave works on, rows claimed from counters; rows 8-byte aligned, W1 16-byte aligned,
  *                         H % 4 == 0, 2046 <= F <= 3326): 0 = never (one wave per row; default -- the ring form measured 25.6 us
  *                         against 22.0 at twitch size, profiles/r06_ring_lab.txt), 1 = whenever the shapes allow, negative = when
  *                         they do and the matrix has at least "feature_ring_min_rows" rows.  fp64 summation order only (as with
@@ -217,6 +217,7 @@ int lt_spmm_route(const lt_graph *g, int32_t ncols);
 
 /* ---- 2-layer GCN forward (GCN.forward, gcn/models.py:19-24, eval mode) ------------------
  * logits[n,C] = A_hat * (relu(A_hat * (X*W1) + b1) * W2) + b2.   H <= 256, C <= 8.
+ * logits is written with leading dimension ldl >= C (columns C .. ldl - 1 are left as they are).
  * lt_gcn2_workspace_bytes: size of the scratch the call needs (S1, S2, split-K partials). */
 size_t lt_gcn2_workspace_bytes(int32_t n, int32_t F, int32_t H, int32_t C);
 int lt_gcn2_forward(const lt_graph *g, const float *X, int64_t ldx, int32_t F,

@@ -157,7 +157,7 @@ template <int CP>
 __device__ __forceinline__ void layer2_long_row(
     int r, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ S2, int C, const float *__restrict__ b2,
-    float *__restrict__ OUT) {
+    float *__restrict__ OUT, long ldo) {
     __shared__ float sv[LT_L2_CHUNK];
     __shared__ float sT[LT_L2_CHUNK][CP];
     const int e0 = rowptr[r], e1 = rowptr[r + 1];
@@ -205,7 +205,7 @@ __device__ __forceinline__ void layer2_long_row(
         if (tid == 0) {
 #pragma unroll
             for (int c = 0; c < CP; ++c)
-                if (c < C) OUT[(size_t)r * C + c] = acc[c] + b2[c];
+                if (c < C) OUT[(size_t)r * ldo + c] = acc[c] + b2[c];
         }
     }
 }
@@ -215,9 +215,9 @@ template <int CP>
 __global__ __launch_bounds__(LT_BLOCK) void k_layer2(
     int n, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ S2, int C,
-    const float *__restrict__ b2, float *__restrict__ OUT, int n_long, const int32_t *__restrict__ long_row) {
+    const float *__restrict__ b2, float *__restrict__ OUT, int n_long, const int32_t *__restrict__ long_row, long ldo) {
     if ((int)blockIdx.x < n_long) {   // the first blocks of the launch: one hub row each
-        layer2_long_row<CP>(long_row[blockIdx.x], rowptr, col, val, S2, C, b2, OUT);
+        layer2_long_row<CP>(long_row[blockIdx.x], rowptr, col, val, S2, C, b2, OUT, ldo);
         return;
     }
     const int gid = (((int)blockIdx.x - n_long) * LT_BLOCK + threadIdx.x) / LT_L2_LANES;
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(LT_BLOCK) void k_layer2(
     if (q == 0) {
 #pragma unroll
         for (int c = 0; c < CP; ++c)
-            if (c < C) OUT[(size_t)gid * C + c] = acc[c] + b2[c];
+            if (c < C) OUT[(size_t)gid * ldo + c] = acc[c] + b2[c];
     }
 }
 
@@ -294,13 +294,14 @@ int lt_launch_layer1(const lt_graph *g, const float *S1, int Hp, const float *b1
 }
 
 int lt_launch_layer2(const lt_graph *g, const float *S2, int C, const float *b2, float *OUT,
-                     hipStream_t st) {
+                     hipStream_t st, int64_t ldo) {
     if (g->n == 0) return LT_OK;
+    if (ldo <= 0) ldo = C;      // (the library's own buffers are dense)
     const unsigned grid = blocks_for_rows(g->n, LT_BLOCK / LT_L2_LANES);
     lt_prof_scope prof_(LT_K_LAYER2, st);
     LT_DISPATCH_CP(lt_cp_for(C),
         hipLaunchKernelGGL((k_layer2<CP_>), dim3(grid + (unsigned)g->p_n_long), dim3(LT_BLOCK), 0, st, g->n, g->rowptr,
-                           g->col, g->val, S2, C, b2, OUT, g->p_n_long, g->p_long_row));
+                           g->col, g->val, S2, C, b2, OUT, g->p_n_long, g->p_long_row, (long)ldo));
     LT_CHECK_LAUNCH();
     return LT_OK;
 }
@@ -375,7 +376,7 @@ extern "C" int lt_gcn2_forward(const lt_graph *g, const float *X, int64_t ldx, i
     if (rc) return rc;
     LT_REQUIRE(X && W1 && b1 && W2 && b2 && logits, "lt_gcn2_forward: NULL tensor pointer");
     LT_REQUIRE(ldx >= F, "lt_gcn2_forward: ldx=%lld < F=%d", (long long)ldx, F);
-    LT_REQUIRE(ldl == C, "lt_gcn2_forward: logits must be dense (ldl == C)");
+    LT_REQUIRE(ldl >= C, "lt_gcn2_forward: ldl=%lld < C=%d", (long long)ldl, C);
     if (g->n == 0) return LT_OK;
     if (!workspace || workspace_bytes < lt_gcn2_workspace_bytes(g->n, F, H, C) || ((uintptr_t)workspace % 256))
         return lt_set_error(LT_ERR_WORKSPACE, "lt_gcn2_forward: workspace needs %zu bytes, 256-byte aligned",
@@ -388,7 +389,7 @@ extern "C" int lt_gcn2_forward(const lt_graph *g, const float *X, int64_t ldx, i
     if (rc) return rc;
     rc = lt_launch_layer1(g, w.S1, Hp, b1e, W2e, C, w.Z1, w.S2, st);
     if (rc) return rc;
-    return lt_launch_layer2(g, w.S2, C, b2, logits, st);
+    return lt_launch_layer2(g, w.S2, C, b2, logits, st, ldl);
 }
 
 // --------------------------------------------------------------------------------------------

@@ -611,7 +611,7 @@ __device__ __forceinline__ void fd_slab_block(unsigned char *fd_smem, int nslab,
                 for (int u = 0; u < 8; ++u) {
                     const int k = k0 + 16 * kq + 8 * h + u;
                     m[u] = k < k1 ? ref[k] : 0.f;
-                    w[u] = k < k1 ? ld4(W1 + (size_t)k * H + cc) : f32x4{0.f, 0.f, 0.f, 0.f};
+                    w[u] = k < k1 ? ld4u(W1 + (size_t)k * H + cc) : f32x4{0.f, 0.f, 0.f, 0.f};
                 }
 #pragma unroll
                 for (int u = 0; u < 8; ++u)
@@ -822,7 +822,7 @@ __global__ __launch_bounds__(64 * FD_WAVES, FD_MIN_WAVES) void k_s1d_feature_row
 #pragma unroll
                 for (int k = 0; k < FD_PU; ++k) {       // (no branch between the loads: they all go out before the first wait)
                     d[k] = mv[e + k];
-                    w[k] = ld4(W1 + (size_t)mj[e + k] * H + c0);
+                    w[k] = ld4u(W1 + (size_t)mj[e + k] * H + c0);
                 }
 #pragma unroll
                 for (int k = 0; k < FD_PU; ++k)
@@ -988,13 +988,14 @@ static int fd_cu_count() {
     }
     return cus[dev];
 }
-// Whether the persistent ring form serves this product (else the row-per-wave kernel): rows 8-byte aligned, four hidden columns per
+// Whether the persistent ring form serves this product (else the row-per-wave kernel): rows 8-byte aligned, W1 16-byte aligned (its
+// rows are asked for by 16-byte loads written in assembly), four hidden columns per
 // lane, 9 .. 13 chunks of 1 KiB per row (two workgroups' rings + reference vector + lists inside one CU's LDS), enough rows
 static bool fd_ring_ok(const lt_baseline *b, int n) {
     const int knob = lt_tune().feature_ring;
     if (knob == 0) return false;
     const int nch = fr_chunks(b->F);
-    return b->H % 4 == 0 && b->H <= 256 && b->Hp == b->H && b->ldx % 2 == 0 && ((uintptr_t)b->X % 8) == 0 && nch >= FR_NCH_MIN &&
+    return b->H % 4 == 0 && b->H <= 256 && b->Hp == b->H && b->ldx % 2 == 0 && ((uintptr_t)b->X % 8) == 0 && ((uintptr_t)b->W1 % 16) == 0 && nch >= FR_NCH_MIN &&
            nch <= FR_NCH_MAX && fr_smem_bytes(nch) <= (size_t)FR_LDS_MAX && n >= (knob > 0 ? 2 : lt_tune().feature_ring_min_rows) &&
            b->ldx >= 260;
 }
@@ -1051,7 +1052,7 @@ __global__ __launch_bounds__(256) void k_ref_product(int F, int H, int Hp, const
             for (int u = 0; u < 16; ++u) {
                 const int k = k0 + 16 * kq + u;
                 m[u] = k < k1 ? ref[k] : 0.f;
-                w[u] = k < k1 ? ld4(W1 + (size_t)k * H + c0) : f32x4{0.f, 0.f, 0.f, 0.f};
+                w[u] = k < k1 ? ld4u(W1 + (size_t)k * H + c0) : f32x4{0.f, 0.f, 0.f, 0.f};
             }
 #pragma unroll
             for (int u = 0; u < 16; ++u)

@@ -367,7 +367,7 @@ int lt_fp64_prepare_items(const lt_baseline *b, const int32_t *off, int nb, cons
 int lt_launch_rows_tiled_f64(const lt_graph *g, const double *S, int64_t lds, int ncols, const float *bias_after,
                              double *out, int64_t ldo, double *seg_out, int64_t ld_seg, hipStream_t st);
 int lt_launch_layer2(const lt_graph *g, const float *S2, int C, const float *b2, float *OUT,
-                     hipStream_t st);
+                     hipStream_t st, int64_t ldo = 0);      // ldo: leading dimension of OUT (0 = dense, C)
 int lt_launch_gemm(const float *A, int64_t lda, const float *B, int64_t ldb, float *C,
                    int64_t ldc, int M, int N, int K, hipStream_t st);
 int lt_launch_gemm_mdev(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,

@@ -21,6 +21,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define LT_L2_LANES 8  // lanes cooperating on one layer-2 row
 
 __device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
+// the same load from a BORROWED tensor (a caller's W1: any 4-byte aligned address); the library's own buffers use ld4
+typedef float f32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ f32x4 ld4u(const float *p) { return *reinterpret_cast<const f32x4a4 *>(p); }
 
 __device__ __forceinline__ f32x4 fma4(float a, f32x4 s, f32x4 acc) {
     acc.x = fmaf(a, s.x, acc.x);

@@ -306,7 +306,7 @@ __global__ __launch_bounds__(LT_BLOCK) void k_rows_tiled_xf64(
     const int total = *zicount;
     const int coff = slice * 4 * GL + 4 * j;
     const bool active = coff < ncols;
-    const bool vec = coff + 3 < ncols && (ldx & 3) == 0;      // 16-byte gathers when the rows of X allow them
+    const bool vec = coff + 3 < ncols && (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;      // 16-byte gathers when the rows of X allow them
     for (long chunk = (long)q * xps + xcd / ns; chunk * IPB < total; chunk += (long)nq * xps) {
         const int k = (int)chunk * IPB + (threadIdx.x >> 6) * GPW + lane / GL;
         if (k >= total) continue;

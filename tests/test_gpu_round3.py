@@ -96,8 +96,10 @@ def test_bench_two_ranks_through_its_own_launcher(gpu, tmp_path, mode, extra):
 
 @pytest.mark.parametrize("ncols", [260, 300, 510, 512, 1000, 12, 9])
 def test_spmm_any_width(gpu, ncols):
-    """lt_spmm_csr_f32 has no width limit (gcn/layers.py:30-36): 256-column slices on the vector path, tails and
-    unaligned widths through the 8-lane kernel; against an fp64 host product, on a graph with hub rows."""
+    """lt_spmm_csr_f32 has no width limit (gcn/layers.py:30-36): widths that are multiples of 4 in 256-column slices on the
+    vector path, the others (510, 9) through the 8-lane kernel WHOLE -- with lds == ncols their rows are not 16-byte aligned,
+    so no slice of them can take the vector path; against an fp64 host product, on a graph with hub rows.  (Vector slices
+    followed by a tail of ncols % 4 columns need lds % 4 == 0 with ncols % 4 != 0: tests/test_abi_layout_gpu.py.)"""
     from test_gpu_parity import _hub_graph
     from linkteller_amd import engine, graph
     a_hat = graph.first_order_gcn(_hub_graph(1200, 6000, 700, seed=5))
