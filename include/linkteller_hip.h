@@ -146,6 +146,8 @@ int lt_device_count(int *count);
  *                         apart, so that a group walks its lists while the next one's rows arrive; 0 = all together.  Bit-identical
  *   "xf64_blocks"         aggregate-first route: blocks per XCD that walk the compacted work items of the rows a call reaches (default 96;
  *                         1 .. 4096).  Bit-identical
+ *   "feature_lists"       feature-difference route, one wave per row: 1 = a refresh reads each row's differing columns from the lists
+ *                         lt_baseline_enable_fp64 built (default: no pass over X), 0 = it lists them from X again (LT_FEATURE_LISTS)
  *   "feature_flags"       feature-difference route, one wave per row: 1 = a row's differing columns are found as flag bits (plain VALU)
  *                         and listed level by level (default: the kernel is bound by the issue of its compare steps), 0 = by a
  *                         ballot per value as in round 5.  Changes the order of a row's list: fp64 summation order only
@@ -241,13 +243,23 @@ int lt_baseline_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F
  * test on it, which is what brings it within 1e-6 of an fp64 run of the reference; without it the
  * delta mode still works but entries that cross a kink carry ~1e-4 relative error. */
 int lt_baseline_enable_fp64(lt_baseline *b, void *stream);
-/* The borrowed inputs (X, weights; same pointers) changed, e.g. once per benchmark step.  Launches nothing: everything
+/* The borrowed weights (same pointers) changed, e.g. once per benchmark step -- and so may have the contents of X, EXCEPT for a
+ * baseline with the fp64 pre-activation on the feature-difference route (lt_baseline_fp64_route == 1): that baseline keeps the
+ * lists of the columns in which each row of X differs from its reference vector, built by lt_baseline_enable_fp64, and changed
+ * contents of X are announced to it by lt_baseline_features_changed instead.  Launches nothing: everything
  * derived from them is marked stale and recomputed by the first call that reads it, on THAT call's stream (a caller that
  * uses several streams orders them itself) -- S1 = X*W1 by LT_MODE_FULL / LT_MODE_SPARSE rows and lt_baseline_logits;
  * Z1 / S2 / OUT by SPARSE rows and lt_baseline_logits (FULL rows never need them: their stage A yields the unperturbed
  * layer as a by-product and stage B forms the baseline logits of the observed nodes itself); the fp64 pre-activation by
  * LT_MODE_DELTA rows, which then read nothing fp32 of the baseline (the probe's S1 row comes off the fp64 product). */
 int lt_baseline_refresh(lt_baseline *b, void *stream);
+/* The contents of X changed (same pointer, same shape): builds the difference lists of the feature-difference route again -- may
+ * synchronise and allocate, like lt_baseline_enable_fp64 -- and marks stale everything lt_baseline_refresh marks stale.  Correct
+ * on every route and without the fp64 pre-activation (it is then lt_baseline_refresh).  Additive within ABI 5. */
+int lt_baseline_features_changed(lt_baseline *b, void *stream);
+/* *entries = the number of (column, difference) entries in the baseline's difference lists, -1 when it keeps none (fp64 not
+ * enabled, another route, a row with more differing columns than a wave's list holds, lists beyond a quarter of X's bytes). */
+int lt_baseline_feature_list_entries(const lt_baseline *b, int64_t *entries);
 /* Multi-GPU: the loop-invariant X*W1 sharded over ranks instead of replicated.
  * lt_baseline_attach_s1: the baseline reads S1 = X*W1 from caller-owned storage from now on ([>= n, Hp] fp32 with
  *   Hp = H rounded up to 4, ld == Hp; e.g. the torch tensor the ranks' all-gather writes); the current S1 is copied in.
@@ -423,6 +435,8 @@ int lt_baseline3_create(const lt_graph *g, const float *X, int64_t ldx, int32_t 
                         const float *W3, const float *b3, int32_t C,
                         void *stream, lt_baseline3 **out);
 int lt_baseline3_refresh(lt_baseline3 *b, void *stream);
+/* lt_baseline_features_changed for the inner 2-layer baseline, and everything lt_baseline3_refresh marks stale. */
+int lt_baseline3_features_changed(lt_baseline3 *b, void *stream);
 int lt_baseline3_destroy(lt_baseline3 *b);
 int lt_baseline3_logits(const lt_baseline3 *b, float *dst, void *stream);
 size_t lt_influence3_workspace_bytes(const lt_baseline3 *b, int32_t n_probe, int32_t n_obs);

@@ -52,6 +52,8 @@ SIGNATURES = {
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.POINTER(C.c_void_p)]),
     "lt_baseline_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lt_baseline_features_changed": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lt_baseline_feature_list_entries": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "lt_baseline_attach_s1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lt_baseline_refresh_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "lt_baseline_enable_fp64": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -84,6 +86,7 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                       C.POINTER(C.c_void_p)]),
     "lt_baseline3_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lt_baseline3_features_changed": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lt_baseline3_destroy": (C.c_int, [C.c_void_p]),
     "lt_baseline3_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lt_influence3_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -231,7 +231,9 @@ class Attacker:
     def baseline(self, mode=None, sd=None) -> engine.Baseline:
         """Loop-invariant model(features, adj) of attacker.py:106: built once per (features, adj, parameters) --
         rebuilt when any of them was replaced, refreshed (X W1 recomputed from the borrowed tensors) on every attack
-        so that in-place weight updates are seen.  With several ranks the product the MODE reads (fp32 X W1 for `full` /
+        so that in-place weight updates are seen.  In-place torch edits of the features are seen too (the refresh compares the
+        tensor's version counter and has the baseline's difference lists of X rebuilt); features written behind torch's back
+        -- through a raw pointer -- are announced with ``baseline().features_changed()``.  With several ranks the product the MODE reads (fp32 X W1 for `full` /
         `sparse`, the fp64 one for `delta`) is sharded or replicated per ``dist.choose_baseline_sharding``."""
         mode = self._mode(mode)
         # (the very state_dict of the last call -- _walk() hands the same object back while no parameter was replaced or moved --

@@ -58,6 +58,7 @@ static lt_tuning tuning_defaults() {
     t.records_early = env_ll("LT_RECORDS_EARLY", 1) != 0 ? 1 : 0;
     t.feature_ring = env_ll("LT_FEATURE_RING", 0) != 0 ? (env_ll("LT_FEATURE_RING", 0) < 0 ? -1 : 1) : 0;
     t.feature_flags = env_ll("LT_FEATURE_FLAGS", 1) != 0 ? 1 : 0;
+    t.feature_lists = env_ll("LT_FEATURE_LISTS", 1) != 0 ? 1 : 0;
     t.export_sparse = env_ll("LT_EXPORT_SPARSE", 1) != 0 ? 1 : 0;
     t.pair_list = env_ll("LT_PAIR_LIST", 1) != 0 ? 1 : 0;
     t.i8_split = env_ll("LT_I8_SPLIT", 1) != 0 ? 1 : 0;
@@ -115,6 +116,7 @@ extern "C" int lt_set_tuning(const char *key, long long value) {
     else if (!strcmp(key, "feature_delta")) t.feature_delta = reset ? d.feature_delta : (value < 0 ? -1 : (value != 0));
     else if (!strcmp(key, "feature_ring")) t.feature_ring = reset ? d.feature_ring : (value < 0 ? -1 : (value != 0));
     else if (!strcmp(key, "feature_flags")) t.feature_flags = reset ? d.feature_flags : (value != 0);
+    else if (!strcmp(key, "feature_lists")) t.feature_lists = reset ? d.feature_lists : (value != 0);
     else if (!strcmp(key, "pair_list")) t.pair_list = reset ? d.pair_list : (value != 0);
     else if (!strcmp(key, "i8_split")) t.i8_split = reset ? d.i8_split : (value != 0);
     else if (!strcmp(key, "gcn3_product_gather")) t.gcn3_product_gather = reset ? d.gcn3_product_gather : (value != 0);

@@ -11,6 +11,7 @@
 // One-off cost per baseline (not per probe); only built when delta mode is used.
 #include <new>
 #include <type_traits>
+#include <vector>
 
 #include "lt_rows.hip.h"
 #include "lt_items.hip.h"
@@ -694,13 +695,25 @@ __device__ __forceinline__ double fr_wave_max_nonneg(double v) {
     const unsigned ml = fr_wave_max_u32(hi == mh ? lo : 0u);
     return __hiloint2double((int)mh, (int)ml);
 }
-template <int VEC, bool ONE>
+// The difference lists of all rows, kept per baseline (fd_lists_build): CSR-like, row i's entries are off[i] .. off[i + 1], an entry
+// is a column and the fp64 difference to the reference vector -- exactly what the wave's LDS list (mj, mv) holds, in its order.
+struct fd_lists {
+    const int *off = nullptr;   // [n + 1]
+    int *j = nullptr;           // [off[n]] columns
+    double *v = nullptr;        // [off[n]] differences
+    int *cnt = nullptr;         // LST == 1: non-NULL = the count pass (cnt[i] = the row's differing columns), NULL = the fill pass
+};
+// LST: 0 the row's list is made from X (every refresh that has no stored lists); 1 the same listing phase, and the list is counted
+// or stored instead of walked (once per baseline: the lists depend on X and the reference vector alone); 2 the list is read from
+// the stored lists -- no pass over X, no reference vector in LDS, no barrier.
+template <int VEC, bool ONE, int LST = 0>
 __global__ __launch_bounds__(64 * FD_WAVES, FD_MIN_WAVES) void k_s1d_feature_rows(
     int n, int F, int H, int Hp, const float *__restrict__ X, long ldx, const float *__restrict__ ref,
     const float *__restrict__ W1, const double *__restrict__ cref, double *__restrict__ S1d, int hint_cap,
     int *__restrict__ dense_hint, int nslab, double *__restrict__ slabs, int32_t *__restrict__ zstate,
     float *__restrict__ S1x, unsigned *__restrict__ gate, double *__restrict__ cref_out, double *__restrict__ S1qs,
-    const lt_bits_job job = lt_bits_job{}, const int job_first = 0, const int flag_bits = 0, const int stagger = 0) {
+    const lt_bits_job job = lt_bits_job{}, const int job_first = 0, const int flag_bits = 0, const int stagger = 0,
+    const fd_lists lists = fd_lists{}) {
     // job.nblocks > 0 (round 5): the blocks from job_first on -- BEHIND the rows in dispatch order, into the CU slots the rows leave
     // free -- are a probe chunk's record blocks or item-table blocks (lt_items.hip.h: nothing in them reads a layer).  They used to ride
     // in the launch that forms the pre-activation and cost it 1.5 us; this launch is seven times longer and bound by the pass over X.
@@ -775,6 +788,7 @@ __global__ __launch_bounds__(64 * FD_WAVES, FD_MIN_WAVES) void k_s1d_feature_row
             }
         }
     };
+    if constexpr (LST != 2) {
     {
         float r[16];                                            // (16 loads in flight per thread, no branch between them)
 #pragma unroll
@@ -803,6 +817,7 @@ __global__ __launch_bounds__(64 * FD_WAVES, FD_MIN_WAVES) void k_s1d_feature_row
         }
     }
     __syncthreads();
+    }
     FD_STAMP(1);
     if (!live) return;
     double *mv = ldv + wid * FD_CAP;
@@ -844,7 +859,15 @@ __global__ __launch_bounds__(64 * FD_WAVES, FD_MIN_WAVES) void k_s1d_feature_row
     // pass 1 (the common case is all there is); differing columns beyond the list's capacity are only counted
     int total = 0;                                  // wave-uniform: differing columns of the row
     bool listed = false;
-    if constexpr (VEC == 2) {
+    if constexpr (LST == 2) {
+        // the stored list of the row: its bounds from wave-uniform addresses, its entries in one coalesced trip (64 per trip)
+        const int iu = __builtin_amdgcn_readfirstlane(i);
+        const int e0 = lists.off[iu];
+        total = min(lists.off[iu + 1] - e0, FD_CAP);      // (lists are only kept when every row fits)
+        for (int e = lane; e < total; e += 64) { mj[e] = lists.j[e0 + e]; mv[e] = lists.v[e0 + e]; }
+        listed = true;
+    }
+    if constexpr (VEC == 2 && LST != 2) {
         if (flag_bits && F <= T && shift == 0) {
             // (round 6) the 52 ballot steps as plain VALU: one bit per value (xor, min, shift-or into four accumulators), then the
             // flagged values appended level by level -- the lane's three lowest in one trip, read again from the row (an L2 hit; a
@@ -904,6 +927,7 @@ __global__ __launch_bounds__(64 * FD_WAVES, FD_MIN_WAVES) void k_s1d_feature_row
             listed = true;
         }
     }
+    if constexpr (LST != 2)
     for (int j0 = 0; j0 < F && !listed; j0 += STEP * UN) {
         if (j0 > 0) load_trip(j0);
 #pragma unroll
@@ -925,7 +949,16 @@ __global__ __launch_bounds__(64 * FD_WAVES, FD_MIN_WAVES) void k_s1d_feature_row
         }
     }
     FD_STAMP(4);
-    if (total <= FD_CAP) {
+    if constexpr (LST == 1) {
+        if (lists.cnt) {
+            if (lane == 0) lists.cnt[i] = total;
+        } else if (total <= FD_CAP) {
+            const int e0 = lists.off[i];
+            for (int e = lane; e < total; e += 64) { lists.j[e0 + e] = mj[e]; lists.v[e0 + e] = mv[e]; }
+        }
+        return;
+    }
+    if (LST == 2 || total <= FD_CAP) {
         walk(total);
     } else {
         // a dense row: what pass 1 listed is incomplete, so the row is read again, one piece at a time, and every piece's
@@ -1434,6 +1467,84 @@ static thread_local bool g_offered_rode = false;
 void lt_fp64_offer_job(const lt_bits_job *job) { g_offered_job = job; g_offered_rode = false; }
 bool lt_fp64_offer_taken() { const bool r = g_offered_rode; g_offered_job = nullptr; g_offered_rode = false; return r; }
 
+// ---- the rows' difference lists, built once per baseline ---------------------------------------------------------------------------
+// A row's list depends on X and the reference vector alone: the weights change from refresh to refresh, the features do not (the
+// graph's incidence lists are kept the same way).  The listing phase of k_s1d_feature_rows itself produces them -- the instantiation,
+// the row -> wave mapping, the shifted window of the last rows and the "feature_flags" value of the refresh -- so a stored list is
+// the wave's LDS list entry for entry and the fp64 sums keep their order.  Count pass, offsets scanned on the host, fill pass.
+// Never an error: without lists every refresh lists the rows from X as before.  Synchronises (only lt_baseline_enable_fp64 and
+// lt_baseline_features_changed come here).
+static void fd_lists_free(lt_baseline *b) {
+    (void)hipFree(b->fd_lst_off); (void)hipFree(b->fd_lst_j); (void)hipFree(b->fd_lst_v); (void)hipFree(b->fd_lst_word);
+    b->fd_lst_off = b->fd_lst_j = b->fd_lst_word = nullptr;
+    b->fd_lst_v = nullptr;
+    b->fd_lst_valid = false;
+}
+static bool fd_vec2(const lt_baseline *b) { return b->ldx % 2 == 0 && b->F % 2 == 0 && ((uintptr_t)b->X % 8) == 0; }
+static bool fd_lists_pass(lt_baseline *b, hipStream_t st, int flags, const fd_lists &ls) {
+    const int n = b->n, F = b->F;
+    const unsigned blocks = (unsigned)((n + FD_WAVES - 1) / FD_WAVES);
+    const bool vec2 = fd_vec2(b), one = F <= 16 * 64 * FD_WAVES;
+    // (no riders: nslab = 0, an empty job; the dense hint goes to the build's own word, so the route decision behaves as without lists)
+#define LT_FD_BUILD(V_, O_)                                                                                                    \
+    hipLaunchKernelGGL((k_s1d_feature_rows<V_, O_, 1>), dim3(blocks), dim3(64 * FD_WAVES), fd_smem_bytes(F), st, n, F, b->H, b->Hp, b->X, \
+                       (long)b->ldx, b->fd_ref, b->W1, (const double *)nullptr, b->S1d, fd_hint_cap(F), b->fd_lst_word, 0, b->fd_slabs, \
+                       (int32_t *)nullptr, (float *)nullptr, (unsigned *)nullptr, b->fd_cref, b->S1qs, lt_bits_job{}, (int)blocks, flags, 0, ls)
+    if (vec2 && one) LT_FD_BUILD(2, true);
+    else if (vec2) LT_FD_BUILD(2, false);
+    else if (one) LT_FD_BUILD(1, true);
+    else LT_FD_BUILD(1, false);
+#undef LT_FD_BUILD
+    return hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+}
+static void fd_lists_build(lt_baseline *b, hipStream_t st) {
+    fd_lists_free(b);
+    if (!b->fd_ref || !b->fd_hint_dev || lt_fp64_agg_active(b) || b->S1d_external || !want_feature_rows(b)) return;
+    const int n = b->n, F = b->F;
+    if (!b->fd_ref_valid) {
+        hipLaunchKernelGGL(k_ref_vector, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, st, n, F, b->X, (long)b->ldx, b->fd_ref);
+        if (hipGetLastError() != hipSuccess) return;
+        b->fd_ref_valid = true;
+    }
+    const int flags = lt_tune().feature_flags;
+    std::vector<int> off((size_t)n + 1);
+    bool ok = hipMalloc((void **)&b->fd_lst_off, ((size_t)n + 1) * sizeof(int)) == hipSuccess &&
+              hipMalloc((void **)&b->fd_lst_word, sizeof(int)) == hipSuccess &&
+              hipMemsetAsync(b->fd_lst_word, 0, sizeof(int), st) == hipSuccess;
+    if (ok) {
+        fd_lists ls;
+        ls.cnt = b->fd_lst_off;
+        ok = fd_lists_pass(b, st, flags, ls) && hipMemcpy(off.data(), b->fd_lst_off, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    long long total = 0;
+    for (int i = 0; ok && i < n; ++i) {
+        const int c = off[(size_t)i];
+        if (c < 0 || c > FD_CAP) ok = false;       // a row the list does not hold: this baseline keeps listing from X
+        off[(size_t)i] = (int)total;
+        total += c;
+    }
+    off[(size_t)n] = (int)total;
+    // (byte arithmetic, not a measured crossover: lists beyond a quarter of X's bytes save too little of the pass to be kept)
+    const long long entry = (long long)(sizeof(int) + sizeof(double));
+    ok = ok && total * entry <= (long long)n * F * (long long)sizeof(float) / 4;
+    ok = ok && hipMemcpy(b->fd_lst_off, off.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMalloc((void **)&b->fd_lst_j, (size_t)(total > 0 ? total : 1) * sizeof(int)) == hipSuccess &&
+         hipMalloc((void **)&b->fd_lst_v, (size_t)(total > 0 ? total : 1) * sizeof(double)) == hipSuccess;
+    if (ok) {
+        fd_lists ls;
+        ls.off = b->fd_lst_off; ls.j = b->fd_lst_j; ls.v = b->fd_lst_v;
+        ok = fd_lists_pass(b, st, flags, ls);
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        fd_lists_free(b);
+        return;
+    }
+    b->fd_lst_valid = true;
+    b->fd_lst_flags = flags;
+    b->fd_lst_entries = total;
+}
+
 static int launch_feature_s1d(lt_baseline *b, hipStream_t st, int n_rows = -1, bool defer = false, int32_t *zstate = nullptr) {
     // (fp32 storage of the fp64-accumulated rows goes with the deferred cref: the small-graph route whose readers know about both)
     const int Hp = b->Hp, H = b->H, n = n_rows < 0 ? b->n : n_rows, F = b->F;
@@ -1491,7 +1602,22 @@ static int launch_feature_s1d(lt_baseline *b, hipStream_t st, int n_rows = -1, b
         blocks += (unsigned)(jb.nblocks + jb.zero_blocks);
         g_offered_rode = true;
     }
-    const bool vec2 = b->ldx % 2 == 0 && F % 2 == 0 && ((uintptr_t)b->X % 8) == 0, one = F <= 16 * 64 * FD_WAVES;
+    const bool vec2 = fd_vec2(b), one = F <= 16 * 64 * FD_WAVES;
+    // the stored lists serve an all-rows launch while the knob that decided their order still has the value they were built under
+    const bool use_lists = n_rows < 0 && b->fd_lst_valid && lt_tune().feature_lists != 0 && lt_tune().feature_ring == 0 &&
+                           b->fd_lst_flags == lt_tune().feature_flags;
+    if (use_lists) {
+        fd_lists ls;
+        ls.off = b->fd_lst_off; ls.j = b->fd_lst_j; ls.v = b->fd_lst_v;
+        hipLaunchKernelGGL((k_s1d_feature_rows<1, true, 2>), dim3(blocks), dim3(64 * FD_WAVES), smem, st, n, F, H, Hp, b->X, (long)b->ldx,
+                           b->fd_ref, b->W1, cref, b->S1d, fd_hint_cap(F), b->fd_hint_dev, nslab, b->fd_slabs, zstate, s1x,
+                           defer ? (unsigned *)b->fd_gate : (unsigned *)nullptr, b->fd_cref, b->S1qs, jb, job_first, lt_tune().feature_flags,
+                           lt_tune().feature_stagger, ls);
+        LT_CHECK_LAUNCH();
+        b->cref_deferred = defer;
+        b->s1_f32 = s1x != nullptr;
+        return LT_OK;
+    }
 #define LT_FD_LAUNCH(V_, O_)                                                                                                  \
     hipLaunchKernelGGL((k_s1d_feature_rows<V_, O_>), dim3(blocks), dim3(64 * FD_WAVES), smem, st, n, F, H, Hp, b->X, (long)b->ldx, \
                        b->fd_ref, b->W1, cref, b->S1d, fd_hint_cap(F), b->fd_hint_dev, nslab, b->fd_slabs, zstate, s1x,           \
@@ -1868,9 +1994,29 @@ extern "C" int lt_baseline_enable_fp64(lt_baseline *b, void *stream) {
     b->S1d_owned = true; b->S1d_external = false; b->feat_sparse = feat; b->agg_default = agg_chosen;
     int rc = lt_baseline_ensure_padding(b, st);   // (the padded bias the fp64 SpMM adds)
     if (rc) return rc;
+    fd_lists_build(b, st);      // (the route's real buffers exist: the difference lists of all rows, once)
     rc = compute_s1d(b, st);
     b->fp64_fresh = rc == LT_OK;
     return rc;
+}
+
+// How many (column, difference) entries the baseline's lists hold, -1 without lists (tests and tools tell the two kernels apart by it)
+extern "C" int lt_baseline_feature_list_entries(const lt_baseline *b, int64_t *entries) {
+    LT_REQUIRE(b != nullptr && entries != nullptr, "lt_baseline_feature_list_entries: NULL argument");
+    *entries = b->fd_lst_valid ? b->fd_lst_entries : -1;
+    return LT_OK;
+}
+
+// The contents of X changed (lt_baseline_refresh announces changed weights only, for a baseline that keeps difference lists): the
+// lists are built again -- the reference vector stays, any is correct -- and everything lt_baseline_refresh marks stale is stale.
+extern "C" int lt_baseline_features_changed(lt_baseline *b, void *stream) {
+    LT_REQUIRE(b != nullptr, "lt_baseline_features_changed: baseline is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    if (b->Z1d) {
+        LT_HIP(hipStreamSynchronize(st));      // (launches in flight may still read the lists freed here)
+        fd_lists_build(b, st);
+    }
+    return lt_baseline_refresh(b, stream);
 }
 
 // ---- the aggregate-first pre-activation by ROW LIST: what lets several ranks share the rows all of them reach -------------------
@@ -2016,6 +2162,7 @@ void lt_baseline_free_fp64(lt_baseline *b) {
     (void)hipFree(b->fd_gate);
     (void)hipFree(b->fd_ref);
     (void)hipFree(b->fd_rs);
+    fd_lists_free(b);
     (void)hipFree(b->S1x);
     (void)hipFree(b->Z1x);
     (void)hipFree(b->S1qs);

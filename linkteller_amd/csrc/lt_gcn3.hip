@@ -439,6 +439,12 @@ extern "C" int lt_baseline3_refresh(lt_baseline3 *b, void *stream) {
     return LT_OK;
 }
 
+extern "C" int lt_baseline3_features_changed(lt_baseline3 *b, void *stream) {
+    LT_REQUIRE(b != nullptr, "lt_baseline3_features_changed: baseline is NULL");
+    b->fp64_fresh = b->pad_fresh = b->fp32_fresh = false;
+    return b->l1 ? lt_baseline_features_changed(b->l1, stream) : LT_OK;
+}
+
 // b1 / b2 / W3 zero-padded to the padded widths (read by the fp32 forward, the fp64 layer-2 pre-activation and the probes' kernels)
 static int ensure3_pad(const lt_baseline3 *cb, hipStream_t st) {
     lt_baseline3 *b = const_cast<lt_baseline3 *>(cb);   // cache state only

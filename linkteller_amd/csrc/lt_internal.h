@@ -110,6 +110,15 @@ struct lt_baseline {
     int *fd_gate = nullptr;     // device words: the slice counter of k_ref_row_product; the ring kernel's row counters (FR_GATE_WORDS)
     int fd_ring_parity = 0;     // which of the two counter sets the next launch of k_s1d_feature_ring uses
     int *fd_hint_host = nullptr, *fd_hint_dev = nullptr;   // mapped host word the feature kernel sets when it meets dense rows
+    // the rows' difference lists (fd_lists_build, lt_fp64.hip): a property of X and fd_ref, built once by lt_baseline_enable_fp64 and
+    // again by lt_baseline_features_changed; NULL / invalid: every refresh lists the rows from X itself
+    int *fd_lst_off = nullptr;  // [n + 1] first entry of each row's list
+    int *fd_lst_j = nullptr;    // [fd_lst_off[n]] columns, in the order the kernel's own listing phase appends them
+    double *fd_lst_v = nullptr; // [fd_lst_off[n]] differences X[i, j] - fd_ref[j]
+    int *fd_lst_word = nullptr; // the build's stand-in for the dense-hint word (the route decision never sees the build)
+    bool fd_lst_valid = false;
+    int64_t fd_lst_entries = 0; // fd_lst_off[n]
+    int fd_lst_flags = 0;       // the "feature_flags" value the lists were built under (it decides their order)
     int feat_sparse = -1;       // what the probe at lt_baseline_enable_fp64 found: 1 sparse differences, 0 dense, -1 not probed
     // aggregate-first route of the fp64 pre-activation (lt_fp64.hip): Z1d[r] = (A_hat X)[r] W1 + b1 on the rows a call's
     // probes reach, nothing for the others -- no n x F x H product, no S1d
@@ -197,6 +206,8 @@ struct lt_tuning {
     int feature_flags;           // the row-per-wave kernel lists a row's differing columns from flag bits (1, default: the kernel is bound by
                                  // the issue of its 52 compare steps -- 24.8 against 25.4 us by events, profiles/r06_feat_lab_timeline.txt) or by
                                  // a ballot per value (0: round 5's list order) (LT_FEATURE_FLAGS)
+    int feature_lists;           // the row-per-wave kernel reads a row's differing columns from the lists kept with the baseline (1, default) or
+                                 // lists them from X on every refresh (0) (LT_FEATURE_LISTS)
     int pair_list;               // SPARSE / DELTA stage B with pair marks: 1 the marked pairs are compacted into a list and walked 8 to a wave (default),
                                  // 0 every pair's group reads its mark (LT_PAIR_LIST)
     int i8_split;                // dense-feature fp64 product: 1 the error-free split on the int8 matrix cores (default), 0 the f64 cores (LT_I8_SPLIT)

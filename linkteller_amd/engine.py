@@ -97,6 +97,27 @@ def gcn2_forward(adj, x, w1, b1, w2, b2) -> torch.Tensor:
     return out
 
 
+def _x_version(x):
+    try:
+        return x._version
+    except RuntimeError:        # (an inference tensor keeps no version counter: its edits are announced by features_changed())
+        return None
+
+
+def _refresh_handle(owner, name, *args):
+    """Every lt_baseline_refresh* call on a handle goes through here.  A refresh announces changed WEIGHTS; a baseline on the
+    feature-difference route keeps lists of X built once, so changed contents of X are announced by *_features_changed first --
+    which this does whenever torch's version counter of the feature tensor moved since the lists were built (an in-place edit
+    followed by refresh() keeps giving what it always gave).  Writes torch does not see (a raw pointer, another library) are
+    announced with ``features_changed()``."""
+    v = _x_version(owner.x)
+    if v != owner._x_seen:
+        changed = "lt_baseline3_features_changed" if isinstance(owner, Baseline3) else "lt_baseline_features_changed"
+        _lib.check(getattr(_lib.lib(), changed)(owner._h, _stream()), changed)
+        owner._x_seen = v
+    _lib.check(getattr(_lib.lib(), name)(owner._h, *args, _stream()), name)
+
+
 class Baseline:
     """Unperturbed forward state (S1, Z1, S2, logits) for the probe loop; see lt_baseline_create."""
 
@@ -117,6 +138,7 @@ class Baseline:
                                                  self.b2.data_ptr(), self.c, _stream(), C.byref(h)),
                    "lt_baseline_create")
         self._h = h
+        self._x_seen = _x_version(self.x)       # the features' version the baseline's difference lists (if any) were built from
         self._finalizer = weakref.finalize(self, _lib.lib().lt_baseline_destroy, h)
         self._ws = {}
         self._host_scratch = {}
@@ -144,24 +166,38 @@ class Baseline:
         from . import dist as lt_dist
         if self._shard is not None and not only64:
             b, e, _ = self._shard
-            _lib.check(_lib.lib().lt_baseline_refresh_rows(self._h, b, e, self._send.data_ptr(), _stream()),
-                       "lt_baseline_refresh_rows")
+            _refresh_handle(self, "lt_baseline_refresh_rows", b, e, self._send.data_ptr())
             lt_dist.all_gather_into(self._s1_full, self._send)
         else:
-            _lib.check(_lib.lib().lt_baseline_refresh(self._h, _stream()), "lt_baseline_refresh")
+            _refresh_handle(self, "lt_baseline_refresh")
         if self._shard64 is not None and not only32:
             b, e, _ = self._shard64
-            _lib.check(_lib.lib().lt_baseline_refresh_rows_fp64(self._h, b, e, self._send64.data_ptr(), _stream()),
-                       "lt_baseline_refresh_rows_fp64")
+            _refresh_handle(self, "lt_baseline_refresh_rows_fp64", b, e, self._send64.data_ptr())
             lt_dist.all_gather_into(self._s1d_full, self._send64)
+
+    def features_changed(self):
+        """The contents of the feature tensor changed in a way torch's version counter does not show (a write through the raw
+        pointer, by another library): the difference lists of the feature route are built again (lt_baseline_features_changed;
+        may synchronise) and everything ``refresh()`` marks stale is stale.  In-place torch edits need no call: ``refresh()``
+        sees the version counter."""
+        _lib.check(_lib.lib().lt_baseline_features_changed(self._h, _stream()), "lt_baseline_features_changed")
+        self._x_seen = _x_version(self.x)
+        return self
 
     def enable_fp64(self):
         """The fp64-accumulated pre-activation `delta` evaluates its ReLU kink test on (lt_baseline_enable_fp64):
         allocates S1d / Z1d (2 * n * Hp * 8 bytes -- 8.6 GB at n = 2 M, H = 256) and computes them once."""
         if not self._fp64:
             _lib.check(_lib.lib().lt_baseline_enable_fp64(self._h, _stream()), "lt_baseline_enable_fp64")
+            self._x_seen = _x_version(self.x)       # (the difference lists were built from these features)
             self._fp64 = True
         return self
+
+    def feature_list_entries(self) -> int:
+        """Entries of the difference lists the baseline keeps for the feature route, -1 when it keeps none."""
+        r = C.c_int64(-1)
+        _lib.check(_lib.lib().lt_baseline_feature_list_entries(self._h, C.byref(r)), "lt_baseline_feature_list_entries")
+        return r.value
 
     def fp64_route(self) -> int:
         """1: the fp64 product comes from the feature rows' differences to a reference row (one pass over X; sharding it
@@ -434,7 +470,7 @@ class WideBaseline:
             for ti in range(len(self.c_slices)):
                 sub = subs[(si, ti)][0]
                 # (marked current first: attaching copies the baseline's own S1 over, and none has been formed yet)
-                _lib.check(_lib.lib().lt_baseline_refresh_rows(sub._h, 0, 0, t.data_ptr(), _stream()), "lt_baseline_refresh_rows")
+                _refresh_handle(sub, "lt_baseline_refresh_rows", 0, 0, t.data_ptr())
                 _lib.check(_lib.lib().lt_baseline_attach_s1(sub._h, t.data_ptr(), hp, _stream()), "lt_baseline_attach_s1")
                 sub._s1_full = t
         self._share_products()
@@ -444,8 +480,7 @@ class WideBaseline:
             t = self._s1[si]
             for ti in range(len(self.c_slices)):
                 sub = self._subs[(si, ti)][0]
-                _lib.check(_lib.lib().lt_baseline_refresh_rows(sub._h, 0, self.n if ti == 0 else 0, t.data_ptr(), _stream()),
-                           "lt_baseline_refresh_rows")
+                _refresh_handle(sub, "lt_baseline_refresh_rows", 0, self.n if ti == 0 else 0, t.data_ptr())
 
     def refresh(self, mode=None):
         """The borrowed inputs changed: the slices are re-cut from them, everything derived is recomputed on next use."""
@@ -461,9 +496,17 @@ class WideBaseline:
             # `delta` reads the fp64 pre-activation only: no fp32 X W1[:, s] at all (75 us per hidden slice at twitch size, half of a
             # 0.34 ms build with H = 512) -- every slice is marked stale, and an fp32 reader that comes later recomputes lazily
             for sub, _ in self._subs.values():
-                _lib.check(_lib.lib().lt_baseline_refresh(sub._h, _stream()), "lt_baseline_refresh")
+                _refresh_handle(sub, "lt_baseline_refresh")
         else:
             self._share_products()      # (marks every slice's layers and fp64 parts stale as lt_baseline_refresh does)
+
+    def features_changed(self):
+        """``Baseline.features_changed`` for every slice's baseline, then ``refresh()``."""
+        if self._subs is not None:
+            for sub, _ in self._subs.values():
+                sub.features_changed()
+        self.refresh()
+        return self
 
     def shard_refresh(self, enable=True):
         return self
@@ -722,12 +765,19 @@ class Baseline3:
                                                   self.h2, self.w3.data_ptr(), self.b3.data_ptr(), self.c, _stream(),
                                                   C.byref(h)), "lt_baseline3_create")
         self._h = h
+        self._x_seen = _x_version(self.x)
         self._finalizer = weakref.finalize(self, _lib.lib().lt_baseline3_destroy, h)
         self._ws = {}
         self._fp64 = False
 
     def refresh(self):
-        _lib.check(_lib.lib().lt_baseline3_refresh(self._h, _stream()), "lt_baseline3_refresh")
+        _refresh_handle(self, "lt_baseline3_refresh")
+
+    def features_changed(self):
+        """``Baseline.features_changed`` for the 3-layer model (lt_baseline3_features_changed)."""
+        _lib.check(_lib.lib().lt_baseline3_features_changed(self._h, _stream()), "lt_baseline3_features_changed")
+        self._x_seen = _x_version(self.x)
+        return self
 
     def logits(self) -> torch.Tensor:
         out = torch.empty((self.n, self.c), dtype=torch.float32, device=self.x.device)
@@ -738,6 +788,7 @@ class Baseline3:
         """fp64 pre-activations of the first two layers for the exact (`delta`) propagation (lt_baseline3_enable_fp64)."""
         if not self._fp64:
             _lib.check(_lib.lib().lt_baseline3_enable_fp64(self._h, _stream()), "lt_baseline3_enable_fp64")
+            self._x_seen = _x_version(self.x)
             self._fp64 = True
         return self
 
