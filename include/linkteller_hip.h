@@ -197,6 +197,46 @@ int lt_graph_reached_rows(const lt_graph *g, const int32_t *probes, int32_t n_pr
  * nodes, a node beyond the incidence cap, more than 256 MB), LT_ERR_WORKSPACE when rec_capacity (words) is too small. */
 int lt_graph_records_host(int32_t n, int64_t nnz, const int32_t *rowptr, const int32_t *col, const float *val,
                           int32_t *meta, int32_t *rec, int64_t rec_capacity, int64_t *rec_words);
+/* The same graph from a CSR that already lies in DEVICE memory of the current device (d_rowptr [n + 1], d_col / d_val [nnz]): read in
+ * stream order on `stream`, validated (the refusals and messages of lt_graph_create; rowptr is checked completely before anything
+ * is read through it, a malformed input is refused and never dereferenced) and copied, so the graph owns its arrays.  Every derived
+ * table is built by kernels; only rowptr, the column totals, the first column of each long-row segment and four counts per node visit
+ * the host.  The call synchronises `stream` and returns a graph that equals lt_graph_create's for the same CSR word for word:
+ * every kernel, baseline and trainer runs on it unchanged. */
+int lt_graph_create_device(int32_t n, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_col, const float *d_val, void *stream,
+                           lt_graph **out);
+/* Read-back of one table of a graph, for tests and tools (synchronous).  dst == NULL: *bytes = the table's size only; an optional
+ * table the graph does not have reports 0 bytes; LT_ERR_WORKSPACE when capacity_bytes is too small.  All tables are int32 except
+ * val / tval (float), cv (pairs of col, val bits) and LT_TABLE_SCALARS (LT_TABLE_SCALAR_COUNT doubles: n, nnz, max_row_nnz,
+ * max_col_nnz, local_frac, hot_frac, p_n_long, p_n_seg, q_n_long, q_n_seg, w_n, dl_max_t, dl_max_tu, dl_touch_frac, tpos present,
+ * cv present, records present).  col, val, tpos and cv carry their 16 zero pad entries; trow / tval hold nnz entries. */
+typedef enum lt_graph_table_id {
+    LT_TABLE_ROWPTR = 0,
+    LT_TABLE_COL = 1,
+    LT_TABLE_VAL = 2,
+    LT_TABLE_TPTR = 3,
+    LT_TABLE_TROW = 4,
+    LT_TABLE_TVAL = 5,
+    LT_TABLE_TPOS = 6,
+    LT_TABLE_CV = 7,
+    LT_TABLE_DL_META = 8,
+    LT_TABLE_DL_REC = 9,
+    LT_TABLE_P_LONG_ROW = 10,
+    LT_TABLE_P_LONG_SEGPTR = 11,
+    LT_TABLE_P_SEG_LONG = 12,
+    LT_TABLE_P_SEG_BEGIN = 13,
+    LT_TABLE_Q_LONG_ROW = 14,
+    LT_TABLE_Q_LONG_SEGPTR = 15,
+    LT_TABLE_Q_SEG_LONG = 16,
+    LT_TABLE_Q_SEG_BEGIN = 17,
+    LT_TABLE_W_E0 = 18,
+    LT_TABLE_W_CNT = 19,
+    LT_TABLE_W_DST = 20,
+    LT_TABLE_SCALARS = 21,
+    LT_TABLE_COUNT = 22
+} lt_graph_table_id;
+#define LT_TABLE_SCALAR_COUNT 17
+int lt_graph_table(const lt_graph *g, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes);
 
 /* ---- dense GEMM C[M,N] = A[M,K] * B[K,N]  (torch.mm at gcn/layers.py:31) ----------------
  * exact-fp32 MFMA (v_mfma_f32_32x32x2_f32): each output is the ordered sum of k-ordered fmaf chains of 128 terms

@@ -36,6 +36,9 @@ SIGNATURES = {
                                 C.POINTER(C.c_int32)]),
     "lt_graph_records_host": (C.c_int, [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int64, C.POINTER(C.c_int64)]),
+    "lt_graph_create_device": (C.c_int, [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_void_p)]),
+    "lt_graph_table": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "lt_gemm_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "lt_spmm_csr_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
@@ -131,6 +134,14 @@ KERNEL_IDS = {"gemm": 0, "layer1": 1, "layer2": 2, "perturb": 3, "full_stageA": 
               "item_stageA": 6, "item_stageB": 7, "spmm": 8, "fp64_product": 9, "fp64_spmm": 10, "item_bits": 11,
               "select_hist": 12, "select_collect": 13}
 ABI_VERSION = 5
+# lt_graph_table: the `which` values (include/linkteller_hip.h, lt_graph_table_id) and the names of the scalar table's entries
+GRAPH_TABLES = {"rowptr": (0, "i4"), "col": (1, "i4"), "val": (2, "f4"), "tptr": (3, "i4"), "trow": (4, "i4"), "tval": (5, "f4"),
+                "tpos": (6, "i4"), "cv": (7, "i4"), "dl_meta": (8, "i4"), "dl_rec": (9, "i4"), "p_long_row": (10, "i4"),
+                "p_long_segptr": (11, "i4"), "p_seg_long": (12, "i4"), "p_seg_begin": (13, "i4"), "q_long_row": (14, "i4"),
+                "q_long_segptr": (15, "i4"), "q_seg_long": (16, "i4"), "q_seg_begin": (17, "i4"), "w_e0": (18, "i4"),
+                "w_cnt": (19, "i4"), "w_dst": (20, "i4"), "scalars": (21, "f8")}
+GRAPH_SCALARS = ("n", "nnz", "max_row_nnz", "max_col_nnz", "local_frac", "hot_frac", "p_n_long", "p_n_seg", "q_n_long", "q_n_seg",
+                 "w_n", "dl_max_t", "dl_max_tu", "dl_touch_frac", "has_tpos", "has_cv", "has_records")
 
 
 def lib():

@@ -164,47 +164,31 @@ extern "C" int lt_device_count(int *count) {
     return LT_OK;
 }
 
-static void free_graph(lt_graph *g) {
-    if (!g) return;
-    (void)hipFree(g->rowptr);
-    (void)hipFree(g->col);
-    (void)hipFree(g->val);
-    (void)hipFree(g->tptr);
-    (void)hipFree(g->trow);
-    (void)hipFree(g->tval);
-    (void)hipFree(g->tpos);
-    (void)hipFree(g->cv);
-    (void)hipFree(g->dl_meta);
-    (void)hipFree(g->dl_rec);
-    (void)hipFree(g->w_e0);
-    (void)hipFree(g->w_cnt);
-    (void)hipFree(g->w_dst);
-    (void)hipFree(g->p_long_row);
-    (void)hipFree(g->p_long_segptr);
-    (void)hipFree(g->p_seg_long);
-    (void)hipFree(g->p_seg_begin);
-    (void)hipFree(g->p_seg_scratch);
-    (void)hipFree(g->q_long_row);
-    (void)hipFree(g->q_long_segptr);
-    (void)hipFree(g->q_seg_long);
-    (void)hipFree(g->q_seg_begin);
-    delete g;
-}
-
 static __global__ void k_interleave_cv(const int32_t *__restrict__ col, const float *__restrict__ val, long long total, int2 *__restrict__ cv) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < total) cv[i] = make_int2(col[i], __float_as_int(val[i]));
+}
+
+// (col, val) interleaved for the tiled SpMM, on the graphs that take it (a failure to allocate only means the kernel reads the two streams)
+void lt_graph_build_cv(lt_graph *g) {
+    const int64_t nnz = g->nnz;
+    if (lt_tiled_wanted(g, 256) && nnz > 0) {
+        int2 *cv = nullptr;
+        if (hipMalloc((void **)&cv, ((size_t)nnz + LT_CSR_PAD) * sizeof(int2)) == hipSuccess) {
+            hipLaunchKernelGGL(k_interleave_cv, dim3((unsigned)(((size_t)nnz + LT_CSR_PAD + 255) / 256)), dim3(256), 0, 0, g->col, g->val,
+                               (long long)nnz + LT_CSR_PAD, cv);
+            if (hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess) g->cv = cv;
+            else (void)hipFree(cv);
+        } else {
+            (void)hipGetLastError();
+        }
+    }
 }
 
 // The fused DELTA route's per-node incidence records (lt_items.hip.h "INCIDENCE RECORD"; lt_influence.hip k_delta_probe_finish):
 // for node v, its items (the CSC column of v) and the entries (u, position in row u) that hold an item, grouped by u ascending,
 // a node's entries in entry order.  Sum over the nodes of |R_v| * column lengths entries -- 1.6 M at twitch size, 25 MB; built on
 // the host from the CSC arrays lt_graph_create has in hand.  Only for graphs whose largest record stays small (no hub rows).
-#define LT_DL_MAX_T 4096             // incidences of one node: where the route still wins.  A k-clique among the probes is k long
-                                     // positions per member (tools/clique_time.py, record route against the item kernels per step:
-                                     // k = 10: 32.5 / 40.7 us, 20: 34.4 / 43.2, 40: 42.9 / 46.2, 56 (~ 3 600 incidences): 49.0 / 50.5,
-                                     // 72 (5 700: lists of two 64-entry stretches): 58.3 / 52.6)
-#define LT_DL_MAX_WORDS ((int64_t)64 << 20)   // 256 MB of records
 struct dl_host {
     std::vector<int32_t> meta, rec;
     int32_t max_t = 0, max_tu = 0;
@@ -564,18 +548,7 @@ extern "C" int lt_graph_create(int32_t n, int64_t nnz, const int32_t *rowptr, co
             G_HIP(hipMemcpy(g->w_dst, tmp.data(), wb, hipMemcpyHostToDevice));
         }
     }
-    // (col, val) interleaved for the tiled SpMM, on the graphs that take it (a failure to allocate only means the kernel reads the two streams)
-    if (lt_tiled_wanted(g, 256) && nnz > 0) {
-        int2 *cv = nullptr;
-        if (hipMalloc((void **)&cv, ((size_t)nnz + LT_CSR_PAD) * sizeof(int2)) == hipSuccess) {
-            hipLaunchKernelGGL(k_interleave_cv, dim3((unsigned)(((size_t)nnz + LT_CSR_PAD + 255) / 256)), dim3(256), 0, 0, g->col, g->val,
-                               (long long)nnz + LT_CSR_PAD, cv);
-            if (hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess) g->cv = cv;
-            else (void)hipFree(cv);
-        } else {
-            (void)hipGetLastError();
-        }
-    }
+    lt_graph_build_cv(g);
     // the fused DELTA route's per-node records (graphs without hub rows; a failure to build them only means the route is not taken)
     if (g->p_n_long == 0 && tpos) {
         try {

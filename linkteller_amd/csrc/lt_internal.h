@@ -66,6 +66,40 @@ struct lt_graph {
 static inline int lt_f64_seg_rows(const lt_graph *g) { return g->p_n_seg > g->q_n_seg ? g->p_n_seg : g->q_n_seg; }   // rows of an fp64 segment scratch
 #define LT_CSR_PAD 16   // zero entries appended to col/val
 
+// limits of the fused DELTA route's incidence records (lt_core.hip build_delta_records, lt_graph_build.hip)
+#define LT_DL_MAX_T 4096             // incidences of one node: where the route still wins.  A k-clique among the probes is k long
+                                     // positions per member (tools/clique_time.py, record route against the item kernels per step:
+                                     // k = 10: 32.5 / 40.7 us, 20: 34.4 / 43.2, 40: 42.9 / 46.2, 56 (~ 3 600 incidences): 49.0 / 50.5,
+                                     // 72 (5 700: lists of two 64-entry stretches): 58.3 / 52.6)
+#define LT_DL_MAX_WORDS ((int64_t)64 << 20)   // 256 MB of records
+// (shared by the two builders: lt_core.hip lt_graph_create, lt_graph_build.hip lt_graph_create_device)
+static inline void free_graph(lt_graph *g) {
+    if (!g) return;
+    (void)hipFree(g->rowptr);
+    (void)hipFree(g->col);
+    (void)hipFree(g->val);
+    (void)hipFree(g->tptr);
+    (void)hipFree(g->trow);
+    (void)hipFree(g->tval);
+    (void)hipFree(g->tpos);
+    (void)hipFree(g->cv);
+    (void)hipFree(g->dl_meta);
+    (void)hipFree(g->dl_rec);
+    (void)hipFree(g->w_e0);
+    (void)hipFree(g->w_cnt);
+    (void)hipFree(g->w_dst);
+    (void)hipFree(g->p_long_row);
+    (void)hipFree(g->p_long_segptr);
+    (void)hipFree(g->p_seg_long);
+    (void)hipFree(g->p_seg_begin);
+    (void)hipFree(g->p_seg_scratch);
+    (void)hipFree(g->q_long_row);
+    (void)hipFree(g->q_long_segptr);
+    (void)hipFree(g->q_seg_long);
+    (void)hipFree(g->q_seg_begin);
+    delete g;
+}
+
 struct lt_baseline {
     const lt_graph *g = nullptr;
     int32_t n = 0, F = 0, H = 0, C = 0;
@@ -300,6 +334,7 @@ int lt_launch_layer1(const lt_graph *g, const float *S1, int Hp, const float *b1
 // the first segment of a long row; short rows get `+ bias_after` (NULL = none) and the optional ReLU and go to
 // out[row]; segment sums go raw to seg_out[segment] for the caller's ordered combine.
 bool lt_tiled_wanted(const lt_graph *g, int ncols);
+void lt_graph_build_cv(lt_graph *g);   // lt_core.hip: g->cv on the graphs that take the tiled SpMM (needs w_n, local_frac, hot_frac; synchronises the device)
 int lt_launch_rows_tiled(const lt_graph *g, const float *S, int64_t lds, int ncols, const float *init,
                          const float *bias_after, int relu, float *out, int64_t ldo, float *seg_out,
                          int64_t ld_seg, hipStream_t st);

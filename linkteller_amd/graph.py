@@ -10,11 +10,14 @@ handing it to the model:
   to the device are the reference's bit for bit.
 * ``sparse_mx_to_torch_sparse_tensor`` (reference utils/load.py:552-559) -- kept for API parity;
   the product path converts to int32 CSR instead (8 B/nnz rather than the reference's 20 B/nnz
-  int64 COO) and uploads it once through ``lt_graph_create``.
+  int64 COO) and uploads it once through ``lt_graph_create``.  An adjacency that already lies on the device (what
+  ``Worker`` ends with: ``adj_2.cuda()``) stays there: ``lt_graph_create_device`` builds the same tables with kernels
+  (``HipGraph.from_device_csr``, ``from_torch_sparse`` on a CUDA tensor; ``LT_GRAPH_BUILD`` selects the builder).
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 import weakref
 
 import numpy as np
@@ -145,21 +148,70 @@ def csr_arrays(mat):
             np.ascontiguousarray(a.indices, dtype=np.int32), np.ascontiguousarray(a.data, dtype=np.float32))
 
 
+def _build_mode() -> str:
+    """``LT_GRAPH_BUILD``: ``auto`` (default: inputs that lie on the device build there, host inputs on the host), ``host``
+    (always ``lt_graph_create``) or ``device`` (always ``lt_graph_create_device``; host inputs are uploaded as canonical CSR)."""
+    mode = os.environ.get("LT_GRAPH_BUILD", "").strip().lower() or "auto"
+    if mode not in ("auto", "host", "device"):
+        raise ValueError(f"LT_GRAPH_BUILD must be auto, host or device, got {mode!r}")
+    return mode
+
+
 class HipGraph:
     """Normalised adjacency resident in HBM as CSR (+ CSC) behind an ``lt_graph`` handle."""
 
     def __init__(self, mat):
         _lib.require_gpu()
         n, rowptr, col, val = csr_arrays(mat)
+        if _build_mode() == "device":
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device())
+            self._create_device(*(torch.from_numpy(a).to(dev) for a in (rowptr, col, val)))
+            return
         h = C.c_void_p()
         _lib.check(_lib.lib().lt_graph_create(n, int(col.shape[0]), rowptr.ctypes.data, col.ctypes.data,
                                               val.ctypes.data, C.byref(h)), "lt_graph_create")
         import torch
+        self._adopt(h, n, int(col.shape[0]), torch.cuda.current_device(), "host")      # lt_graph_create uploads to the current device
+
+    def _adopt(self, h, n, nnz, device_index, built_on):
         self._h = h
         self.n = n
-        self.nnz = int(col.shape[0])
-        self.device_index = torch.cuda.current_device()      # lt_graph_create uploads to the current device
+        self.nnz = nnz
+        self.device_index = device_index
+        self.built_on = built_on          # "host" (lt_graph_create) or "device" (lt_graph_create_device)
         self._finalizer = weakref.finalize(self, _lib.lib().lt_graph_destroy, h)
+
+    def _create_device(self, rowptr, col, val):
+        import torch
+        for name, t, dt in (("rowptr", rowptr, torch.int32), ("col", col, torch.int32), ("val", val, torch.float32)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise TypeError(f"from_device_csr: {name} must be a CUDA tensor")
+            if t.dtype != dt or t.dim() != 1:
+                raise TypeError(f"from_device_csr: {name} must be a 1-D {dt} tensor, got {t.dtype} with {t.dim()} dimensions")
+        if not (rowptr.device == col.device == val.device):
+            raise ValueError("from_device_csr: rowptr, col and val lie on different devices")
+        if rowptr.numel() < 1 or col.numel() != val.numel():
+            raise ValueError(f"from_device_csr: rowptr of {rowptr.numel()} words, {col.numel()} columns, {val.numel()} values")
+        rowptr, col, val = rowptr.contiguous(), col.contiguous(), val.contiguous()
+        n, nnz = rowptr.numel() - 1, col.numel()
+        h = C.c_void_p()
+        with torch.cuda.device(rowptr.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().lt_graph_create_device(n, nnz, rowptr.data_ptr(), col.data_ptr() if nnz else None,
+                                                         val.data_ptr() if nnz else None, stream, C.byref(h)),
+                       "lt_graph_create_device")
+        self._adopt(h, n, nnz, rowptr.device.index, "device")
+
+    @classmethod
+    def from_device_csr(cls, rowptr, col, val):
+        """A graph from a canonical CSR that already lies on the device: int32 ``rowptr`` [n + 1], int32 ``col`` and float32
+        ``val`` [nnz] CUDA tensors, columns strictly increasing inside each row.  Read on torch's current stream, validated and
+        copied by ``lt_graph_create_device``; every derived table is built on the device."""
+        _lib.require_gpu()
+        g = cls.__new__(cls)
+        g._create_device(rowptr, col, val)
+        return g
 
     @property
     def handle(self):
@@ -171,9 +223,40 @@ class HipGraph:
         _lib.check(_lib.lib().lt_graph_info(self._h, None, None, C.byref(m)), "lt_graph_info")
         return m.value
 
+    def table(self, name: str) -> np.ndarray:
+        """One table of the graph read back through ``lt_graph_table`` (``_lib.GRAPH_TABLES``; an absent table is empty)."""
+        which, dtype = _lib.GRAPH_TABLES[name]
+        size = C.c_int64()
+        _lib.check(_lib.lib().lt_graph_table(self._h, which, None, 0, C.byref(size)), "lt_graph_table")
+        out = np.empty(size.value // np.dtype(dtype).itemsize, dtype=dtype)
+        if size.value:
+            _lib.check(_lib.lib().lt_graph_table(self._h, which, out.ctypes.data, out.nbytes, C.byref(size)), "lt_graph_table")
+        return out
+
+    def scalars(self) -> dict:
+        return dict(zip(_lib.GRAPH_SCALARS, self.table("scalars").tolist()))
+
     @classmethod
     def from_torch_sparse(cls, t):
-        """Accepts what the reference feeds its model: an (uncoalesced) sparse COO float tensor."""
+        """Accepts what the reference feeds its model: an (uncoalesced) sparse COO float tensor.  A tensor that lies on the device
+        is coalesced there and handed to the device builder, unless coalescing summed duplicates: the reference rounds to
+        float32 before duplicates are summed and the device's summation order is not fixed, so that case (like every CPU
+        tensor, and everything under ``LT_GRAPH_BUILD=host``) takes the host route."""
+        import torch
+        if t.is_cuda and _build_mode() != "host":
+            t = t.detach()
+            if t.dim() != 2 or t.shape[0] != t.shape[1]:
+                raise ValueError(f"adjacency must be square, got {tuple(t.shape)}")
+            c = t.coalesce()
+            if c._nnz() == t._nnz():
+                if c._nnz() >= 2**31 - 1:
+                    raise ValueError("nnz does not fit int32 row pointers")
+                n = int(t.shape[0])
+                idx = c.indices()
+                rowptr = torch.zeros(n + 1, dtype=torch.int64, device=c.device)
+                rowptr[1:] = torch.cumsum(torch.bincount(idx[0], minlength=n), 0)
+                return cls.from_device_csr(rowptr.to(torch.int32), idx[1].to(torch.int32).contiguous(),
+                                           c.values().to(torch.float32).contiguous())
         t = t.detach().cpu().coalesce()
         idx = t.indices().numpy()
         m = sp.coo_matrix((t.values().numpy().astype(np.float32), (idx[0], idx[1])), shape=tuple(t.shape))
