@@ -37,7 +37,8 @@ extern "C" {
                             kernels), lt_spmm_gather_ceiling (measurement support); every version-2 entry point is unchanged.
                             Additive within 5: training of the 2-layer GCN (lt_gcn2_trainer_*) and lt_adam_step; no entry point changed.
                             Additive within 5: training of the 3-layer GCN (lt_gcn3_trainer_*); no entry point changed.
-                            Additive within 5: edge recovery (lt_top_pairs_lower, profile classes 12-13); no entry point changed */
+                            Additive within 5: edge recovery (lt_top_pairs_lower, profile classes 12-13); no entry point changed.
+                            Additive within 5: attack metrics (lt_score_curve, profile classes 14-15); no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -528,6 +529,33 @@ size_t lt_top_pairs_workspace_bytes(int32_t n, int64_t m);
 int lt_top_pairs_lower(const float *scores, int64_t lds, int32_t n, int64_t m, int64_t *out_idx, float *out_score,
                        int64_t *out_info, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- attack metrics: the table behind roc_curve / precision_recall_curve / average_precision_score (attacker.py:378-389) --------
+ * Item k (of n_items) has label labels[k] (uint8, 0 or 1) and score scores[index[k]], or scores[k] when index_or_null is NULL.
+ * With an index, n_scores is the extent of scores in ELEMENTS and every index must lie in [0, n_scores): the index addresses storage,
+ * so a strided score matrix is read through i * lds + j, an element may be listed twice, and the diagonal and the padding are
+ * simply never listed.  Without one, n_scores >= n_items.  Every pointer is device memory.
+ * Values are ordered as lt_top_pairs_lower orders them: -0.0 counts as +0.0, subnormals are kept as they are.  With
+ * v_1 > v_2 > ... > v_D the distinct values, entries [0, D) of the three output arrays (capacity n_items each) are written:
+ *   thresholds[d] = v_d (the zero group reports +0.0), tps[d] = #{k : y_k = 1, s_k >= v_d}, fps[d] = #{k : y_k = 0, s_k >= v_d}
+ * -- sklearn's _binary_clf_curve for float32 scores -- and summary (int64 [8]):
+ *   [0] D   [1] P = all positives   [2] N = all negatives
+ *   [3] auc2 = sum_d neg_d (2 tps[d - 1] + pos_d), tps[-1] = 0, pos_d / neg_d the counts AT v_d: AUC = auc2 / (2 P N) exactly
+ *   [4] the bit pattern of the float64 AP = sum_d (pos_d / P) (tps[d] / (tps[d] + fps[d])), summed in ONE fixed order (thread order
+ *       inside a block, then block order): two calls give the same bits; 0 when P = 0
+ *   [5] items whose score is NaN or +-Inf   [6] items whose index is outside [0, n_scores)   [7] items whose label is > 1
+ * When [5], [6] or [7] is non-zero the other outputs are unspecified; no access leaves the buffers all the same (a bad index is
+ * replaced by 0 before the load).  Every output is a function of the multiset of (value, label) pairs: item order does not show.
+ * Enqueue only, no synchronisation, no host round trip: one gather pass, an LSD radix sort of 32-bit keys (8 bits a pass, the label
+ * as payload), run ends + two scans + a compaction to D entries, a last pass for auc2 and AP; stream order is the only barrier
+ * between blocks.  LT_ERR_INVALID before anything is enqueued: a NULL pointer other than index_or_null, n_items outside
+ * [1, 2^31 - 1], n_scores < 1, a NULL index with n_scores < n_items, a workspace smaller than lt_score_curve_workspace_bytes(n_items)
+ * or not 8-byte aligned.  The query returns 0 for an invalid n_items.  Additive in ABI 5. */
+size_t lt_score_curve_workspace_bytes(int64_t n_items);
+int lt_score_curve(const float *scores, int64_t n_scores, const int64_t *index_or_null,
+                   const uint8_t *labels, int64_t n_items,
+                   float *thresholds, int64_t *tps, int64_t *fps, int64_t *summary,
+                   void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- training of the 2-layer GCN (reference gcn_trainer.py:144-170 train_one_epoch + optim.Adam) ----
  * lt_gcn2_trainer_create borrows the graph, X [n, ldx], labels (int32 [n], device, each in [0, C)) and the four parameter
  * tensors (W1 [F, H], b1 [H], W2 [H, C], b2 [C], dense fp32 device buffers), which every epoch updates IN PLACE; it owns
@@ -625,7 +653,9 @@ typedef enum lt_kernel_id {
     LT_K_ITEM_BITS = 11,  /* k_item_bits (+ the pair-mark kernels): item offsets, (probe, row) table, membership bitmap */
     LT_K_SELECT_HIST = 12,    /* lt_top_pairs_lower: the clear of its workspace header + the four k_sel_hist digit passes */
     LT_K_SELECT_COLLECT = 13, /* lt_top_pairs_lower: k_sel_count + k_sel_scan + k_sel_write (the ordered compaction) */
-    LT_K_COUNT = 14
+    LT_K_METRICS_SORT = 14,   /* lt_score_curve: the clear of its workspace header, k_mc_keys and the four hist / scan / scatter passes */
+    LT_K_METRICS_CURVE = 15,  /* lt_score_curve: k_mc_count + k_mc_block_scan + k_mc_write + k_mc_terms + k_mc_summary */
+    LT_K_COUNT = 16
 } lt_kernel_id;
 int lt_profile_enable(int mask);
 int lt_profile_reset(void);

@@ -100,6 +100,9 @@ SIGNATURES = {
     "lt_top_pairs_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "lt_top_pairs_lower": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),
+    "lt_score_curve_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "lt_score_curve": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "lt_baseline3_enable_fp64": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lt_influence3_rows_mode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -132,7 +135,7 @@ SIGNATURES = {
 }
 KERNEL_IDS = {"gemm": 0, "layer1": 1, "layer2": 2, "perturb": 3, "full_stageA": 4, "full_stageB": 5,
               "item_stageA": 6, "item_stageB": 7, "spmm": 8, "fp64_product": 9, "fp64_spmm": 10, "item_bits": 11,
-              "select_hist": 12, "select_collect": 13}
+              "select_hist": 12, "select_collect": 13, "metrics_sort": 14, "metrics_curve": 15}
 ABI_VERSION = 5
 # lt_graph_table: the `which` values (include/linkteller_hip.h, lt_graph_table_id) and the names of the scalar table's entries
 GRAPH_TABLES = {"rowptr": (0, "i4"), "col": (1, "i4"), "val": (2, "f4"), "tptr": (3, "i4"), "trow": (4, "i4"), "tval": (5, "f4"),

@@ -22,6 +22,7 @@ from sklearn import metrics
 
 from . import dist as lt_dist
 from . import engine
+from ._lib import LinkTellerHipError
 from .sampling import construct_balanced_edge_sets, construct_edge_sets_from_random_subgraph
 
 
@@ -506,6 +507,94 @@ class Attacker:
         os.makedirs(osp.dirname(filename), exist_ok=True)
         torch.save(r, filename)
         print(f"recovered edges saved to: {filename}")
+
+    # ------------------------------------------------------------------------------------------
+    def _metric_lists(self, lds, dev):
+        """(index, labels) of the efficient attack's sampled pairs on the device: pair (u, v) -- perturb v, observe u -- is the
+        storage element ``ind[v] * lds + ind[u]`` of the rows, the cell ``link_prediction_attack_efficient`` reads; the existing
+        pairs first (label 1), then the others.  Built once per sample on the host and uploaded once: the cache holds the very
+        edge lists it was built from, so a new ``prepare_test_data()`` (new list objects) replaces it."""
+        c = getattr(self, "_metric_cache", None)
+        if (c is not None and c[0] is self.exist_edges and c[1] is self.nonexist_edges and c[2] is self.test_nodes
+                and c[3] == (lds, dev)):
+            return c[4], c[5]
+        nodes = np.asarray(self.test_nodes, dtype=np.int64)
+        node2ind = np.full(int(nodes.max()) + 1, -1, dtype=np.int64)
+        node2ind[nodes] = np.arange(len(nodes))
+        ex = np.asarray(self.exist_edges, dtype=np.int64).reshape(-1, 2)
+        nex = np.asarray(self.nonexist_edges, dtype=np.int64).reshape(-1, 2)
+        pairs = np.concatenate([ex, nex])
+        if pairs.size and (pairs.min() < 0 or pairs.max() >= node2ind.size or (node2ind[pairs] < 0).any()):
+            raise IndexError("a sampled pair names a node outside the sampled nodes")
+        index = node2ind[pairs[:, 1]] * int(lds) + node2ind[pairs[:, 0]]
+        labels = np.zeros(len(pairs), dtype=np.uint8)
+        labels[:len(ex)] = 1
+        index_t, labels_t = torch.from_numpy(index).to(dev), torch.from_numpy(labels).to(dev)
+        self._metric_cache = (self.exist_edges, self.nonexist_edges, self.test_nodes, (lds, dev), index_t, labels_t)
+        return index_t, labels_t
+
+    def _pair_curve(self, probe, observed, labels, mode=None):
+        """``engine.score_curve`` over a LIST of pairs: straight from the device tensor ``Baseline.influence_pairs`` returns where
+        ``pair_scores`` takes that route (the labels permuted as ``engine.group_pairs`` orders the pairs), else from
+        ``pair_scores``' host result, uploaded (fp32 values widened on the way down: the narrowing is exact)."""
+        dev = self.features.device
+        kind, sd = self._walk()
+        if kind == "gcn2" and self.features.is_cuda:
+            m = self._mode(mode)
+            base = self.baseline(m, sd)
+            if isinstance(base, engine.Baseline):
+                n = int(self.features.shape[0])
+                for ids, what in ((probe, "probe"), (observed, "observed")):
+                    if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= n):
+                        raise IndexError(f"{what}: node id out of range for {n} nodes")
+                nodes, ptr, obs, order = engine.group_pairs(probe, observed)
+                out = base.influence_pairs(nodes, ptr, obs, float(self.args.influence), m)
+                return engine.score_curve(out, torch.from_numpy(np.ascontiguousarray(labels[order])).to(dev))
+        s = self.pair_scores(probe, observed, mode)
+        if not self.features.is_cuda:
+            raise LinkTellerHipError("evaluate: the metrics run on the GPU; there is no CPU path")
+        return engine.score_curve(torch.from_numpy(s.astype(np.float32)).to(dev), torch.from_numpy(labels).to(dev))
+
+    def evaluate(self, mode=None, curves=False) -> dict:
+        """AUC and AP of the attack without the host's three sorts (the reference's ``compute_and_save``, attacker.py:378-389,
+        minus its file): the scores stay on the device, ``engine.score_curve`` ranks and counts them there, and eight words --
+        with ``curves=True`` also the D distinct thresholds' counts -- cross PCIe.  Sets ``self.auc`` (the exact Mann-Whitney
+        value ``auc2 / (2 P N)``; the trapezoid of ``compute_and_save`` agrees to rounding) and ``self.ap``, prints the same two
+        lines, writes no file.  Returns ``{"auc", "ap", "n_thresholds", "n_pos", "n_neg"}``, with ``curves=True`` also
+        ``"curves"``: ``metrics.curves_from_counts(...)``, the arrays ``compute_and_save`` stores, bit for bit.  Needs
+        ``prepare_test_data()``.  Efficient attack on an ``unbalanced*`` sample: the n_test x n_test rows of ``_rows`` (every
+        model kind it serves) read through a cached index; naive attack and ``balanced-full``: the listed pairs' scores.  The
+        baseline attacks' scores are host arithmetic: ``NotImplementedError``.  With several ranks every rank forms all rows
+        itself: no collective of its own to mismatch."""
+        from . import metrics as lt_metrics
+        am = str(getattr(self.args, "attack_mode", "efficient"))
+        st = str(self.args.sample_type)
+        if am in ("baseline", "baseline-feat"):
+            raise NotImplementedError(f"evaluate: attack_mode = {am} scores its pairs on the host (baseline_attack)")
+        if am not in ("efficient", "naive"):
+            raise NotImplementedError(f"attack_mode = {am} not implemented!")
+        ex = np.asarray(self.exist_edges, dtype=np.int64).reshape(-1, 2)
+        nex = np.asarray(self.nonexist_edges, dtype=np.int64).reshape(-1, 2)
+        if am == "efficient" and st.startswith("unbalanced"):
+            nodes = np.asarray(self.test_nodes, dtype=np.int64)
+            probes, observed = self._device_nodes(nodes, 0, len(nodes))
+            rows = self._rows(probes, observed, mode)
+            index, labels = self._metric_lists(int(rows.stride(0)) if rows.shape[0] > 1 else int(rows.shape[1]), rows.device)
+            curve = engine.score_curve(rows, labels, index)
+        else:
+            labels = np.zeros(len(ex) + len(nex), dtype=np.uint8)
+            labels[:len(ex)] = 1
+            # naive (attacker.py:143-163): perturb v, observe u; balanced-full (attacker.py:250-284): perturb u, observe v
+            p, o = (1, 0) if am == "naive" else (0, 1)
+            curve = self._pair_curve(np.concatenate([ex[:, p], nex[:, p]]), np.concatenate([ex[:, o], nex[:, o]]), labels, mode)
+        out = curve.summary()                                    # the wait
+        engine.node_check()
+        self.auc, self.ap = out["auc"], out["ap"]
+        print("auc =", self.auc)
+        print("ap =", self.ap)
+        if curves:
+            out["curves"] = lt_metrics.curves_from_counts(*curve.counts())
+        return out
 
     # ------------------------------------------------------------------------------------------
     def _baseline_vectors(self):

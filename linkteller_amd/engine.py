@@ -880,6 +880,99 @@ def top_pairs_lower(scores: torch.Tensor, m: int):
     return idx, val, info
 
 
+_curve_ws = {}       # score_curve's workspace: only the latest (device, size) is kept, sizes repeat across calls
+
+
+class ScoreCurve:
+    """What ``score_curve`` enqueued, still on the device: ``thresholds`` (fp32), ``tps``, ``fps`` (int64), each of capacity
+    n_items with entries [0, D) written, and ``raw`` -- the eight summary words of lt_score_curve (include/linkteller_hip.h)."""
+
+    def __init__(self, thresholds, tps, fps, raw, n_items):
+        self.thresholds, self.tps, self.fps, self.raw, self.n_items = thresholds, tps, fps, raw, n_items
+        self._host = None
+
+    def _words(self):
+        if self._host is None:
+            self._host = [int(v) for v in self.raw.cpu().tolist()]      # ONE copy of 8 words, one wait
+        return self._host
+
+    def summary(self) -> dict:
+        """``{"n_thresholds", "n_pos", "n_neg", "auc", "ap"}`` after one copy of 8 words and one wait (cached).  ``auc`` is
+        ``auc2 / (2 P N)``, a true division of Python ints -- NaN when one class is missing (the counts are still right; sklearn's
+        ``roc_auc_score`` raises there); ``ap`` is 0.0 without positives.  Raises ``IndexError`` when an index lay outside the
+        scores, ``ValueError`` when a listed score was NaN / Inf (as sklearn does) or a label was neither 0 nor 1."""
+        import struct
+        w = self._words()
+        if w[6]:
+            raise IndexError(f"score_curve: {w[6]} of {self.n_items} indices outside the scores")
+        if w[5]:
+            raise ValueError(f"score_curve: {w[5]} of {self.n_items} scores are NaN or infinite")
+        if w[7]:
+            raise ValueError(f"score_curve: {w[7]} of {self.n_items} labels are neither 0 nor 1")
+        d, p, n, auc2 = w[0], w[1], w[2], w[3]
+        return {"n_thresholds": d, "n_pos": p, "n_neg": n, "auc": auc2 / (2 * p * n) if p and n else float("nan"),
+                "ap": struct.unpack("<d", struct.pack("<q", w[4]))[0]}
+
+    def counts(self):
+        """``(thresholds, tps, fps)`` as numpy arrays of the D written entries (one more copy of each array's head)."""
+        d = self.summary()["n_thresholds"]
+        return self.thresholds[:d].cpu().numpy(), self.tps[:d].cpu().numpy(), self.fps[:d].cpu().numpy()
+
+
+def score_curve(scores: torch.Tensor, labels: torch.Tensor, index: torch.Tensor = None) -> ScoreCurve:
+    """The counts table behind the attack's ROC / PR curves, AUC and AP on the device (lt_score_curve; the reference's three
+    sklearn calls of attacker.py:378-389).  Item k has label ``labels[k]`` (uint8, 0 / 1) and score ``scores.view(-1)[k]`` -- or,
+    with ``index`` (int64), the STORAGE element ``index[k]`` of ``scores``, counted from its first element: a strided matrix
+    is addressed as ``i * scores.stride(0) + j``, elements may repeat, what is not listed is not read.  ``scores``: float32 CUDA
+    tensor with last-dimension stride 1 (without an index: contiguous).  Nothing is brought to the host here; the returned
+    ``ScoreCurve`` does that on request.  Enqueues on the current stream and does not synchronise."""
+    for t, name in ((scores, "scores"), (labels, "labels")) + (((index, "index"),) if index is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if not t.is_cuda:
+            raise _lib.LinkTellerHipError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+    if scores.dtype != torch.float32 or scores.dim() < 1:
+        raise TypeError(f"scores must be a float32 tensor of at least one dimension, got {scores.dtype} {tuple(scores.shape)}")
+    if labels.dtype != torch.uint8 or labels.dim() != 1 or not labels.is_contiguous():
+        raise TypeError(f"labels must be a contiguous 1-d uint8 tensor, got {labels.dtype} {tuple(labels.shape)}")
+    if scores.numel() and scores.stride(-1) != 1 and scores.shape[-1] > 1:
+        raise ValueError("scores must have last-dimension stride 1 (rows may be strided)")
+    n_items = int(labels.numel())
+    if n_items < 1:
+        raise ValueError("score_curve: no items")
+    dev = scores.device
+    if labels.device != dev or (index is not None and index.device != dev):
+        raise ValueError("scores, labels and index must live on one device")
+    if index is not None:
+        if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous() or index.numel() != n_items:
+            raise TypeError(f"index must be a contiguous int64 tensor of {n_items} entries, got {index.dtype} {tuple(index.shape)}")
+        # the extent of the view in storage elements, from its first element
+        n_scores = 1 + sum((s - 1) * st for s, st in zip(scores.shape, scores.stride())) if scores.numel() else 0
+    else:
+        if not scores.is_contiguous():
+            raise ValueError("scores must be contiguous when no index is given")
+        n_scores = int(scores.numel())
+        if n_scores < n_items:
+            raise ValueError(f"{n_scores} scores for {n_items} labels")
+    if n_scores < 1:
+        raise ValueError("score_curve: scores holds no element")
+    thresholds = torch.empty(n_items, dtype=torch.float32, device=dev)
+    tps = torch.empty(n_items, dtype=torch.int64, device=dev)
+    fps = torch.empty(n_items, dtype=torch.int64, device=dev)
+    raw = torch.empty(8, dtype=torch.int64, device=dev)
+    need = _lib.lib().lt_score_curve_workspace_bytes(n_items)
+    key = (dev, need)
+    ws = _curve_ws.get(key)
+    if ws is None:
+        ws = _workspace(need, dev)
+        _curve_ws.clear()
+        _curve_ws[key] = ws
+    _lib.check(_lib.lib().lt_score_curve(scores.data_ptr(), n_scores, index.data_ptr() if index is not None else None,
+                                         labels.data_ptr(), n_items, thresholds.data_ptr(), tps.data_ptr(), fps.data_ptr(),
+                                         raw.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "lt_score_curve")
+    return ScoreCurve(thresholds, tps, fps, raw, n_items)
+
+
 def export_rows_f64(rows: torch.Tensor):
     """The finished rows as a float64 numpy array on the host (the reference's ``influence_val = np.zeros(...)`` filled by
     n_test**2 ``.item()`` round trips, attacker.py:216-229) -- ONE launch that widens on the device and writes straight into

@@ -53,7 +53,10 @@ _SWITCHES = ["no-cuda", "fastmode", "approx", "attack", "test", "break-down", "d
              "train",
              # addition: after the efficient attack on an unbalanced* sample, recover the edge list under a density belief
              # (Attacker.recover_edges; the reference's attack_stats_all.py) and save it next to the result file
-             "recover"]
+             "recover",
+             # addition: with --attack and the efficient or naive attack, print auc / ap from the device-side metrics
+             # (Attacker.evaluate) instead of running the attack method: no matrix on the host, no result file
+             "metrics-only"]
 
 
 def build_parser():
@@ -120,9 +123,20 @@ def check_recover(args):
         raise ValueError(f"--density-belief {args.density_belief}: a density belief is > 0 (0 = the ladder around the true density)")
 
 
+def check_metrics_only(args):
+    """``--metrics-only`` serves the attacks whose scores are formed on the device (efficient, naive); the baseline attacks'
+    scores are host arithmetic and are refused here, before a Worker is built or the GPU is touched."""
+    if not getattr(args, "metrics_only", False):
+        return
+    if args.attack_mode in ("baseline", "baseline-feat"):
+        raise NotImplementedError(f"--metrics-only needs --attack-mode efficient or naive (got attack-mode={args.attack_mode}: "
+                                  "the baseline attacks score their pairs on the host)")
+
+
 def main(argv=None):
     args = get_arguments(argv)
     check_recover(args)
+    check_metrics_only(args)
     import os
     if args.train and not args.test:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:

@@ -114,7 +114,9 @@ class GCNTrainer:
             self.attacker = Attacker(args=a, model=self.model, worker=self.worker)
             self.attacker.prepare_test_data()
             t = time.time()
-            if a.attack_mode == "efficient":                      # gcn_trainer.py:326-337
+            if getattr(a, "metrics_only", False):                 # addition: auc / ap from the device, no result file
+                self.attacker.evaluate()
+            elif a.attack_mode == "efficient":                    # gcn_trainer.py:326-337
                 if a.sample_type == "balanced-full":
                     self.attacker.link_prediction_attack_efficient_balanced()
                 else:
