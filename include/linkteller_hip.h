@@ -507,6 +507,55 @@ int lt_influence3_rows_mode(const lt_baseline3 *b, const int32_t *probe_nodes, i
 int lt_lapgraph_select(int32_t n, const int32_t *lower_rowptr, const int32_t *lower_col, double *cells, int64_t n_keep,
                        int64_t *out_idx, void *work, size_t work_bytes, double *threshold_out, void *stream);
 
+/* ---- edge-DP noise from a counter-based stream: LapGraph and EdgeRand without an N x N matrix ------------
+ * lt_lapgraph_select above needs numpy's N x N draw.  The functions below evaluate a documented Philox4x32-10 stream per cell on
+ * the device instead: the noise is never stored, the selection needs O(kept edges) memory.  A given seed gives a DIFFERENT
+ * graph than numpy's stream does; the stream is this contract, as the dropout mask is the trainers':
+ *   cell      a strict-lower-triangle pair (i, j), j < i, with the linear index t = i (i - 1) / 2 + j (64 bits)
+ *   block     q = t >> 1; counter (q & 0xffffffff, q >> 32, stream, 0), key (seed & 0xffffffff, seed >> 32) -> words w[0 .. 3];
+ *             cell t takes a = w[2 (t & 1)] and b = w[2 (t & 1) + 1]
+ *   stream    0: LapGraph's cell noise, 1: LapGraph's edge-count draw (cell 0 only; drawn by the host), 2: EdgeRand
+ *   uniform   k = (a << 20) | (b >> 12) (52 bits); u = (2 k + 1) 2^-53, exact, in (0, 1); coin = b & 1 (not a bit of k)
+ *   LapGraph  g = 2 u if k < 2^51, else 1 / (2 (1 - u)); key = g c for an edge cell, g otherwise, with c = exp(eps2) computed once
+ *             by the caller (`edge_factor`).  The key is exp((a_ij + Laplace(1 / eps2)) eps2) for the inverse-CDF Laplace draw of
+ *             u: ranking by key is ranking by adjacency + noise.  One multiply and at most one divide, each correctly rounded
+ *             (the library is built with -ffp-contract=off and no fast-math): numpy and the device agree bit for bit.
+ *   order     total: key descending, then t ascending (equally: flat index i * n + j ascending).  The selection is the first
+ *             n_keep cells of that order.
+ *   EdgeRand  a cell is re-drawn iff k < s_threshold = floor(s 2^52), s = 2 / (e^eps + 1); coin 1 sets the pair, 0 clears it.
+ * The adjacency is a device CSR (int32; columns sorted and unique within a row; entries j >= i are ignored; d_col must be a
+ * valid pointer even for a graph without entries).  Cells are reported as flat indices i * n + j (int64).
+ *
+ * lt_philox_cells_scan: every cell of rows [row_begin, row_end) whose key is >= key_min, as (out_cell[p], out_key[p]) in no
+ * particular order.  *d_count (device int64) receives the number found, also when it exceeds `capacity`; nothing is written
+ * past `capacity`.  Enqueue only.  LT_ERR_INVALID before anything is enqueued: NULL pointers, n < 2, rows outside
+ * 0 <= row_begin <= row_end <= n, capacity < 0, edge_factor negative or not finite, key_min negative or NaN.
+ *
+ * lt_lapgraph_philox: the first n_keep cells of the order above, to out_idx ([n_keep] int64, device, unordered).  It scans with
+ * a key_min from the closed-form tail of the key distribution (or key_hint when > 0) into a buffer of 3 n_keep + 4096
+ * candidates, scans again with a moved key_min if fewer than n_keep or more than the buffer came back, and selects exactly among
+ * the candidates (a radix select over the key bits, the tied group resolved by ascending t).  The result does not depend on
+ * key_hint or on the number of passes.  info (HOST int64 [8]): [0] the threshold key's bit pattern, [1] candidates of the last
+ * scan, [2] scan passes, [3] cells above the threshold key, [4] cells tied at it that were taken, [5] cells tied at it in
+ * total ([3] + [4] == n_keep), [6] the last key_min's bit pattern, [7] 0.  Synchronises the stream (it reads the counts back).
+ * Any 1 <= n_keep <= n (n - 1) / 2 and any finite edge_factor >= 0.  LT_ERR_INVALID before any device call: NULL pointers,
+ * n < 2, n_keep out of range, a bad edge_factor, a workspace smaller than lt_lapgraph_philox_workspace reports or not 8-byte
+ * aligned.  LT_ERR_UNSUPPORTED: more cells are tied at one key around the threshold than the candidate buffer holds (only
+ * edge_factor == 0 on a graph of more than 3 n_keep + 4096 edges can do that).  The workspace is linear in n_keep (it does
+ * not depend on n or nnz); nothing is O(n^2).
+ *
+ * lt_edgerand_philox: the re-drawn cells of rows [row_begin, row_end) with their coins (out_coin uint8), same count / capacity
+ * contract as the scan; needs no adjacency.  s_threshold <= 2^52.  Additive in ABI 5. */
+int lt_philox_cells_scan(int32_t n, int32_t row_begin, int32_t row_end, const int32_t *d_rowptr, const int32_t *d_col,
+                         uint64_t seed, double edge_factor, double key_min, int64_t *out_cell, double *out_key,
+                         int64_t capacity, int64_t *d_count, void *stream);
+int lt_lapgraph_philox_workspace(int32_t n, int64_t nnz, int64_t n_keep, size_t *bytes);
+int lt_lapgraph_philox(int32_t n, const int32_t *d_rowptr, const int32_t *d_col, uint64_t seed, double edge_factor,
+                       int64_t n_keep, double key_hint, int64_t *out_idx, int64_t *info, void *ws, size_t ws_bytes,
+                       void *stream);
+int lt_edgerand_philox(int32_t n, int32_t row_begin, int32_t row_end, uint64_t seed, uint64_t s_threshold, int64_t *out_cell,
+                       uint8_t *out_coin, int64_t capacity, int64_t *d_count, void *stream);
+
 /* ---- edge recovery: the m highest-scoring pairs of sampled nodes (attack_stats_all.py:106-116: n_pos = ceil(ratio * n_total),
  * ind = np.argpartition(pred, -n_pos)[-n_pos:] over the saved score list, then precision / recall / F1 of y[ind]) -----------
  * scores: device [n, lds] fp32, what lt_influence_rows / lt_influence3_rows* wrote for probes == observed == the sampled nodes.

@@ -97,6 +97,13 @@ SIGNATURES = {
                                      C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "lt_lapgraph_select": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.POINTER(C.c_double), C.c_void_p]),
+    "lt_philox_cells_scan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_double,
+                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "lt_lapgraph_philox_workspace": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "lt_lapgraph_philox": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_int64, C.c_double, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lt_edgerand_philox": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_void_p]),
     "lt_top_pairs_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "lt_top_pairs_lower": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),

@@ -22,6 +22,7 @@
 
 #include <new>
 
+#include "lt_philox.hip.h"
 #include "lt_rows.hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -31,19 +32,8 @@ typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 #define TR_ROWS_PER_BLOCK 32   // k_tr_bwd_rows: rows summed by one block (its partial is one slab of the column sums)
 
 // --------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al., SC'11): counter (c0, c1, c2, c3), key (k0, k1)
+// The dropout mask: Philox4x32-10 (lt_philox.hip.h)
 // --------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 lt_philox4x32_10(uint4 c, uint2 k) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r) { k.x += 0x9E3779B9u; k.y += 0xBB67AE85u; }
-        const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
-        const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
-        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-    }
-    return c;
-}
-
 // word (i & 3) of Philox(counter (q lo, q hi, epoch, layer), key (seed lo, seed hi)), q = i >> 2
 __device__ __forceinline__ uint4 lt_drop_block(uint64_t q, uint32_t epoch, uint64_t seed, uint32_t layer) {
     return lt_philox4x32_10(make_uint4((uint32_t)q, (uint32_t)(q >> 32), epoch, layer),

@@ -5,6 +5,11 @@ EdgeRand (``--perturb-type discrete``, reference worker.py:213-278) and LapGraph
 The random draws are host numpy, consuming numpy's legacy global stream in the reference's draw order so a
 given ``--noise-seed`` yields the reference's graph (pinned by tests/golden/dp_adjacency.npz); LapGraph's
 O(N^2) add + top-k select run on the GPU when one is visible (``lt_lapgraph_select``, csrc/lt_dp.hip).
+
+``rng="philox"`` is the second, opt-in noise source: the counter-based cell stream of include/linkteller_hip.h
+("edge-DP noise from a counter-based stream"), evaluated per cell on the device (``lt_lapgraph_philox``,
+``lt_edgerand_philox``).  No N x N matrix exists anywhere, so it serves graphs the numpy route cannot hold; a given seed
+gives a different graph than numpy's stream does.  It needs a GPU.
 """
 from __future__ import annotations
 
@@ -29,13 +34,23 @@ def _symmetric_from_upper(rows, cols, n):
     return m + m.T
 
 
-def perturb_adj_discrete(adj, epsilon, noise_seed):
+def _check_rng(rng):
+    if rng not in ("numpy", "philox"):
+        raise ValueError(f"rng = {rng!r}: 'numpy' or 'philox'")
+
+
+def perturb_adj_discrete(adj, epsilon, noise_seed, rng="numpy"):
     """EdgeRand: every cell is re-drawn with probability s = 2/(e^eps+1); re-drawn cells of the upper
     triangle become 1 or 0 with probability 1/2.  Draw order: one N x N binomial, then one binomial
-    per selected cell in row-major order (worker.py:222-233)."""
+    per selected cell in row-major order (worker.py:222-233).
+
+    rng="philox": the same distribution per unordered pair from the device's cell stream (stream 2); no N x N draw."""
+    _check_rng(rng)
     s = 2 / (np.exp(epsilon) + 1)
     print(f"s = {s:.4f}")
     n = adj.shape[0]
+    if rng == "philox":
+        return _edgerand_philox(adj, s, noise_seed)
     np.random.seed(noise_seed)
     rows, cols = np.nonzero(np.random.binomial(1, s, (n, n)))
     coin = np.random.binomial(1, 1 / 2, rows.shape[0])
@@ -59,7 +74,7 @@ def _lapgraph_inputs(adj, epsilon, noise_seed, noise_type, delta):
     return n, noise, n_keep
 
 
-def perturb_adj_continuous(adj, epsilon, noise_seed, noise_type="laplace", delta=1e-5, backend="auto"):
+def perturb_adj_continuous(adj, epsilon, noise_seed, noise_type="laplace", delta=1e-5, backend="auto", rng="numpy"):
     """LapGraph: Laplace(1/eps2) noise on the strict lower triangle, keep the top-(E + noise) cells,
     symmetrise (worker.py:281-335).  eps is split 1 % / 99 % between the edge count and the cells.
     The reference selects the top cells with a 50-way split + argpartition; the selected *set* is the
@@ -67,7 +82,16 @@ def perturb_adj_continuous(adj, epsilon, noise_seed, noise_type="laplace", delta
 
     backend: "hip" -- the noise (numpy's stream, drawn here) is uploaded and the add + top-k select run on the GPU
     (lt_lapgraph_select); "host" -- numpy argpartition, as the reference; "auto" -- "hip" when a HIP device is visible.
-    Both give the same cells (tests/golden/dp_adjacency.npz)."""
+    Both give the same cells (tests/golden/dp_adjacency.npz).
+
+    rng="philox": cell noise and edge count come from the device's cell stream (streams 0 and 1) instead of numpy's; only
+    the CSR is uploaded and the selection runs in O(kept edges) memory (lt_lapgraph_philox).  Laplace only; needs a GPU;
+    ``backend`` does not apply."""
+    _check_rng(rng)
+    if rng == "philox":
+        if noise_type != "laplace":
+            raise NotImplementedError(f"noise {noise_type} is not implemented for rng='philox' (laplace only)")
+        return _lapgraph_philox(adj, epsilon, noise_seed)
     if backend == "auto":
         import torch
         backend = "hip" if torch.cuda.is_available() else "host"
@@ -106,8 +130,143 @@ def _lapgraph_select_hip(adj, noise, n_keep):
     return out.cpu().numpy()
 
 
-def perturb_adj(adj, perturb_type, epsilon, noise_seed, noise_type="laplace", delta=1e-5, backend="auto"):
+def perturb_adj(adj, perturb_type, epsilon, noise_seed, noise_type="laplace", delta=1e-5, backend="auto", rng="numpy"):
     """Dispatch of worker.py:206-210."""
     if perturb_type == "discrete":
-        return perturb_adj_discrete(adj, epsilon, noise_seed)
-    return perturb_adj_continuous(adj, epsilon, noise_seed, noise_type, delta, backend=backend)
+        return perturb_adj_discrete(adj, epsilon, noise_seed, rng=rng)
+    return perturb_adj_continuous(adj, epsilon, noise_seed, noise_type, delta, backend=backend, rng=rng)
+
+
+# ---- rng="philox": the cell stream of include/linkteller_hip.h ------------------------------------------------------------
+
+def _philox4x32_10(counter, key):
+    """One Philox4x32-10 block in Python integers (the host needs a single block: the edge-count draw)."""
+    c0, c1, c2, c3 = counter
+    k0, k1 = key
+    for r in range(10):
+        if r:
+            k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c3 ^ k1, p0 & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def _seed64(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def philox_edge_count_draw(seed, eps_1):
+    """LapGraph's edge-count noise: the inverse-CDF Laplace(1 / eps_1) draw of cell 0 of stream 1."""
+    seed = _seed64(seed)
+    a, b = _philox4x32_10((0, 0, 1, 0), (seed & 0xFFFFFFFF, seed >> 32))[:2]
+    k = (a << 20) | (b >> 12)
+    u = np.float64(2 * k + 1) * np.float64(2.0 ** -53)
+    return float(np.log(2.0 * u) / eps_1 if k < (1 << 51) else -np.log(2.0 * (1.0 - u)) / eps_1)
+
+
+def edgerand_threshold(s):
+    """floor(s 2^52): a cell is re-drawn iff its 52-bit integer is below it."""
+    return int(np.floor(np.float64(s) * np.float64(2.0 ** 52)))
+
+
+def _device_csr(adj):
+    """(rowptr, col) int32 on the current device: sorted, unique, no explicit zeros; col holds one spare element so that an
+    empty graph still has a pointer to give."""
+    import torch
+    low = sp.csr_matrix(adj, copy=True)
+    low.sum_duplicates()
+    low.eliminate_zeros()
+    low.sort_indices()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rowptr = torch.from_numpy(low.indptr.astype(np.int32)).to(dev)
+    col = torch.from_numpy(np.append(low.indices.astype(np.int32), np.int32(0))).to(dev)
+    return rowptr, col, int(low.nnz)
+
+
+def lapgraph_philox_select(adj, seed, edge_factor, n_keep, key_hint=0.0):
+    """The first ``n_keep`` cells of the stream's order (key descending, then cell ascending) on the device: (flat indices
+    i * n + j sorted ascending, info) with ``info`` the int64 [8] of lt_lapgraph_philox."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    _lib.require_gpu()
+    n = adj.shape[0]
+    rowptr, col, nnz = _device_csr(adj)
+    need = C.c_size_t(0)
+    _lib.check(_lib.lib().lt_lapgraph_philox_workspace(n, nnz, int(n_keep), C.byref(need)), "lt_lapgraph_philox_workspace")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=rowptr.device)
+    out = torch.empty(int(n_keep), dtype=torch.int64, device=rowptr.device)
+    info = np.zeros(8, dtype=np.int64)
+    _lib.check(_lib.lib().lt_lapgraph_philox(n, rowptr.data_ptr(), col.data_ptr(), _seed64(seed), float(edge_factor), int(n_keep),
+                                             float(key_hint), out.data_ptr(), info.ctypes.data, ws.data_ptr(), ws.numel(),
+                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "lt_lapgraph_philox")
+    return np.sort(out.cpu().numpy()), info
+
+
+def _lapgraph_philox(adj, epsilon, noise_seed):
+    from . import _lib
+    _lib.require_gpu()
+    n = adj.shape[0]
+    n_edges = len(adj.data) // 2
+    eps_1 = epsilon * 0.01
+    eps_2 = epsilon - eps_1
+    total = n * (n - 1) // 2
+    n_keep = n_edges + int(philox_edge_count_draw(noise_seed, eps_1))
+    print(f"edge number from {n_edges} to {n_keep}")
+    if not 1 <= n_keep <= total:
+        raise ValueError(f"LapGraph: the noisy edge count {n_keep} is outside [1, {total}]")
+    top, _ = lapgraph_philox_select(adj, noise_seed, np.exp(eps_2), n_keep)
+    mat = sp.csr_matrix((np.ones(n_keep, dtype=np.int32), (top // n, top % n)), shape=(n, n))
+    return mat + mat.T
+
+
+def edgerand_philox_cells(n, seed, s_threshold, rows=None, capacity=None):
+    """The re-drawn cells of rows [rows[0], rows[1]) (default: all) and their coins, sorted by cell: (flat indices i * n + j,
+    coins uint8, count).  ``count`` is what the device found; with a ``capacity`` below it only ``capacity`` cells come back."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    _lib.require_gpu()
+    r0, r1 = (0, n) if rows is None else rows
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if capacity is None:
+        cells_in = r1 * (r1 - 1) // 2 - r0 * (r0 - 1) // 2 if r0 else r1 * (r1 - 1) // 2
+        expect = cells_in * (s_threshold / 2.0 ** 52)
+        capacity = int(expect + 8 * np.sqrt(expect) + 1024)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    while True:
+        cell = torch.empty(max(capacity, 1), dtype=torch.int64, device=dev)
+        coin = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().lt_edgerand_philox(n, r0, r1, _seed64(seed), int(s_threshold), cell.data_ptr(), coin.data_ptr(),
+                                                 int(capacity), count.data_ptr(), stream), "lt_edgerand_philox")
+        found = int(count.item())
+        if found <= capacity or rows is not None or capacity == 0:
+            break
+        capacity = found                      # the 8 sigma of slack did not do: the count is known now
+    m = min(found, capacity)
+    cell, coin = cell[:m].cpu().numpy(), coin[:m].cpu().numpy()
+    order = np.argsort(cell, kind="stable")
+    return cell[order], coin[order], found
+
+
+def _edgerand_philox(adj, s, noise_seed):
+    import torch
+    from . import _lib
+    _lib.require_gpu()
+    n = adj.shape[0]
+    thr = edgerand_threshold(s)
+    expect = int(s * (n * (n - 1) // 2))
+    held = 9 * (expect + 8 * int(np.sqrt(expect)) + 1024)          # int64 cell + uint8 coin on the device
+    free = torch.cuda.mem_get_info()[0]
+    if held > 0.8 * free:
+        raise MemoryError(f"EdgeRand with rng='philox' expects {expect} re-drawn cells ({held} bytes on the device, "
+                          f"{free} free): the perturbed graph cannot be held; raise epsilon")
+    cell, coin, _ = edgerand_philox_cells(n, noise_seed, thr)
+    i, j = cell // n, cell % n                                     # j < i
+    add = _symmetric_from_upper(j[coin == 1], i[coin == 1], n)
+    sub = _symmetric_from_upper(j[coin == 0], i[coin == 0], n)
+    noisy = adj + add - sub
+    noisy.data[noisy.data == -1] = 0          # removed a non-edge: stays absent (explicit zero, as on the numpy route)
+    noisy.data[noisy.data == 2] = 1           # added an existing edge
+    return noisy

@@ -46,6 +46,10 @@ _OPTIONS = {
     "influence-mode": (str, "delta", ["full", "sparse", "delta"]), "data-root": (str, "./data"),
     # addition: with --recover, a single density belief k > 0 instead of the ladder r/4 .. 4r (0 = the ladder)
     "density-belief": (float, 0.0),
+    # addition: where the edge-DP noise of --mode vanilla comes from.  'numpy' is the reference's stream (a --noise-seed gives
+    # the reference's graph; an N x N draw on the host); 'philox' is the per-cell stream of include/linkteller_hip.h,
+    # evaluated on the GPU with no N x N matrix -- a different graph for the same seed, under the same result file name
+    "noise-rng": (str, "numpy", ["numpy", "philox"]),
 }
 _SWITCHES = ["no-cuda", "fastmode", "approx", "attack", "test", "break-down", "display", "same-size",
              "eval-degree", "trainable", "early", "fnormalize",

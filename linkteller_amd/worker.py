@@ -80,8 +80,9 @@ class Worker:
     def prepare_data(self):
         a = self.args
         if self.mode == "vanilla":                                # serve the model on DP graphs, worker.py:632-635
-            self.adj_1 = dp.perturb_adj(self.adj_1, a.perturb_type, a.epsilon, a.noise_seed, a.noise_type, a.delta)
-            self.adj_2 = dp.perturb_adj(self.adj_2, a.perturb_type, a.epsilon, a.noise_seed, a.noise_type, a.delta)
+            noise_rng = getattr(a, "noise_rng", "numpy")          # --noise-rng, an addition: callers' Namespaces may lack it
+            self.adj_1 = dp.perturb_adj(self.adj_1, a.perturb_type, a.epsilon, a.noise_seed, a.noise_type, a.delta, rng=noise_rng)
+            self.adj_2 = dp.perturb_adj(self.adj_2, a.perturb_type, a.epsilon, a.noise_seed, a.noise_type, a.delta, rng=noise_rng)
             print("perturbing done!")
         elif self.mode != "vanilla-clean":
             raise NotImplementedError("mode = {} not implemented!".format(self.mode))
