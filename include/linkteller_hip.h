@@ -58,7 +58,9 @@ typedef enum lt_influence_mode {
     LT_MODE_SPARSE = 1, /* bit-identical to FULL, but only rows whose value can differ from the
                            baseline (the 1-/2-hop set of the probe) are recomputed             */
     LT_MODE_DELTA = 2   /* propagates the perturbation itself (piecewise-linear through ReLU):
-                           no cancellation, agrees with an fp64 evaluation of the reference      */
+                           no cancellation, agrees with an fp64 evaluation of the reference
+                           (within 1e-5 of the largest score on the value domain stated at
+                           lt_baseline_enable_fp64)                                              */
 } lt_influence_mode;
 
 typedef struct lt_graph lt_graph;       /* device-resident normalised adjacency (CSR + CSC) */
@@ -282,7 +284,13 @@ int lt_baseline_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F
 /* Adds an fp64-accumulated copy of the pre-activation Z1 (one more X*W1 on the f64 matrix cores +
  * one fp64 SpMM; redone after every lt_baseline_refresh when next needed).  LT_MODE_DELTA then evaluates the ReLU kink
  * test on it, which is what brings it within 1e-6 of an fp64 run of the reference; without it the
- * delta mode still works but entries that cross a kink carry ~1e-4 relative error. */
+ * delta mode still works but entries that cross a kink carry ~1e-4 relative error.
+ * Value domain: by default the product rows are kept as 31-bit fixed point against each ROW's largest value (dense and
+ * feature-difference routes) and the int8 split cuts X / W1 to 39 / 31 bits against the largest value of a (row, K slice) /
+ * (column, K slice); a stored error reaches a unit that crosses its kink divided by the perturbation.  Measured
+ * (tests/test_value_domain_gpu.py): within 1e-5 of the largest score up to a 2^12 scale imbalance between hidden units or range
+ * between feature columns; with a whole row of units at their kinks up to 4x (16x: up to 2.7e-5).  The aggregate-first
+ * route keeps fp64 and has no such limit; "s1_f32" = 0 with "i8_split" = 0 lifts it on every route (<= 2.5e-7 at 2^20). */
 int lt_baseline_enable_fp64(lt_baseline *b, void *stream);
 /* The borrowed weights (same pointers) changed, e.g. once per benchmark step -- and so may have the contents of X, EXCEPT for a
  * baseline with the fp64 pre-activation on the feature-difference route (lt_baseline_fp64_route == 1): that baseline keeps the
