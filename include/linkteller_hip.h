@@ -564,6 +564,61 @@ int lt_lapgraph_philox(int32_t n, const int32_t *d_rowptr, const int32_t *d_col,
 int lt_edgerand_philox(int32_t n, int32_t row_begin, int32_t row_end, uint64_t seed, uint64_t s_threshold, int64_t *out_cell,
                        uint8_t *out_coin, int64_t capacity, int64_t *d_count, void *stream);
 
+/* ---- a DP graph stays on the device: listed cells -> symmetric CSR -> normalised CSR --------------------
+ * lt_sym_csr_from_cells.  cells[k] = i * n + j with j < i (int64, device, any order: what lt_lapgraph_philox and
+ * lt_edgerand_philox write).  Coin 1 sets the unordered pair {i, j}, coin 0 clears it; without coins (coins_or_null == NULL) every
+ * cell sets.  The base is a device CSR (int32, columns sorted and unique per row, both triangles stored) or absent (both pointers
+ * NULL, base_nnz == 0).  Row r of the result is
+ *     {c in base row r : the pair {r, c} is not listed with coin 0}  u  {c : the pair {r, c} is listed with coin 1},
+ * columns strictly increasing; diagonal entries of the base pass through untouched.  LapGraph is base = NULL without coins,
+ * EdgeRand is base = the clean adjacency with coins.
+ * d_info (device int64 [4]): [0] the nnz of the result, [1] the cells that are not a strict-lower-triangle cell of an n x n
+ * matrix, [2] the listed cells that repeat a cell listed before them (m minus the distinct cells), [3] 0.  With [1] or [2]
+ * non-zero the result is unspecified, but no access leaves the buffers.  Nothing is written past out_capacity (entries of
+ * out_col); [0] is reported all the same, the capacity contract of lt_philox_cells_scan.  base_nnz + 2 m always suffices.
+ * out_rowptr: [n + 1].  The base's row offsets are taken as given (clamped to [0, base_nnz]); they are not validated.
+ * Enqueue only, no host round trip: the 2 m directed entries are sorted by (row, col) with two stable LSD radix sorts (the kernels
+ * of lt_graph_create_device's transpose), row extents come from a bisection of the sorted rows, every base and listed entry finds
+ * its place in its row's merged order by a bisection of the other side, and an ordered compaction (flags, scan, write) keeps what
+ * the rule above keeps.  Stream order is the only barrier between blocks.  The output is a pure function of the input: two calls
+ * give identical bytes, whatever the order of the cells.
+ * LT_ERR_INVALID before anything is enqueued: NULL pointers other than the two _or_null (and the base pair, which is given or
+ * absent as a pair), n < 2, m < 0, base_nnz < 0, out_capacity < 0, base_nnz + 2 m >= 2^31 - 1, a workspace smaller than
+ * lt_sym_csr_workspace_bytes(n, base_nnz, m) or not 8-byte aligned.  m == 0 with a base copies the base; m == 0 without one
+ * gives the empty graph.  The query returns 0 for invalid arguments; it is linear in base_nnz + m plus O(n) words.
+ *
+ * lt_normalize_csr: the six normalisers of the reference (utils/load.py:562-627) on a UNIT PATTERN -- every stored entry counts as
+ * 1, what a DP graph is -- in the float64 arithmetic numpy gives an integer adjacency, narrowed once to float32:
+ *   a_rc = 1, plus 1 on the diagonal for LT_NORM_AUG_NORM_ADJ, LT_NORM_AUG_RWALK and LT_NORM_BINGGE (a missing diagonal entry is
+ *          inserted, one that is present becomes 2);   s_r = stored entries of row r, plus 1 for those three;   d_r = inv_pow[s_r]
+ *   value = fl64(fl64(d_r * a_rc) * d_c) for the power -1/2 forms (FIRST_ORDER_GCN, BINGGE, NORM_ADJ, AUG_NORM_ADJ),
+ *           fl64(d_r * a_rc) for the two random-walk forms (RWALK, AUG_RWALK);
+ *   then + 1.0 on the diagonal in float64 for FIRST_ORDER_GCN and BINGGE (the entry is inserted if absent);
+ *   then one round-to-nearest-even narrowing to float32.
+ * inv_pow (device double [n + 2]) is the caller's: inv_pow[s] = s^p as numpy's np.power(np.arange(n + 2.0), p) gives it, p = -1/2
+ * with the infinity at s = 0 replaced by 0 for the four power -1/2 forms, p = -1 with the infinity kept for the two random-walk
+ * forms.  The table makes the values numpy's bit for bit without leaning on the device's pow.
+ * out_rowptr [n + 1], out_col / out_val: out_capacity entries; nnz + n always suffices and nothing is written past it.
+ * d_info (device int64 [4]): [0] the nnz written (nnz + n - diagonals present for the four identity-adding forms, nnz for the
+ * others), [1] the rows whose columns are not strictly increasing or not in [0, n); with [1] non-zero the output is unspecified,
+ * but in bounds.  rowptr is taken as given (clamped to [0, nnz]).  Enqueue only: row lengths, a one-block scan, a fill with a
+ * quarter wave per row.  LT_ERR_INVALID before anything is enqueued: NULL pointers, n < 1, nnz < 0 or >= 2^31 - 1 - n, an unknown
+ * norm, negative capacity.  Both are additive in ABI 5. */
+typedef enum lt_norm {
+    LT_NORM_FIRST_ORDER_GCN = 0, /* I + D^-1/2 A D^-1/2                  */
+    LT_NORM_BINGGE = 1,          /* (D+I)^-1/2 (A+I) (D+I)^-1/2 + I      */
+    LT_NORM_NORM_ADJ = 2,        /* D^-1/2 A D^-1/2                      */
+    LT_NORM_AUG_RWALK = 3,       /* (D+I)^-1 (A+I)                       */
+    LT_NORM_RWALK = 4,           /* D^-1 A                               */
+    LT_NORM_AUG_NORM_ADJ = 5     /* (D+I)^-1/2 (A+I) (D+I)^-1/2          */
+} lt_norm;
+size_t lt_sym_csr_workspace_bytes(int32_t n, int64_t base_nnz, int64_t m);
+int lt_sym_csr_from_cells(int32_t n, const int32_t *base_rowptr_or_null, const int32_t *base_col_or_null, int64_t base_nnz,
+                          const int64_t *cells, const uint8_t *coins_or_null, int64_t m, int32_t *out_rowptr, int32_t *out_col,
+                          int64_t out_capacity, int64_t *d_info, void *ws, size_t ws_bytes, void *stream);
+int lt_normalize_csr(int32_t n, const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t norm, const double *inv_pow,
+                     int32_t *out_rowptr, int32_t *out_col, float *out_val, int64_t out_capacity, int64_t *d_info, void *stream);
+
 /* ---- edge recovery: the m highest-scoring pairs of sampled nodes (attack_stats_all.py:106-116: n_pos = ceil(ratio * n_total),
  * ind = np.argpartition(pred, -n_pos)[-n_pos:] over the saved score list, then precision / recall / F1 of y[ind]) -----------
  * scores: device [n, lds] fp32, what lt_influence_rows / lt_influence3_rows* wrote for probes == observed == the sampled nodes.

@@ -104,6 +104,11 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "lt_edgerand_philox": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p]),
+    "lt_sym_csr_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64]),
+    "lt_sym_csr_from_cells": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lt_normalize_csr": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "lt_top_pairs_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "lt_top_pairs_lower": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),
@@ -144,6 +149,8 @@ KERNEL_IDS = {"gemm": 0, "layer1": 1, "layer2": 2, "perturb": 3, "full_stageA": 
               "item_stageA": 6, "item_stageB": 7, "spmm": 8, "fp64_product": 9, "fp64_spmm": 10, "item_bits": 11,
               "select_hist": 12, "select_collect": 13, "metrics_sort": 14, "metrics_curve": 15}
 ABI_VERSION = 5
+# lt_normalize_csr: the `norm` values (include/linkteller_hip.h, lt_norm) by the names of graph._NORMALIZERS
+NORM_CODES = {"FirstOrderGCN": 0, "BingGeNormAdj": 1, "NormAdj": 2, "AugRWalk": 3, "RWalk": 4, "AugNormAdj": 5}
 # lt_graph_table: the `which` values (include/linkteller_hip.h, lt_graph_table_id) and the names of the scalar table's entries
 GRAPH_TABLES = {"rowptr": (0, "i4"), "col": (1, "i4"), "val": (2, "f4"), "tptr": (3, "i4"), "trow": (4, "i4"), "tval": (5, "f4"),
                 "tpos": (6, "i4"), "cv": (7, "i4"), "dl_meta": (8, "i4"), "dl_rec": (9, "i4"), "p_long_row": (10, "i4"),

@@ -10,6 +10,9 @@ O(N^2) add + top-k select run on the GPU when one is visible (``lt_lapgraph_sele
 ("edge-DP noise from a counter-based stream"), evaluated per cell on the device (``lt_lapgraph_philox``,
 ``lt_edgerand_philox``).  No N x N matrix exists anywhere, so it serves graphs the numpy route cannot hold; a given seed
 gives a different graph than numpy's stream does.  It needs a GPU.
+
+``perturb_adj_device`` is that route with the graph kept on the device: the cells the two generators write become a symmetric
+CSR there (``lt_sym_csr_from_cells``, csrc/lt_dp_graph.hip) and nothing of O(E) visits the host.
 """
 from __future__ import annotations
 
@@ -183,15 +186,12 @@ def _device_csr(adj):
     return rowptr, col, int(low.nnz)
 
 
-def lapgraph_philox_select(adj, seed, edge_factor, n_keep, key_hint=0.0):
-    """The first ``n_keep`` cells of the stream's order (key descending, then cell ascending) on the device: (flat indices
-    i * n + j sorted ascending, info) with ``info`` the int64 [8] of lt_lapgraph_philox."""
+def _lapgraph_philox_cells(rowptr, col, nnz, seed, edge_factor, n_keep, key_hint=0.0):
+    """``lt_lapgraph_philox`` on a device CSR: (the selected cells, an unordered int64 CUDA tensor [n_keep]; info, host int64 [8])."""
     import ctypes as C
     import torch
     from . import _lib
-    _lib.require_gpu()
-    n = adj.shape[0]
-    rowptr, col, nnz = _device_csr(adj)
+    n = rowptr.numel() - 1
     need = C.c_size_t(0)
     _lib.check(_lib.lib().lt_lapgraph_philox_workspace(n, nnz, int(n_keep), C.byref(need)), "lt_lapgraph_philox_workspace")
     ws = torch.empty(need.value, dtype=torch.uint8, device=rowptr.device)
@@ -200,33 +200,46 @@ def lapgraph_philox_select(adj, seed, edge_factor, n_keep, key_hint=0.0):
     _lib.check(_lib.lib().lt_lapgraph_philox(n, rowptr.data_ptr(), col.data_ptr(), _seed64(seed), float(edge_factor), int(n_keep),
                                              float(key_hint), out.data_ptr(), info.ctypes.data, ws.data_ptr(), ws.numel(),
                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)), "lt_lapgraph_philox")
+    return out, info
+
+
+def lapgraph_philox_select(adj, seed, edge_factor, n_keep, key_hint=0.0):
+    """The first ``n_keep`` cells of the stream's order (key descending, then cell ascending) on the device: (flat indices
+    i * n + j sorted ascending, info) with ``info`` the int64 [8] of lt_lapgraph_philox."""
+    from . import _lib
+    _lib.require_gpu()
+    out, info = _lapgraph_philox_cells(*_device_csr(adj), seed, edge_factor, n_keep, key_hint)
     return np.sort(out.cpu().numpy()), info
+
+
+def _lapgraph_philox_n_keep(n, n_edges, epsilon, noise_seed):
+    """(n_keep, eps_2): the noisy edge count of the 1 % / 99 % split, printed and checked as on the numpy route."""
+    eps_1 = epsilon * 0.01
+    total = n * (n - 1) // 2
+    n_keep = n_edges + int(philox_edge_count_draw(noise_seed, eps_1))
+    print(f"edge number from {n_edges} to {n_keep}")
+    if not 1 <= n_keep <= total:
+        raise ValueError(f"LapGraph: the noisy edge count {n_keep} is outside [1, {total}]")
+    return n_keep, epsilon - eps_1
 
 
 def _lapgraph_philox(adj, epsilon, noise_seed):
     from . import _lib
     _lib.require_gpu()
     n = adj.shape[0]
-    n_edges = len(adj.data) // 2
-    eps_1 = epsilon * 0.01
-    eps_2 = epsilon - eps_1
-    total = n * (n - 1) // 2
-    n_keep = n_edges + int(philox_edge_count_draw(noise_seed, eps_1))
-    print(f"edge number from {n_edges} to {n_keep}")
-    if not 1 <= n_keep <= total:
-        raise ValueError(f"LapGraph: the noisy edge count {n_keep} is outside [1, {total}]")
+    n_keep, eps_2 = _lapgraph_philox_n_keep(n, len(adj.data) // 2, epsilon, noise_seed)
     top, _ = lapgraph_philox_select(adj, noise_seed, np.exp(eps_2), n_keep)
     mat = sp.csr_matrix((np.ones(n_keep, dtype=np.int32), (top // n, top % n)), shape=(n, n))
     return mat + mat.T
 
 
-def edgerand_philox_cells(n, seed, s_threshold, rows=None, capacity=None):
-    """The re-drawn cells of rows [rows[0], rows[1]) (default: all) and their coins, sorted by cell: (flat indices i * n + j,
-    coins uint8, count).  ``count`` is what the device found; with a ``capacity`` below it only ``capacity`` cells come back."""
+def _edgerand_philox_cells_device(n, seed, s_threshold, rows=None, capacity=None):
+    """``lt_edgerand_philox`` over rows [rows[0], rows[1]) (default: all): (cells int64, coins uint8 -- CUDA tensors in the
+    device's order, cut to what was written --, the count the device found).  Without ``rows`` a capacity that proves too small
+    is raised to the count and the call repeated."""
     import ctypes as C
     import torch
     from . import _lib
-    _lib.require_gpu()
     r0, r1 = (0, n) if rows is None else rows
     dev = torch.device("cuda", torch.cuda.current_device())
     if capacity is None:
@@ -245,24 +258,37 @@ def edgerand_philox_cells(n, seed, s_threshold, rows=None, capacity=None):
             break
         capacity = found                      # the 8 sigma of slack did not do: the count is known now
     m = min(found, capacity)
-    cell, coin = cell[:m].cpu().numpy(), coin[:m].cpu().numpy()
+    return cell[:m], coin[:m], found
+
+
+def edgerand_philox_cells(n, seed, s_threshold, rows=None, capacity=None):
+    """The re-drawn cells of rows [rows[0], rows[1]) (default: all) and their coins, sorted by cell: (flat indices i * n + j,
+    coins uint8, count).  ``count`` is what the device found; with a ``capacity`` below it only ``capacity`` cells come back."""
+    from . import _lib
+    _lib.require_gpu()
+    cell, coin, found = _edgerand_philox_cells_device(n, seed, s_threshold, rows, capacity)
+    cell, coin = cell.cpu().numpy(), coin.cpu().numpy()
     order = np.argsort(cell, kind="stable")
     return cell[order], coin[order], found
 
 
-def _edgerand_philox(adj, s, noise_seed):
+def _edgerand_philox_guard(n, s, bytes_per_cell):
+    """EdgeRand's output grows with s n^2 / 2: refuse what the device cannot hold (``bytes_per_cell`` per re-drawn cell)."""
     import torch
-    from . import _lib
-    _lib.require_gpu()
-    n = adj.shape[0]
-    thr = edgerand_threshold(s)
     expect = int(s * (n * (n - 1) // 2))
-    held = 9 * (expect + 8 * int(np.sqrt(expect)) + 1024)          # int64 cell + uint8 coin on the device
+    held = bytes_per_cell * (expect + 8 * int(np.sqrt(expect)) + 1024)
     free = torch.cuda.mem_get_info()[0]
     if held > 0.8 * free:
         raise MemoryError(f"EdgeRand with rng='philox' expects {expect} re-drawn cells ({held} bytes on the device, "
                           f"{free} free): the perturbed graph cannot be held; raise epsilon")
-    cell, coin, _ = edgerand_philox_cells(n, noise_seed, thr)
+
+
+def _edgerand_philox(adj, s, noise_seed):
+    from . import _lib
+    _lib.require_gpu()
+    n = adj.shape[0]
+    _edgerand_philox_guard(n, s, 9)                                # int64 cell + uint8 coin on the device
+    cell, coin, _ = edgerand_philox_cells(n, noise_seed, edgerand_threshold(s))
     i, j = cell // n, cell % n                                     # j < i
     add = _symmetric_from_upper(j[coin == 1], i[coin == 1], n)
     sub = _symmetric_from_upper(j[coin == 0], i[coin == 0], n)
@@ -270,3 +296,89 @@ def _edgerand_philox(adj, s, noise_seed):
     noisy.data[noisy.data == -1] = 0          # removed a non-edge: stays absent (explicit zero, as on the numpy route)
     noisy.data[noisy.data == 2] = 1           # added an existing edge
     return noisy
+
+
+# ---- the philox route with the graph kept on the device ------------------------------------------------------
+
+def sym_csr_from_cells(n, cells, coins=None, base=None):
+    """``lt_sym_csr_from_cells``: the listed lower-triangle cells (int64 CUDA tensor of flat indices i * n + j, j < i; ``coins``
+    uint8 or None = every cell sets) merged with ``base`` (a ``(rowptr, col, nnz)`` triple of int32 CUDA tensors, or None) into a
+    symmetric CSR.  Returns (rowptr int32 [n + 1], col int32 [base nnz + 2 m, which always suffices], info int64 [4] on the
+    device): the caller reads ``info`` (nnz, bad cells, repeated cells) and cuts ``col``."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    _lib.require_gpu()
+    m = int(cells.numel())
+    dev = cells.device
+    b_rowptr, b_col, b_nnz = base if base is not None else (None, None, 0)
+    capacity = b_nnz + 2 * m
+    need = _lib.lib().lt_sym_csr_workspace_bytes(n, b_nnz, m)
+    if need == 0:
+        raise ValueError(f"lt_sym_csr_from_cells: n = {n}, {b_nnz} base entries and {m} cells are outside what int32 row pointers hold")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    col = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
+    info = torch.empty(4, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().lt_sym_csr_from_cells(
+            n, b_rowptr.data_ptr() if base is not None else None, b_col.data_ptr() if base is not None else None, b_nnz,
+            cells.data_ptr(), coins.data_ptr() if coins is not None else None, m, rowptr.data_ptr(), col.data_ptr(), capacity,
+            info.data_ptr(), ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "lt_sym_csr_from_cells")
+    return rowptr, col, info
+
+
+def _checked_sym_csr(n, cells, coins, base):
+    """(rowptr, col) cut to the result's nnz; the generators' cells are distinct strict-lower cells, anything else is a bug."""
+    rowptr, col, info = sym_csr_from_cells(n, cells, coins, base)
+    nnz, bad, repeated, _ = info.tolist()                                # the one read-back of this stage: 32 bytes
+    if bad or repeated:
+        raise RuntimeError(f"lt_sym_csr_from_cells: {bad} cells outside the strict lower triangle, {repeated} repeated cells")
+    return rowptr, col[:nnz]
+
+
+def _as_device_csr(adj):
+    """(rowptr, col, nnz) on the device from a scipy matrix (``_device_csr``) or from a (rowptr, col) pair of int32 CUDA tensors
+    (canonical: columns sorted and unique per row; ``col`` may carry spare elements behind rowptr[n] entries)."""
+    import torch
+    if isinstance(adj, (tuple, list)):
+        rowptr, col = adj
+        for name, t in (("rowptr", rowptr), ("col", col)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1:
+                raise TypeError(f"perturb_adj_device: {name} must be a 1-D int32 CUDA tensor")
+        if rowptr.numel() < 1 or rowptr.device != col.device:
+            raise ValueError("perturb_adj_device: rowptr is empty or lies on another device than col")
+        nnz = int(rowptr[-1].item())
+        if not 0 <= nnz <= col.numel():
+            raise ValueError(f"perturb_adj_device: rowptr[n] = {nnz} with {col.numel()} columns")
+        rowptr, col = rowptr.contiguous(), col.contiguous()
+        if col.numel() == nnz:                                           # the kernels want a pointer even for an empty graph
+            col = torch.cat([col, col.new_zeros(1)])
+        return rowptr, col, nnz
+    return _device_csr(adj)
+
+
+def perturb_adj_device(adj, perturb_type, epsilon, noise_seed, noise_type="laplace", delta=1e-5):
+    """``perturb_adj(..., rng="philox")`` with the result left on the device: (rowptr, col) int32 CUDA tensors of the perturbed
+    0/1 graph, columns strictly increasing, no explicit zeros (the host EdgeRand route keeps a cleared non-edge as an explicit
+    zero; it is the same graph).  ``adj``: a scipy matrix, or a (rowptr, col) pair of int32 CUDA tensors.  Draws, prints and
+    refusals are the philox route's: Laplace only, a GPU is needed, EdgeRand refuses a graph the device cannot hold."""
+    import torch
+    from . import _lib
+    if perturb_type != "discrete" and noise_type != "laplace":
+        raise NotImplementedError(f"noise {noise_type} is not implemented for rng='philox' (laplace only)")
+    _lib.require_gpu()
+    rowptr, col, nnz = _as_device_csr(adj)
+    n = rowptr.numel() - 1
+    with torch.cuda.device(rowptr.device):
+        if perturb_type == "discrete":
+            s = 2 / (np.exp(epsilon) + 1)
+            print(f"s = {s:.4f}")
+            # per re-drawn cell: int64 cell + uint8 coin, then two directed entries of four sort words, a merged column and a flag
+            _edgerand_philox_guard(n, s, 9 + 2 * 24)
+            cell, coin, _ = _edgerand_philox_cells_device(n, noise_seed, edgerand_threshold(s))
+            return _checked_sym_csr(n, cell, coin, (rowptr, col, nnz))
+        # (the host route counts the entries of the matrix it is given)
+        n_keep, eps_2 = _lapgraph_philox_n_keep(n, len(adj.data) // 2 if sp.issparse(adj) else nnz // 2, epsilon, noise_seed)
+        out, _ = _lapgraph_philox_cells(rowptr, col, nnz, noise_seed, np.exp(eps_2), n_keep)
+        return _checked_sym_csr(n, out, None, None)

@@ -132,6 +132,62 @@ def sparse_mx_to_torch_sparse_tensor(sparse_mx):
 
 
 # ----------------------------------------------------------------------------------------------
+# the same on the device, for a 0/1 pattern that already lies there (a DP graph: dp.perturb_adj_device)
+# ----------------------------------------------------------------------------------------------
+def inv_power_table(name: str, n: int) -> np.ndarray:
+    """float64 [n + 2]: what ``_inv_power`` gives the row sums 0 .. n + 1 under the normaliser ``name`` -- the table
+    ``lt_normalize_csr`` reads instead of computing a power on the device."""
+    if name not in _NORMALIZERS:
+        raise NotImplementedError(f"normalization {name!r} not implemented")
+    walk = name in ("RWalk", "AugRWalk")
+    return _inv_power(np.arange(n + 2, dtype=np.float64), -1.0 if walk else -0.5, not walk)
+
+
+def normalize_device(name: str, rowptr, col):
+    """``csr_arrays(fetch_normalization(name)(a))`` for the 0/1 matrix ``a`` whose pattern is the device CSR (``rowptr`` int32
+    [n + 1], ``col`` int32, CUDA tensors, columns strictly increasing): (rowptr, col, val) on the device, structure and float32
+    bits equal to the host's (``lt_normalize_csr``).  Reads 32 bytes back: the nnz and the count of malformed rows."""
+    import torch
+    if name not in _NORMALIZERS:
+        raise NotImplementedError(f"normalization {name!r} not implemented")
+    _lib.require_gpu()
+    for what, t in (("rowptr", rowptr), ("col", col)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1:
+            raise TypeError(f"normalize_device: {what} must be a 1-D int32 CUDA tensor")
+    if rowptr.numel() < 2 or rowptr.device != col.device:
+        raise ValueError("normalize_device: rowptr needs n + 1 >= 2 words on the device of col")
+    rowptr, col = rowptr.contiguous(), col.contiguous()
+    n, nnz = rowptr.numel() - 1, col.numel()
+    dev = rowptr.device
+    inv_pow = torch.from_numpy(inv_power_table(name, n)).to(dev)
+    capacity = nnz + n
+    out_rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    out_col = torch.empty(capacity, dtype=torch.int32, device=dev)
+    out_val = torch.empty(capacity, dtype=torch.float32, device=dev)
+    info = torch.empty(4, dtype=torch.int64, device=dev)
+    col_arg = col if nnz else col.new_zeros(1)                            # a pointer even for an empty graph
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().lt_normalize_csr(n, rowptr.data_ptr(), col_arg.data_ptr(), nnz, _lib.NORM_CODES[name], inv_pow.data_ptr(),
+                                               out_rowptr.data_ptr(), out_col.data_ptr(), out_val.data_ptr(), capacity,
+                                               info.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                   "lt_normalize_csr")
+    out_nnz, bad = info[:2].tolist()
+    if bad:
+        raise ValueError(f"normalize_device: {bad} rows whose columns are not strictly increasing or not in [0, {n})")
+    return out_rowptr, out_col[:out_nnz], out_val[:out_nnz]
+
+
+def torch_sparse_from_device_csr(rowptr, col, val):
+    """The sparse COO CUDA tensor ``sparse_mx_to_torch_sparse_tensor(m).cuda()`` gives for the matrix of this device CSR: int64
+    indices in row-major order, float32 values, not marked coalesced.  Torch ops on the device, no kernel of ours."""
+    import torch
+    n = rowptr.numel() - 1
+    rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=rowptr.device), torch.diff(rowptr).to(torch.int64),
+                                   output_size=int(col.numel()))
+    return torch.sparse_coo_tensor(torch.stack((rows, col.to(torch.int64))), val.to(torch.float32), torch.Size((n, n)))
+
+
+# ----------------------------------------------------------------------------------------------
 # device graph handle
 # ----------------------------------------------------------------------------------------------
 def csr_arrays(mat):
@@ -212,6 +268,12 @@ class HipGraph:
         g = cls.__new__(cls)
         g._create_device(rowptr, col, val)
         return g
+
+    @classmethod
+    def from_device_pattern(cls, rowptr, col, norm):
+        """A graph from a 0/1 pattern on the device (``dp.perturb_adj_device``): normalised there (``normalize_device``) and
+        handed to ``from_device_csr``."""
+        return cls.from_device_csr(*normalize_device(norm, rowptr, col))
 
     @property
     def handle(self):

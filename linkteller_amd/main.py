@@ -50,6 +50,10 @@ _OPTIONS = {
     # the reference's graph; an N x N draw on the host); 'philox' is the per-cell stream of include/linkteller_hip.h,
     # evaluated on the GPU with no N x N matrix -- a different graph for the same seed, under the same result file name
     "noise-rng": (str, "numpy", ["numpy", "philox"]),
+    # addition: where the DP graphs of --mode vanilla are assembled and normalised.  'host' is scipy, as the reference; 'device'
+    # keeps the cells of --noise-rng philox on the GPU from the noise seed to the served graph (symmetric CSR, normaliser and
+    # sparse tensor are built there: the same graph, the same float32 values)
+    "dp-build": (str, "host", ["host", "device"]),
 }
 _SWITCHES = ["no-cuda", "fastmode", "approx", "attack", "test", "break-down", "display", "same-size",
              "eval-degree", "trainable", "early", "fnormalize",
@@ -137,10 +141,21 @@ def check_metrics_only(args):
                                   "the baseline attacks score their pairs on the host)")
 
 
+def check_dp_build(args):
+    """``--dp-build device`` assembles the graphs the philox stream generates on the device: it is refused here, before a Worker
+    is built or the GPU is touched, unless ``--mode vanilla --noise-rng philox`` asks for such graphs."""
+    if getattr(args, "dp_build", "host") != "device":
+        return
+    if not (args.mode == "vanilla" and args.noise_rng == "philox"):
+        raise NotImplementedError("--dp-build device needs --mode vanilla and --noise-rng philox "
+                                  f"(got mode={args.mode}, noise-rng={args.noise_rng}: those graphs are built on the host)")
+
+
 def main(argv=None):
     args = get_arguments(argv)
     check_recover(args)
     check_metrics_only(args)
+    check_dp_build(args)
     import os
     if args.train and not args.test:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:

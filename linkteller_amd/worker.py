@@ -79,6 +79,9 @@ class Worker:
 
     def prepare_data(self):
         a = self.args
+        if self.mode == "vanilla" and getattr(a, "dp_build", "host") == "device":   # --dp-build, an addition: the DP graphs never
+            self._prepare_dp_on_device()                                            # leave the device
+            return
         if self.mode == "vanilla":                                # serve the model on DP graphs, worker.py:632-635
             noise_rng = getattr(a, "noise_rng", "numpy")          # --noise-rng, an addition: callers' Namespaces may lack it
             self.adj_1 = dp.perturb_adj(self.adj_1, a.perturb_type, a.epsilon, a.noise_seed, a.noise_type, a.delta, rng=noise_rng)
@@ -94,3 +97,19 @@ class Worker:
             self.features_1, self.features_2 = self.features_1.cuda(), self.features_2.cuda()
             self.labels_1, self.labels_2 = self.labels_1.cuda(), self.labels_2.cuda()
             self.adj_1, self.adj_2 = self.adj_1.cuda(), self.adj_2.cuda()
+
+    def _prepare_dp_on_device(self):
+        """``--dp-build device`` (with ``--noise-rng philox``): scipy -> perturbed CSR -> normalised CSR -> sparse tensor, all on the
+        GPU; ``adj_1`` / ``adj_2`` hold what the host route's ``.cuda()`` tensors hold, without its explicit zeros."""
+        from .graph import normalize_device, torch_sparse_from_device_csr
+        a = self.args
+        if getattr(a, "noise_rng", "numpy") != "philox":
+            raise NotImplementedError("dp_build = device needs noise_rng = philox (the numpy stream is drawn on the host)")
+        pattern_1 = dp.perturb_adj_device(self.adj_1, a.perturb_type, a.epsilon, a.noise_seed, a.noise_type, a.delta)
+        pattern_2 = dp.perturb_adj_device(self.adj_2, a.perturb_type, a.epsilon, a.noise_seed, a.noise_type, a.delta)
+        print("perturbing done!")
+        self.adj_1 = torch_sparse_from_device_csr(*normalize_device(a.norm, *pattern_1))
+        self.adj_2 = torch_sparse_from_device_csr(*normalize_device(a.norm, *pattern_2))
+        print("Normalizing Adj done!")
+        self.features_1, self.features_2 = self.features_1.cuda(), self.features_2.cuda()
+        self.labels_1, self.labels_2 = self.labels_1.cuda(), self.labels_2.cuda()
