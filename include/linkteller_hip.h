@@ -38,7 +38,9 @@ extern "C" {
                             Additive within 5: training of the 2-layer GCN (lt_gcn2_trainer_*) and lt_adam_step; no entry point changed.
                             Additive within 5: training of the 3-layer GCN (lt_gcn3_trainer_*); no entry point changed.
                             Additive within 5: edge recovery (lt_top_pairs_lower, profile classes 12-13); no entry point changed.
-                            Additive within 5: attack metrics (lt_score_curve, profile classes 14-15); no entry point changed */
+                            Additive within 5: attack metrics (lt_score_curve, profile classes 14-15); no entry point changed.
+                            Additive within 5: the attack's node pairs (lt_sample_square_labels, lt_group_pairs, lt_upper_edge_count,
+                            lt_sample_balanced_philox); no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -523,6 +525,7 @@ int lt_lapgraph_select(int32_t n, const int32_t *lower_rowptr, const int32_t *lo
  *   block     q = t >> 1; counter (q & 0xffffffff, q >> 32, stream, 0), key (seed & 0xffffffff, seed >> 32) -> words w[0 .. 3];
  *             cell t takes a = w[2 (t & 1)] and b = w[2 (t & 1) + 1]
  *   stream    0: LapGraph's cell noise, 1: LapGraph's edge-count draw (cell 0 only; drawn by the host), 2: EdgeRand
+ *             (3: the non-edge draws of lt_sample_balanced_philox, which are indexed by draw and not by cell; stated there)
  *   uniform   k = (a << 20) | (b >> 12) (52 bits); u = (2 k + 1) 2^-53, exact, in (0, 1); coin = b & 1 (not a bit of k)
  *   LapGraph  g = 2 u if k < 2^51, else 1 / (2 (1 - u)); key = g c for an edge cell, g otherwise, with c = exp(eps2) computed once
  *             by the caller (`edge_factor`).  The key is exp((a_ij + Laplace(1 / eps2)) eps2) for the inverse-CDF Laplace draw of
@@ -667,6 +670,71 @@ int lt_score_curve(const float *scores, int64_t n_scores, const int64_t *index_o
                    const uint8_t *labels, int64_t n_items,
                    float *thresholds, int64_t *tps, int64_t *fps, int64_t *summary,
                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- the attack's node pairs: which pairs are scored and which of them are edges -------------------------
+ * The adjacency of the four functions is a device CSR of int32 (d_rowptr [n + 1], d_col, nnz stored entries) whose columns are
+ * sorted and unique within a row.  A stored entry counts whatever its value: structural presence, what the reference's
+ * _get_edge_sets_among_nodes (utils/load.py:304-326) and construct_balanced_edge_sets (utils/load.py:219-249) read.  d_col must be
+ * a valid pointer even for a graph without entries.  Row offsets are taken as given (clamped to [0, nnz]).
+ *
+ * lt_sample_square_labels: all pairs of a node sample.  nodes[k]: int32, device, distinct ids in [0, n), in ANY order (a sample is
+ * not sorted).  Pair (i, j), i < j, of POSITIONS has slot p = i (2 k - i - 1) / 2 + (j - i - 1) -- row-major over the strict upper
+ * triangle, the reference's enumeration order -- of T = k (k - 1) / 2:
+ *   out_labels[p] (uint8) = 1 iff nodes[j] is stored in row nodes[i] (directed, as in the reference), else 0
+ *   out_index_or_null[p] (int64) = j * lds + i: the storage element of the cell "perturb nodes[j], observe nodes[i]" in score rows
+ *                                  of stride lds >= k (what lt_score_curve takes as its index)
+ *   d_info (device int64 [4]): [0] labels set, [1] nodes outside [0, n), [2] nodes that repeat an earlier one, [3] 0.  With [1] or
+ *                              [2] non-zero the outputs are unspecified, but no access leaves the buffers.
+ * Enqueue only, no host round trip: a position map pos[node] in the workspace is cleared, scattered and checked back; one block
+ * per position i clears its stretch of labels and writes its stretch of the index, then walks row nodes[i] block-wide (a hub row
+ * costs its length / 256 trips) and sets the label of every column c with pos[c] > i.  The count is an integer atomic.
+ * LT_ERR_INVALID before anything is enqueued: NULL pointers other than the index, n < 1, k < 2, lds < k, nnz outside [0, 2^31 - 1),
+ * a workspace smaller than lt_sample_square_workspace_bytes(n, k) or not 8-byte aligned.  The query returns 0 for invalid arguments.
+ *
+ * lt_group_pairs: probe[m], observed[m] (int32, device, ids in [0, n)) -> the grouped layout of lt_influence_pairs:
+ *   out_order [m] int32    the STABLE sort of the pairs by probe (the pairs of one probe keep their input order, repeats are kept)
+ *   out_obs   [m] int32    observed[out_order[p]]
+ *   out_nodes [m] int32    entries [0, G): the distinct probes, ascending
+ *   out_ptr   [m + 1] int64, DEVICE   entries [0, G]: group g is [out_ptr[g], out_ptr[g + 1]) of out_obs
+ *   d_info (device int64 [4]): [0] G, [1] ids (of either list) outside [0, n): the result is then unspecified, but in bounds; [2], [3] 0
+ * Enqueue only: the stable LSD radix sort of lt_graph_create_device (the digit passes that order [0, n - 1], the pair's index as
+ * payload), run ends, a scan, a compaction of the group heads.  LT_ERR_INVALID before anything is enqueued: NULL pointers, n < 1,
+ * m outside [1, 2^31 - 2], a workspace smaller than lt_group_pairs_workspace_bytes(m) or not 8-byte aligned.
+ *
+ * lt_upper_edge_count: *d_count (device int64) = E, the stored entries with col > row.  Enqueue only.
+ *
+ * lt_sample_balanced_philox: the `balanced-full` pair lists as two int32 device arrays out_u, out_v of 2 E entries.
+ *   [0, E)    the edges: every stored entry with col > row as (row, col), rows ascending, columns ascending within a row
+ *   [E, 2 E)  the non-edges: the first E ACCEPTED draws of STREAM 3 of the Philox contract above, in draw order:
+ *               draw t = 0, 1, 2, ... (64 bits); counter (t & 0xffffffff, t >> 32, 3, 0), key (seed & 0xffffffff, seed >> 32)
+ *               -> words w[0 .. 3];  u = (uint64(w[0]) * n) >> 32,  v = (uint64(w[1]) * n) >> 32;  w[2], w[3] are unused.
+ *               n < 2^31; the multiply-shift favours an id over another by at most n 2^-32 in probability.
+ *             A draw is accepted iff v is not stored in row u AND u is not stored in row v.  The reference's quirks are kept:
+ *             u == v is accepted unless (u, u) is stored, repeated pairs are kept, both directions are tested.  Like the DP
+ *             streams, a seed gives a DIFFERENT sample than numpy's generator would.
+ * Draws are evaluated in rounds of round_draws consecutive t (0: a default near 9 E / 8, at most 2^22; at most 2^24): flags (two
+ * bisections of sorted rows per draw), a scan, an ordered write of the accepted draws that still fit.  The host reads the running
+ * count after each round, so the call SYNCHRONISES the stream, as lt_lapgraph_philox does.  The result is a pure function of
+ * (graph, seed): it depends on neither round_draws nor the number of rounds.  E is the caller's, from lt_upper_edge_count; max_draws
+ * bounds t (0: 64 E + 4096).  info (HOST int64 [8]): [0] E, [1] draws consumed (t of the last accepted draw + 1), [2] rounds,
+ * [3] accepted draws with u == v, the rest 0.  E == 0 writes nothing and succeeds.
+ * LT_ERR_INVALID: NULL pointers, n < 1, E outside [0, 2^30), nnz outside [0, 2^31 - 1), max_draws < 0, round_draws outside
+ * [0, 2^24], a workspace smaller than lt_sample_balanced_workspace_bytes(n, E, round_draws) or not 8-byte aligned -- all before any
+ * device call -- and an E that is not the graph's (after one count).  LT_ERR_UNSUPPORTED: fewer than E draws were accepted within
+ * max_draws (the message names the counts; the reference's loop would not end on such a graph); [1] is then the draws evaluated.
+ * All additive in ABI 5. */
+size_t lt_sample_square_workspace_bytes(int32_t n, int32_t k);
+int lt_sample_square_labels(int32_t n, const int32_t *d_rowptr, const int32_t *d_col, int64_t nnz, const int32_t *nodes, int32_t k,
+                            int64_t lds, uint8_t *out_labels, int64_t *out_index_or_null, int64_t *d_info, void *ws, size_t ws_bytes,
+                            void *stream);
+size_t lt_group_pairs_workspace_bytes(int64_t m);
+int lt_group_pairs(int32_t n, const int32_t *probe, const int32_t *observed, int64_t m, int32_t *out_nodes, int64_t *out_ptr,
+                   int32_t *out_obs, int32_t *out_order, int64_t *d_info, void *ws, size_t ws_bytes, void *stream);
+int lt_upper_edge_count(int32_t n, const int32_t *d_rowptr, const int32_t *d_col, int64_t nnz, int64_t *d_count, void *stream);
+size_t lt_sample_balanced_workspace_bytes(int32_t n, int64_t E, int64_t round_draws);
+int lt_sample_balanced_philox(int32_t n, const int32_t *d_rowptr, const int32_t *d_col, int64_t nnz, int64_t E, uint64_t seed,
+                              int64_t max_draws, int64_t round_draws, int32_t *out_u, int32_t *out_v, int64_t *info, void *ws,
+                              size_t ws_bytes, void *stream);
 
 /* ---- training of the 2-layer GCN (reference gcn_trainer.py:144-170 train_one_epoch + optim.Adam) ----
  * lt_gcn2_trainer_create borrows the graph, X [n, ldx], labels (int32 [n], device, each in [0, C)) and the four parameter

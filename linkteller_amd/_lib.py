@@ -115,6 +115,16 @@ SIGNATURES = {
     "lt_score_curve_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "lt_score_curve": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lt_sample_square_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "lt_sample_square_labels": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lt_group_pairs_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "lt_group_pairs": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lt_upper_edge_count": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "lt_sample_balanced_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64]),
+    "lt_sample_balanced_philox": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "lt_baseline3_enable_fp64": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lt_influence3_rows_mode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),

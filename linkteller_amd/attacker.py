@@ -47,10 +47,36 @@ class Attacker:
         self.influence_val = None
 
     # ------------------------------------------------------------------------------------------
-    def prepare_test_data(self):
+    def prepare_test_data(self, pairs="host", rng="numpy"):
         """attacker.py:33-48.  'balanced' and 'bfs' cannot run in the reference either (tuple
-        arity / signature mismatches at attacker.py:46-47); 'balanced-full' can."""
+        arity / signature mismatches at attacker.py:46-47); 'balanced-full' can.
+
+        ``pairs="device"`` / ``rng="philox"`` (additions; the defaults are the reference's host route) keep the pairs on the GPU:
+          * ``unbalanced*`` with ``pairs="device"``: the nodes are drawn as on the host route (the same ``np.random`` stream, the
+            same sample); their pairs are never enumerated on the host.  ``evaluate`` (efficient attack) reads labels and index
+            from ``sampling.square_labels_device``, built on first use; ``recover_edges`` takes the edge count and ``is_edge``
+            from the label triangle.
+          * ``balanced-full`` with ``rng="philox"`` (implies device pairs): edges and non-edges come from
+            ``sampling.balanced_pairs_philox`` -- Philox stream 3, DIFFERENT non-edges than numpy's stream gives for the seed --
+            and stay on the device; ``evaluate`` groups them with ``engine.group_pairs_device`` and scores them with
+            ``Baseline.influence_pairs``.  ``balanced-full`` with ``pairs="device"`` and ``rng="numpy"`` is the host route: the
+            numpy stream is a host loop.
+          * ``rng="philox"`` with an ``unbalanced*`` type is a ``ValueError``: its node draw stays on numpy.
+        Both need a GPU (``LinkTellerHipError`` without one).  Whatever the device routes do not serve -- the attack methods that
+        write a result file, the naive and baseline attacks on an ``unbalanced*`` sample, a model ``engine.Baseline`` does not
+        serve on the pair-list route, CPU features -- FALLS BACK to the host lists: ``exist_edges`` / ``nonexist_edges`` are
+        materialised from one download on first access (the arrays the host route builds, element for element, for the
+        ``unbalanced*`` types) and everything proceeds as on the host route, raising what it raises there."""
         st = self.args.sample_type
+        if pairs not in ("host", "device"):
+            raise ValueError(f"pairs = {pairs!r}: 'host' or 'device'")
+        if rng not in ("numpy", "philox"):
+            raise ValueError(f"rng = {rng!r}: 'numpy' or 'philox'")
+        if rng == "philox" and st != "balanced-full":
+            raise ValueError(f"rng = 'philox' serves sample_type = balanced-full only (got {st}: its nodes are drawn from numpy's stream)")
+        self._sample_dev = None
+        if rng == "philox" or (pairs == "device" and str(st).startswith("unbalanced")):
+            return self._prepare_on_device(st)
         func = {"unbalanced": construct_edge_sets_from_random_subgraph,
                 "unbalanced-lo": construct_edge_sets_from_random_subgraph,
                 "unbalanced-hi": construct_edge_sets_from_random_subgraph,
@@ -61,6 +87,90 @@ class Attacker:
         (self.exist_edges, self.nonexist_edges), self.test_nodes = func(
             self.dataset, st, self.worker.adj_ori, self.args.n_test)
         print("generating testing (non-)edge set done!")
+
+    # ---- the pairs on the device ------------------------------------------------------------------------
+    def _pattern_csr(self):
+        """The structural pattern of ``worker.adj_ori`` on the device, uploaded once per adjacency object."""
+        from . import sampling
+        c = getattr(self, "_pattern_cache", None)
+        if c is None or c[0] is not self.worker.adj_ori:
+            c = self._pattern_cache = (self.worker.adj_ori, sampling.device_pattern_csr(self.worker.adj_ori))
+        return c[1]
+
+    def _prepare_on_device(self, st):
+        import scipy.sparse as sp
+        from . import _lib, sampling
+        _lib.require_gpu()
+        csr = self._pattern_csr()
+        self.__dict__.pop("_exist_edges", None)
+        self.__dict__.pop("_nonexist_edges", None)
+        if st == "balanced-full":
+            u, v, n_edges, info = sampling.balanced_pairs_philox(csr, self.args.sample_seed)
+            self.test_nodes = list(range(self.worker.n_nodes))
+            self._sample_dev = {"kind": "balanced", "u": u, "v": v, "n_edges": n_edges, "info": info}
+            print(f"sampling done! len(edge_set) = {n_edges}, len(nonedge_set) = {n_edges}")
+        else:
+            np.random.seed(self.args.sample_seed)
+            nodes = sampling.draw_subgraph_nodes(self.dataset, st, sp.csr_matrix(self.worker.adj_ori), self.args.n_test)
+            print("#nodes =", len(nodes))
+            self.test_nodes = nodes
+            self._sample_dev = {"kind": "square", "lists": {}, "n_edges": None}
+        print("generating testing (non-)edge set done!")
+
+    def _square_lists(self, lds, dev):
+        """(index, labels, info) of the sampled square on the device for score rows of stride ``lds``: built on first use, kept
+        per stride (the labels of the first build serve every stride)."""
+        from . import sampling
+        d = self._sample_dev
+        hit = d["lists"].get((lds, dev))
+        if hit is None:
+            probes, _ = self._device_nodes(np.asarray(self.test_nodes, dtype=np.int64), 0, len(self.test_nodes))
+            hit = d["lists"][(lds, dev)] = sampling.square_labels_device(self._pattern_csr(), probes, lds)
+        return hit
+
+    def _square_n_edges(self, info):
+        """The sample's edge count (and the device's check of the node list) from an info block: one copy of 4 words, once."""
+        from . import sampling
+        d = self._sample_dev
+        if d["n_edges"] is None:
+            d["n_edges"] = sampling.check_square_info(info)
+        return d["n_edges"]
+
+    def _materialise_pairs(self):
+        """The host lists of a device-prepared sample, from ONE download (the label triangle / the two pair arrays)."""
+        from . import sampling
+        d = self._sample_dev
+        if d["kind"] == "square":
+            nodes = np.asarray(self.test_nodes, dtype=np.int64)
+            k = len(nodes)
+            if d["lists"]:
+                _, labels, info = next(iter(d["lists"].values()))
+            else:
+                _, labels, info = sampling.square_labels_device(self._pattern_csr(), nodes, k, index=False)
+            self._square_n_edges(info)
+            present = labels.cpu().numpy() != 0
+            iu, ju = np.triu_indices(k, k=1)
+            pairs = np.stack([nodes[iu], nodes[ju]], axis=1)
+            ex, nex = pairs[present], pairs[~present]
+            print("#edges_set =", len(ex))
+            print("#nonedge_set =", len(nex))
+        else:
+            e = d["n_edges"]
+            uv = np.stack([d["u"].cpu().numpy().astype(np.int64), d["v"].cpu().numpy().astype(np.int64)], axis=1)
+            ex, nex = uv[:e], uv[e:]
+        self.__dict__["_exist_edges"], self.__dict__["_nonexist_edges"] = ex, nex
+
+    def _host_list(self, name):
+        if name not in self.__dict__:
+            if getattr(self, "_sample_dev", None) is None:
+                raise AttributeError(f"'Attacker' object has no attribute '{name[1:]}'")
+            self._materialise_pairs()
+        return self.__dict__[name]
+
+    exist_edges = property(lambda self: self._host_list("_exist_edges"),
+                           lambda self, value: self.__dict__.__setitem__("_exist_edges", value))
+    nonexist_edges = property(lambda self: self._host_list("_nonexist_edges"),
+                              lambda self, value: self.__dict__.__setitem__("_nonexist_edges", value))
 
     # ------------------------------------------------------------------------------------------
     _TWO = ("gc1.weight", "gc1.bias", "gc2.weight", "gc2.bias")
@@ -461,23 +571,37 @@ class Attacker:
         if n < 2:
             raise ValueError("recover_edges: fewer than two sampled nodes")
         n_total = n * (n - 1) // 2
-        n_edges = len(self.exist_edges)
+        dev_sample = getattr(self, "_sample_dev", None)
+        dev_sample = dev_sample if (dev_sample is not None and dev_sample["kind"] == "square" and self.features.is_cuda) else None
+        probes, observed = self._device_nodes(nodes, 0, n)
+        if dev_sample is not None:
+            # the sample was prepared on the device: its edge count is info[0] of the label build (the wait of this call's set-up)
+            _, tri, tri_info = self._square_lists(n, self.features.device)
+            n_edges = self._square_n_edges(tri_info)
+        else:
+            n_edges = len(self.exist_edges)
         beliefs = recover.density_ladder(n_edges, n) if beliefs is None else [float(b) for b in beliefs]
         counts = recover.belief_counts(beliefs, n_total)
         m = int(counts.max())
-        probes, observed = self._device_nodes(nodes, 0, n)
         rows = self._rows(probes, observed, mode)
         idx_d, val_d, info = engine.top_pairs_lower(rows, m)
+        if dev_sample is not None:
+            # cell (i, j), j < i, is the pair of positions (j, i): slot j (2 n - j - 1) / 2 + (i - j - 1) of the label triangle
+            ci_d, cj_d = idx_d // n, idx_d % n
+            present_d = tri[cj_d * (2 * n - cj_d - 1) // 2 + (ci_d - cj_d - 1)]
         idx, val, raw = idx_d.cpu().numpy(), val_d.cpu().numpy(), info["raw"].cpu().numpy()
         engine.node_check()
         order = np.lexsort((idx, -val.astype(np.float64)))      # ascending cell index -> rank order
         idx, val = idx[order], val[order]
         ci, cj = idx // n, idx % n
-        import scipy.sparse as sp
-        adj = sp.csr_matrix(self.worker.adj_ori)
-        pattern = sp.csr_matrix((np.ones(adj.indices.shape[0], dtype=np.int8), adj.indices, adj.indptr), shape=adj.shape)
         u, v = nodes[cj], nodes[ci]
-        present = np.asarray(pattern[u, v]).reshape(-1) != 0     # structural presence of v in row u, as edge_sets_among_nodes reads it
+        if dev_sample is not None:
+            present = present_d.cpu().numpy()[order] != 0
+        else:
+            import scipy.sparse as sp
+            adj = sp.csr_matrix(self.worker.adj_ori)
+            pattern = sp.csr_matrix((np.ones(adj.indices.shape[0], dtype=np.int8), adj.indices, adj.indptr), shape=adj.shape)
+            present = np.asarray(pattern[u, v]).reshape(-1) != 0     # structural presence of v in row u, as edge_sets_among_nodes reads it
         stats = recover.recovery_stats(present, n_edges, counts)
         self.recovered = {
             "pairs": np.stack([u, v], axis=1).astype(np.int64), "scores": val.astype(np.float64), "is_edge": present,
@@ -555,6 +679,23 @@ class Attacker:
             raise LinkTellerHipError("evaluate: the metrics run on the GPU; there is no CPU path")
         return engine.score_curve(torch.from_numpy(s.astype(np.float32)).to(dev), torch.from_numpy(labels).to(dev))
 
+    def _pair_curve_device(self, probe, observed, n_edges, mode=None):
+        """``_pair_curve`` for pair lists that live on the device (int32 CUDA tensors, the first ``n_edges`` pairs labelled 1):
+        ``engine.group_pairs_device`` + ``Baseline.influence_pairs`` + ``engine.score_curve``, the labels permuted by the device
+        ``order``.  None when the model is not a 2-layer GCN served by ``engine.Baseline`` (the caller takes the host lists)."""
+        kind, sd = self._walk()
+        if kind != "gcn2" or not self.features.is_cuda or probe.numel() == 0:
+            return None
+        m = self._mode(mode)
+        base = self.baseline(m, sd)
+        if not isinstance(base, engine.Baseline):
+            return None
+        nodes, ptr, obs, order = engine.group_pairs_device(probe, observed, int(self.features.shape[0]))
+        out = base.influence_pairs(nodes, ptr, obs, float(self.args.influence), m)
+        labels = torch.zeros(probe.numel(), dtype=torch.uint8, device=probe.device)
+        labels[:n_edges] = 1
+        return engine.score_curve(out, labels[order.long()])
+
     def evaluate(self, mode=None, curves=False) -> dict:
         """AUC and AP of the attack without the host's three sorts (the reference's ``compute_and_save``, attacker.py:378-389,
         minus its file): the scores stay on the device, ``engine.score_curve`` ranks and counts them there, and eight words --
@@ -564,7 +705,9 @@ class Attacker:
         ``"curves"``: ``metrics.curves_from_counts(...)``, the arrays ``compute_and_save`` stores, bit for bit.  Needs
         ``prepare_test_data()``.  Efficient attack on an ``unbalanced*`` sample: the n_test x n_test rows of ``_rows`` (every
         model kind it serves) read through a cached index; naive attack and ``balanced-full``: the listed pairs' scores.  The
-        baseline attacks' scores are host arithmetic: ``NotImplementedError``.  With several ranks every rank forms all rows
+        baseline attacks' scores are host arithmetic: ``NotImplementedError``.  After ``prepare_test_data(pairs="device")`` the
+        square's labels and index are ``sampling.square_labels_device``'s, after ``prepare_test_data(rng="philox")`` the pair
+        lists are grouped on the device (``_pair_curve_device``); no host pair list is built for either.  With several ranks every rank forms all rows
         itself: no collective of its own to mismatch."""
         from . import metrics as lt_metrics
         am = str(getattr(self.args, "attack_mode", "efficient"))
@@ -573,15 +716,25 @@ class Attacker:
             raise NotImplementedError(f"evaluate: attack_mode = {am} scores its pairs on the host (baseline_attack)")
         if am not in ("efficient", "naive"):
             raise NotImplementedError(f"attack_mode = {am} not implemented!")
-        ex = np.asarray(self.exist_edges, dtype=np.int64).reshape(-1, 2)
-        nex = np.asarray(self.nonexist_edges, dtype=np.int64).reshape(-1, 2)
+        dev_sample = getattr(self, "_sample_dev", None) if self.features.is_cuda else None
+        curve = tri_info = None
         if am == "efficient" and st.startswith("unbalanced"):
             nodes = np.asarray(self.test_nodes, dtype=np.int64)
             probes, observed = self._device_nodes(nodes, 0, len(nodes))
             rows = self._rows(probes, observed, mode)
-            index, labels = self._metric_lists(int(rows.stride(0)) if rows.shape[0] > 1 else int(rows.shape[1]), rows.device)
+            lds = int(rows.stride(0)) if rows.shape[0] > 1 else int(rows.shape[1])
+            if dev_sample is not None and dev_sample["kind"] == "square" and len(nodes) > 1:
+                index, labels, tri_info = self._square_lists(lds, rows.device)     # (prepared on the device: no host pair list)
+            else:
+                index, labels = self._metric_lists(lds, rows.device)
             curve = engine.score_curve(rows, labels, index)
-        else:
+        elif dev_sample is not None and dev_sample["kind"] == "balanced":
+            # the philox pair lists never left the device: perturb u, observe v (efficient) / perturb v, observe u (naive)
+            p, o = (dev_sample["v"], dev_sample["u"]) if am == "naive" else (dev_sample["u"], dev_sample["v"])
+            curve = self._pair_curve_device(p, o, dev_sample["n_edges"], mode)
+        if curve is None:
+            ex = np.asarray(self.exist_edges, dtype=np.int64).reshape(-1, 2)
+            nex = np.asarray(self.nonexist_edges, dtype=np.int64).reshape(-1, 2)
             labels = np.zeros(len(ex) + len(nex), dtype=np.uint8)
             labels[:len(ex)] = 1
             # naive (attacker.py:143-163): perturb v, observe u; balanced-full (attacker.py:250-284): perturb u, observe v
@@ -589,6 +742,8 @@ class Attacker:
             curve = self._pair_curve(np.concatenate([ex[:, p], nex[:, p]]), np.concatenate([ex[:, o], nex[:, o]]), labels, mode)
         out = curve.summary()                                    # the wait
         engine.node_check()
+        if tri_info is not None:
+            self._square_n_edges(tri_info)                       # (the device's check of the sampled nodes, once per sample)
         self.auc, self.ap = out["auc"], out["ap"]
         print("auc =", self.auc)
         print("ap =", self.ap)

@@ -836,6 +836,46 @@ def group_pairs(probe, observed):
     return nodes.astype(np.int32), pair_ptr, observed[order].astype(np.int32), order
 
 
+def group_pairs_device(probe: torch.Tensor, observed: torch.Tensor, n: int = None):
+    """``group_pairs`` on the device (lt_group_pairs): two equal-length int32 CUDA tensors of node ids -> ``(probe_nodes, pair_ptr,
+    pair_obs, order)`` as CUDA tensors, equal to the host function's arrays element for element (``probe_nodes`` int32,
+    ``pair_ptr`` int64, ``pair_obs`` int32, ``order`` int32: the stable sort of the pairs by probe).  ``n``: the ids lie in
+    [0, n) (default: 2^31 - 1, four digit passes; the graph's node count saves passes).  The number of groups is the one word that
+    comes to the host (one wait) to cut ``probe_nodes`` and ``pair_ptr``; ids outside [0, n) raise ``IndexError`` there.
+    ``Baseline.influence_pairs`` takes the result as it is (its ``pair_ptr`` is copied to the host there)."""
+    for t, name in ((probe, "probe"), (observed, "observed")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if not t.is_cuda:
+            raise _lib.LinkTellerHipError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != torch.int32 or t.dim() != 1:
+            raise TypeError(f"{name} must be a 1-d int32 tensor, got {t.dtype} {tuple(t.shape)}")
+    if probe.shape != observed.shape or probe.device != observed.device:
+        raise ValueError(f"probe and observed differ in length or device: {probe.numel()} / {observed.numel()}")
+    probe, observed = probe.contiguous(), observed.contiguous()
+    m, dev = int(probe.numel()), probe.device
+    if m < 1:
+        raise ValueError("group_pairs_device: no pairs")
+    n = (1 << 31) - 1 if n is None else int(n)
+    need = _lib.lib().lt_group_pairs_workspace_bytes(m)
+    if need == 0:
+        raise ValueError(f"group_pairs_device: {m} pairs are outside what the library serves")
+    ws = _workspace(need, dev)
+    nodes = torch.empty(m, dtype=torch.int32, device=dev)
+    ptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    obs = torch.empty(m, dtype=torch.int32, device=dev)
+    order = torch.empty(m, dtype=torch.int32, device=dev)
+    info = torch.empty(4, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().lt_group_pairs(n, probe.data_ptr(), observed.data_ptr(), m, nodes.data_ptr(), ptr.data_ptr(),
+                                             obs.data_ptr(), order.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                   "lt_group_pairs")
+    groups, outside = [int(v) for v in info[:2].tolist()]
+    if outside:
+        raise IndexError(f"group_pairs_device: {outside} node ids outside [0, {n})")
+    return nodes[:groups], ptr[:groups + 1], obs, order
+
+
 _select_ws = {}      # top_pairs_lower's workspace: only the latest (device, size) is kept, sizes repeat across calls
 
 

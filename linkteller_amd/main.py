@@ -54,6 +54,14 @@ _OPTIONS = {
     # keeps the cells of --noise-rng philox on the GPU from the noise seed to the served graph (symmetric CSR, normaliser and
     # sparse tensor are built there: the same graph, the same float32 values)
     "dp-build": (str, "host", ["host", "device"]),
+    # addition: where the attack's node pairs are enumerated and labelled.  'host' is numpy / scipy, as the reference; 'device'
+    # keeps the label triangle of an unbalanced* sample (and, with --sample-rng philox, the balanced-full pair lists) on the GPU:
+    # the same pairs, the same labels (Attacker.prepare_test_data)
+    "sample-build": (str, "host", ["host", "device"]),
+    # addition: where the non-edges of --sample-type balanced-full come from.  'numpy' is the reference's stream (a --sample-seed
+    # gives the reference's pairs; a Python loop on the host); 'philox' is stream 3 of include/linkteller_hip.h, evaluated on the
+    # GPU -- different pairs for the same seed, under the same result file name
+    "sample-rng": (str, "numpy", ["numpy", "philox"]),
 }
 _SWITCHES = ["no-cuda", "fastmode", "approx", "attack", "test", "break-down", "display", "same-size",
              "eval-degree", "trainable", "early", "fnormalize",
@@ -151,11 +159,26 @@ def check_dp_build(args):
                                   f"(got mode={args.mode}, noise-rng={args.noise_rng}: those graphs are built on the host)")
 
 
+def check_sample_build(args):
+    """``--sample-build device`` / ``--sample-rng philox`` move the attack's pair preparation to the GPU: they are refused here,
+    before a Worker is built or the GPU is touched, without ``--attack``, and the philox stream without ``--sample-type
+    balanced-full`` (the node draw of the unbalanced* samples stays on numpy's stream)."""
+    build, rng = getattr(args, "sample_build", "host"), getattr(args, "sample_rng", "numpy")
+    if build == "host" and rng == "numpy":
+        return
+    if not args.attack:
+        raise NotImplementedError(f"--sample-build {build} / --sample-rng {rng} need --attack (they prepare the attack's node pairs)")
+    if rng == "philox" and args.sample_type != "balanced-full":
+        raise NotImplementedError(f"--sample-rng philox needs --sample-type balanced-full (got sample-type={args.sample_type}: "
+                                  "its nodes are drawn from numpy's stream)")
+
+
 def main(argv=None):
     args = get_arguments(argv)
     check_recover(args)
     check_metrics_only(args)
     check_dp_build(args)
+    check_sample_build(args)
     import os
     if args.train and not args.test:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:

@@ -112,7 +112,11 @@ class GCNTrainer:
             if getattr(a, "recover", False) and not (a.attack_mode == "efficient" and str(a.sample_type).startswith("unbalanced")):
                 raise NotImplementedError("recover: served after the efficient attack on an unbalanced* sample only")
             self.attacker = Attacker(args=a, model=self.model, worker=self.worker)
-            self.attacker.prepare_test_data()
+            build, rng = getattr(a, "sample_build", "host"), getattr(a, "sample_rng", "numpy")
+            if build == "host" and rng == "numpy":
+                self.attacker.prepare_test_data()
+            else:                                                 # addition: --sample-build / --sample-rng
+                self.attacker.prepare_test_data(pairs=build, rng=rng)
             t = time.time()
             if getattr(a, "metrics_only", False):                 # addition: auc / ap from the device, no result file
                 self.attacker.evaluate()
