@@ -332,6 +332,19 @@ int lt_baseline_refresh_rows(lt_baseline *b, int32_t row_begin, int32_t row_end,
 int lt_baseline_attach_s1d(lt_baseline *b, double *S1d, int64_t ld, void *stream);
 int lt_baseline_refresh_rows_fp64(lt_baseline *b, int32_t row_begin, int32_t row_end, double *dst, void *stream);
 int lt_baseline_fp64_route(const lt_baseline *b, int32_t *route);
+/* For tests of the kernels that form them: the fp64 arrays of the S1d routes as they stand, copied on `stream` to caller buffers the
+ * device can write.  LT_ERR_UNSUPPORTED on the aggregate-first route (no product rows), and while the product is stale: between
+ * lt_baseline_refresh and the next call that re-forms it (any LT_MODE_DELTA call).  lt_baseline_enable_fp64 forms the product itself,
+ * so straight after it the call succeeds with the product rows and cref in place and NO pre-activation row formed yet (forms[2] = 0,
+ * every state word 0); the pre-activation is formed by the LT_MODE_DELTA calls, for all rows or for the rows a call reads.
+ * product: [n, Hp] the product rows -- forms[0] = 1: 32-bit fixed point (int32) with the rows' scales in scales[n], forms[0] = 0:
+ * doubles (scales untouched); size it for doubles.  preact: [n, Hp] the pre-activation -- forms[1] = 1: fp32, 0: doubles; size it
+ * for doubles.  row_state: [n] the rows' state words (1 = the row of preact is valid), meaningful when forms[2] = 0; forms[2] = 1:
+ * every row of preact is valid.  forms[3] = 1: the product rows lack the reference vector's product (deferred cref).  cref: [Hp]
+ * that product m W1 of the feature-difference route as the refresh formed it, forms[4] = 1 (0 on the other route: cref untouched).
+ * forms: int32[5], host memory, written before the call returns.  Additive within ABI 5. */
+int lt_baseline_fp64_arrays(const lt_baseline *b, void *product, double *scales, double *cref, void *preact, int32_t *row_state,
+                            int32_t *forms, void *stream);
 /* The on-demand route by ROW LIST (lt_baseline_fp64_route == 2; LT_ERR_UNSUPPORTED otherwise): a call of lt_influence_rows forms
  * the fp64 pre-activation Z1d on the rows ITS probes reach.  On a heavy-tailed graph most of that work lies in hub rows every
  * rank's probes reach (BASELINE configs[4], 8 ranks x 512 probes: ~3 800 rows of >= 1 024 entries hold 84 % of a rank's gathers,

@@ -63,6 +63,8 @@ SIGNATURES = {
     "lt_baseline_attach_s1d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lt_baseline_refresh_rows_fp64": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "lt_baseline_fp64_route": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "lt_baseline_fp64_arrays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                                          C.c_void_p]),
     "lt_baseline_destroy": (C.c_int, [C.c_void_p]),
     "lt_baseline_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lt_influence_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),

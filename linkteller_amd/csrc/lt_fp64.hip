@@ -653,26 +653,48 @@ __device__ __forceinline__ void fd_slab_block(unsigned char *fd_smem, int nslab,
         if (threadIdx.x == 0) s_last = __hip_atomic_fetch_add(gate, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)nslab - 1u ? 1u : 0u;
         __syncthreads();
         if (!s_last) return;
-        const int zq = threadIdx.x >> 6;
-        for (int cb = 0; cb < Hp; cb += 64) {
-            const int c = cb + (threadIdx.x & 63);
-            double acc = 0.0;
-            if (c < H)
-                for (int z0 = 0; z0 < nslab; z0 += 32) {
-                    double t[8];
+        // These loads pass the L2 (a trip to the fabric and back each), and the launch cannot end before this block does: at twitch
+        // size it took 15.6 us with the 500 record blocks riding and 15.4 without them, with the rows' lists walked 6 or 12 deep,
+        // with 31 or 16 KB of LDS per block (profiles/fp64_row_trips_ab.txt) -- and 13.8 with this chain cut from eight trips to
+        // two.  FD_SUM_ZU slices x FD_SUM_CB column groups per thread go out in ONE trip, no branch between the loads (clamped
+        // addresses, a select afterwards): two trips for H = 256 and up to 52 slices (F <= 3328).  The order of the additions
+        // is unchanged (a padded slice adds +0.0 to a sum that started from +0.0: nothing), so cref keeps its bits.
+        // The two constants are sized to the twitch features (F = 3170: 50 slices, H = 256): F = 3329 .. 4096 pays a whole
+        // second pass for its last slices, and for H <= 64 the second column group's 13 loads are redundant (clamped onto column
+        // H - 1, not added).  Four column groups in one trip would be 104 VGPRs in a kernel whose rows need their 79.
+        constexpr int FD_SUM_ZU = 13, FD_SUM_CB = 2;
+        const int zq = threadIdx.x >> 6, ln = threadIdx.x & 63;
+        for (int cb = 0; cb < Hp; cb += 64 * FD_SUM_CB) {
+            double acc[FD_SUM_CB];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int z = z0 + zq + 4 * u;
-                        t[u] = z < nslab ? __hip_atomic_load(slabs + (size_t)z * H + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-                    }
+            for (int q = 0; q < FD_SUM_CB; ++q) acc[q] = 0.0;
+            for (int z0 = 0; z0 < nslab; z0 += 4 * FD_SUM_ZU) {
+                double t[FD_SUM_CB][FD_SUM_ZU];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) acc += t[u];
+                for (int q = 0; q < FD_SUM_CB; ++q) {
+                    const int cl = min(cb + 64 * q + ln, H - 1);
+#pragma unroll
+                    for (int u = 0; u < FD_SUM_ZU; ++u)
+                        t[q][u] = __hip_atomic_load(slabs + (size_t)min(z0 + zq + 4 * u, nslab - 1) * H + cl, __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT);
                 }
+#pragma unroll
+                for (int q = 0; q < FD_SUM_CB; ++q)
+#pragma unroll
+                    for (int u = 0; u < FD_SUM_ZU; ++u)
+                        acc[q] += (z0 + zq + 4 * u < nslab && cb + 64 * q + ln < H) ? t[q][u] : 0.0;
+            }
             __syncthreads();
-            s_p[zq][threadIdx.x & 63] = acc;
+#pragma unroll
+            for (int q = 0; q < FD_SUM_CB; ++q) s_p[zq][64 * q + ln] = acc[q];
             __syncthreads();
-            if (zq == 0 && c < Hp)
-                cref_out[c] = c < H ? ((s_p[0][threadIdx.x] + s_p[1][threadIdx.x]) + s_p[2][threadIdx.x]) + s_p[3][threadIdx.x] : 0.0;
+            if (zq == 0) {
+#pragma unroll
+                for (int q = 0; q < FD_SUM_CB; ++q) {
+                    const int c = cb + 64 * q + ln, i = 64 * q + ln;
+                    if (c < Hp) cref_out[c] = c < H ? ((s_p[0][i] + s_p[1][i]) + s_p[2][i]) + s_p[3][i] : 0.0;
+                }
+            }
         }
         if (threadIdx.x == 0) __hip_atomic_store(gate, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
         return;
@@ -844,7 +866,10 @@ __global__ __launch_bounds__(64 * FD_WAVES, FD_MIN_WAVES) void k_s1d_feature_row
 #pragma unroll
                     for (int t = 0; t < 4; ++t) acc[t] = fma(d[k], (double)w[k][t], acc[t]);
                 // (round 6 re-measured the trip depth with __launch_bounds__(256, 5) holding the fifth wave: 6 / 8 / 12 rows in flight,
-                // the differences read when used: 22.6 / 22.4 / 22.5 us -- the walk's trips are not what bounds the launch)
+                // the differences read when used: 22.6 / 22.4 / 22.5 us -- the walk's trips are not what bounds the launch.  That was the
+                // UNLISTED kernel, bound by its pass over X.  The listed refresh (LST = 2) was measured on its own since, 6 rows per trip
+                // through this LDS list against 12 per trip from registers by v_readlane with an exact-count tail and 16 instead of
+                // 31 KB of LDS: 16.2 / 16.2 us -- not the walk either; the last slab block ends that launch, fd_slab_block)
             }
         } else if (own) {
             for (int e = 0; e < padded; ++e) {
@@ -1665,7 +1690,7 @@ static int compute_s1d(lt_baseline *b, hipStream_t st) {
             if (rc) return rc;
             b->s1_f32 = true;
         }
-    } else if (want_feature_rows(b)) {
+    } else if (feat) {      // (the value read above: the one that decided who clears zstate)
         // (writes the pad columns of S1d as zeros itself.)  The deferred cref + fp32 storage are for products the caches hold
         // (a fixed size rule, not the "tiled_min_bytes" knob, so that knob keeps every bit); beyond it the rows carry cref
         // themselves in fp64 and the SpMM may take the tiled route
@@ -2090,6 +2115,40 @@ extern "C" int lt_baseline_scatter_rows_fp64(lt_baseline *b, const int32_t *rows
 extern "C" int lt_baseline_fp64_route(const lt_baseline *b, int32_t *route) {
     LT_REQUIRE(b != nullptr && route != nullptr, "lt_baseline_fp64_route: NULL argument");
     *route = !b->Z1d ? -1 : (lt_fp64_agg_active(b) ? 2 : (want_feature_rows(b) ? 1 : 0));
+    return LT_OK;
+}
+
+// What the last refresh left in the two fp64 arrays, as stored (for tests: `delta`'s scores round Z once to fp32 and hardly see a
+// reordered fp64 chain).  Enqueues copies on `stream`; forms[] is written at once.
+extern "C" int lt_baseline_fp64_arrays(const lt_baseline *b, void *product, double *scales, double *cref, void *preact,
+                                       int32_t *row_state, int32_t *forms, void *stream) {
+    LT_REQUIRE(b != nullptr && product != nullptr && scales != nullptr && cref != nullptr && preact != nullptr && row_state != nullptr &&
+                   forms != nullptr, "lt_baseline_fp64_arrays: NULL argument");
+    LT_REQUIRE(b->Z1d != nullptr, "lt_baseline_fp64_arrays: call lt_baseline_enable_fp64 first");
+    if (lt_fp64_agg_active(b) || !b->S1d)
+        return lt_set_error(LT_ERR_UNSUPPORTED, "lt_baseline_fp64_arrays: this baseline forms its pre-activation aggregate-first "
+                                                "(no product rows: lt_baseline_fp64_route == 2)");
+    if (!b->fp64_fresh)
+        return lt_set_error(LT_ERR_UNSUPPORTED, "lt_baseline_fp64_arrays: nothing formed since the last refresh (read after a `delta` call)");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)b->n, nh = n * (size_t)b->Hp;
+    const bool px = b->s1_f32 && b->S1x && b->S1qs, zx = b->z1x_valid && b->Z1x;
+    forms[0] = px ? 1 : 0;
+    forms[1] = zx ? 1 : 0;
+    forms[2] = b->z_all_valid ? 1 : 0;
+    forms[3] = b->cref_deferred ? 1 : 0;
+    forms[4] = b->fd_cref && want_feature_rows(b) ? 1 : 0;
+    if (n == 0) return LT_OK;
+    if (forms[4]) LT_HIP(hipMemcpyAsync(cref, b->fd_cref, (size_t)b->Hp * sizeof(double), hipMemcpyDefault, st));
+    if (px) {
+        LT_HIP(hipMemcpyAsync(product, b->S1x, nh * sizeof(float), hipMemcpyDefault, st));
+        LT_HIP(hipMemcpyAsync(scales, b->S1qs, n * sizeof(double), hipMemcpyDefault, st));
+    } else {
+        LT_HIP(hipMemcpyAsync(product, b->S1d, nh * sizeof(double), hipMemcpyDefault, st));
+    }
+    if (zx) LT_HIP(hipMemcpyAsync(preact, b->Z1x, nh * sizeof(float), hipMemcpyDefault, st));
+    else LT_HIP(hipMemcpyAsync(preact, b->Z1d, nh * sizeof(double), hipMemcpyDefault, st));
+    LT_HIP(hipMemcpyAsync(row_state, b->zstate, n * sizeof(int32_t), hipMemcpyDefault, st));
     return LT_OK;
 }
 

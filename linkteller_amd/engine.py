@@ -206,6 +206,30 @@ class Baseline:
         _lib.check(_lib.lib().lt_baseline_fp64_route(self._h, C.byref(r)), "lt_baseline_fp64_route")
         return r.value
 
+    def fp64_arrays(self) -> dict:
+        """The fp64 product rows and the pre-activation as the last refresh stored them (lt_baseline_fp64_arrays; read after a
+        `delta` call): {"product": int32 fixed point [n, Hp] + "scales" [n] float64, or float64 [n, Hp] with scales None;
+        "preact": float32 or float64 [n, Hp]; "valid": bool [n], the rows of preact that are formed; "deferred_cref": bool;
+        "cref": float64 [Hp], the reference vector's product m W1 on the feature-difference route, else None}.
+        Not on the aggregate-first route."""
+        dev, n, hp = self.x.device, self.n, (self.h + 3) // 4 * 4
+        prod = torch.empty(max(n * hp, 1), dtype=torch.float64, device=dev)
+        pre = torch.empty(max(n * hp, 1), dtype=torch.float64, device=dev)
+        scales = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        state = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        cref = torch.empty(hp, dtype=torch.float64, device=dev)
+        forms = (C.c_int32 * 5)()
+        _lib.check(_lib.lib().lt_baseline_fp64_arrays(self._h, prod.data_ptr(), scales.data_ptr(), cref.data_ptr(), pre.data_ptr(),
+                                                      state.data_ptr(), forms, _stream()), "lt_baseline_fp64_arrays")
+        if forms[0]:
+            product, sc = prod.view(torch.int32)[:n * hp].view(n, hp).clone(), scales[:n].clone()
+        else:
+            product, sc = prod[:n * hp].view(n, hp), None
+        preact = pre.view(torch.float32)[:n * hp].view(n, hp).clone() if forms[1] else pre[:n * hp].view(n, hp)
+        valid = torch.ones(n, dtype=torch.bool, device=dev) if forms[2] else state[:n] == 1
+        return {"product": product, "scales": sc, "preact": preact, "valid": valid, "deferred_cref": bool(forms[3]),
+                "cref": cref if forms[4] else None}
+
     # ---- the on-demand pre-activation by row list (fp64_route() == 2): hub rows shared between ranks, dist.share_hub_rows ----
     def reached_rows(self, probe_nodes, min_entries: int) -> torch.Tensor:
         """Sorted int32 device list of the rows of >= min_entries entries that the probes reach in one hop (lt_graph_reached_rows;
