@@ -445,7 +445,30 @@ int lt_influence_matrix_host(const lt_baseline *b, const int32_t *probe_nodes, i
                              float *out, int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
                              void *stream);
 
-/* The packed calls of lt_influence_matrix_host on this baseline so far: out4[0] = calls whose index run the host consumed before
+/* One host-landed step in ONE call: lt_baseline_refresh (on request), lt_influence_matrix_host and lt_node_check.  The arguments
+ * of lt_influence_matrix_host, then
+ *   flags        LT_STEP_REFRESH: mark the baseline stale exactly as lt_baseline_refresh does -- behind every check that stands in
+ *                front of the first launch (arguments, a pending node-id flag, the workspace, dst): a call refused by one of
+ *                those enqueued nothing and marked nothing.  (The grid-limit checks of the probe chunks come later: a call
+ *                they refuse has run the launches that recompute the baseline, and the refresh is spent.)
+ *                LT_STEP_DST_PINNED: the caller vouches that dst is pinned host memory it allocated.  On the packed route only
+ *                the host touches dst, and the runtime is then not asked what kind of pointer it is; on every route where
+ *                the GPU writes dst it is resolved as lt_influence_matrix_host resolves it, flag or no flag.
+ *   bad_probe, bad_observe   optional: behind the wait the node-id flag is read and cleared as by lt_node_check.  A flag raised
+ *                by THIS call's lists returns LT_ERR_INDEX from this call with the two words filled (1 = that list held an id
+ *                outside [0, n)); the matrix of such a call is meaningless.  Both are 0 after any other return -- also when
+ *                the call is refused on entry with LT_ERR_INDEX because an EARLIER call left its flag uncollected (that
+ *                report clears the flag, as in every probe call; nothing was enqueued).
+ * LT_ERR_WORKSPACE: nothing was enqueued and nothing marked stale; lt_last_error names the size needed.  Counted by
+ * lt_host_landing_stats like lt_influence_matrix_host.  Same values as the three calls, bit for bit.  Additive in ABI 5. */
+#define LT_STEP_REFRESH 1
+#define LT_STEP_DST_PINNED 2
+int lt_influence_step_host(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
+                           const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode,
+                           float *out, int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
+                           void *stream, int32_t flags, int32_t *bad_probe, int32_t *bad_observe);
+
+/* The packed calls of lt_influence_matrix_host / lt_influence_step_host on this baseline so far: out4[0] = calls whose index run the host consumed before
  * the stream wait, [1] = calls that did everything after it, [2] = nanoseconds spent between the wait's return and the matrix
  * being complete, summed over both, [3] = ("export_early" = 2) index words the early look saw differently from the finished
  * run -- anything but 0 means the publication is broken.  Additive in ABI 5. */

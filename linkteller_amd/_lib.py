@@ -82,6 +82,9 @@ SIGNATURES = {
     "lt_influence_matrix_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
                                            C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
                                            C.c_void_p]),
+    "lt_influence_step_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
+                                         C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lt_host_landing_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "lt_influence_rows_vec": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
                                         C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -195,6 +198,8 @@ def lib():
 
 
 LT_ERR_INDEX = -6
+LT_ERR_WORKSPACE = -4
+STEP_REFRESH, STEP_DST_PINNED = 1, 2      # lt_influence_step_host flags (LT_STEP_*)
 
 
 def check(status: int, what: str = ""):

@@ -436,10 +436,7 @@ static int refresh_padding(lt_baseline *b, hipStream_t st) {
 extern "C" int lt_baseline_refresh(lt_baseline *b, void *stream) {
     LT_REQUIRE(b != nullptr, "lt_baseline_refresh: baseline is NULL");
     (void)stream;
-    b->s1_fresh = false;
-    b->pad_fresh = false;
-    b->layers_fresh = false;
-    b->fp64_fresh = false;
+    lt_baseline_mark_stale(b);
     return LT_OK;
 }
 

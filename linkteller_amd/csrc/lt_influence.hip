@@ -2494,6 +2494,13 @@ struct lt_pairs_job {
     const int32_t *obs;      // device [n_pairs]
     int64_t n_pairs;
 };
+// lt_influence_step_host: what the call does inside influence_rows_impl, at the one place where it is known that nothing refuses the
+// call any more and which route it takes -- dst resolved only where the GPU writes it, then the baseline marked stale
+struct lt_host_job {
+    double *dst_raw;    // resolved (lt_export_resolve) when the call does NOT take the packed route; NULL: dst64 is resolved already
+    const char *who;
+    bool refresh;       // LT_STEP_REFRESH
+};
 static void lt_compact_job(lt_bits_job &j, const lt_compact_out &c, long row0) {
     j.cidx = c.idx; j.ccur = c.cur; j.ccur_next = c.cur_next; j.ctick = c.tick; j.cready = c.ready;
     j.crow0 = row0; j.cld = c.ld; j.ccap = c.cap;
@@ -2502,7 +2509,7 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
                                const int32_t *observe_nodes, int32_t n_obs, float delta,
                                int32_t mode, float *out, int64_t ldo, void *workspace,
                                size_t workspace_bytes, void *stream, float *vec, double *dst64 = nullptr, int64_t ldd = 0,
-                               lt_compact_out *cmp = nullptr, const lt_pairs_job *pj = nullptr);
+                               lt_compact_out *cmp = nullptr, const lt_pairs_job *pj = nullptr, const lt_host_job *hj = nullptr);
 
 // lt_influence_rows + the finished rows as float64 in dst (device memory, or pinned host memory: the reference's influence_val,
 // attacker.py:216-229): the fused DELTA route's blocks write their own rows there, every other route ends with the launch of
@@ -2535,11 +2542,6 @@ extern "C" int lt_influence_rows_f64(const lt_baseline *b, const int32_t *probe_
 #define LT_COMPACT_MAX_FRAC 0.25              // mean touched share of a row up to which "export_compact" = 1 packs (see NOTES.md)
 #define LT_COMPACT_MAX_BYTES ((size_t)256 << 20)   // pinned staging beyond this: whole rows
 #define LT_EARLY_QUERY_EVERY 256              // looks at the ready word between two hipStreamQuery calls
-static inline int64_t lt_now_ns() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (int64_t)ts.tv_sec * 1000000000ll + ts.tv_nsec;
-}
 #ifdef LT_HOST_LAB
 #include <vector>
 static volatile uint32_t g_host_lab_sink;
@@ -2551,20 +2553,39 @@ extern "C" int lt_host_landing_stats(const lt_baseline *b, int64_t *out4) {
     out4[0] = b->stage_early; out4[1] = b->stage_late; out4[2] = b->stage_post_ns; out4[3] = b->stage_mismatch;
     return LT_OK;
 }
-extern "C" int lt_influence_matrix_host(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
-                                        const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode, float *out,
-                                        int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
-                                        void *stream) {
-    LT_REQUIRE(b != nullptr, "lt_influence_matrix_host: baseline is NULL");
-    LT_REQUIRE(dst != nullptr || n_probe == 0 || n_obs == 0, "lt_influence_matrix_host: dst is NULL");
-    LT_REQUIRE(ldd >= n_obs, "lt_influence_matrix_host: ldd smaller than the row");
+#ifdef LT_HOST_LAB
+// tools/host_lab/step_parts.py: monotonic nanoseconds of the last host-landed call -- [0] entry, [1] first launch returned,
+// [2] last launch returned, [3] zero-fill done, [4] wait returned, [5] matrix placed (node check included)
+int64_t g_lt_lab_stamp[6];
+extern "C" void lt_host_lab_stamps(int64_t *out6) { for (int i = 0; i < 6; ++i) out6[i] = g_lt_lab_stamp[i]; }
+#define LT_LAB_STAMP(i) (g_lt_lab_stamp[i] = lt_now_ns())
+#else
+#define LT_LAB_STAMP(i) ((void)0)
+#endif
+// The body of lt_influence_matrix_host (flags = 0, who names it) and of lt_influence_step_host
+static int influence_host_impl(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
+                               const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode, float *out,
+                               int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
+                               void *stream, int32_t flags, const char *who) {
+#ifdef LT_HOST_LAB
+    g_lt_lab_stamp[0] = lt_now_ns();
+    g_lt_lab_stamp[1] = 0;      // (set by the first LT_CHECK_LAUNCH behind it)
+#endif
+    LT_REQUIRE(b != nullptr, "%s: baseline is NULL", who);
+    LT_REQUIRE(dst != nullptr || n_probe == 0 || n_obs == 0, "%s: dst is NULL", who);
+    LT_REQUIRE(ldd >= n_obs, "%s: ldd smaller than the row", who);
     hipStream_t st = (hipStream_t)stream;
     double *dev = nullptr;
     bool host_dst = false;
-    if (n_probe > 0 && n_obs > 0) {
-        const int rc = lt_export_resolve(dst, &dev, "lt_influence_matrix_host", &host_dst);
+    // dst: asked of the runtime here, as ever -- unless the caller vouches for pinned memory: then only where the GPU writes it,
+    // which influence_rows_impl knows (the packed route never does)
+    const bool lazy = (flags & LT_STEP_DST_PINNED) != 0 && n_probe > 0 && n_obs > 0;
+    if (lazy) host_dst = true;
+    else if (n_probe > 0 && n_obs > 0) {
+        const int rc = lt_export_resolve(dst, &dev, who, &host_dst);
         if (rc) return rc;
     }
+    const lt_host_job hj = {lazy ? dst : (double *)nullptr, who, (flags & LT_STEP_REFRESH) != 0};
     const int ec = lt_tune().export_compact, early = lt_tune().export_early;
     const size_t cells = (size_t)(n_probe > 0 ? n_probe : 0) * (size_t)(n_obs > 0 ? n_obs : 0);
     const size_t run_bytes = lt_align_up(cells * sizeof(uint32_t), 256);      // index run | value run | the ready word's line
@@ -2618,7 +2639,8 @@ extern "C" int lt_influence_matrix_host(const lt_baseline *b, const int32_t *pro
         __atomic_store_n(h_ready, 0u, __ATOMIC_RELEASE);
     }
     const int rc = influence_rows_impl(b, probe_nodes, n_probe, observe_nodes, n_obs, delta, mode, out, ldo, workspace,
-                                       workspace_bytes, stream, nullptr, dev, ldd, want ? &cmp : nullptr);
+                                       workspace_bytes, stream, nullptr, dev, ldd, want ? &cmp : nullptr, nullptr, &hj);
+    LT_LAB_STAMP(2);
     if (cmp.taken) b->stage_parity ^= 1;     // (the launches that used this cursor cleared the other one)
     if (rc) {
         if (cmp.taken) {       // (launches already queued may still write the staging block; cursors and ticket may be left dirty)
@@ -2628,13 +2650,16 @@ extern "C" int lt_influence_matrix_host(const lt_baseline *b, const int32_t *pro
         return rc;
     }
     if (!cmp.taken) {
+        LT_LAB_STAMP(3);
         LT_HIP(hipStreamSynchronize(st));
+        LT_LAB_STAMP(4);
         return LT_OK;
     }
     // np.zeros (attacker.py:216), here, while the GPU computes; the padding columns stay as they are
     if (ldd == n_obs) memset(dst, 0, cells * sizeof(double));
     else
         for (int32_t i = 0; i < n_probe; ++i) memset(dst + (size_t)i * ldd, 0, (size_t)n_obs * sizeof(double));
+    LT_LAB_STAMP(3);
     const uint32_t *idx = reinterpret_cast<const uint32_t *>(hs);
     const float *val = reinterpret_cast<const float *>(hs + run_bytes);
     const uint64_t lim = (uint64_t)n_probe * (uint64_t)ldd;
@@ -2678,6 +2703,7 @@ extern "C" int lt_influence_matrix_host(const lt_baseline *b, const int32_t *pro
         }
     }
     LT_HIP(hipStreamSynchronize(st));
+    LT_LAB_STAMP(4);
 #ifdef LT_HOST_LAB      // tools/host_lab/early_ab.py --forms: where the post-wait section's time goes (forms 1 and 2 are not the product)
     {
         const int form = lt_host_lab_env("LT_HOST_LAB_FORM");
@@ -2707,7 +2733,7 @@ extern "C" int lt_influence_matrix_host(const lt_baseline *b, const int32_t *pro
 #endif
     const int64_t t0 = lt_now_ns();
     const unsigned r_end = __atomic_load_n(h_ready, __ATOMIC_ACQUIRE);
-    if (r_end == 0u) return lt_set_error(LT_ERR_HIP, "lt_influence_matrix_host: the packed run was not published");
+    if (r_end == 0u) return lt_set_error(LT_ERR_HIP, "%s: the packed run was not published", who);
     const size_t total = std::min<size_t>((size_t)__atomic_load_n(h_ready + 1, __ATOMIC_RELAXED), cells);
     for (size_t e = 0; e < total; ++e) {
         const uint32_t x = idx[e];
@@ -2723,6 +2749,30 @@ extern "C" int lt_influence_matrix_host(const lt_baseline *b, const int32_t *pro
         }
     } else ++b->stage_late;
     return LT_OK;
+}
+extern "C" int lt_influence_matrix_host(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
+                                        const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode, float *out,
+                                        int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
+                                        void *stream) {
+    const int rc = influence_host_impl(b, probe_nodes, n_probe, observe_nodes, n_obs, delta, mode, out, ldo, dst, ldd, workspace,
+                                       workspace_bytes, stream, 0, "lt_influence_matrix_host");
+    LT_LAB_STAMP(5);
+    return rc;
+}
+// refresh + lt_influence_matrix_host + lt_node_check in one call (include/linkteller_hip.h)
+extern "C" int lt_influence_step_host(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
+                                      const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode, float *out,
+                                      int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
+                                      void *stream, int32_t flags, int32_t *bad_probe, int32_t *bad_observe) {
+    if (bad_probe) *bad_probe = 0;
+    if (bad_observe) *bad_observe = 0;
+    LT_REQUIRE((flags & ~(LT_STEP_REFRESH | LT_STEP_DST_PINNED)) == 0, "lt_influence_step_host: unknown flags 0x%x", (unsigned)flags);
+    int rc = influence_host_impl(b, probe_nodes, n_probe, observe_nodes, n_obs, delta, mode, out, ldo, dst, ldd, workspace,
+                                 workspace_bytes, stream, flags, "lt_influence_step_host");
+    // (behind the wait: the flag words are this call's kernels' -- a refused call launched nothing and leaves them alone)
+    if (!rc && n_probe > 0 && n_obs > 0) rc = lt_node_check(bad_probe, bad_observe);
+    LT_LAB_STAMP(5);
+    return rc;
 }
 
 extern "C" int lt_influence_rows(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
@@ -2779,14 +2829,17 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
                                const int32_t *observe_nodes, int32_t n_obs, float delta,
                                int32_t mode, float *out, int64_t ldo, void *workspace,
                                size_t workspace_bytes, void *stream, float *vec, double *dst64, int64_t ldd,
-                               lt_compact_out *cmp, const lt_pairs_job *pj) {
+                               lt_compact_out *cmp, const lt_pairs_job *pj, const lt_host_job *hj) {
     lt_prof_call prof_call_;
     int32_t exported_rows = 0;      // (dst64) rows the fused route's blocks wrote themselves: the chunks are in probe order
     LT_REQUIRE(b != nullptr, "lt_influence_rows: baseline is NULL");
     LT_REQUIRE(n_probe >= 0 && n_obs >= 0, "lt_influence_rows: negative count");
     LT_REQUIRE(mode >= LT_MODE_FULL && mode <= LT_MODE_DELTA, "lt_influence_rows: unknown mode %d", mode);
     LT_REQUIRE(delta != 0.f && delta == delta, "lt_influence_rows: delta must be a non-zero number");
-    if (n_probe == 0 || (pj ? pj->n_pairs == 0 : n_obs == 0)) return LT_OK;
+    if (n_probe == 0 || (pj ? pj->n_pairs == 0 : n_obs == 0)) {
+        if (hj && hj->refresh) lt_baseline_mark_stale(b);      // (the refresh of a call with an empty list still is one)
+        return LT_OK;
+    }
     LT_REQUIRE(probe_nodes && (pj ? pj->obs : observe_nodes) && out, "lt_influence_rows: NULL pointer");
     LT_REQUIRE(ldo >= n_obs, "lt_influence_rows: ldo=%lld < n_obs=%d", (long long)ldo, n_obs);
     LT_REQUIRE(b->n > 0, "lt_influence_rows: empty graph");
@@ -2822,7 +2875,13 @@ static int influence_rows_impl(const lt_baseline *b, const int32_t *probe_nodes,
         dst64 = nullptr;
         cmp->taken = true;
         cmp->chunks = (n_probe + w.chunk - 1) / w.chunk;
+    } else if (hj && hj->dst_raw) {      // (the GPU writes dst: its device-side alias, or the refusal of a pageable pointer)
+        const int rc = lt_export_resolve(hj->dst_raw, &dst64, hj->who);
+        if (rc) return rc;
     }
+    // Every check in front of the first launch is behind us: a refresh asked for with the call happens now, in front of the ensure_*
+    // calls that act on it (the grid-limit checks further down come after those launches: the refresh has then been consumed)
+    if (hj && hj->refresh) lt_baseline_mark_stale(b);
     const bool use_marks = !fused && mode != LT_MODE_FULL && w.pm_cnt != nullptr &&
                            (w.bits == nullptr || (long long)(n_probe < w.chunk ? n_probe : w.chunk) * n_obs >= lt_tune().pair_marks);
     // observed hubs (stageB_long_block): members found from the short side, or every entry tested against every probe.

@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <time.h>
 
 #include "linkteller_hip.h"
 
@@ -194,6 +195,13 @@ struct lt_baseline {
     mutable uint32_t *stage_copy = nullptr;   // "export_early" = 2: the indices as the early look saw them
     mutable size_t stage_copy_words = 0;
 };
+// what lt_baseline_refresh marks stale (lt_influence_step_host does the same inside its call)
+static inline void lt_baseline_mark_stale(const lt_baseline *b) {
+    b->s1_fresh = false;
+    b->pad_fresh = false;
+    b->layers_fresh = false;
+    b->fp64_fresh = false;
+}
 
 int lt_set_error(int code, const char *fmt, ...);
 
@@ -279,8 +287,24 @@ int lt_export_rows_dev(const float *src, int64_t lds, int32_t rows, int32_t cols
                                 hipGetErrorString(e_), __FILE__, __LINE__);                \
     } while (0)
 
+static inline int64_t lt_now_ns() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (int64_t)ts.tv_sec * 1000000000ll + ts.tv_nsec;
+}
+// -DLT_HOST_LAB only (tools/host_lab/step_parts.py; nothing of it is in a product build): stamp [1] of a host-landed call, the
+// moment its first launch has returned.  "Launch" = the first KERNEL launch checked with LT_CHECK_LAUNCH in any translation unit
+// (at the headline shape the product rows'); a hipMemsetAsync / hipMemcpyAsync in front of it does not set the stamp.
+#ifdef LT_HOST_LAB
+extern int64_t g_lt_lab_stamp[6];
+#define LT_LAB_FIRST_LAUNCH() do { if (!g_lt_lab_stamp[1]) g_lt_lab_stamp[1] = lt_now_ns(); } while (0)
+#else
+#define LT_LAB_FIRST_LAUNCH() ((void)0)
+#endif
+
 #define LT_CHECK_LAUNCH()                                                                  \
     do {                                                                                   \
+        LT_LAB_FIRST_LAUNCH();                                                             \
         hipError_t e_ = hipGetLastError();                                                 \
         if (e_ != hipSuccess)                                                              \
             return lt_set_error(LT_ERR_HIP, "kernel launch failed: %s (%s:%d)",            \

@@ -48,6 +48,11 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def _pinned_f64(rows: int, cols: int) -> torch.Tensor:
+    # a block of torch's pinned-memory cache: recycled when its last owner is released, so a fresh one per step allocates nothing
+    return torch.empty((rows, cols), dtype=torch.float64, pin_memory=True)
+
+
 def gemm(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """a @ b on the matrix cores in exact fp32 (reference gcn/layers.py:31 torch.mm)."""
     a, b = _f32(a, "a"), _f32(b, "b")
@@ -389,23 +394,56 @@ class Baseline:
         array; lt_influence_matrix_host), then the device-side node-id check (IndexError, as the reference raises).  On the
         fused `delta` route the host zero-fills the matrix while the GPU computes and only the touched values cross PCIe,
         packed; other routes write whole rows without an export launch of their own where the route allows.  ``refresh``:
-        mark the loop-invariant baseline stale first (``refresh(mode)``) -- the call then recomputes it."""
+        mark the loop-invariant baseline stale first (``refresh(mode)``) -- the call then recomputes it.
+        A baseline without a sharded refresh does all of that -- refresh, rows, wait, node check -- in ONE library call
+        (lt_influence_step_host): the node lists are converted once, the cached workspace is passed as it is (the library says
+        when it is too small: one retry) and the IndexError comes from that call's own return code.  A sharded refresh runs
+        collectives, so such a baseline keeps the separate calls; a call with an empty list is its refresh and nothing else."""
         dev = self.x.device
         probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
         obs = _as_nodes(observe_nodes, self.n, dev, "observe_nodes")
         npb, nob = probes.numel(), obs.numel()
-        host = torch.empty((npb, nob), dtype=torch.float64, pin_memory=True)
+        host = _pinned_f64(npb, nob)
         key = ("scratch", npb, nob)
         out = self._host_scratch.get(key)
         if out is None:
             out = torch.empty((npb, nob), dtype=torch.float32, device=dev)
             self._host_scratch = {key: out}
+        if self._shard is not None or self._shard64 is not None or not (npb and nob):      # (an empty list: the refresh, no rows call)
+            if refresh:
+                self.refresh(mode)
+            if npb and nob:
+                self.influence_rows(probes, obs, delta, mode, out=out, host=host, wait=True)
+                node_check()
+            return host.numpy()
+        m = _lib.MODES[mode] if isinstance(mode, str) else int(mode)
+        if m == _lib.MODE_DELTA and not self._fp64:
+            self.enable_fp64()
         if refresh:
-            self.refresh(mode)
-        if npb and nob:
-            self.influence_rows(probes, obs, delta, mode, out=out, host=host, wait=True)
-            node_check()
+            # (what _refresh_handle does in front of every refresh: in-place torch edits of X are announced first)
+            v = _x_version(self.x)
+            if v != self._x_seen:
+                _lib.check(_lib.lib().lt_baseline_features_changed(self._h, _stream()), "lt_baseline_features_changed")
+                self._x_seen = v
+        flags = (_lib.STEP_REFRESH | _lib.STEP_DST_PINNED) if refresh else _lib.STEP_DST_PINNED
+        step = _lib.lib().lt_influence_step_host
+        ws = next(iter(self._ws.values()), None)
+        if ws is None:
+            ws = self._step_workspace(npb, nob, m, dev)
+        args = (self._h, probes.data_ptr(), npb, obs.data_ptr(), nob, float(delta), m, out.data_ptr(), nob, host.data_ptr(),
+                max(nob, 1))
+        rc = step(*args, ws.data_ptr(), ws.numel(), _stream(), flags, None, None)
+        if rc == _lib.LT_ERR_WORKSPACE:      # (refused before anything was enqueued or marked stale: ask, regrow, call again -- once)
+            ws = self._step_workspace(npb, nob, m, dev)
+            rc = step(*args, ws.data_ptr(), ws.numel(), _stream(), flags, None, None)
+        if rc:
+            _lib.check(rc, "lt_influence_step_host")
         return host.numpy()
+
+    def _step_workspace(self, npb, nob, m, dev):
+        ws = _workspace(_lib.lib().lt_influence_workspace_bytes(self._h, npb, nob, m), dev)
+        self._ws = {(npb, nob, m): ws}
+        return ws
 
     def host_landing_stats(self) -> dict:
         """The packed ``influence_matrix_host`` calls on this baseline so far (lt_host_landing_stats): how many consumed the
