@@ -40,7 +40,8 @@ extern "C" {
                             Additive within 5: edge recovery (lt_top_pairs_lower, profile classes 12-13); no entry point changed.
                             Additive within 5: attack metrics (lt_score_curve, profile classes 14-15); no entry point changed.
                             Additive within 5: the attack's node pairs (lt_sample_square_labels, lt_group_pairs, lt_upper_edge_count,
-                            lt_sample_balanced_philox); no entry point changed */
+                            lt_sample_balanced_philox); no entry point changed.
+                            Additive within 5: the baseline attacks' scores (lt_corr_square, lt_corr_pairs); no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -771,6 +772,32 @@ size_t lt_sample_balanced_workspace_bytes(int32_t n, int64_t E, int64_t round_dr
 int lt_sample_balanced_philox(int32_t n, const int32_t *d_rowptr, const int32_t *d_col, int64_t nnz, int64_t E, uint64_t seed,
                               int64_t max_draws, int64_t round_draws, int32_t *out_u, int32_t *out_v, int64_t *info, void *ws,
                               size_t ws_bytes, void *stream);
+
+/* ---- the baseline attacks' scores (LSA2-post / LSA2-attr, attacker.py:287-375): correlation of mean-centred rows ---------------------
+ * V: device [n, ldv] fp32 (posteriors or features), ldv >= D, any 4-byte alignment.  The score of two rows is
+ *   corr(a, b) = <x_a - m, x_b - m> / ||x_a - m|| / ||x_b - m||
+ * with the fp32 inputs widened exactly and the mean m, the centring, every product and every sum in fp64; ONE rounding to fp32
+ * happens at the store.  No floating-point atomics: column sums go through a fixed partition of the rows (a function of the row
+ * count alone) added in partition order, the Gram's K slices (a function of (k, D) alone) are added in slice order; two calls
+ * give equal bits.
+ * lt_corr_square: out[i * ldo + j] = corr(nodes[i], nodes[j]), i, j < k; m = the column mean over the k listed rows (a repeated
+ *   id counts as often as it is listed).  The full k x k square is written and equals its transpose bit for bit (every lower
+ *   64 x 64 tile is formed once on v_mfma_f64_16x16x4_f64 and stored twice); words j >= k of a row are left alone.  The norms are
+ *   the square roots of the reduced Gram's own diagonal.
+ * lt_corr_pairs: out[p] = corr(u[p], v[p]), p < m; the mean is taken over ALL n rows; u[p] == v[p] is allowed (the reference's
+ *   balanced-full sample produces it).
+ * nodes, u, v: device int32.  info (device int64 [4]): [0] rows (square) / pairs (pair list) with a zero-norm row -- a row whose
+ * centred vector is zero; every cell it touches is NaN, as the reference's 0 / 0 is; [1] node ids outside [0, n): such an id is
+ * never used as an address, every cell it touches is NaN, and the square's mean is taken over the valid listed rows; [2], [3] 0.
+ * Enqueue only, no synchronisation.  LT_ERR_INVALID before any device call: NULL pointers, n < 1, D < 1, k < 0, m outside
+ * [0, 2^31 - 1], ldv < D, ldo < k, a workspace smaller than lt_corr_workspace_bytes(n, D, k, 0) / (n, D, 0, m) or not 8-byte
+ * aligned.  k == 0 / m == 0: a successful no-op.  The query serves both calls (the larger need) and returns 0 for invalid
+ * arguments.  Additive in ABI 5. */
+size_t lt_corr_workspace_bytes(int32_t n, int32_t D, int32_t k, int64_t n_pairs);
+int lt_corr_square(const float *V, int64_t ldv, int32_t n, int32_t D, const int32_t *nodes, int32_t k, float *out, int64_t ldo,
+                   int64_t *info, void *ws, size_t ws_bytes, void *stream);
+int lt_corr_pairs(const float *V, int64_t ldv, int32_t n, int32_t D, const int32_t *u, const int32_t *v, int64_t m, float *out,
+                  int64_t *info, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- training of the 2-layer GCN (reference gcn_trainer.py:144-170 train_one_epoch + optim.Adam) ----
  * lt_gcn2_trainer_create borrows the graph, X [n, ldx], labels (int32 [n], device, each in [0, C)) and the four parameter

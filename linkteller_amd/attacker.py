@@ -560,7 +560,10 @@ class Attacker:
         is the pair (test_nodes[j], test_nodes[i]) scored by perturbing test_nodes[i], as ``link_prediction_attack_efficient``
         reads it -- and m indices and scores cross PCIe instead of the matrix.  The order (score descending, then cell index) is
         total, so a smaller belief's prediction is a prefix of the ranked list.  Needs ``prepare_test_data()`` with an
-        ``unbalanced*`` sample type.  With several ranks every rank forms all rows itself: no collective of its own to mismatch."""
+        ``unbalanced*`` sample type.  With several ranks every rank forms all rows itself: no collective of its own to mismatch.
+        For ``attack_mode`` baseline / baseline-feat with ``args.baseline_scores == "device"`` the rows are the correlation square
+        of ``engine.corr_square`` (symmetric) instead of influence rows; a sampled node whose centred vector is zero makes its
+        row NaN and raises ``ValueError`` (a ranking over NaNs is undefined)."""
         from . import recover
         st = str(self.args.sample_type)
         if not st.startswith("unbalanced"):
@@ -583,8 +586,14 @@ class Attacker:
         beliefs = recover.density_ladder(n_edges, n) if beliefs is None else [float(b) for b in beliefs]
         counts = recover.belief_counts(beliefs, n_total)
         m = int(counts.max())
-        rows = self._rows(probes, observed, mode)
+        cinfo = None
+        if str(getattr(self.args, "attack_mode", "efficient")) in ("baseline", "baseline-feat") and self._baseline_route() == "device":
+            rows, cinfo = self._baseline_square_device()     # (addition: the baseline attacks' correlation square, symmetric)
+        else:
+            rows = self._rows(probes, observed, mode)
         idx_d, val_d, info = engine.top_pairs_lower(rows, m)
+        if cinfo is not None:
+            cinfo.check(nan_ok=False)     # (a zero-norm row makes whole rows NaN: lt_top_pairs_lower's set would be unspecified)
         if dev_sample is not None:
             # cell (i, j), j < i, is the pair of positions (j, i): slot j (2 n - j - 1) / 2 + (i - j - 1) of the label triangle
             ci_d, cj_d = idx_d // n, idx_d % n
@@ -705,20 +714,47 @@ class Attacker:
         ``"curves"``: ``metrics.curves_from_counts(...)``, the arrays ``compute_and_save`` stores, bit for bit.  Needs
         ``prepare_test_data()``.  Efficient attack on an ``unbalanced*`` sample: the n_test x n_test rows of ``_rows`` (every
         model kind it serves) read through a cached index; naive attack and ``balanced-full``: the listed pairs' scores.  The
-        baseline attacks' scores are host arithmetic: ``NotImplementedError``.  After ``prepare_test_data(pairs="device")`` the
+        baseline attacks' scores are host arithmetic: ``NotImplementedError`` -- unless ``args.baseline_scores == "device"``: then
+        their square (``engine.corr_square``) is read through the same index, their pair list is ``engine.corr_pairs``'.  After ``prepare_test_data(pairs="device")`` the
         square's labels and index are ``sampling.square_labels_device``'s, after ``prepare_test_data(rng="philox")`` the pair
         lists are grouped on the device (``_pair_curve_device``); no host pair list is built for either.  With several ranks every rank forms all rows
         itself: no collective of its own to mismatch."""
         from . import metrics as lt_metrics
         am = str(getattr(self.args, "attack_mode", "efficient"))
         st = str(self.args.sample_type)
-        if am in ("baseline", "baseline-feat"):
+        corr_info = None
+        if am in ("baseline", "baseline-feat") and self._baseline_route() != "device":
             raise NotImplementedError(f"evaluate: attack_mode = {am} scores its pairs on the host (baseline_attack)")
-        if am not in ("efficient", "naive"):
+        if am not in ("efficient", "naive", "baseline", "baseline-feat"):
             raise NotImplementedError(f"attack_mode = {am} not implemented!")
         dev_sample = getattr(self, "_sample_dev", None) if self.features.is_cuda else None
         curve = tri_info = None
-        if am == "efficient" and st.startswith("unbalanced"):
+        if am in ("baseline", "baseline-feat"):
+            # baseline_scores = device: the correlations are formed on the device and stay there (corr_square / corr_pairs)
+            if st.startswith("unbalanced"):
+                nodes = np.asarray(self.test_nodes, dtype=np.int64)
+                rows, corr_info = self._baseline_square_device()
+                lds = int(rows.shape[1])
+                # the square is symmetric bit for bit: the efficient attack's cell (ind[v], ind[u]) holds the pair's score
+                if dev_sample is not None and dev_sample["kind"] == "square" and len(nodes) > 1:
+                    index, labels, tri_info = self._square_lists(lds, rows.device)
+                else:
+                    index, labels = self._metric_lists(lds, rows.device)
+                curve = engine.score_curve(rows, labels, index)
+            elif st == "balanced-full":
+                vec = self._baseline_vectors_device()
+                if dev_sample is not None and dev_sample["kind"] == "balanced":      # the philox pair lists never left the device
+                    u, v, n_edges = dev_sample["u"], dev_sample["v"], int(dev_sample["n_edges"])
+                    labels = torch.zeros(u.numel(), dtype=torch.uint8, device=u.device)
+                    labels[:n_edges] = 1
+                else:
+                    u, v, labels = self._baseline_pair_lists(vec.device)
+                scores, corr_info = engine.corr_pairs(vec, u, v)
+                curve = engine.score_curve(scores, labels)
+            else:
+                raise NotImplementedError(f"sample_type = {st} not implemented!")
+            corr_info.check()                                    # (IndexError before the NaN cells of a bad id reach the curve)
+        elif am == "efficient" and st.startswith("unbalanced"):
             nodes = np.asarray(self.test_nodes, dtype=np.int64)
             probes, observed = self._device_nodes(nodes, 0, len(nodes))
             rows = self._rows(probes, observed, mode)
@@ -764,15 +800,65 @@ class Attacker:
             return self.features.float().cpu()
         raise NotImplementedError(f"attack_mode={am} not implemented!")
 
+    # ---- baseline_scores = device (an addition) -----------------------------------------------------------
+    def _baseline_route(self):
+        route = getattr(self.args, "baseline_scores", "host")
+        if route not in ("host", "device"):
+            raise ValueError(f"baseline_scores = {route!r}: 'host' or 'device'")
+        return route
+
+    def _baseline_vectors_device(self):
+        """The vectors of ``_baseline_vectors``, left on the device: softmax (sigmoid for ppi) of the model's output, or the
+        features.  The softmax / sigmoid is a torch op on the device tensor."""
+        if not self.features.is_cuda:
+            raise LinkTellerHipError("baseline_scores = device: the scores are formed on the GPU; there is no CPU path")
+        am = self.args.attack_mode
+        if am == "baseline":
+            with torch.no_grad():
+                out = self.model(self.features, self.adj)
+                post = torch.softmax(out, dim=1) if self.dataset != "ppi" else torch.sigmoid(out)
+            return post.float()
+        if am == "baseline-feat":
+            return self.features.float()
+        raise NotImplementedError(f"attack_mode={am} not implemented!")
+
+    def _baseline_square_device(self):
+        """(square, info) of ``engine.corr_square`` over the sampled nodes: fp32 [n_test, n_test] on the device."""
+        vec = self._baseline_vectors_device()
+        nodes = np.asarray(self.test_nodes, dtype=np.int64)
+        _, observed = self._device_nodes(nodes, 0, len(nodes))
+        return engine.corr_square(vec, observed)
+
+    def _baseline_pair_lists(self, dev):
+        """(u, v, labels) of the host pair lists on the device: the existing pairs first (label 1), then the others."""
+        ex = np.asarray(self.exist_edges, dtype=np.int64).reshape(-1, 2)
+        nex = np.asarray(self.nonexist_edges, dtype=np.int64).reshape(-1, 2)
+        pairs = np.concatenate([ex, nex])
+        n = int(self.features.shape[0])
+        if pairs.size and (pairs.min() < 0 or pairs.max() >= n):
+            raise IndexError(f"a sampled pair names a node outside the {n} nodes")
+        labels = np.zeros(len(pairs), dtype=np.uint8)
+        labels[:len(ex)] = 1
+        u = torch.from_numpy(np.ascontiguousarray(pairs[:, 0], dtype=np.int32)).to(dev)
+        v = torch.from_numpy(np.ascontiguousarray(pairs[:, 1], dtype=np.int32)).to(dev)
+        return u, v, torch.from_numpy(labels).to(dev)
+
     def baseline_attack(self):
         """LSA2-post / LSA2-attr, attacker.py:287-334: correlation of mean-centred vectors, the mean taken
-        over the sampled nodes; fp32 arithmetic, scores widened to float64 like the reference's matrix."""
+        over the sampled nodes; fp32 arithmetic, scores widened to float64 like the reference's matrix.
+        ``args.baseline_scores == "device"``: the square is ``engine.corr_square``'s (fp64 arithmetic, one rounding to fp32), one
+        copy brings it back; the same pairs are read from it and the same file is written."""
         t = time.time()
-        vec = self._baseline_vectors()
         nodes = torch.as_tensor(np.asarray(self.test_nodes, dtype=np.int64))
-        d = vec[nodes] - torch.mean(vec[nodes], dim=0)
-        nrm = torch.norm(d, dim=1)
-        corr = ((d @ d.T) / nrm[:, None] / nrm[None, :]).numpy().astype(np.float64)
+        if self._baseline_route() == "device":
+            sq, cinfo = self._baseline_square_device()
+            corr = sq.cpu().numpy().astype(np.float64)
+            cinfo.check()
+        else:
+            vec = self._baseline_vectors()
+            d = vec[nodes] - torch.mean(vec[nodes], dim=0)
+            nrm = torch.norm(d, dim=1)
+            corr = ((d @ d.T) / nrm[:, None] / nrm[None, :]).numpy().astype(np.float64)
         print(f"time for computing correlation value: {time.time() - t}")
         node2ind = np.full(int(nodes.max()) + 1, -1, dtype=np.int64)
         node2ind[nodes.numpy()] = np.arange(len(nodes))
@@ -785,8 +871,19 @@ class Attacker:
         self.compute_and_save(scores(self.exist_edges), scores(self.nonexist_edges))
 
     def baseline_attack_balanced(self):
-        """attacker.py:337-375: same correlation with the mean over all nodes, one value per listed pair."""
+        """attacker.py:337-375: same correlation with the mean over all nodes, one value per listed pair.
+        ``args.baseline_scores == "device"``: the scores are ``engine.corr_pairs``', one copy of one float per pair."""
         t = time.time()
+        if self._baseline_route() == "device":
+            vec = self._baseline_vectors_device()
+            u, v, labels = self._baseline_pair_lists(vec.device)
+            out, cinfo = engine.corr_pairs(vec, u, v)
+            s = out.cpu().numpy().astype(np.float64)
+            cinfo.check()
+            n_ex = len(np.asarray(self.exist_edges, dtype=np.int64).reshape(-1, 2))
+            print(f"time for computing correlation value: {time.time() - t}")
+            self.compute_and_save(list(s[:n_ex]), list(s[n_ex:]))
+            return
         vec = self._baseline_vectors()
         d = vec - torch.mean(vec, dim=0)
         nrm = torch.norm(d, dim=1)

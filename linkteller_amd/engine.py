@@ -1075,6 +1075,105 @@ def score_curve(scores: torch.Tensor, labels: torch.Tensor, index: torch.Tensor 
     return ScoreCurve(thresholds, tps, fps, raw, n_items)
 
 
+_corr_ws = {}        # corr_square / corr_pairs' workspace: one per device, the largest size asked for so far
+
+
+class CorrInfo:
+    """The four info words of lt_corr_square / lt_corr_pairs, still on the device (``raw``, int64 [4]: [0] zero-norm rows / pairs,
+    [1] node ids outside [0, n)).  ``check()`` brings them over -- one copy of four words, the caller's wait -- and raises."""
+
+    def __init__(self, raw, what, n):
+        self.raw, self.what, self.n = raw, what, n
+        self._host = None
+
+    def check(self, nan_ok: bool = True) -> dict:
+        """``{"zero_norm", "bad_ids"}``.  ``IndexError`` when a node id lay outside [0, n) (its cells are NaN); ``ValueError`` when
+        ``nan_ok`` is false and a zero-norm row made cells NaN (with ``nan_ok`` the NaNs stand, as in the reference's 0 / 0)."""
+        if self._host is None:
+            self._host = [int(v) for v in self.raw.cpu().tolist()]
+        zero, bad = self._host[0], self._host[1]
+        if bad:
+            raise IndexError(f"{self.what}: {bad} node ids outside [0, {self.n})")
+        if zero and not nan_ok:
+            raise ValueError(f"{self.what}: {zero} zero-norm rows / pairs (a centred vector is zero): their scores are NaN")
+        return {"zero_norm": zero, "bad_ids": bad}
+
+
+def _corr_operands(vectors, lists, what):
+    if not isinstance(vectors, torch.Tensor):
+        raise TypeError("vectors must be a torch.Tensor")
+    if not vectors.is_cuda:
+        raise _lib.LinkTellerHipError(f"vectors must live on the GPU (got {vectors.device}); there is no CPU path")
+    if vectors.dtype != torch.float32 or vectors.dim() != 2:
+        raise TypeError(f"vectors must be a 2-d float32 tensor, got {vectors.dtype} {tuple(vectors.shape)}")
+    n, d = int(vectors.shape[0]), int(vectors.shape[1])
+    if n < 1 or d < 1:
+        raise ValueError(f"{what}: vectors of shape {tuple(vectors.shape)} hold no element")
+    if d > 1 and vectors.stride(1) != 1:
+        raise ValueError("vectors must have last-dimension stride 1 (rows may be strided)")
+    ldv = int(vectors.stride(0)) if n > 1 else d
+    if ldv < d:
+        raise ValueError(f"row stride {ldv} smaller than the {d} columns")
+    out = []
+    for name, t in lists:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if not t.is_cuda:
+            raise _lib.LinkTellerHipError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != torch.int32 or t.dim() != 1:
+            raise TypeError(f"{name} must be a 1-d int32 tensor, got {t.dtype} {tuple(t.shape)}")
+        if t.device != vectors.device:
+            raise ValueError(f"vectors and {name} must live on one device")
+        out.append(t.contiguous())
+    return n, d, ldv, out
+
+
+def _corr_workspace(n, d, k, m, dev):
+    need = _lib.lib().lt_corr_workspace_bytes(n, d, k, m)
+    if need == 0:
+        raise ValueError(f"corr: n={n}, D={d}, k={k}, pairs={m} are outside what the library serves")
+    ws = _corr_ws.get(dev)
+    if ws is None or ws.numel() < need:      # (one per device, grown to the largest need: alternating calls and sizes reallocate nothing)
+        ws = _corr_ws[dev] = _workspace(need, dev)
+    return ws
+
+
+def corr_square(vectors: torch.Tensor, nodes: torch.Tensor):
+    """The baseline attacks' correlation square on the device (lt_corr_square; the reference's ``d @ d.T / nrm / nrm``,
+    attacker.py:305-313) -> ``(out, info)``: ``out`` fp32 [k, k], ``out[i, j]`` the correlation of rows ``nodes[i]`` and ``nodes[j]``
+    of ``vectors`` ([n, D] float32 CUDA, rows may be strided) centred by the column mean over the k listed rows; symmetric bit for
+    bit; fp64 arithmetic, one rounding.  ``nodes``: int32 CUDA.  Nothing is brought to the host here: ``info.check()`` (a
+    ``CorrInfo``) does that after the caller's wait and raises ``IndexError`` for ids outside [0, n)."""
+    n, d, ldv, (nodes,) = _corr_operands(vectors, (("nodes", nodes),), "corr_square")
+    k, dev = int(nodes.numel()), vectors.device
+    out = torch.empty((k, k), dtype=torch.float32, device=dev)
+    raw = torch.zeros(4, dtype=torch.int64, device=dev)
+    if k:
+        ws = _corr_workspace(n, d, k, 0, dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().lt_corr_square(vectors.data_ptr(), ldv, n, d, nodes.data_ptr(), k, out.data_ptr(), k, raw.data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), _stream()), "lt_corr_square")
+    return out, CorrInfo(raw, "corr_square", n)
+
+
+def corr_pairs(vectors: torch.Tensor, u: torch.Tensor, v: torch.Tensor):
+    """The baseline attacks' correlation of listed pairs on the device (lt_corr_pairs; attacker.py:337-375) -> ``(out, info)``:
+    ``out`` fp32 [m], ``out[p]`` the correlation of rows ``u[p]`` and ``v[p]`` of ``vectors`` centred by the column mean over ALL
+    n rows (``u[p] == v[p]`` is allowed).  Otherwise as ``corr_square``."""
+    n, d, ldv, (u, v) = _corr_operands(vectors, (("u", u), ("v", v)), "corr_pairs")
+    if u.shape != v.shape:
+        raise ValueError(f"u and v differ in length: {u.numel()} / {v.numel()}")
+    m, dev = int(u.numel()), vectors.device
+    out = torch.empty(m, dtype=torch.float32, device=dev)
+    raw = torch.zeros(4, dtype=torch.int64, device=dev)
+    if m:
+        ws = _corr_workspace(n, d, 0, m, dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().lt_corr_pairs(vectors.data_ptr(), ldv, n, d, u.data_ptr(), v.data_ptr(), m, out.data_ptr(),
+                                                raw.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "lt_corr_pairs")
+    return out, CorrInfo(raw, "corr_pairs", n)
+
+
 def export_rows_f64(rows: torch.Tensor):
     """The finished rows as a float64 numpy array on the host (the reference's ``influence_val = np.zeros(...)`` filled by
     n_test**2 ``.item()`` round trips, attacker.py:216-229) -- ONE launch that widens on the device and writes straight into

@@ -62,6 +62,10 @@ _OPTIONS = {
     # gives the reference's pairs; a Python loop on the host); 'philox' is stream 3 of include/linkteller_hip.h, evaluated on the
     # GPU -- different pairs for the same seed, under the same result file name
     "sample-rng": (str, "numpy", ["numpy", "philox"]),
+    # addition: where the baseline attacks (--attack-mode baseline / baseline-feat) score their pairs.  'host' is the reference's
+    # fp32 torch arithmetic on the CPU; 'device' forms the correlations on the GPU in fp64 (lt_corr_square / lt_corr_pairs), writes
+    # the same result file, and lets --metrics-only and --recover serve the baseline attacks
+    "baseline-scores": (str, "host", ["host", "device"]),
 }
 _SWITCHES = ["no-cuda", "fastmode", "approx", "attack", "test", "break-down", "display", "same-size",
              "eval-degree", "trainable", "early", "fnormalize",
@@ -127,11 +131,14 @@ def init_distributed():
 
 
 def check_recover(args):
-    """``--recover`` is served after ``--attack --attack-mode efficient`` on an ``unbalanced*`` sample only; anything else is
+    """``--recover`` is served after ``--attack --attack-mode efficient`` on an ``unbalanced*`` sample only (with
+    ``--baseline-scores device`` also after the baseline attacks, whose square then lives on the device); anything else is
     refused here, before a Worker is built or the GPU is touched."""
     if not getattr(args, "recover", False):
         return
-    if not (args.attack and args.attack_mode == "efficient" and str(args.sample_type).startswith("unbalanced")):
+    # (--baseline-scores device: the baseline attacks' square is on the device too and is ranked like the efficient attack's)
+    served = ("efficient", "baseline", "baseline-feat") if getattr(args, "baseline_scores", "host") == "device" else ("efficient",)
+    if not (args.attack and args.attack_mode in served and str(args.sample_type).startswith("unbalanced")):
         raise NotImplementedError("--recover needs --attack --attack-mode efficient and --sample-type unbalanced / unbalanced-lo / "
                                   f"unbalanced-hi (got attack={args.attack}, attack-mode={args.attack_mode}, "
                                   f"sample-type={args.sample_type})")
@@ -141,12 +148,23 @@ def check_recover(args):
 
 def check_metrics_only(args):
     """``--metrics-only`` serves the attacks whose scores are formed on the device (efficient, naive); the baseline attacks'
-    scores are host arithmetic and are refused here, before a Worker is built or the GPU is touched."""
+    scores are host arithmetic and are refused here, before a Worker is built or the GPU is touched -- unless
+    ``--baseline-scores device`` forms them on the device too."""
     if not getattr(args, "metrics_only", False):
         return
-    if args.attack_mode in ("baseline", "baseline-feat"):
+    if args.attack_mode in ("baseline", "baseline-feat") and getattr(args, "baseline_scores", "host") != "device":
         raise NotImplementedError(f"--metrics-only needs --attack-mode efficient or naive (got attack-mode={args.attack_mode}: "
                                   "the baseline attacks score their pairs on the host)")
+
+
+def check_baseline_scores(args):
+    """``--baseline-scores device`` moves the baseline attacks' scores to the GPU: it is refused here, before a Worker is built or
+    the GPU is touched, unless ``--attack --attack-mode baseline`` / ``baseline-feat`` asks for such scores."""
+    if getattr(args, "baseline_scores", "host") != "device":
+        return
+    if not (args.attack and args.attack_mode in ("baseline", "baseline-feat")):
+        raise NotImplementedError("--baseline-scores device needs --attack and --attack-mode baseline / baseline-feat "
+                                  f"(got attack={args.attack}, attack-mode={args.attack_mode})")
 
 
 def check_dp_build(args):
@@ -175,6 +193,7 @@ def check_sample_build(args):
 
 def main(argv=None):
     args = get_arguments(argv)
+    check_baseline_scores(args)
     check_recover(args)
     check_metrics_only(args)
     check_dp_build(args)

@@ -109,7 +109,9 @@ class GCNTrainer:
     def eval_output(self, output, mode="clean", eval_degree=False):
         a = self.args
         if a.attack:
-            if getattr(a, "recover", False) and not (a.attack_mode == "efficient" and str(a.sample_type).startswith("unbalanced")):
+            # (addition: with baseline_scores = device the baseline attacks' square lives on the device and is ranked there too)
+            served = ("efficient", "baseline", "baseline-feat") if getattr(a, "baseline_scores", "host") == "device" else ("efficient",)
+            if getattr(a, "recover", False) and not (a.attack_mode in served and str(a.sample_type).startswith("unbalanced")):
                 raise NotImplementedError("recover: served after the efficient attack on an unbalanced* sample only")
             self.attacker = Attacker(args=a, model=self.model, worker=self.worker)
             build, rng = getattr(a, "sample_build", "host"), getattr(a, "sample_rng", "numpy")
