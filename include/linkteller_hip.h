@@ -41,7 +41,9 @@ extern "C" {
                             Additive within 5: attack metrics (lt_score_curve, profile classes 14-15); no entry point changed.
                             Additive within 5: the attack's node pairs (lt_sample_square_labels, lt_group_pairs, lt_upper_edge_count,
                             lt_sample_balanced_philox); no entry point changed.
-                            Additive within 5: the baseline attacks' scores (lt_corr_square, lt_corr_pairs); no entry point changed */
+                            Additive within 5: the baseline attacks' scores (lt_corr_square, lt_corr_pairs); no entry point changed.
+                            Additive within 5: validation every epoch (lt_eval_head, lt_early_stop_*, lt_gcn*_trainer_attach_validation /
+                            _run_validated / _val_state / _restore_best / _val_logits); no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -872,6 +874,74 @@ int lt_gcn3_trainer_destroy(lt_gcn3_trainer *t);
  * count after this update. */
 int lt_adam_step(int64_t n, float *p, const float *g, float *m, float *v, int64_t step, double lr, double beta1,
                  double beta2, double eps, double weight_decay, void *stream);
+
+/* ---- validation every epoch: evaluation head, early-stopping state, best-model snapshot (reference gcn_trainer.py:167-174,
+ * 195-196, 235-238 and utils/early_stopping.py).  Additive within ABI 5; everything is opt-in.
+ *
+ * lt_eval_head: mean cross-entropy and confusion matrix of logits Z [n, ldz] (fp32, device) against labels (int32 [n], device),
+ * enqueue-only, in two launches.  Row stage: one thread per row, ceil(n / 256) blocks, the training head's per-row arithmetic
+ * (loss_r = (max + logf(sum expf(z - max))) - z[y], predicted class = first argmax); each block reduces its 256 row losses
+ * with a fixed tree and counts its C x C cells as integers.  Finish stage: one block adds the blocks' partials in a fixed
+ * order.  loss (device, one float) = the sum / n; confusion (device, int32 [C, C], row = true class, column = predicted
+ * class), whose trace is the correct count.  No float atomics: the outputs are a pure function of the inputs.  A label
+ * outside [0, C) counts in no cell (its row's loss reads z[y] as 0, as the training head does): checking labels is the
+ * caller's job here, lt_gcn*_trainer_attach_validation does it.  LT_ERR_INVALID before any launch: n <= 0, C outside
+ * [1, 8], ldz < C, a NULL pointer; LT_ERR_WORKSPACE: workspace (device, 4-byte aligned) smaller than
+ * lt_eval_head_workspace_bytes(n, C) (0 for unsupported n / C).
+ *
+ * The early-stopping state is 8 int32 words of device memory the caller owns:
+ *   [0] best_loss (the fp32 bits)  [1] best_epoch  [2] counter  [3] stop_epoch (-1 while running)
+ *   [4] improved (the last update's flag)  [5] seen (1 once an epoch has been applied)  [6], [7] 0
+ * lt_early_stop_reset writes the initial state (best_epoch = stop_epoch = -1, the rest 0).  lt_early_stop_update applies one
+ * epoch's loss (a device word) -- EarlyStopping.__call__ with delta = 0:
+ *   stop_epoch >= 0:  improved = 0, nothing else changes (the state is frozen)
+ *   seen && loss > best_loss:  ++counter, improved = 0; if (patience > 0 && counter >= patience) stop_epoch = epoch
+ *   otherwise:  best_loss = loss, best_epoch = epoch, counter = 0, improved = 1
+ * so a tie is an improvement, and a NaN loss (or a NaN best) compares false and becomes the best, as `score < best_score`
+ * does in the reference.  patience = 0: keep the best, never stop.  Both calls are enqueue-only (one launch).
+ * LT_ERR_INVALID before the launch: a NULL pointer, patience < 0, epoch < 0.
+ *
+ * Per trainer (`gcn2` and `gcn3` alike):
+ * lt_gcn*_trainer_attach_validation borrows the held-out graph g2, X2 [n2, ldx2] and labels2 (int32 [n2], device); the
+ * trainer allocates the forward's buffers at n2 rows (with split-K slabs chosen for n2), the head's partials, the state
+ * block and, with keep_best = 1, a snapshot buffer of the parameters' size.  It synchronises (labels2 is read back and
+ * checked).  LT_ERR_INVALID, with nothing allocated or launched: a second attach; a NULL argument; n2 != the graph's node
+ * count or an empty graph; ldx2 < F; a label outside [0, C); keep_best outside {0, 1}; patience < 0; g2, X2 or labels2 not in
+ * device memory of the device the trainer's X lives on.
+ * lt_gcn*_trainer_run_validated enqueues n_epochs epochs, no host synchronisation.  Per epoch e (0-based, counted since the
+ * trainer was created): the training epoch of lt_gcn*_trainer_run, unchanged; then, with the updated parameters, the
+ * forward's launches with dropout off on (g2, X2) -- for gcn2 the launches of lt_gcn2_forward, hence its bits -- the
+ * evaluation head, the state update (inside the finish launch) and, with keep_best, one predicated launch that copies the
+ * live parameters into the snapshot when `improved` is set and returns at once when it is not.  record [n_epochs, 2] as
+ * lt_gcn*_trainer_run; val_loss [n_epochs] fp32; val_counts [n_epochs, C * C] int32 (device).  Epochs enqueued after a stop
+ * still run and still fill their rows of the three outputs; they change the live parameters and nothing else: state and
+ * snapshot are frozen, so the selected model does not depend on how many epochs were enqueued past the stop.
+ * LT_ERR_INVALID before any launch: no validation attached, n_epochs < 0, a NULL output with n_epochs > 0.
+ * lt_gcn*_trainer_run on a trainer with validation attached keeps its meaning: no validation.
+ * lt_gcn*_trainer_val_state copies the 8 state words to `state` (host) and synchronises the stream.
+ * lt_gcn*_trainer_restore_best (keep_best only, else LT_ERR_INVALID) enqueues the copy of the snapshot into the live
+ * parameters (nothing happens before the first validated epoch); the padded copies follow at the next run, as always.
+ * lt_gcn*_trainer_val_logits: test accessor, the last validation logits [n2, C] written with leading dimension ldz >= C. */
+size_t lt_eval_head_workspace_bytes(int32_t n, int32_t C);
+int lt_eval_head(const float *Z, int64_t ldz, const int32_t *labels, int32_t n, int32_t C, float *loss, int32_t *confusion,
+                 void *workspace, size_t workspace_bytes, void *stream);
+#define LT_EARLY_STOP_WORDS 8
+int lt_early_stop_reset(int32_t *state, void *stream);
+int lt_early_stop_update(const float *loss, int32_t patience, int32_t epoch, int32_t *state, void *stream);
+int lt_gcn2_trainer_attach_validation(lt_gcn2_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
+                                      const int32_t *labels2, int32_t keep_best, int32_t patience, void *stream);
+int lt_gcn2_trainer_run_validated(lt_gcn2_trainer *t, int32_t n_epochs, float *record, float *val_loss, int32_t *val_counts,
+                                  void *stream);
+int lt_gcn2_trainer_val_state(const lt_gcn2_trainer *t, int32_t *state, void *stream);
+int lt_gcn2_trainer_restore_best(lt_gcn2_trainer *t, void *stream);
+int lt_gcn2_trainer_val_logits(const lt_gcn2_trainer *t, float *Z, int64_t ldz, void *stream);
+int lt_gcn3_trainer_attach_validation(lt_gcn3_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
+                                      const int32_t *labels2, int32_t keep_best, int32_t patience, void *stream);
+int lt_gcn3_trainer_run_validated(lt_gcn3_trainer *t, int32_t n_epochs, float *record, float *val_loss, int32_t *val_counts,
+                                  void *stream);
+int lt_gcn3_trainer_val_state(const lt_gcn3_trainer *t, int32_t *state, void *stream);
+int lt_gcn3_trainer_restore_best(lt_gcn3_trainer *t, void *stream);
+int lt_gcn3_trainer_val_logits(const lt_gcn3_trainer *t, float *Z, int64_t ldz, void *stream);
 
 /* ---- per-kernel timing (used by bench.py for the roofline object) --------------------------
  * lt_profile_enable(mask): bit k of mask set = launches of kernel class k are bracketed by a pair of

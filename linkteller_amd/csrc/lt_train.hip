@@ -495,6 +495,231 @@ extern "C" int lt_adam_step(int64_t n, float *p, const float *g, float *m, float
 }
 
 // --------------------------------------------------------------------------------------------
+// Validation (reference gcn_trainer.py:167-174 + utils/early_stopping.py): the evaluation head in two kernels, the
+// early-stopping state in device memory, the predicated snapshot of the parameters.
+// --------------------------------------------------------------------------------------------
+// Row stage: k_tr_ce's per-row arithmetic (the same operations in the same order: the same row losses and argmax), one
+// thread per row.  Block b leaves the tree sum of its 256 row losses in part_loss[b] and its C x C confusion cells
+// (true class, predicted class) in part_cnt[b, C * C]; a label outside [0, C) counts in no cell.
+template <int CP>
+__global__ __launch_bounds__(TR_BLOCK) void k_val_rows(int n, const float *__restrict__ Z, long ldz, int C,
+                                                       const int32_t *__restrict__ labels, float *__restrict__ part_loss,
+                                                       int32_t *__restrict__ part_cnt) {
+    __shared__ float sl[TR_BLOCK];
+    __shared__ int sc[CP * CP];
+    const int t = threadIdx.x;
+    const int r = blockIdx.x * TR_BLOCK + t;
+    if (t < CP * CP) sc[t] = 0;
+    __syncthreads();
+    float l = 0.f;
+    if (r < n) {
+        const int y = labels[r];
+        float z[CP];
+#pragma unroll
+        for (int c = 0; c < CP; ++c) z[c] = c < C ? Z[(size_t)r * ldz + c] : -INFINITY;
+        float mx = z[0];
+        int arg = 0;
+#pragma unroll
+        for (int c = 1; c < CP; ++c)
+            if (c < C && z[c] > mx) { mx = z[c]; arg = c; }
+        float s = 0.f, zy = 0.f;
+#pragma unroll
+        for (int c = 0; c < CP; ++c) {
+            const float e = c < C ? expf(z[c] - mx) : 0.f;
+            s += e;
+            if (c == y) zy = z[c];
+        }
+        l = (mx + logf(s)) - zy;
+        if ((unsigned)y < (unsigned)C) atomicAdd(&sc[y * C + arg], 1);   // integer LDS atomics: the counts do not depend on order
+    }
+    sl[t] = l;
+    __syncthreads();
+    for (int w = TR_BLOCK / 2; w >= 1; w >>= 1) {
+        if (t < w) sl[t] += sl[t + w];
+        __syncthreads();
+    }
+    if (t == 0) part_loss[blockIdx.x] = sl[0];
+    if (t < C * C) part_cnt[(size_t)blockIdx.x * (C * C) + t] = sc[t];
+}
+
+// The early-stopping state: 8 words of device memory.
+#define VAL_STATE_WORDS 8
+enum { VS_BEST_LOSS = 0, VS_BEST_EPOCH = 1, VS_COUNTER = 2, VS_STOP_EPOCH = 3, VS_IMPROVED = 4, VS_SEEN = 5 };
+
+// EarlyStopping.__call__ with delta = 0 on the loss itself (score = -loss: `score < best_score` is `loss > best`, false for
+// a tie and for a NaN on either side).  patience 0: never stops.
+__device__ __forceinline__ void val_state_update(int32_t *s, float loss, int patience, int epoch) {
+    if (s[VS_STOP_EPOCH] >= 0) {
+        s[VS_IMPROVED] = 0;
+        return;
+    }
+    const float best = __int_as_float(s[VS_BEST_LOSS]);
+    if (s[VS_SEEN] > 0 && loss > best) {
+        const int c = s[VS_COUNTER] + 1;
+        s[VS_COUNTER] = c;
+        s[VS_IMPROVED] = 0;
+        if (patience > 0 && c >= patience) s[VS_STOP_EPOCH] = epoch;
+    } else {
+        s[VS_BEST_LOSS] = __float_as_int(loss);
+        s[VS_BEST_EPOCH] = epoch;
+        s[VS_COUNTER] = 0;
+        s[VS_IMPROVED] = 1;
+    }
+    s[VS_SEEN] = 1;
+}
+
+// Finish stage, one block: thread t adds the partial losses t, t + 256, ... in ascending block order, then the fixed tree;
+// the cells are integers (lane group k of 4 takes the partials k, k + 4, ...).  Thread 0 writes the mean loss and, when a
+// state block is given, applies the epoch to it.
+__global__ __launch_bounds__(TR_BLOCK) void k_val_finish(int n_blk, int n, int C, const float *__restrict__ part_loss,
+                                                         const int32_t *__restrict__ part_cnt, float *__restrict__ loss_out,
+                                                         int32_t *__restrict__ conf_out, int32_t *state, int patience,
+                                                         int epoch) {
+    __shared__ float sl[TR_BLOCK];
+    __shared__ int sc[4][64];
+    const int t = threadIdx.x, cc = C * C;
+    float l = 0.f;
+    for (int b = t; b < n_blk; b += TR_BLOCK) l += part_loss[b];
+    sl[t] = l;
+    const int cell = t & 63, grp = t >> 6;
+    int k = 0;
+    if (cell < cc)
+        for (int b = grp; b < n_blk; b += 4) k += part_cnt[(size_t)b * cc + cell];
+    sc[grp][cell] = k;
+    __syncthreads();
+    for (int w = TR_BLOCK / 2; w >= 1; w >>= 1) {
+        if (t < w) sl[t] += sl[t + w];
+        __syncthreads();
+    }
+    if (t < cc) conf_out[t] = (sc[0][t] + sc[1][t]) + (sc[2][t] + sc[3][t]);
+    if (t == 0) {
+        const float mean = sl[0] / (float)n;
+        *loss_out = mean;
+        if (state) val_state_update(state, mean, patience, epoch);
+    }
+}
+
+__global__ void k_val_state(const float *__restrict__ loss, int32_t *state, int patience, int epoch) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) val_state_update(state, *loss, patience, epoch);
+}
+
+__global__ void k_val_state_reset(int32_t *state) {
+    const int t = threadIdx.x;
+    if (t < VAL_STATE_WORDS) state[t] = (t == VS_BEST_EPOCH || t == VS_STOP_EPOCH) ? -1 : 0;
+}
+
+// Predicated copy between the live parameter tensors (segment k = elements [o[k - 1], o[k]) of the concatenation) and the
+// contiguous snapshot: every thread reads *flag, a word an earlier launch on the stream wrote, and returns when it is 0.
+// V floats per thread: the host picks the widest V for which every pointer is V * 4-byte aligned and every segment starts
+// at a multiple of V; a vector that would cross its segment's end (the last one only, then) is copied element by element.
+struct lt_snap_segs {
+    float *p[6];
+    int64_t o[6];
+};
+
+template <int V>
+__global__ __launch_bounds__(256) void k_val_snapshot(lt_snap_segs T, float *__restrict__ snap,
+                                                      const int32_t *__restrict__ flag, int to_live) {
+    if (*flag == 0) return;
+    const int64_t e0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (e0 >= T.o[5]) return;
+    const int k = e0 < T.o[0] ? 0 : e0 < T.o[1] ? 1 : e0 < T.o[2] ? 2 : e0 < T.o[3] ? 3 : e0 < T.o[4] ? 4 : 5;
+    const int64_t end = T.o[k], j = k ? e0 - T.o[k - 1] : e0;
+    float *p;      // a switch over constant indices, as in k_tr3_adam
+    switch (k) {
+        case 0: p = T.p[0]; break;
+        case 1: p = T.p[1]; break;
+        case 2: p = T.p[2]; break;
+        case 3: p = T.p[3]; break;
+        case 4: p = T.p[4]; break;
+        default: p = T.p[5]; break;
+    }
+    float *live = p + j, *kept = snap + e0;
+    float *dst = to_live ? live : kept;
+    const float *src = to_live ? kept : live;
+    typedef float fvec __attribute__((ext_vector_type(V)));
+    if (e0 + V <= end) {
+        *reinterpret_cast<fvec *>(dst) = *reinterpret_cast<const fvec *>(src);
+    } else {
+        for (int i = 0; i < V && e0 + i < end; ++i) dst[i] = src[i];
+    }
+}
+
+static int snap_width(const lt_snap_segs &T, const float *snap) {
+    int V = 4;
+    for (; V > 1; V >>= 1) {
+        bool ok = ((uintptr_t)snap % (V * sizeof(float))) == 0;
+        for (int k = 0; k < 6 && ok; ++k) {
+            const int64_t b = k ? T.o[k - 1] : 0;
+            if (T.o[k] == b) continue;      // an empty segment (the 2-layer trainer has four)
+            ok = (b % V) == 0 && ((uintptr_t)T.p[k] % (V * sizeof(float))) == 0;
+        }
+        if (ok) break;
+    }
+    return V;
+}
+
+static int launch_snapshot(const lt_snap_segs &T, float *snap, const int32_t *flag, int to_live, hipStream_t st) {
+    const int V = snap_width(T, snap);
+    const int64_t threads = (T.o[5] + V - 1) / V;
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (V == 4) hipLaunchKernelGGL((k_val_snapshot<4>), grid, dim3(256), 0, st, T, snap, flag, to_live);
+    else if (V == 2) hipLaunchKernelGGL((k_val_snapshot<2>), grid, dim3(256), 0, st, T, snap, flag, to_live);
+    else hipLaunchKernelGGL((k_val_snapshot<1>), grid, dim3(256), 0, st, T, snap, flag, to_live);
+    LT_CHECK_LAUNCH();
+    return LT_OK;
+}
+
+// What a trainer with validation attached owns: the forward's buffers at the validation graph's size, the head's partials,
+// the state block and (keep_best) the snapshot.
+struct lt_val {
+    const lt_graph *g = nullptr;
+    int32_t n = 0;
+    const float *X = nullptr;
+    int64_t ldx = 0;
+    const int32_t *labels = nullptr;
+    int32_t keep_best = 0, patience = 0;
+    int32_t kslice = 0;           // split-K slicing of X2 W1, chosen for n2 (the forward's choice at that size)
+    int32_t n_blk = 0;            // blocks of k_val_rows
+    float *S1 = nullptr, *Z1 = nullptr;    // [n2, Hp1]; Z1 only feeds the tiled layer-1 route (2-layer model)
+    float *H1 = nullptr;                   // [n2, Hp1] 3-layer model: relu(A S1 + b1)
+    float *S2 = nullptr, *Z2 = nullptr;    // [n2, Hp2] 3-layer model
+    float *Sc = nullptr, *Z = nullptr;     // [n2, C]: the last product and the validation logits
+    float *slabs = nullptr, *seg_part = nullptr;
+    float *part_loss = nullptr;            // [n_blk]
+    int32_t *part_cnt = nullptr;           // [n_blk, C * C]
+    int32_t *state = nullptr;              // [VAL_STATE_WORDS]
+    float *snap = nullptr;                 // [n_param] (keep_best)
+};
+
+static void free_val(lt_val *v) {
+    if (!v) return;
+    float *bufs[] = {v->S1, v->Z1, v->H1, v->S2, v->Z2, v->Sc, v->Z, v->slabs, v->seg_part, v->part_loss, v->snap};
+    for (float *b : bufs) (void)hipFree(b);
+    (void)hipFree(v->part_cnt);
+    (void)hipFree(v->state);
+    delete v;
+}
+
+static size_t val_head_bytes(int n, int C) {
+    const size_t n_blk = (size_t)((n + TR_BLOCK - 1) / TR_BLOCK);
+    return n_blk * (1 + (size_t)C * C) * sizeof(float);
+}
+
+static int launch_val_head(const float *Z, long ldz, const int32_t *labels, int n, int C, float *part_loss,
+                           int32_t *part_cnt, float *loss_out, int32_t *conf_out, int32_t *state, int patience, int epoch,
+                           hipStream_t st) {
+    const int n_blk = (n + TR_BLOCK - 1) / TR_BLOCK;
+    LT_DISPATCH_CP(lt_cp_for(C), hipLaunchKernelGGL((k_val_rows<CP_>), dim3((unsigned)n_blk), dim3(TR_BLOCK), 0, st, n, Z, ldz,
+                                                    C, labels, part_loss, part_cnt));
+    LT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_val_finish, dim3(1), dim3(TR_BLOCK), 0, st, n_blk, n, C, part_loss, part_cnt, loss_out, conf_out,
+                       state, patience, epoch);
+    LT_CHECK_LAUNCH();
+    return LT_OK;
+}
+
+// --------------------------------------------------------------------------------------------
 // trainer state
 // --------------------------------------------------------------------------------------------
 struct lt_gcn2_trainer {
@@ -518,10 +743,12 @@ struct lt_gcn2_trainer {
     float *slabs = nullptr, *tn_slabs = nullptr, *part = nullptr, *seg_part = nullptr;
     float *grad = nullptr, *m = nullptr, *v = nullptr;   // [F*H | H | H*C | C]
     int64_t n_param = 0;
+    lt_val *val = nullptr;        // lt_gcn2_trainer_attach_validation (owned)
 };
 
 static void free_trainer(lt_gcn2_trainer *t) {
     if (!t) return;
+    free_val(t->val);
     float *bufs[] = {t->S1, t->Z1, t->H1d, t->dZ1, t->dS1, t->S2, t->Z2, t->dZ2, t->dS2, t->loss_r, t->b1p, t->W2p,
                      t->slabs, t->tn_slabs, t->part, t->seg_part, t->grad, t->m, t->v};
     for (float *b : bufs) (void)hipFree(b);
@@ -977,10 +1204,12 @@ struct lt_gcn3_trainer {
     float *b1p = nullptr, *b2p = nullptr, *W3p = nullptr;
     float *slabs = nullptr, *tn1_slabs = nullptr, *tn2_slabs = nullptr, *part = nullptr, *part1 = nullptr, *seg_part = nullptr;
     float *grad = nullptr, *m = nullptr, *v = nullptr;
+    lt_val *val = nullptr;                    // lt_gcn3_trainer_attach_validation (owned)
 };
 
 static void free_trainer3(lt_gcn3_trainer *t) {
     if (!t) return;
+    free_val(t->val);
     float *bufs[] = {t->S1, t->H1d, t->dZ1, t->dS1, t->S2, t->Z2, t->H2d, t->dZ2, t->dS2, t->S3, t->Z3, t->dZ3, t->dS3,
                      t->loss_r, t->b1p, t->b2p, t->W3p, t->slabs, t->tn1_slabs, t->tn2_slabs, t->part, t->part1,
                      t->seg_part, t->grad, t->m, t->v};
@@ -1238,4 +1467,326 @@ extern "C" int lt_gcn3_trainer_hidden(const lt_gcn3_trainer *t, int32_t layer, f
     LT_HIP(hipMemcpy2DAsync(dst, (size_t)ld * sizeof(float), layer == 1 ? t->H1d : t->H2d, (size_t)Hp * sizeof(float),
                             (size_t)H * sizeof(float), (size_t)t->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return LT_OK;
+}
+
+// ============================================================================================
+// Validation: the standalone head and state update, and per-epoch validation inside both trainers.
+// ============================================================================================
+extern "C" size_t lt_eval_head_workspace_bytes(int32_t n, int32_t C) {
+    if (n <= 0 || C <= 0 || C > LT_MAX_C) return 0;
+    return val_head_bytes(n, C);
+}
+
+extern "C" int lt_eval_head(const float *Z, int64_t ldz, const int32_t *labels, int32_t n, int32_t C, float *loss,
+                            int32_t *confusion, void *workspace, size_t workspace_bytes, void *stream) {
+    LT_REQUIRE(n > 0, "lt_eval_head: n=%d, must be positive", n);
+    LT_REQUIRE(C > 0 && C <= LT_MAX_C, "lt_eval_head: C=%d (supported: 1 .. %d)", C, LT_MAX_C);
+    LT_REQUIRE(Z && labels && loss && confusion, "lt_eval_head: NULL pointer");
+    LT_REQUIRE(ldz >= C, "lt_eval_head: ldz=%lld < C=%d", (long long)ldz, C);
+    if (!workspace || workspace_bytes < val_head_bytes(n, C) || ((uintptr_t)workspace % sizeof(float)))
+        return lt_set_error(LT_ERR_WORKSPACE, "lt_eval_head: workspace needs %zu bytes, 4-byte aligned", val_head_bytes(n, C));
+    const int n_blk = (n + TR_BLOCK - 1) / TR_BLOCK;
+    float *part_loss = (float *)workspace;
+    return launch_val_head(Z, (long)ldz, labels, n, C, part_loss, (int32_t *)(part_loss + n_blk), loss, confusion, nullptr, 0, 0,
+                           (hipStream_t)stream);
+}
+
+extern "C" int lt_early_stop_reset(int32_t *state, void *stream) {
+    LT_REQUIRE(state != nullptr, "lt_early_stop_reset: state is NULL");
+    hipLaunchKernelGGL(k_val_state_reset, dim3(1), dim3(64), 0, (hipStream_t)stream, state);
+    LT_CHECK_LAUNCH();
+    return LT_OK;
+}
+
+extern "C" int lt_early_stop_update(const float *loss, int32_t patience, int32_t epoch, int32_t *state, void *stream) {
+    LT_REQUIRE(loss != nullptr && state != nullptr, "lt_early_stop_update: NULL pointer");
+    LT_REQUIRE(patience >= 0, "lt_early_stop_update: patience=%d, must be >= 0 (0: never stop)", patience);
+    LT_REQUIRE(epoch >= 0, "lt_early_stop_update: epoch=%d, must be >= 0", epoch);
+    hipLaunchKernelGGL(k_val_state, dim3(1), dim3(64), 0, (hipStream_t)stream, loss, state, patience, epoch);
+    LT_CHECK_LAUNCH();
+    return LT_OK;
+}
+
+// the device a pointer's memory lives on, -1 for anything that is not device memory
+static int ptr_device(const void *p) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return at.type == hipMemoryTypeDevice ? at.device : -1;
+}
+
+// Everything lt_gcn*_trainer_attach_validation checks and allocates.  Hp2 = 0: the 2-layer model.
+static int val_attach(const char *who, lt_val **slot, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
+                      const int32_t *labels2, int32_t keep_best, int32_t patience, const float *X, int F, int H1, int Hp1,
+                      int Hp2, int C, int64_t n_param, hipStream_t st) {
+    LT_REQUIRE(*slot == nullptr, "%s: validation is already attached to this trainer", who);
+    LT_REQUIRE(g2 != nullptr && X2 != nullptr && labels2 != nullptr, "%s: NULL argument", who);
+    LT_REQUIRE(g2->n > 0, "%s: empty graph", who);
+    LT_REQUIRE(n2 == g2->n, "%s: X2 has %d rows, the graph %d nodes", who, n2, g2->n);
+    LT_REQUIRE(ldx2 >= F, "%s: ldx2=%lld < F=%d", who, (long long)ldx2, F);
+    LT_REQUIRE(keep_best == 0 || keep_best == 1, "%s: keep_best=%d, must be 0 or 1", who, keep_best);
+    LT_REQUIRE(patience >= 0, "%s: patience=%d, must be >= 0 (0: never stop)", who, patience);
+    const int dev = ptr_device(X);
+    LT_REQUIRE(dev >= 0 && ptr_device(X2) == dev && ptr_device(g2->rowptr) == dev && ptr_device(labels2) == dev,
+               "%s: the validation graph, X2 and labels2 must live on the trainer's device (%d)", who, dev);
+    {
+        int32_t *host = new (std::nothrow) int32_t[(size_t)n2];
+        if (!host) return lt_set_error(LT_ERR_NOMEM, "%s: out of host memory", who);
+        hipError_t e = hipMemcpyAsync(host, labels2, (size_t)n2 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        int bad = -1;
+        if (e == hipSuccess)
+            for (int i = 0; i < n2 && bad < 0; ++i)
+                if (host[i] < 0 || host[i] >= C) bad = i;
+        const int bad_label = bad >= 0 ? host[bad] : 0;
+        delete[] host;
+        if (e != hipSuccess) return lt_set_error(LT_ERR_HIP, "%s: reading labels2 failed: %s", who, hipGetErrorString(e));
+        LT_REQUIRE(bad < 0, "%s: labels2[%d]=%d outside [0, %d)", who, bad, bad_label, C);
+    }
+    lt_val *v = new (std::nothrow) lt_val();
+    if (!v) return lt_set_error(LT_ERR_NOMEM, "%s: out of host memory", who);
+    v->g = g2; v->n = n2; v->X = X2; v->ldx = ldx2; v->labels = labels2;
+    v->keep_best = keep_best; v->patience = patience;
+    v->kslice = lt_gemm_pick_kslice(n2, H1, F);
+    v->n_blk = (n2 + TR_BLOCK - 1) / TR_BLOCK;
+    const size_t nh1 = (size_t)n2 * Hp1 * sizeof(float), nh2 = (size_t)n2 * Hp2 * sizeof(float);
+    const size_t nc = (size_t)n2 * C * sizeof(float);
+    const int hpm = Hp1 > Hp2 ? Hp1 : Hp2;
+#define V_HIP(call)                                                                         \
+    do {                                                                                    \
+        hipError_t e_ = (call);                                                             \
+        if (e_ != hipSuccess) {                                                             \
+            free_val(v);                                                                    \
+            return lt_set_error(LT_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
+        }                                                                                   \
+    } while (0)
+    V_HIP(hipMalloc((void **)&v->S1, nh1));
+    V_HIP(hipMemsetAsync(v->S1, 0, nh1, st));      // the GEMM writes H of the Hp columns
+    if (Hp2 == 0) {
+        V_HIP(hipMalloc((void **)&v->Z1, nh1));
+    } else {
+        V_HIP(hipMalloc((void **)&v->H1, nh1));
+        V_HIP(hipMalloc((void **)&v->S2, nh2));
+        V_HIP(hipMalloc((void **)&v->Z2, nh2));
+        V_HIP(hipMemsetAsync(v->S2, 0, nh2, st));
+    }
+    V_HIP(hipMalloc((void **)&v->Sc, nc));
+    V_HIP(hipMalloc((void **)&v->Z, nc));
+    const size_t sb = lt_gemm_splitk_slab_bytes(n2, H1, F, v->kslice);
+    if (sb) V_HIP(hipMalloc((void **)&v->slabs, sb));
+    if (g2->p_n_seg > 0) V_HIP(hipMalloc((void **)&v->seg_part, (size_t)g2->p_n_seg * hpm * sizeof(float)));
+    V_HIP(hipMalloc((void **)&v->part_loss, (size_t)v->n_blk * sizeof(float)));
+    V_HIP(hipMalloc((void **)&v->part_cnt, (size_t)v->n_blk * C * C * sizeof(int32_t)));
+    V_HIP(hipMalloc((void **)&v->state, VAL_STATE_WORDS * sizeof(int32_t)));
+    if (keep_best) V_HIP(hipMalloc((void **)&v->snap, (size_t)n_param * sizeof(float)));
+#undef V_HIP
+    hipLaunchKernelGGL(k_val_state_reset, dim3(1), dim3(64), 0, st, v->state);
+    {
+        hipError_t e_ = hipGetLastError();
+        if (e_ != hipSuccess) {
+            free_val(v);
+            return lt_set_error(LT_ERR_HIP, "%s: kernel launch failed: %s", who, hipGetErrorString(e_));
+        }
+    }
+    *slot = v;
+    return LT_OK;
+}
+
+// head, state and snapshot behind a validation forward; e = the epoch just trained (0-based, since creation)
+static int val_finish_epoch(lt_val *v, int C, const lt_snap_segs &T, int64_t e, float *val_loss, int32_t *val_counts,
+                            hipStream_t st) {
+    int rc = launch_val_head(v->Z, (long)C, v->labels, v->n, C, v->part_loss, v->part_cnt, val_loss, val_counts, v->state,
+                             v->patience, (int)e, st);
+    if (rc) return rc;
+    if (v->keep_best) return launch_snapshot(T, v->snap, v->state + VS_IMPROVED, 0, st);
+    return LT_OK;
+}
+
+static int val_read_state(const char *who, const lt_val *v, int32_t *state_host, hipStream_t st) {
+    LT_REQUIRE(v != nullptr, "%s: no validation attached", who);
+    LT_REQUIRE(state_host != nullptr, "%s: state is NULL", who);
+    LT_HIP(hipMemcpyAsync(state_host, v->state, VAL_STATE_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    LT_HIP(hipStreamSynchronize(st));
+    return LT_OK;
+}
+
+static int val_copy_logits(const char *who, const lt_val *v, int C, float *Z, int64_t ldz, hipStream_t st) {
+    LT_REQUIRE(v != nullptr, "%s: no validation attached", who);
+    LT_REQUIRE(Z != nullptr, "%s: Z is NULL", who);
+    LT_REQUIRE(ldz >= C, "%s: ldz=%lld < C=%d", who, (long long)ldz, C);
+    LT_HIP(hipMemcpy2DAsync(Z, (size_t)ldz * sizeof(float), v->Z, (size_t)C * sizeof(float), (size_t)C * sizeof(float),
+                            (size_t)v->n, hipMemcpyDeviceToDevice, st));
+    return LT_OK;
+}
+
+// ---- the 2-layer trainer ----
+static lt_snap_segs snap_segs2(const lt_gcn2_trainer *t) {
+    lt_snap_segs T;
+    const int64_t o1 = (int64_t)t->F * t->H, o2 = o1 + t->H, o3 = o2 + (int64_t)t->H * t->C;
+    float *ps[6] = {t->W1, t->b1, t->W2, t->b2, nullptr, nullptr};
+    const int64_t os[6] = {o1, o2, o3, t->n_param, t->n_param, t->n_param};
+    for (int k = 0; k < 6; ++k) { T.p[k] = ps[k]; T.o[k] = os[k]; }
+    return T;
+}
+
+// the forward of run_epoch on the validation graph, dropout off: lt_gcn2_forward's launches at n2 (its logits' bits)
+static int val_forward2(lt_gcn2_trainer *t, hipStream_t st) {
+    lt_val *v = t->val;
+    const int F = t->F, H = t->H, C = t->C, Hp = t->Hp;
+    int rc;
+    if (v->slabs)
+        rc = lt_launch_gemm_splitk(v->X, v->ldx, t->W1, H, v->S1, Hp, v->n, H, F, v->kslice, v->slabs, st);
+    else
+        rc = lt_launch_gemm(v->X, v->ldx, t->W1, H, v->S1, Hp, v->n, H, F, st);
+    if (rc) return rc;
+    rc = lt_launch_layer1(v->g, v->S1, Hp, t->b1p, t->W2p, C, lt_tiled_wanted(v->g, Hp) ? v->Z1 : nullptr, v->Sc, st,
+                          v->seg_part);
+    if (rc) return rc;
+    return lt_launch_layer2(v->g, v->Sc, C, t->b2, v->Z, st);
+}
+
+extern "C" int lt_gcn2_trainer_attach_validation(lt_gcn2_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2,
+                                                 int32_t n2, const int32_t *labels2, int32_t keep_best, int32_t patience,
+                                                 void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_attach_validation: trainer is NULL");
+    return val_attach("lt_gcn2_trainer_attach_validation", &t->val, g2, X2, ldx2, n2, labels2, keep_best, patience, t->X, t->F,
+                      t->H, t->Hp, 0, t->C, t->n_param, (hipStream_t)stream);
+}
+
+extern "C" int lt_gcn2_trainer_run_validated(lt_gcn2_trainer *t, int32_t n_epochs, float *record, float *val_loss,
+                                             int32_t *val_counts, void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_run_validated: trainer is NULL");
+    LT_REQUIRE(t->val != nullptr, "lt_gcn2_trainer_run_validated: no validation attached");
+    LT_REQUIRE(n_epochs >= 0, "lt_gcn2_trainer_run_validated: n_epochs=%d", n_epochs);
+    if (n_epochs == 0) return LT_OK;
+    LT_REQUIRE(record && val_loss && val_counts, "lt_gcn2_trainer_run_validated: NULL output");
+    LT_REQUIRE(t->epoch + n_epochs <= (int64_t)INT32_MAX, "lt_gcn2_trainer_run_validated: epoch counter would pass 2^31");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_tr_pad, dim3((t->Hp * (t->C + 1) + 255) / 256), dim3(256), 0, st, t->b1, t->W2, t->H, t->Hp, t->C,
+                       t->b1p, t->W2p);
+    LT_CHECK_LAUNCH();
+    const lt_snap_segs T = snap_segs2(t);
+    const size_t cc = (size_t)t->C * t->C;
+    for (int32_t j = 0; j < n_epochs; ++j) {
+        const int64_t e = t->epoch;
+        int rc = run_epoch(t, record + 2 * (size_t)j, st);
+        if (rc) return rc;
+        rc = val_forward2(t, st);
+        if (rc) return rc;
+        rc = val_finish_epoch(t->val, t->C, T, e, val_loss + j, val_counts + cc * (size_t)j, st);
+        if (rc) return rc;
+    }
+    return LT_OK;
+}
+
+extern "C" int lt_gcn2_trainer_val_state(const lt_gcn2_trainer *t, int32_t *state, void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_val_state: trainer is NULL");
+    return val_read_state("lt_gcn2_trainer_val_state", t->val, state, (hipStream_t)stream);
+}
+
+extern "C" int lt_gcn2_trainer_restore_best(lt_gcn2_trainer *t, void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_restore_best: trainer is NULL");
+    LT_REQUIRE(t->val != nullptr && t->val->keep_best, "lt_gcn2_trainer_restore_best: no validation with keep_best attached");
+    return launch_snapshot(snap_segs2(t), t->val->snap, t->val->state + VS_SEEN, 1, (hipStream_t)stream);
+}
+
+extern "C" int lt_gcn2_trainer_val_logits(const lt_gcn2_trainer *t, float *Z, int64_t ldz, void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_val_logits: trainer is NULL");
+    return val_copy_logits("lt_gcn2_trainer_val_logits", t->val, t->C, Z, ldz, (hipStream_t)stream);
+}
+
+// ---- the 3-layer trainer ----
+static lt_snap_segs snap_segs3(const lt_gcn3_trainer *t) {
+    lt_snap_segs T;
+    for (int k = 0; k < 6; ++k) { T.p[k] = t->P[k]; T.o[k] = t->off[k]; }
+    return T;
+}
+
+// the forward of run_epoch3 on the validation graph, dropout off (k_tr_dropout with no mask only repeats layer 1's S3 bits,
+// so it is not launched)
+static int val_forward3(lt_gcn3_trainer *t, hipStream_t st) {
+    lt_val *v = t->val;
+    const lt_graph *g = v->g;
+    const int n = v->n, F = t->F, H1 = t->H1, H2 = t->H2, C = t->C, Hp1 = t->Hp1, Hp2 = t->Hp2;
+    const int lpr1 = lt_lpr_for(Hp1);
+    const int rpb1 = (TR_BLOCK / 64) * (64 / lpr1);
+    int rc;
+    if (v->slabs)
+        rc = lt_launch_gemm_splitk(v->X, v->ldx, t->P[0], H1, v->S1, Hp1, n, H1, F, v->kslice, v->slabs, st);
+    else
+        rc = lt_launch_gemm(v->X, v->ldx, t->P[0], H1, v->S1, Hp1, n, H1, F, st);
+    if (rc) return rc;
+    lt_drop_args d;
+    d.on = 0; d.thresh = 0; d.scale = 1.f; d.epoch = 0; d.seed = 0; d.layer = 0;
+    const int have_long = g->p_n_long > 0 ? 1 : 0;
+    const unsigned seg_blocks = have_long ? rows_grid(g->p_n_seg, rpb1) : 0u;
+    LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k_tr3_layer1<LPR_>), dim3(rows_grid(n, rpb1) + seg_blocks), dim3(TR_BLOCK), 0, st,
+                                             n, g->rowptr, g->col, g->val, v->S1, Hp1, H1, t->b1p, d, v->H1, have_long,
+                                             (int)seg_blocks, g->p_n_seg, g->p_seg_long, g->p_seg_begin, g->p_long_row,
+                                             v->seg_part));
+    LT_CHECK_LAUNCH();
+    if (have_long) {
+        LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k_tr3_layer1_long<LPR_>), dim3(rows_grid(g->p_n_long, rpb1)), dim3(TR_BLOCK),
+                                                 0, st, g->p_n_long, g->p_long_row, g->p_long_segptr, v->seg_part, Hp1, H1, d,
+                                                 v->H1));
+        LT_CHECK_LAUNCH();
+    }
+    rc = lt_launch_gemm(v->H1, Hp1, t->P[2], H2, v->S2, Hp2, n, H2, H1, st);
+    if (rc) return rc;
+    rc = lt_launch_layer1(g, v->S2, Hp2, t->b2p, t->W3p, C, v->Z2, v->Sc, st, v->seg_part);
+    if (rc) return rc;
+    return lt_launch_layer2(g, v->Sc, C, t->P[5], v->Z, st);
+}
+
+extern "C" int lt_gcn3_trainer_attach_validation(lt_gcn3_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2,
+                                                 int32_t n2, const int32_t *labels2, int32_t keep_best, int32_t patience,
+                                                 void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_attach_validation: trainer is NULL");
+    return val_attach("lt_gcn3_trainer_attach_validation", &t->val, g2, X2, ldx2, n2, labels2, keep_best, patience, t->X, t->F,
+                      t->H1, t->Hp1, t->Hp2, t->C, t->off[5], (hipStream_t)stream);
+}
+
+extern "C" int lt_gcn3_trainer_run_validated(lt_gcn3_trainer *t, int32_t n_epochs, float *record, float *val_loss,
+                                             int32_t *val_counts, void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_run_validated: trainer is NULL");
+    LT_REQUIRE(t->val != nullptr, "lt_gcn3_trainer_run_validated: no validation attached");
+    LT_REQUIRE(n_epochs >= 0, "lt_gcn3_trainer_run_validated: n_epochs=%d", n_epochs);
+    if (n_epochs == 0) return LT_OK;
+    LT_REQUIRE(record && val_loss && val_counts, "lt_gcn3_trainer_run_validated: NULL output");
+    LT_REQUIRE(t->epoch + n_epochs <= (int64_t)INT32_MAX, "lt_gcn3_trainer_run_validated: epoch counter would pass 2^31");
+    hipStream_t st = (hipStream_t)stream;
+    const int mx = t->Hp1 > t->Hp2 * t->C ? t->Hp1 : t->Hp2 * t->C;
+    hipLaunchKernelGGL(k_tr3_pad, dim3((mx + 255) / 256), dim3(256), 0, st, t->P[1], t->H1, t->Hp1, t->P[3], t->H2, t->Hp2,
+                       t->P[4], t->C, t->b1p, t->b2p, t->W3p);
+    LT_CHECK_LAUNCH();
+    const lt_snap_segs T = snap_segs3(t);
+    const size_t cc = (size_t)t->C * t->C;
+    for (int32_t j = 0; j < n_epochs; ++j) {
+        const int64_t e = t->epoch;
+        int rc = run_epoch3(t, record + 2 * (size_t)j, st);
+        if (rc) return rc;
+        rc = val_forward3(t, st);
+        if (rc) return rc;
+        rc = val_finish_epoch(t->val, t->C, T, e, val_loss + j, val_counts + cc * (size_t)j, st);
+        if (rc) return rc;
+    }
+    return LT_OK;
+}
+
+extern "C" int lt_gcn3_trainer_val_state(const lt_gcn3_trainer *t, int32_t *state, void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_val_state: trainer is NULL");
+    return val_read_state("lt_gcn3_trainer_val_state", t->val, state, (hipStream_t)stream);
+}
+
+extern "C" int lt_gcn3_trainer_restore_best(lt_gcn3_trainer *t, void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_restore_best: trainer is NULL");
+    LT_REQUIRE(t->val != nullptr && t->val->keep_best, "lt_gcn3_trainer_restore_best: no validation with keep_best attached");
+    return launch_snapshot(snap_segs3(t), t->val->snap, t->val->state + VS_SEEN, 1, (hipStream_t)stream);
+}
+
+extern "C" int lt_gcn3_trainer_val_logits(const lt_gcn3_trainer *t, float *Z, int64_t ldz, void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_val_logits: trainer is NULL");
+    return val_copy_logits("lt_gcn3_trainer_val_logits", t->val, t->C, Z, ldz, (hipStream_t)stream);
 }

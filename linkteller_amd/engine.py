@@ -631,13 +631,179 @@ class WideBaseline:
         return out
 
 
-class GCN2Trainer:
+class _ValidationMixin:
+    """Per-epoch validation of a GPU trainer (lt_gcn*_trainer_attach_validation / _run_validated / _val_state / _restore_best /
+    _val_logits): after every optimiser step the held-out graph is forwarded with dropout off, the evaluation head leaves the
+    mean loss and the C x C confusion counts, the early-stopping state (EarlyStopping with delta = 0, kept in device memory)
+    takes the loss, and with ``keep_best`` a predicated launch copies the parameters when the epoch improved -- all enqueued
+    behind the epoch, no host round trip.  ``_PREFIX`` names the C entry points."""
+
+    _PREFIX = ""
+    _val = None
+
+    def _call(self, name, *args):
+        fn = f"{self._PREFIX}_{name}"
+        _lib.check(getattr(_lib.lib(), fn)(self._h, *args), fn)
+
+    def attach_validation(self, adj2, x2, labels2, keep_best=False, patience=0):
+        """Attach the held-out graph (reference: ``features_2``, ``adj_2``, ``labels_2``); once per trainer.  ``keep_best``: keep a
+        snapshot of the parameters of the best validation loss (``restore_best``).  ``patience`` > 0: stop ``run_validated``
+        after that many epochs without improvement; 0: never stop."""
+        if self._val is not None:
+            raise ValueError("validation is already attached to this trainer")
+        if int(patience) < 0:
+            raise ValueError(f"patience must be >= 0, got {patience}")
+        g2: HipGraph = as_hip_graph(adj2)
+        x2 = _f32(x2, "x2")
+        if x2.dim() != 2 or x2.shape[1] != self.f:
+            raise ValueError(f"x2 must be [n2, {self.f}], got {tuple(x2.shape)}")
+        if x2.shape[0] != g2.n:
+            raise ValueError(f"x2 has {x2.shape[0]} rows, the validation graph {g2.n} nodes")
+        if g2.device_index != self.x.device.index or x2.device != self.x.device:
+            raise ValueError(f"the trainer lives on {self.x.device}: the validation graph is on cuda:{g2.device_index}, "
+                             f"x2 on {x2.device}")
+        _require_finite(features_2=x2)
+        if not isinstance(labels2, torch.Tensor):
+            labels2 = torch.as_tensor(labels2)
+        labels2 = labels2.reshape(-1)
+        if labels2.numel() != g2.n:
+            raise ValueError(f"labels2: {labels2.numel()} entries for {g2.n} nodes")
+        if labels2.numel() and (int(labels2.min()) < 0 or int(labels2.max()) >= self.c):
+            raise ValueError(f"labels2 outside [0, {self.c})")
+        labels2 = labels2.to(device=self.x.device, dtype=torch.int32).contiguous()
+        self._call("attach_validation", g2.handle, x2.data_ptr(), x2.shape[1], x2.shape[0], labels2.data_ptr(),
+                   int(bool(keep_best)), int(patience), _stream())
+        self._val = (g2, x2, labels2)       # borrowed by the library: kept alive here
+        self.n2, self.keep_best, self.patience = g2.n, bool(keep_best), int(patience)
+
+    def _require_val(self):
+        if self._val is None:
+            raise ValueError("no validation attached: call attach_validation() first")
+
+    def run_validated_async(self, epochs: int):
+        """Enqueue ``epochs`` validated epochs without syncing; returns the device tensors (record [epochs, 2], val_loss
+        [epochs], val_counts [epochs, C, C])."""
+        self._require_val()
+        k, dev = max(int(epochs), 0), self.x.device
+        record = torch.empty((k, 2), dtype=torch.float32, device=dev)
+        val_loss = torch.empty((k,), dtype=torch.float32, device=dev)
+        val_counts = torch.empty((k, self.c, self.c), dtype=torch.int32, device=dev)
+        self._call("run_validated", int(epochs), record.data_ptr(), val_loss.data_ptr(), val_counts.data_ptr(), _stream())
+        for p in self.params:
+            torch.autograd.graph.increment_version(p)
+        return record, val_loss, val_counts
+
+    def run_validated(self, epochs: int, chunk=None) -> dict:
+        """Run up to ``epochs`` validated epochs.  Returns a dict of CPU arrays ``loss``, ``correct`` (the train record),
+        ``val_loss`` [k] float32 and ``val_counts`` [k, C, C] int32 (row = true class, column = predicted; the trace is the
+        correct count), and the ints ``best_epoch`` and ``stop_epoch`` (0-based, counted since the trainer was created;
+        ``stop_epoch`` is -1 when the run did not stop).  With ``patience`` > 0 the epochs are enqueued ``chunk`` at a time
+        (default: the patience, the fewest epochs after which a stop is possible) and the 32-byte state is read after each
+        chunk; the run ends at a stop and the arrays are cut behind the stop epoch.  Epochs of a chunk behind the stop have
+        run (they moved the live parameters) but neither state nor snapshot: the result does not depend on ``chunk``."""
+        self._require_val()
+        epochs = max(int(epochs), 0)
+        if self.patience > 0:
+            chunk = self.patience if chunk is None else int(chunk)
+            if chunk <= 0:
+                raise ValueError(f"chunk must be positive, got {chunk}")
+        else:
+            chunk = max(epochs, 1)
+        first, parts, done = self.epoch, [], 0
+        state = self.val_state()
+        while done < epochs and state["stop_epoch"] < 0:
+            k = min(chunk, epochs - done)
+            parts.append(self.run_validated_async(k))
+            done += k
+            state = self.val_state()
+        keep = done if state["stop_epoch"] < 0 else min(done, state["stop_epoch"] + 1 - first)
+        cat = (lambda i, shape, dt: torch.cat([p[i] for p in parts])[:keep].cpu().numpy() if parts
+               else torch.empty(shape, dtype=dt).numpy())
+        rec = cat(0, (0, 2), torch.float32)
+        return {"loss": rec[:, 0].copy(), "correct": rec[:, 1].astype("int64"), "val_loss": cat(1, (0,), torch.float32),
+                "val_counts": cat(2, (0, self.c, self.c), torch.int32), "best_epoch": state["best_epoch"],
+                "stop_epoch": state["stop_epoch"]}
+
+    def val_state(self) -> dict:
+        """The early-stopping state (synchronises): ``best_loss`` (float; ``best_loss_bits`` its fp32 bits), ``best_epoch``,
+        ``counter``, ``stop_epoch`` (-1 while running), ``improved``, ``seen``."""
+        self._require_val()
+        words = (C.c_int32 * 8)()
+        self._call("val_state", words, _stream())
+        w = [int(v) for v in words]
+        import struct
+        return {"best_loss": struct.unpack("<f", struct.pack("<i", w[0]))[0], "best_loss_bits": w[0] & 0xffffffff,
+                "best_epoch": w[1], "counter": w[2], "stop_epoch": w[3], "improved": w[4], "seen": w[5]}
+
+    def restore_best(self):
+        """Copy the snapshot of the best epoch into the live parameters (needs ``keep_best``)."""
+        self._require_val()
+        if not self.keep_best:
+            raise ValueError("restore_best() needs attach_validation(..., keep_best=True)")
+        self._call("restore_best", _stream())
+        for p in self.params:
+            torch.autograd.graph.increment_version(p)
+
+    def val_logits(self) -> torch.Tensor:
+        """The last validated epoch's logits on the held-out graph [n2, C] (eval mode, after that epoch's update)."""
+        self._require_val()
+        out = torch.empty((self.n2, self.c), dtype=torch.float32, device=self.x.device)
+        self._call("val_logits", out.data_ptr(), self.c, _stream())
+        return out
+
+
+def eval_head(logits: torch.Tensor, labels: torch.Tensor):
+    """Mean cross-entropy (device float32 scalar tensor) and confusion matrix (int32 [C, C], row = true class, column = first
+    argmax) of ``logits`` [n, C] -- a strided view with unit column stride is read in place -- against ``labels``
+    (lt_eval_head).  Enqueue-only."""
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2):
+        raise ValueError("logits must be a 2-d float32 device tensor")
+    n, c = logits.shape
+    if n and (logits.stride(1) != 1 or logits.stride(0) < c):
+        logits = logits.contiguous()
+    labels = labels.reshape(-1).to(device=logits.device, dtype=torch.int32).contiguous()
+    if labels.numel() != n:
+        raise ValueError(f"labels: {labels.numel()} entries for {n} rows")
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    conf = torch.empty((c, c), dtype=torch.int32, device=logits.device)
+    ws = _workspace(_lib.lib().lt_eval_head_workspace_bytes(n, c), logits.device)
+    _lib.check(_lib.lib().lt_eval_head(logits.data_ptr(), logits.stride(0) if n else c, labels.data_ptr(), n, c, loss.data_ptr(),
+                                       conf.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "lt_eval_head")
+    return loss, conf
+
+
+class EarlyStopState:
+    """The early-stopping state block on its own (lt_early_stop_reset / lt_early_stop_update): 8 int32 words of device memory."""
+
+    def __init__(self, patience: int, device="cuda"):
+        if int(patience) < 0:
+            raise ValueError(f"patience must be >= 0, got {patience}")
+        self.patience = int(patience)
+        self.words = torch.empty(8, dtype=torch.int32, device=device)
+        _lib.check(_lib.lib().lt_early_stop_reset(self.words.data_ptr(), _stream()), "lt_early_stop_reset")
+
+    def update(self, loss: torch.Tensor, epoch: int):
+        """Apply one epoch's loss (a float32 device tensor of one element); enqueue-only."""
+        if not (loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1):
+            raise ValueError("loss must be a float32 device tensor of one element")
+        _lib.check(_lib.lib().lt_early_stop_update(loss.data_ptr(), self.patience, int(epoch), self.words.data_ptr(), _stream()),
+                   "lt_early_stop_update")
+
+    def read(self):
+        """The 8 words as a CPU int32 array (synchronises)."""
+        return self.words.cpu().numpy()
+
+
+class GCN2Trainer(_ValidationMixin):
     """Training of the 2-layer GCN on the GPU (lt_gcn2_trainer_*): one epoch is the reference's ``train_one_epoch`` on a
     transfer dataset (gcn_trainer.py:144-170) -- forward with dropout, mean cross-entropy, backward, ``optim.Adam`` with
     weight decay -- as ~15 stream-ordered launches on torch's current stream and no host synchronisation.  ``w1, b1, w2, b2``
     are updated IN PLACE (their version counters are bumped after every ``run``); the trainer owns the Adam moments.
     Dropout is a Philox4x32-10 mask keyed by ``seed`` and the epoch counter (include/linkteller_hip.h), so it can be
-    rebuilt exactly; it is not torch's generator.  Limits: hidden width <= 256, classes <= 8."""
+    rebuilt exactly; it is not torch's generator.  Limits: hidden width <= 256, classes <= 8.  Validation every epoch,
+    best-model snapshot and early stopping: ``attach_validation`` / ``run_validated`` (_ValidationMixin)."""
+
+    _PREFIX = "lt_gcn2_trainer"
 
     def __init__(self, adj, x, labels, w1, b1, w2, b2, *, lr, weight_decay, dropout, seed):
         if not 0.0 <= float(dropout) <= 1.0:      # F.dropout's message
@@ -707,12 +873,14 @@ class GCN2Trainer:
         return out
 
 
-class GCN3Trainer:
+class GCN3Trainer(_ValidationMixin):
     """Training of the 3-layer GCN3 on the GPU (lt_gcn3_trainer_*): the epoch of ``GCN2Trainer`` one layer up -- two hidden
     layers with independent Philox masks (the counter's layer word), the backward through the middle layer on the matrix
     cores, one Adam launch over the six tensors -- as stream-ordered launches on torch's current stream and no host
     synchronisation.  ``w1 .. b3`` are updated IN PLACE (version counters bumped after every ``run``).  Limits: hidden
-    widths <= 256, classes <= 8."""
+    widths <= 256, classes <= 8.  Validation as for ``GCN2Trainer`` (_ValidationMixin)."""
+
+    _PREFIX = "lt_gcn3_trainer"
 
     def __init__(self, adj, x, labels, w1, b1, w2, b2, w3, b3, *, lr, weight_decay, dropout, seed):
         if not 0.0 <= float(dropout) <= 1.0:      # F.dropout's message

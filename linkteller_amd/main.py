@@ -11,7 +11,10 @@ Every flag of the reference is accepted with its default.  ``--test`` runs infer
     python -m linkteller_amd.main --train --mode vanilla --eps 5 --dataset twitch/ES/RU --hidden 256 \
         --norm FirstOrderGCN --attack --sample-type unbalanced --n-test 500
 
-Without either switch the run is refused (a default run does not start a 500-epoch job by itself).
+Without either switch the run is refused (a default run does not start a 500-epoch job by itself).  With ``--train``,
+``--validate log | best | early`` (an addition, default ``off``) validates on the held-out graph after every epoch on the GPU:
+``loss_val`` / ``acc_val`` in the log, the model of the best validation loss saved, and a stop after ``--patience`` epochs
+without improvement.
 """
 from __future__ import annotations
 
@@ -66,6 +69,19 @@ _OPTIONS = {
     # fp32 torch arithmetic on the CPU; 'device' forms the correlations on the GPU in fp64 (lt_corr_square / lt_corr_pairs), writes
     # the same result file, and lets --metrics-only and --recover serve the baseline attacks
     "baseline-scores": (str, "host", ["host", "device"]),
+    # addition: with --train, validate on the held-out graph (features_2, adj_2, labels_2) after every epoch, on the GPU
+    # (gcn_trainer.py:167-174).  'log': loss_val / acc_val in every epoch's log tuple; 'best': as log, and the model of the best
+    # validation loss is restored and saved; 'early': as best, and the run stops after --patience epochs without improvement
+    # (utils/early_stopping.py, 'early stop at epoch {e}').  'off' (default): every record, log line and bit as without it
+    "validate": (str, "off", ["off", "log", "best", "early"]),
+}
+_HELP = {
+    "validate": "with --train: validate on the held-out graph after every epoch on the GPU.  log: loss_val / acc_val in the log; "
+                "best: also restore and save the model of the best validation loss; early: also stop after --patience epochs "
+                "without improvement.  Default off.",
+    "patience": "epochs without improvement before --validate early stops (default 10)",
+    "early": "accepted and inert, as in the reference on transfer datasets (it never reaches EarlyStopping there); making it "
+             "live would change existing runs.  Early stopping is --validate early.",
 }
 _SWITCHES = ["no-cuda", "fastmode", "approx", "attack", "test", "break-down", "display", "same-size",
              "eval-degree", "trainable", "early", "fnormalize",
@@ -85,9 +101,11 @@ def build_parser():
         kw = dict(type=spec[0], default=spec[1])
         if len(spec) > 2:
             kw["choices"] = spec[2]
+        if name in _HELP:
+            kw["help"] = _HELP[name]
         p.add_argument(f"--{name}", **kw)
     for name in _SWITCHES:
-        p.add_argument(f"--{name}", action="store_true", default=False)
+        p.add_argument(f"--{name}", action="store_true", default=False, **({"help": _HELP[name]} if name in _HELP else {}))
     p.set_defaults(assign_seed=42)
     return p
 
@@ -191,8 +209,22 @@ def check_sample_build(args):
                                   "its nodes are drawn from numpy's stream)")
 
 
+def check_validate(args):
+    """``--validate log / best / early`` validates the epochs of ``--train``: anything but ``off`` is refused here, before a
+    Worker is built or the GPU is touched, unless the run trains (``--train`` without ``--test``); ``early`` needs a
+    ``--patience`` of at least 1."""
+    mode = getattr(args, "validate", "off")
+    if mode == "off":
+        return
+    if not args.train or args.test:
+        raise NotImplementedError(f"--validate {mode} needs --train without --test (it validates the epochs of a training run)")
+    if mode == "early" and args.patience < 1:
+        raise ValueError(f"--validate early needs --patience >= 1 (got {args.patience})")
+
+
 def main(argv=None):
     args = get_arguments(argv)
+    check_validate(args)
     check_baseline_scores(args)
     check_recover(args)
     check_metrics_only(args)

@@ -71,20 +71,55 @@ class GCNTrainer:
         t_total = time.time()
         self.model.train()
         n_epochs = int(a.num_epochs)
-        loss, correct = self.gpu_trainer.run(n_epochs)
-        per_epoch = (time.time() - t_total) / max(n_epochs, 1)
-        n = self.gpu_trainer.n
-        for epoch in range(n_epochs):
-            logging.info("[epoch {}]".format(epoch))
-            output_info = "Epoch: {:04d}".format(epoch + 1), \
-                "loss_train: {:.4f}".format(float(loss[epoch])), \
-                "acc_train: {:.4f}".format(int(correct[epoch]) / n), \
-                "time: {:.4f}s".format(per_epoch)
-            logging.info(output_info)
+        validate = getattr(a, "validate", "off")
+        if validate != "off":
+            self._train_validated(n_epochs, validate, t_total)
+        else:
+            loss, correct = self.gpu_trainer.run(n_epochs)
+            per_epoch = (time.time() - t_total) / max(n_epochs, 1)
+            n = self.gpu_trainer.n
+            for epoch in range(n_epochs):
+                logging.info("[epoch {}]".format(epoch))
+                output_info = "Epoch: {:04d}".format(epoch + 1), \
+                    "loss_train: {:.4f}".format(float(loss[epoch])), \
+                    "acc_train: {:.4f}".format(int(correct[epoch]) / n), \
+                    "time: {:.4f}s".format(per_epoch)
+                logging.info(output_info)
         self.model.eval()
         torch.save(self.model.state_dict(), os.path.join(self.model_path, "model.pt"))
         print("Optimization Finished!")
         print("Total time elapsed: {:.4f}s".format(time.time() - t_total))
+
+    def _train_validated(self, n_epochs, validate, t_total):
+        """``--validate log / best / early`` (an addition; the reference validates a transfer dataset every epoch,
+        gcn_trainer.py:167-174, and selects a model only on the other datasets, :195-196, :235-238): every epoch is followed
+        on the device by the forward of (features_2, adj_2), the evaluation head and the early-stopping state.  The log
+        tuple gains ``loss_val`` / ``acc_val`` as the reference's non-transfer line has them (gcn_trainer.py:198-203);
+        ``best`` and ``early`` restore the parameters of the best validation loss before ``model.pt`` is written."""
+        w, tr = self.worker, self.gpu_trainer
+        keep = validate in ("best", "early")
+        tr.attach_validation(w.adj_2, w.features_2, w.labels_2, keep_best=keep,
+                             patience=int(self.args.patience) if validate == "early" else 0)
+        r = tr.run_validated(n_epochs)
+        done = len(r["loss"])
+        per_epoch = (time.time() - t_total) / max(done, 1)
+        n, n2 = tr.n, tr.n2
+        for epoch in range(done):
+            logging.info("[epoch {}]".format(epoch))
+            output_info = "Epoch: {:04d}".format(epoch + 1), \
+                "loss_train: {:.4f}".format(float(r["loss"][epoch])), \
+                "acc_train: {:.4f}".format(int(r["correct"][epoch]) / n), \
+                "loss_val: {:.4f}".format(float(r["val_loss"][epoch])), \
+                "acc_val: {:.4f}".format(int(r["val_counts"][epoch].trace()) / n2), \
+                "time: {:.4f}s".format(per_epoch)
+            logging.info(output_info)
+        if validate == "early" and r["stop_epoch"] >= 0:
+            logging.info(f"early stop at epoch {r['stop_epoch']}")
+        if keep and done:
+            tr.restore_best()
+            info = f"best validation loss {float(r['val_loss'][r['best_epoch']]):.4f} at epoch {r['best_epoch']}: that model is saved"
+            print(info)
+            logging.info(info)
 
     def forward(self, mode="train"):
         w = self.worker
