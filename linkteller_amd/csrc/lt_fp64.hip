@@ -1226,8 +1226,13 @@ static int quant_rows(lt_baseline *b, const double *S, hipStream_t st) {
 #include "lt_i8_split.hip.h"
 // "i8_split": the product on the int8 matrix cores as an error-free split (lt_i8_split.hip.h: X as five, W1 as four signed base-256
 // digits, the fourteen digit pairs of order >= 3, exact integer sums per order, one rounding per K slice) when the baseline holds
-// the digit buffers (shapes lt_i8_shapes_ok) -- rows within 5e-10 of the row's largest value of the fp64 product, the error of the
-// 32-bit fixed-point rows they are stored as
+// the digit buffers (shapes lt_i8_shapes_ok).  The error is bounded per TERM, not against the row: a K slice of K_s columns adds at
+// most K_s 2^(ex + ew) (2^-31 + 2^-36.4 + 2^-39) -- W1 cut to 31 bits, the six digit pairs dropped, X cut to 39 bits; 2^ex and 2^ew
+// bound the slice's largest |x| of the row and |w| of the column -- plus one fp64 rounding (tests/test_i8_split_cpu.py: the bound and
+// inputs that reach 0.97 of it).  That is no fraction of the row's largest value: gaussian features measure 1e-10 .. 2e-10 of it
+// (F = 300 .. 1000), below the 4.7e-10 step of the 32-bit fixed-point rows the product is stored as; with 60-sigma outliers, which
+// set a slice's scale for the whole row, 3.6e-10 .. 5.4e-10; the rows tests/i8_split_restate.py plants at the edges of the fixed
+// point lie well beyond it (1.7e-7 for a row of 1e-30, whose exponent is clamped at -96)
 static bool i8_route(const lt_baseline *b) {
     return lt_tune().i8_split != 0 && b->i8_wd != nullptr && b->i8_ew != nullptr && lt_i8_shapes_ok(b->n, b->H, b->F);
 }

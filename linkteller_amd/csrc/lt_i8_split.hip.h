@@ -5,10 +5,11 @@
 // profiles/r05_i8_split_lab.txt, NOTES.md (rounds 5 and 6).
 //
 //   * per (row, K slice) of X and per (column, K slice) of W1 one power-of-two scale; X becomes a 39-bit fixed-point integer
-//     (FIVE signed base-256 digits: an fp32 within 2^-15 of its row's largest value is represented exactly), W1 a 31-bit one (four);
+//     (FIVE signed base-256 digits: an fp32 whose exponent is at most 14 below that of its row's largest value is represented exactly),
+//     W1 a 31-bit one (four);
 //   * q_x * q_w = sum_{i,j} dx_i dw_j 256^(i+j): the FOURTEEN digit pairs of order i + j >= 3 go through the matrix cores, one int32
-//     accumulator per ORDER (products <= 2^14, K < 2^15 deep, <= 4 pairs: below 2^31, so the integer sums are EXACT); the orders
-//     below carry < 2^-38 of a term of full scale;
+//     accumulator per ORDER (products <= 2^14, K < 2^15 deep, <= 4 pairs: below 2^31, so the integer sums are EXACT); the six pairs
+//     of the orders below carry at most 197121 * 2^-54 = 2^-36.4 of a term of full scale (2^ex 2^ew), next to the 2^-31 of W1's cut;
 //   * the accumulators of an element combine exactly in int64, convert to fp64 with one rounding and are scaled by the power of
 //     two: one fp64 partial per K slice (split-K slabs as lt_fp64.hip sums them).  Integer sums do not depend on their order: a
 //     row has the same bits whichever tile, wave or rank formed it.
@@ -27,7 +28,7 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 #define I8_BM 64
 #define I8_BN 128
 #define I8_KS 32            // K columns per step (one MFMA deep)
-#define I8_XD 5             // digits of X (39-bit fixed point: an fp32 within 2^-15 of its row's largest value is EXACT)
+#define I8_XD 5             // digits of X (39-bit fixed point: an fp32 whose exponent is at most 14 below the row's largest is EXACT)
 #define I8_WD 4             // digits of W1 (31-bit fixed point)
 #define I8_A_BYTES (I8_XD * I8_BM * I8_KS)
 #define I8_B_BYTES (I8_WD * I8_BN * I8_KS)
