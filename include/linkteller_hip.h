@@ -43,7 +43,9 @@ extern "C" {
                             lt_sample_balanced_philox); no entry point changed.
                             Additive within 5: the baseline attacks' scores (lt_corr_square, lt_corr_pairs); no entry point changed.
                             Additive within 5: validation every epoch (lt_eval_head, lt_early_stop_*, lt_gcn*_trainer_attach_validation /
-                            _run_validated / _val_state / _restore_best / _val_logits); no entry point changed */
+                            _run_validated / _val_state / _restore_best / _val_logits); no entry point changed.
+                            Additive within 5: evaluation over a row list (lt_eval_head_rows, lt_eval_head_rows_workspace_bytes,
+                            lt_gcn*_trainer_attach_validation_rows); no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -921,7 +923,24 @@ int lt_adam_step(int64_t n, float *p, const float *g, float *m, float *v, int64_
  * lt_gcn*_trainer_val_state copies the 8 state words to `state` (host) and synchronises the stream.
  * lt_gcn*_trainer_restore_best (keep_best only, else LT_ERR_INVALID) enqueues the copy of the snapshot into the live
  * parameters (nothing happens before the first validated epoch); the padded copies follow at the next run, as always.
- * lt_gcn*_trainer_val_logits: test accessor, the last validation logits [n2, C] written with leading dimension ldz >= C. */
+ * lt_gcn*_trainer_val_logits: test accessor, the last validation logits [n2, C] written with leading dimension ldz >= C.
+ *
+ * Row lists (datasets with one graph and a split of its nodes: reference gcn_trainer.py:183-196, 354-383; DESIGN.md section
+ * 10.3).  Additive within ABI 5.
+ * lt_eval_head_rows: lt_eval_head over a list.  rows (int32 [m], device) holds node ids in any order, repeats allowed, each
+ * occurrence counting; list entry i scores logits row rows[i] against labels[rows[i]] with lt_eval_head's per-row arithmetic
+ * (the same operations in the same order, first argmax).  Entry i belongs to block i / 256; block tree and finish stage are
+ * lt_eval_head's, in two launches (and one 4-byte memset when n_bad is given).  loss = the sum / m; confusion covers the listed
+ * entries only.  An id outside [0, n) is never dereferenced: it contributes nothing, the divisor stays m, and it is counted in
+ * *n_bad (int32, device; may be NULL).  With rows = 0 .. n - 1 the outputs are lt_eval_head's bits.  Enqueue-only, no float
+ * atomics, a pure function of the inputs.  LT_ERR_INVALID before any launch: m <= 0, n <= 0, C outside [1, 8], ldz < C, a NULL
+ * pointer other than n_bad; LT_ERR_WORKSPACE: workspace (device, 4-byte aligned) smaller than
+ * lt_eval_head_rows_workspace_bytes(m, C) (0 for unsupported m / C).
+ * lt_gcn*_trainer_attach_validation_rows is lt_gcn*_trainer_attach_validation plus the list: rows (int32 [m], device, the
+ * trainer's device) is borrowed, read back once and checked on the host -- m <= 0, a NULL list or an id outside [0, n2) is
+ * LT_ERR_INVALID (the message names the first offender), with nothing allocated.  lt_gcn*_trainer_run_validated then applies
+ * the head to the list: val_loss, val_counts, the early-stopping state and the snapshot follow the listed rows; everything
+ * else in its contract is unchanged.  lt_eval_head and lt_gcn*_trainer_attach_validation keep every bit and every launch. */
 size_t lt_eval_head_workspace_bytes(int32_t n, int32_t C);
 int lt_eval_head(const float *Z, int64_t ldz, const int32_t *labels, int32_t n, int32_t C, float *loss, int32_t *confusion,
                  void *workspace, size_t workspace_bytes, void *stream);
@@ -942,6 +961,15 @@ int lt_gcn3_trainer_run_validated(lt_gcn3_trainer *t, int32_t n_epochs, float *r
 int lt_gcn3_trainer_val_state(const lt_gcn3_trainer *t, int32_t *state, void *stream);
 int lt_gcn3_trainer_restore_best(lt_gcn3_trainer *t, void *stream);
 int lt_gcn3_trainer_val_logits(const lt_gcn3_trainer *t, float *Z, int64_t ldz, void *stream);
+size_t lt_eval_head_rows_workspace_bytes(int32_t m, int32_t C);
+int lt_eval_head_rows(const float *Z, int64_t ldz, const int32_t *labels, int32_t n, int32_t C, const int32_t *rows, int32_t m,
+                      float *loss, int32_t *confusion, int32_t *n_bad, void *workspace, size_t workspace_bytes, void *stream);
+int lt_gcn2_trainer_attach_validation_rows(lt_gcn2_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
+                                           const int32_t *labels2, int32_t keep_best, int32_t patience, const int32_t *rows,
+                                           int32_t m, void *stream);
+int lt_gcn3_trainer_attach_validation_rows(lt_gcn3_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
+                                           const int32_t *labels2, int32_t keep_best, int32_t patience, const int32_t *rows,
+                                           int32_t m, void *stream);
 
 /* ---- per-kernel timing (used by bench.py for the roofline object) --------------------------
  * lt_profile_enable(mask): bit k of mask set = launches of kernel class k are bracketed by a pair of

@@ -178,6 +178,13 @@ SIGNATURES = {
     "lt_gcn3_trainer_val_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "lt_gcn3_trainer_restore_best": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lt_gcn3_trainer_val_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "lt_eval_head_rows_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "lt_eval_head_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lt_gcn2_trainer_attach_validation_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "lt_gcn3_trainer_attach_validation_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "lt_profile_enable": (C.c_int, [C.c_int]),
     "lt_profile_reset": (C.c_int, []),
     "lt_profile_summary": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -542,6 +542,60 @@ __global__ __launch_bounds__(TR_BLOCK) void k_val_rows(int n, const float *__res
     if (t < C * C) part_cnt[(size_t)blockIdx.x * (C * C) + t] = sc[t];
 }
 
+// Row stage over a list: entry i = blockIdx.x * 256 + t scores logits row rows[i] against labels[rows[i]] with k_val_rows'
+// per-row arithmetic (the same operations in the same order), the same block tree and the same partials, so the list
+// 0 .. n - 1 leaves k_val_rows' bits.  An id outside [0, n) is never dereferenced: its entry adds 0 to the loss and counts in
+// no cell; each block adds its number of such entries to *n_bad (an integer atomic: the total does not depend on order).
+template <int CP>
+__global__ __launch_bounds__(TR_BLOCK) void k_val_rows_list(int n, int m, const int32_t *__restrict__ rows,
+                                                            const float *__restrict__ Z, long ldz, int C,
+                                                            const int32_t *__restrict__ labels, float *__restrict__ part_loss,
+                                                            int32_t *__restrict__ part_cnt, int32_t *n_bad) {
+    __shared__ float sl[TR_BLOCK];
+    __shared__ int sc[CP * CP];
+    __shared__ int sbad;
+    const int t = threadIdx.x;
+    const int i = blockIdx.x * TR_BLOCK + t;
+    if (t < CP * CP) sc[t] = 0;
+    if (t == 0) sbad = 0;
+    __syncthreads();
+    float l = 0.f;
+    if (i < m) {
+        const int r = rows[i];
+        if ((unsigned)r < (unsigned)n) {
+            const int y = labels[r];
+            float z[CP];
+#pragma unroll
+            for (int c = 0; c < CP; ++c) z[c] = c < C ? Z[(size_t)r * ldz + c] : -INFINITY;
+            float mx = z[0];
+            int arg = 0;
+#pragma unroll
+            for (int c = 1; c < CP; ++c)
+                if (c < C && z[c] > mx) { mx = z[c]; arg = c; }
+            float s = 0.f, zy = 0.f;
+#pragma unroll
+            for (int c = 0; c < CP; ++c) {
+                const float e = c < C ? expf(z[c] - mx) : 0.f;
+                s += e;
+                if (c == y) zy = z[c];
+            }
+            l = (mx + logf(s)) - zy;
+            if ((unsigned)y < (unsigned)C) atomicAdd(&sc[y * C + arg], 1);
+        } else if (n_bad) {
+            atomicAdd(&sbad, 1);
+        }
+    }
+    sl[t] = l;
+    __syncthreads();
+    for (int w = TR_BLOCK / 2; w >= 1; w >>= 1) {
+        if (t < w) sl[t] += sl[t + w];
+        __syncthreads();
+    }
+    if (t == 0) part_loss[blockIdx.x] = sl[0];
+    if (t < C * C) part_cnt[(size_t)blockIdx.x * (C * C) + t] = sc[t];
+    if (t == 0 && n_bad && sbad) atomicAdd(n_bad, sbad);
+}
+
 // The early-stopping state: 8 words of device memory.
 #define VAL_STATE_WORDS 8
 enum { VS_BEST_LOSS = 0, VS_BEST_EPOCH = 1, VS_COUNTER = 2, VS_STOP_EPOCH = 3, VS_IMPROVED = 4, VS_SEEN = 5 };
@@ -678,9 +732,11 @@ struct lt_val {
     const float *X = nullptr;
     int64_t ldx = 0;
     const int32_t *labels = nullptr;
+    const int32_t *rows = nullptr;         // attach_validation_rows: the head scores these m rows (borrowed); NULL: all n
+    int32_t m = 0;
     int32_t keep_best = 0, patience = 0;
     int32_t kslice = 0;           // split-K slicing of X2 W1, chosen for n2 (the forward's choice at that size)
-    int32_t n_blk = 0;            // blocks of k_val_rows
+    int32_t n_blk = 0;            // blocks of k_val_rows (of k_val_rows_list with a row list)
     float *S1 = nullptr, *Z1 = nullptr;    // [n2, Hp1]; Z1 only feeds the tiled layer-1 route (2-layer model)
     float *H1 = nullptr;                   // [n2, Hp1] 3-layer model: relu(A S1 + b1)
     float *S2 = nullptr, *Z2 = nullptr;    // [n2, Hp2] 3-layer model
@@ -714,6 +770,20 @@ static int launch_val_head(const float *Z, long ldz, const int32_t *labels, int 
                                                     C, labels, part_loss, part_cnt));
     LT_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_val_finish, dim3(1), dim3(TR_BLOCK), 0, st, n_blk, n, C, part_loss, part_cnt, loss_out, conf_out,
+                       state, patience, epoch);
+    LT_CHECK_LAUNCH();
+    return LT_OK;
+}
+
+// the head over a row list: k_val_rows_list over ceil(m / 256) blocks, then the finish stage with m as the divisor
+static int launch_val_head_rows(const float *Z, long ldz, const int32_t *labels, int n, int C, const int32_t *rows, int m,
+                                float *part_loss, int32_t *part_cnt, float *loss_out, int32_t *conf_out, int32_t *n_bad,
+                                int32_t *state, int patience, int epoch, hipStream_t st) {
+    const int n_blk = (m + TR_BLOCK - 1) / TR_BLOCK;
+    LT_DISPATCH_CP(lt_cp_for(C), hipLaunchKernelGGL((k_val_rows_list<CP_>), dim3((unsigned)n_blk), dim3(TR_BLOCK), 0, st, n, m,
+                                                    rows, Z, ldz, C, labels, part_loss, part_cnt, n_bad));
+    LT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_val_finish, dim3(1), dim3(TR_BLOCK), 0, st, n_blk, m, C, part_loss, part_cnt, loss_out, conf_out,
                        state, patience, epoch);
     LT_CHECK_LAUNCH();
     return LT_OK;
@@ -1491,6 +1561,30 @@ extern "C" int lt_eval_head(const float *Z, int64_t ldz, const int32_t *labels, 
                            (hipStream_t)stream);
 }
 
+extern "C" size_t lt_eval_head_rows_workspace_bytes(int32_t m, int32_t C) {
+    if (m <= 0 || C <= 0 || C > LT_MAX_C) return 0;
+    return val_head_bytes(m, C);
+}
+
+extern "C" int lt_eval_head_rows(const float *Z, int64_t ldz, const int32_t *labels, int32_t n, int32_t C, const int32_t *rows,
+                                 int32_t m, float *loss, int32_t *confusion, int32_t *n_bad, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+    LT_REQUIRE(m > 0, "lt_eval_head_rows: m=%d, must be positive", m);
+    LT_REQUIRE(n > 0, "lt_eval_head_rows: n=%d, must be positive", n);
+    LT_REQUIRE(C > 0 && C <= LT_MAX_C, "lt_eval_head_rows: C=%d (supported: 1 .. %d)", C, LT_MAX_C);
+    LT_REQUIRE(Z && labels && rows && loss && confusion, "lt_eval_head_rows: NULL pointer");
+    LT_REQUIRE(ldz >= C, "lt_eval_head_rows: ldz=%lld < C=%d", (long long)ldz, C);
+    if (!workspace || workspace_bytes < val_head_bytes(m, C) || ((uintptr_t)workspace % sizeof(float)))
+        return lt_set_error(LT_ERR_WORKSPACE, "lt_eval_head_rows: workspace needs %zu bytes, 4-byte aligned",
+                            val_head_bytes(m, C));
+    hipStream_t st = (hipStream_t)stream;
+    if (n_bad) LT_HIP(hipMemsetAsync(n_bad, 0, sizeof(int32_t), st));
+    const int n_blk = (m + TR_BLOCK - 1) / TR_BLOCK;
+    float *part_loss = (float *)workspace;
+    return launch_val_head_rows(Z, (long)ldz, labels, n, C, rows, m, part_loss, (int32_t *)(part_loss + n_blk), loss, confusion,
+                                n_bad, nullptr, 0, 0, st);
+}
+
 extern "C" int lt_early_stop_reset(int32_t *state, void *stream) {
     LT_REQUIRE(state != nullptr, "lt_early_stop_reset: state is NULL");
     hipLaunchKernelGGL(k_val_state_reset, dim3(1), dim3(64), 0, (hipStream_t)stream, state);
@@ -1520,7 +1614,8 @@ static int ptr_device(const void *p) {
 // Everything lt_gcn*_trainer_attach_validation checks and allocates.  Hp2 = 0: the 2-layer model.
 static int val_attach(const char *who, lt_val **slot, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
                       const int32_t *labels2, int32_t keep_best, int32_t patience, const float *X, int F, int H1, int Hp1,
-                      int Hp2, int C, int64_t n_param, hipStream_t st) {
+                      int Hp2, int C, int64_t n_param, hipStream_t st, int with_rows = 0, const int32_t *rows = nullptr,
+                      int32_t m = 0) {
     LT_REQUIRE(*slot == nullptr, "%s: validation is already attached to this trainer", who);
     LT_REQUIRE(g2 != nullptr && X2 != nullptr && labels2 != nullptr, "%s: NULL argument", who);
     LT_REQUIRE(g2->n > 0, "%s: empty graph", who);
@@ -1531,6 +1626,11 @@ static int val_attach(const char *who, lt_val **slot, const lt_graph *g2, const 
     const int dev = ptr_device(X);
     LT_REQUIRE(dev >= 0 && ptr_device(X2) == dev && ptr_device(g2->rowptr) == dev && ptr_device(labels2) == dev,
                "%s: the validation graph, X2 and labels2 must live on the trainer's device (%d)", who, dev);
+    if (with_rows) {
+        LT_REQUIRE(rows != nullptr, "%s: rows is NULL", who);
+        LT_REQUIRE(m > 0, "%s: m=%d, must be positive", who, m);
+        LT_REQUIRE(ptr_device(rows) == dev, "%s: rows must live on the trainer's device (%d)", who, dev);
+    }
     {
         int32_t *host = new (std::nothrow) int32_t[(size_t)n2];
         if (!host) return lt_set_error(LT_ERR_NOMEM, "%s: out of host memory", who);
@@ -1545,12 +1645,28 @@ static int val_attach(const char *who, lt_val **slot, const lt_graph *g2, const 
         if (e != hipSuccess) return lt_set_error(LT_ERR_HIP, "%s: reading labels2 failed: %s", who, hipGetErrorString(e));
         LT_REQUIRE(bad < 0, "%s: labels2[%d]=%d outside [0, %d)", who, bad, bad_label, C);
     }
+    if (with_rows) {      // the list is read back once and checked here: the head then never meets an id outside [0, n2)
+        int32_t *host = new (std::nothrow) int32_t[(size_t)m];
+        if (!host) return lt_set_error(LT_ERR_NOMEM, "%s: out of host memory", who);
+        hipError_t e = hipMemcpyAsync(host, rows, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        int bad = -1;
+        if (e == hipSuccess)
+            for (int i = 0; i < m && bad < 0; ++i)
+                if (host[i] < 0 || host[i] >= n2) bad = i;
+        const int bad_row = bad >= 0 ? host[bad] : 0;
+        delete[] host;
+        if (e != hipSuccess) return lt_set_error(LT_ERR_HIP, "%s: reading rows failed: %s", who, hipGetErrorString(e));
+        LT_REQUIRE(bad < 0, "%s: rows[%d]=%d outside [0, %d)", who, bad, bad_row, n2);
+    }
     lt_val *v = new (std::nothrow) lt_val();
     if (!v) return lt_set_error(LT_ERR_NOMEM, "%s: out of host memory", who);
     v->g = g2; v->n = n2; v->X = X2; v->ldx = ldx2; v->labels = labels2;
     v->keep_best = keep_best; v->patience = patience;
     v->kslice = lt_gemm_pick_kslice(n2, H1, F);
-    v->n_blk = (n2 + TR_BLOCK - 1) / TR_BLOCK;
+    v->rows = with_rows ? rows : nullptr;
+    v->m = with_rows ? m : 0;
+    v->n_blk = ((with_rows ? m : n2) + TR_BLOCK - 1) / TR_BLOCK;
     const size_t nh1 = (size_t)n2 * Hp1 * sizeof(float), nh2 = (size_t)n2 * Hp2 * sizeof(float);
     const size_t nc = (size_t)n2 * C * sizeof(float);
     const int hpm = Hp1 > Hp2 ? Hp1 : Hp2;
@@ -1597,8 +1713,10 @@ static int val_attach(const char *who, lt_val **slot, const lt_graph *g2, const 
 // head, state and snapshot behind a validation forward; e = the epoch just trained (0-based, since creation)
 static int val_finish_epoch(lt_val *v, int C, const lt_snap_segs &T, int64_t e, float *val_loss, int32_t *val_counts,
                             hipStream_t st) {
-    int rc = launch_val_head(v->Z, (long)C, v->labels, v->n, C, v->part_loss, v->part_cnt, val_loss, val_counts, v->state,
-                             v->patience, (int)e, st);
+    int rc = v->rows ? launch_val_head_rows(v->Z, (long)C, v->labels, v->n, C, v->rows, v->m, v->part_loss, v->part_cnt, val_loss,
+                                            val_counts, nullptr, v->state, v->patience, (int)e, st)
+                     : launch_val_head(v->Z, (long)C, v->labels, v->n, C, v->part_loss, v->part_cnt, val_loss, val_counts,
+                                       v->state, v->patience, (int)e, st);
     if (rc) return rc;
     if (v->keep_best) return launch_snapshot(T, v->snap, v->state + VS_IMPROVED, 0, st);
     return LT_OK;
@@ -1653,6 +1771,14 @@ extern "C" int lt_gcn2_trainer_attach_validation(lt_gcn2_trainer *t, const lt_gr
     LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_attach_validation: trainer is NULL");
     return val_attach("lt_gcn2_trainer_attach_validation", &t->val, g2, X2, ldx2, n2, labels2, keep_best, patience, t->X, t->F,
                       t->H, t->Hp, 0, t->C, t->n_param, (hipStream_t)stream);
+}
+
+extern "C" int lt_gcn2_trainer_attach_validation_rows(lt_gcn2_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2,
+                                                      int32_t n2, const int32_t *labels2, int32_t keep_best, int32_t patience,
+                                                      const int32_t *rows, int32_t m, void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_attach_validation_rows: trainer is NULL");
+    return val_attach("lt_gcn2_trainer_attach_validation_rows", &t->val, g2, X2, ldx2, n2, labels2, keep_best, patience, t->X,
+                      t->F, t->H, t->Hp, 0, t->C, t->n_param, (hipStream_t)stream, 1, rows, m);
 }
 
 extern "C" int lt_gcn2_trainer_run_validated(lt_gcn2_trainer *t, int32_t n_epochs, float *record, float *val_loss,
@@ -1746,6 +1872,14 @@ extern "C" int lt_gcn3_trainer_attach_validation(lt_gcn3_trainer *t, const lt_gr
     LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_attach_validation: trainer is NULL");
     return val_attach("lt_gcn3_trainer_attach_validation", &t->val, g2, X2, ldx2, n2, labels2, keep_best, patience, t->X, t->F,
                       t->H1, t->Hp1, t->Hp2, t->C, t->off[5], (hipStream_t)stream);
+}
+
+extern "C" int lt_gcn3_trainer_attach_validation_rows(lt_gcn3_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2,
+                                                      int32_t n2, const int32_t *labels2, int32_t keep_best, int32_t patience,
+                                                      const int32_t *rows, int32_t m, void *stream) {
+    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_attach_validation_rows: trainer is NULL");
+    return val_attach("lt_gcn3_trainer_attach_validation_rows", &t->val, g2, X2, ldx2, n2, labels2, keep_best, patience, t->X,
+                      t->F, t->H1, t->Hp1, t->Hp2, t->C, t->off[5], (hipStream_t)stream, 1, rows, m);
 }
 
 extern "C" int lt_gcn3_trainer_run_validated(lt_gcn3_trainer *t, int32_t n_epochs, float *record, float *val_loss,

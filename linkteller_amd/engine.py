@@ -645,10 +645,12 @@ class _ValidationMixin:
         fn = f"{self._PREFIX}_{name}"
         _lib.check(getattr(_lib.lib(), fn)(self._h, *args), fn)
 
-    def attach_validation(self, adj2, x2, labels2, keep_best=False, patience=0):
+    def attach_validation(self, adj2, x2, labels2, keep_best=False, patience=0, rows=None):
         """Attach the held-out graph (reference: ``features_2``, ``adj_2``, ``labels_2``); once per trainer.  ``keep_best``: keep a
         snapshot of the parameters of the best validation loss (``restore_best``).  ``patience`` > 0: stop ``run_validated``
-        after that many epochs without improvement; 0: never stop."""
+        after that many epochs without improvement; 0: never stop.  ``rows`` (a tensor or an array of node ids of the held-out
+        graph, any order, repeats count): the head scores these rows only (the reference's ``idx_val`` of a dataset with one
+        graph and a split of its nodes, gcn_trainer.py:183-196); an id outside [0, n2) raises ``IndexError``."""
         if self._val is not None:
             raise ValueError("validation is already attached to this trainer")
         if int(patience) < 0:
@@ -671,9 +673,16 @@ class _ValidationMixin:
         if labels2.numel() and (int(labels2.min()) < 0 or int(labels2.max()) >= self.c):
             raise ValueError(f"labels2 outside [0, {self.c})")
         labels2 = labels2.to(device=self.x.device, dtype=torch.int32).contiguous()
-        self._call("attach_validation", g2.handle, x2.data_ptr(), x2.shape[1], x2.shape[0], labels2.data_ptr(),
-                   int(bool(keep_best)), int(patience), _stream())
-        self._val = (g2, x2, labels2)       # borrowed by the library: kept alive here
+        if rows is None:
+            self._call("attach_validation", g2.handle, x2.data_ptr(), x2.shape[1], x2.shape[0], labels2.data_ptr(),
+                       int(bool(keep_best)), int(patience), _stream())
+        else:
+            rows = _as_rows(rows, g2.n, self.x.device, "rows")
+            if rows.numel() == 0:
+                raise ValueError("rows is empty: a validation loss over no row is undefined")
+            self._call("attach_validation_rows", g2.handle, x2.data_ptr(), x2.shape[1], x2.shape[0], labels2.data_ptr(),
+                       int(bool(keep_best)), int(patience), rows.data_ptr(), rows.numel(), _stream())
+        self._val = (g2, x2, labels2, rows)       # borrowed by the library: kept alive here
         self.n2, self.keep_best, self.patience = g2.n, bool(keep_best), int(patience)
 
     def _require_val(self):
@@ -752,10 +761,12 @@ class _ValidationMixin:
         return out
 
 
-def eval_head(logits: torch.Tensor, labels: torch.Tensor):
+def eval_head(logits: torch.Tensor, labels: torch.Tensor, rows=None):
     """Mean cross-entropy (device float32 scalar tensor) and confusion matrix (int32 [C, C], row = true class, column = first
     argmax) of ``logits`` [n, C] -- a strided view with unit column stride is read in place -- against ``labels``
-    (lt_eval_head).  Enqueue-only."""
+    (lt_eval_head).  Enqueue-only.  With ``rows`` (a tensor or an array of row ids, any order, repeats count) only the listed
+    rows are scored: ``F.cross_entropy(logits[rows], labels[rows])`` without the gathered copies (lt_eval_head_rows); the ids
+    are checked first (a synchronisation when they live on the device) and one outside [0, n) raises ``IndexError``."""
     if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2):
         raise ValueError("logits must be a 2-d float32 device tensor")
     n, c = logits.shape
@@ -766,10 +777,39 @@ def eval_head(logits: torch.Tensor, labels: torch.Tensor):
         raise ValueError(f"labels: {labels.numel()} entries for {n} rows")
     loss = torch.empty((), dtype=torch.float32, device=logits.device)
     conf = torch.empty((c, c), dtype=torch.int32, device=logits.device)
+    if rows is not None:
+        rows = _as_rows(rows, n, logits.device, "rows")
+        m = rows.numel()
+        ws = _workspace(_lib.lib().lt_eval_head_rows_workspace_bytes(m, c), logits.device)
+        _lib.check(_lib.lib().lt_eval_head_rows(logits.data_ptr(), logits.stride(0) if n else c, labels.data_ptr(), n, c,
+                                                rows.data_ptr(), m, loss.data_ptr(), conf.data_ptr(), None, ws.data_ptr(),
+                                                ws.numel(), _stream()), "lt_eval_head_rows")
+        return loss, conf
     ws = _workspace(_lib.lib().lt_eval_head_workspace_bytes(n, c), logits.device)
     _lib.check(_lib.lib().lt_eval_head(logits.data_ptr(), logits.stride(0) if n else c, labels.data_ptr(), n, c, loss.data_ptr(),
                                        conf.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "lt_eval_head")
     return loss, conf
+
+
+def f1_from_confusion(conf):
+    """(micro, macro, weighted) F1 in float64 from C x C integer counts (row = true class, column = predicted class), with the
+    conventions of ``sklearn.metrics.f1_score`` on the labels present (reference gcn_trainer.py:354-383 calls it three times): a
+    class with no true and no predicted member is left out of the macro mean, a zero division gives 0, the weights are the
+    supports."""
+    import numpy as np
+    k = conf.detach().cpu().numpy() if isinstance(conf, torch.Tensor) else np.asarray(conf)
+    if k.ndim != 2 or k.shape[0] != k.shape[1]:
+        raise ValueError(f"conf must be [C, C], got {k.shape}")
+    k = k.astype(np.int64)
+    tp, true, pred = np.diag(k), k.sum(axis=1), k.sum(axis=0)
+    total = int(k.sum())
+    micro = float(tp.sum()) / total if total else 0.0      # single label: micro F1 = accuracy (sum fp = sum fn)
+    den = true + pred                                       # F1_c = 2 tp / (2 tp + fp + fn) = 2 tp / (true + pred)
+    f1 = np.where(den > 0, 2.0 * tp / np.maximum(den, 1), 0.0)
+    present = den > 0
+    macro = float(f1[present].mean()) if present.any() else 0.0
+    weighted = float((f1 * true).sum() / total) if total else 0.0
+    return micro, macro, weighted
 
 
 class EarlyStopState:
@@ -1366,6 +1406,18 @@ def node_check():
     """Raise IndexError when a probe / observed list of a COMPLETED call held a node id outside [0, n) (lt_node_check: the
     lists are device memory, so the kernels check them; call after synchronising)."""
     _lib.check(_lib.lib().lt_node_check(None, None), "lt_node_check")
+
+
+def _as_rows(rows, n, device, name) -> torch.Tensor:
+    """Row list (tensor or array, any integer dtype) -> contiguous int32 tensor on ``device``; every id is checked here, an id
+    outside [0, n) raises ``IndexError`` as indexing does in the reference."""
+    t = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(rows)
+    if t.dtype.is_floating_point or t.dtype == torch.bool or t.is_complex():
+        raise TypeError(f"{name} must hold integer ids, got {t.dtype}")
+    t = t.reshape(-1)
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+        raise IndexError(f"{name} out of range [0, {n})")
+    return t.to(device=device, dtype=torch.int32).contiguous()
 
 
 def _as_nodes(nodes, n, device, name) -> torch.Tensor:

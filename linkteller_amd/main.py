@@ -14,7 +14,9 @@ Every flag of the reference is accepted with its default.  ``--test`` runs infer
 Without either switch the run is refused (a default run does not start a 500-epoch job by itself).  With ``--train``,
 ``--validate log | best | early`` (an addition, default ``off``) validates on the held-out graph after every epoch on the GPU:
 ``loss_val`` / ``acc_val`` in the log, the model of the best validation loss saved, and a stop after ``--patience`` epochs
-without improvement.
+without improvement.  ``--dataset flickr`` (one graph with a train / validation / test split of its nodes; also ``reddit``,
+``ppi``, ``ppi-large`` with ``--test``) trains on the induced training subgraph, is validated on ``idx_val`` of the full graph
+after every epoch -- ``--early`` stops it as in the reference -- and is tested on ``idx_test`` with micro / macro / weighted F1.
 """
 from __future__ import annotations
 
@@ -80,8 +82,10 @@ _HELP = {
                 "best: also restore and save the model of the best validation loss; early: also stop after --patience epochs "
                 "without improvement.  Default off.",
     "patience": "epochs without improvement before --validate early stops (default 10)",
-    "early": "accepted and inert, as in the reference on transfer datasets (it never reaches EarlyStopping there); making it "
-             "live would change existing runs.  Early stopping is --validate early.",
+    "early": "with --train on flickr / reddit / ppi / ppi-large (one graph with a split of its nodes): stop after --patience "
+             "epochs without improvement of the validation loss over idx_val and save the best model, as the reference does; a "
+             "run that never stops saves the last model.  On transfer datasets (twitch/<A>/<B>) accepted and inert, as in the "
+             "reference (it never reaches EarlyStopping there): early stopping is --validate early.",
 }
 _SWITCHES = ["no-cuda", "fastmode", "approx", "attack", "test", "break-down", "display", "same-size",
              "eval-degree", "trainable", "early", "fnormalize",
@@ -222,9 +226,32 @@ def check_validate(args):
         raise ValueError(f"--validate early needs --patience >= 1 (got {args.patience})")
 
 
+_SPLIT_DATASETS = ("reddit", "flickr", "ppi", "ppi-large")      # worker.GRAPHSAINT (not imported: no torch before the checks)
+_SPLIT_MULTI_LABEL = ("reddit", "ppi", "ppi-large")              # these need --train's follow-up: a BCE head, more than 8 classes
+
+
+def check_split_dataset(args):
+    """``--train`` on a dataset with one graph and a split of its nodes: what the flags alone decide is refused here, before a
+    Worker is built or the GPU is touched -- ``--fastmode`` (the reference then indexes the training subgraph's logits with
+    ids of the full graph), a ``--patience`` below 1 with ``--early``, and the datasets whose published form is multi-label or
+    wider than 8 classes (ppi, ppi-large: 121 labels per node; reddit: 41 classes), which load, test and attack from a saved
+    model.  A dataset under one of the other names is judged by its own files in ``GCNTrainer.init_model``."""
+    if args.dataset not in _SPLIT_DATASETS or not args.train or args.test:
+        return
+    if args.fastmode:
+        raise NotImplementedError(f"--fastmode is refused on --dataset {args.dataset} (the reference then indexes the training "
+                                  "subgraph's logits with ids of the full graph)")
+    if args.early and args.patience < 1:
+        raise ValueError(f"--early needs --patience >= 1 (got {args.patience})")
+    if args.dataset in _SPLIT_MULTI_LABEL:
+        raise NotImplementedError(f"--train on --dataset {args.dataset}: training is implemented for a single label and at most 8 "
+                                  "classes (flickr); this dataset loads, tests and attacks from a saved model (--test --model-path)")
+
+
 def main(argv=None):
     args = get_arguments(argv)
     check_validate(args)
+    check_split_dataset(args)
     check_baseline_scores(args)
     check_recover(args)
     check_metrics_only(args)

@@ -169,3 +169,23 @@ def write_musae_dataset(root: str, code: str, adj, n_feat_ids: int, seed: int):
         fh.write("id,days,mature,views,partner,new_id\n" +
                  "".join(f"{1000 + i},1,{bool(i % 3 == 0)},5,False,{i}\n" for i in perm))
     return feats
+
+
+def write_graphsaint_dataset(root: str, name: str, adj, features, labels, roles):
+    """Writes ``<root>/<name>/{role.json,feats.npy,class_map.json,adj_full.npz}`` in the GraphSAINT layout the reference reads
+    for flickr / ppi / ppi-large / reddit (utils/load.py:115-148, 209-216): ``roles`` is a dict with the node id lists
+    ``tr`` / ``va`` / ``te`` (any order), ``features`` a float array [n, F] stored as it is, ``labels`` [n] (single label: one
+    int per node) or [n, L] (multi-label: a 0/1 list per node), ``adj`` the full graph, stored as the four arrays of its CSR."""
+    import json
+    import os
+    d = os.path.join(root, name)
+    os.makedirs(d)
+    with open(os.path.join(d, "role.json"), "w") as fh:
+        json.dump({k: [int(i) for i in roles[k]] for k in ("tr", "va", "te")}, fh)
+    np.save(os.path.join(d, "feats.npy"), np.asarray(features))
+    labels = np.asarray(labels)
+    with open(os.path.join(d, "class_map.json"), "w") as fh:
+        json.dump({str(i): (int(v) if labels.ndim == 1 else [int(x) for x in v]) for i, v in enumerate(labels)}, fh)
+    a = sp.csr_matrix(adj)
+    np.savez(os.path.join(d, "adj_full.npz"), data=a.data, indices=a.indices, indptr=a.indptr, shape=np.asarray(a.shape))
+    return d

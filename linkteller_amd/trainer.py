@@ -52,19 +52,27 @@ class GCNTrainer:
             # the optimizer state of gcn_trainer.py:106-108: Adam's moments live in the GPU trainer, which updates the
             # model's parameters in place
             from .engine import GCN2Trainer, GCN3Trainer
-            if not w.transfer:
-                raise NotImplementedError(f"dataset = {self.dataset}: training is implemented for transfer datasets")
+            if w.transfer:
+                train_on = (w.adj_1, w.features_1, w.labels_1)
+            else:                                              # gcn_trainer.py:131, 154: the induced training subgraph
+                if getattr(a, "fastmode", False):
+                    raise NotImplementedError(f"dataset = {self.dataset}: --fastmode is refused (the reference then indexes the "
+                                              "training subgraph's logits with ids of the full graph)")
+                if w.multi_label > 1 or w.n_classes > 8:
+                    raise NotImplementedError(
+                        f"dataset = {self.dataset}: training is implemented for a single label and at most 8 classes (got "
+                        f"multi_label = {w.multi_label}, n_classes = {w.n_classes}); load a trained model with --test --model-path")
+                train_on = (w.adj_train, w.features_train, w.labels[torch.as_tensor(w.idx_train, device=w.labels.device)])
             layers = [self.model.gc1, self.model.gc2] + ([self.model.gc3] if a.n_layer == 3 else [])
             params = [t.detach() for g in layers for t in (g.weight, g.bias)]
             self.gpu_trainer = (GCN3Trainer if a.n_layer == 3 else GCN2Trainer)(
-                w.adj_1, w.features_1, w.labels_1, *params, lr=a.lr, weight_decay=a.weight_decay, dropout=a.dropout,
-                seed=a.seed)
+                *train_on, *params, lr=a.lr, weight_decay=a.weight_decay, dropout=a.dropout, seed=a.seed)
 
     def train(self):
         """gcn_trainer.py:200-243 on a transfer dataset: ``num_epochs`` epochs on (features_1, adj_1, labels_1), the
         per-epoch log line of train_one_epoch, ``model.pt`` under ``model_<dataset>/<subdir>``.  The epochs run back to back
         on the device and the per-epoch record is read once at the end, so the ``time`` of an epoch's line is the run's wall
-        time divided by the number of epochs."""
+        time divided by the number of epochs.  A dataset with one graph and a split of its nodes: ``_train_split``."""
         if self.gpu_trainer is None:
             raise RuntimeError("init_model() without a model path first")
         a = self.args
@@ -72,7 +80,9 @@ class GCNTrainer:
         self.model.train()
         n_epochs = int(a.num_epochs)
         validate = getattr(a, "validate", "off")
-        if validate != "off":
+        if not self.worker.transfer:
+            self._train_split(n_epochs, validate, t_total)
+        elif validate != "off":
             self._train_validated(n_epochs, validate, t_total)
         else:
             loss, correct = self.gpu_trainer.run(n_epochs)
@@ -121,11 +131,80 @@ class GCNTrainer:
             print(info)
             logging.info(info)
 
+    def _train_split(self, n_epochs, validate, t_total):
+        """gcn_trainer.py:183-206, 229-238 on a dataset with one graph and a split of its nodes: always validated -- every epoch
+        is followed on the device by the forward of (features, adj_full) and the evaluation head over ``idx_val``
+        (``attach_validation(..., rows=idx_val)``).  ``--early`` has the reference's meaning here: the run stops after
+        ``--patience`` epochs without improvement and saves the best model, a run that never stops saves the last one.
+        ``--validate best`` / ``early`` keep the project's meaning (the best model is always restored); ``off`` is ``log``."""
+        a, w, tr = self.args, self.worker, self.gpu_trainer
+        early = bool(getattr(a, "early", False))
+        keep = early or validate in ("best", "early")
+        tr.attach_validation(w.adj_full, w.features, w.labels, rows=w.idx_val, keep_best=keep,
+                             patience=int(a.patience) if (early or validate == "early") else 0)
+        r = tr.run_validated(n_epochs)
+        done = len(r["loss"])
+        per_epoch = (time.time() - t_total) / max(done, 1)
+        n, n_val = tr.n, len(w.idx_val)
+        for epoch in range(done):
+            logging.info("[epoch {}]".format(epoch))
+            output_info = "Epoch: {:04d}".format(epoch + 1), \
+                "loss_train: {:.4f}".format(float(r["loss"][epoch])), \
+                "acc_train: {:.4f}".format(int(r["correct"][epoch]) / n), \
+                "loss_val: {:.4f}".format(float(r["val_loss"][epoch])), \
+                "acc_val: {:.4f}".format(int(r["val_counts"][epoch].trace()) / n_val), \
+                "time: {:.4f}s".format(per_epoch)
+            logging.info(output_info)
+        stopped = r["stop_epoch"] >= 0
+        if stopped:
+            logging.info(f"early stop at epoch {r['stop_epoch']}")
+        if done and (validate in ("best", "early") or (early and stopped)):
+            tr.restore_best()
+            info = f"best validation loss {float(r['val_loss'][r['best_epoch']]):.4f} at epoch {r['best_epoch']}: that model is saved"
+            print(info)
+            logging.info(info)
+
     def forward(self, mode="train"):
         w = self.worker
-        if not w.transfer:
-            raise NotImplementedError(f"dataset = {self.dataset} not implemented!")
+        if not w.transfer:                                     # gcn_trainer.py:129-132
+            return self.model(w.features_train, w.adj_train) if mode == "train" else self.model(w.features, w.adj_full)
         return self.model(w.features_1, w.adj_1) if mode == "train" else self.model(w.features_2, w.adj_2)
+
+    def _eval_split(self, output, mode):
+        """gcn_trainer.py:341-384 for a dataset with a split: validation loss / F1 over ``idx_val``, test loss and micro / macro /
+        weighted F1 over ``idx_test``.  Single label with at most 8 classes: the evaluation head over the row list on the
+        device and ``f1_from_confusion``; multi-label or wider: host torch / sklearn, as the reference does."""
+        w = self.worker
+        if w.multi_label == 1 and w.n_classes <= 8:
+            from .engine import eval_head, f1_from_confusion
+
+            def score(rows):
+                loss, conf = eval_head(output, w.labels, rows=rows)
+                return float(loss), f1_from_confusion(conf)
+        else:
+            from sklearn.metrics import f1_score
+
+            def score(rows):
+                rows = torch.as_tensor(rows, device=output.device)
+                out, target = output[rows], w.labels[rows]
+                if w.multi_label == 1:                        # gcn_trainer.py:60-64, 246-252
+                    loss = F.cross_entropy(out, target.squeeze())
+                    preds = F.softmax(out, dim=1).max(1)[1].type_as(target)
+                else:
+                    loss = F.binary_cross_entropy_with_logits(out, target.float())
+                    preds = torch.sigmoid(out) > 0.5
+                t, p = target.cpu(), preds.detach().cpu()
+                return loss.item(), tuple(f1_score(t, p, average=k) for k in ("micro", "macro", "weighted"))
+        loss_valid, acc_valid = score(w.idx_val)
+        info = f"[{mode}] Validation set results: loss = {loss_valid:.4f} f1_score = {acc_valid[0]:.4f}"
+        print(info)
+        logging.info(info)
+        loss_test, acc_test = score(w.idx_test)
+        info = f"[{mode}] Test set results: loss = {loss_test:.4f} " \
+               f"f1_score [micro, macro, weighted] = {acc_test[0]:.4f} {acc_test[1]:.4f} {acc_test[2]:.4f}"
+        print(info)
+        logging.info(info)
+        self.split_results = {"loss_valid": loss_valid, "f1_valid": acc_valid, "loss_test": loss_test, "f1_test": acc_test}
 
     def rare_class_f1(self, output, labels):
         """gcn_trainer.py:262-284: F1 / precision / recall / AP of the minority class."""
@@ -176,6 +255,9 @@ class GCNTrainer:
                 belief = float(getattr(a, "density_belief", 0.0) or 0.0)
                 self.attacker.recover_edges(beliefs=[belief] if belief > 0 else None)
                 self.attacker.save_recovered()
+        if not self.worker.transfer:
+            self._eval_split(output, mode)
+            return
         labels = self.worker.labels_2
         loss_test = F.cross_entropy(output, labels.squeeze())
         acc = self.rare_class_f1(output, labels)
