@@ -1,20 +1,31 @@
-// Training of the 2-layer GCN: one epoch of GCNTrainer.train_one_epoch on a transfer dataset (reference gcn_trainer.py:144-170,
-// gcn/models.py:19-24, F.cross_entropy, torch.optim.Adam), as stream-ordered launches with no host synchronisation.
+// Training of the 2-layer GCN and the 3-layer GCN3: one epoch of GCNTrainer.train_one_epoch (reference gcn_trainer.py:144-170,
+// gcn/models.py:19-46, F.cross_entropy, torch.optim.Adam), as stream-ordered launches with no host synchronisation.  Both
+// models run ONE epoch (run_epoch): the "top chain" -- the last hidden layer, the class layer, the loss head and their
+// backward -- behind an optional FRONT layer, which only GCN3 has.  S is the product the top chain starts from, b the bias of
+// its hidden layer, Wc / bc the class layer's parameters.
 //
-//   S1 = X W1                   lt_launch_gemm(_splitk)        the forward's product, same slicing: same bits
-//   Z1 = A S1 + b1              lt_launch_layer1 (Z1 stored)   the forward's chains
-//   H1d = dropout(relu(Z1)),    k_tr_dropout                   Philox4x32-10 mask; S2 with relu_w2_partial's order
-//   S2 = H1d W2
-//   Z2 = A S2 + b2              lt_launch_layer2               the forward's layer 2: with p = 0, Z2 IS gcn2_forward's output
-//   loss, dZ2, correct          k_tr_ce, k_tr_ce_reduce        per-row CE head, then one block: mean loss, count, db2
-//   dS2 = A^T dZ2               k_tr_spmm_t_narrow             CSC rows (A is not symmetric in general)
-//   dZ1, db1 / dW2 partials     k_tr_bwd_rows                  dZ1 = [H1d > 0] (dS2 W2^T) / (1 - p); fixed-order row blocks
-//   db1, dW2                    k_tr_colsum                    the blocks' partials in block order
-//   dS1 = A^T dZ1               k_tr_spmm_t_wide               row_dot chains over the CSC
-//   dW1 = X^T dS1               k_gemm_tn_mfma + k_sum_slabs   v_mfma_f32_32x32x2_f32, A^T staged through LDS, split-K
-//   Adam                        k_tr_adam                      one launch over W1 | b1 | W2 | b2
-//
-// The 3-layer GCN's epoch (lt_gcn3_trainer_*) is built from the same kernels further down, with its own launch table.
+//   front layer (GCN3)
+//   S1 = X W1                      lt_launch_gemm(_splitk)        the forward's product, same slicing: same bits
+//   Hf = drop_0(relu(A S1 + b1))   k_tr3_layer1 (+ _long)         row_dot chains from the bias, ReLU and the Philox mask (layer
+//                                                                 word 0) as the epilogue: Z1 never exists in memory
+//   S = Hf W2                      lt_launch_gemm
+//   top chain (without a front layer: S = X W1, the product above)
+//   Z = A S + b                    lt_launch_layer1 (Z stored)    the forward's chains
+//   Hd = drop(relu(Z)), Sc = Hd Wc k_tr_dropout                   Philox4x32-10 mask, layer word = hidden layers in front of
+//                                                                 it (0 or 1); Sc with relu_w2_partial's order
+//   Zc = A Sc + bc                 lt_launch_layer2               the forward's last layer: with p = 0, Zc IS the forward's output
+//   loss, dZc, correct, dbc        k_tr_ce, k_tr_ce_reduce        per-row CE head, then one block: mean loss, count, dbc
+//   dSc = A^T dZc                  k_tr_spmm_t_narrow             CSC rows (A is not symmetric in general)
+//   dZ, db | dWc partials          k_tr_bwd_rows                  dZ = [Hd > 0] (dSc Wc^T) / (1 - p); fixed-order row blocks
+//   db, dWc                        k_tr_colsum                    the blocks' partials in block order
+//   dS = A^T dZ                    k_tr_spmm_t_wide               row_dot chains over the CSC
+//   front layer's backward (GCN3)
+//   dW2 = Hf^T dS                  k_gemm_tn_mfma + k_sum_slabs
+//   dZ1 = [Hf > 0] scale (dS W2^T), db1 slabs       k_tr3_dz_mfma, then k_tr_colsum
+//   dS1 = A^T dZ1                  k_tr_spmm_t_wide
+//   both
+//   dW1 = X^T dS1                  k_gemm_tn_mfma + k_sum_slabs   v_mfma_f32_32x32x2_f32, A^T staged through LDS, split-K
+//   Adam                           k_tr_adam / k_tr3_adam         one launch over W1 | b1 | W2 | b2 (| W3 | b3) and the padded copies
 //
 // Every reduction has a fixed order (no float atomics): two trainings with the same inputs give the same bits.
 // Built with -ffp-contract=off: the only fused operations are explicit fmaf calls and the MFMAs.
@@ -456,8 +467,19 @@ __global__ void k_adam(int64_t n, float *__restrict__ p, const float *__restrict
     v[i] = vi;
 }
 
-// The four parameter tensors in one launch: index i of the concatenation W1 | b1 | W2 | b2 (the layout of the gradient and
-// moment buffers).  The b1 / W2 copies the row kernels read (b1p [Hp], W2p [Hp, C], zero-padded) follow the update.
+// A model's parameter tensors as six segments of one concatenation W1 | b1 | W2 | b2 | W3 | b3, the layout of the gradient,
+// moment and snapshot buffers: segment k is p[k], o[k] is where it ends.  The 2-layer model has four: o[4] = o[5] = o[3].
+struct lt_snap_segs {
+    float *p[6];
+    int64_t o[6];
+};
+
+// The row kernels read zero-padded copies of some parameters (a bias [H] as [Hp], a weight [H, C] as [Hp, C]): the 2-layer
+// model of b1 and W2 (b1p, W2p), GCN3 of b1, b2 and W3.  The Adam launch keeps them current and a pad launch rebuilds them
+// from the borrowed parameters.  Each model has its own pair of kernels: one pair over the six-segment table measured 0.3 %
+// slower per epoch for the 2-layer model at H = 256 (NOTES.md, the trainer-core entry), so the two were kept.
+
+// The four parameter tensors of the 2-layer model in one launch: index i of the concatenation W1 | b1 | W2 | b2.
 __global__ void k_tr_adam(int64_t total, int64_t o1, int64_t o2, int64_t o3, float *__restrict__ W1,
                           float *__restrict__ b1, float *__restrict__ W2, float *__restrict__ b2,
                           const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
@@ -482,6 +504,46 @@ __global__ void k_tr_pad(const float *__restrict__ b1, const float *__restrict__
     if (j >= 0 && j < Hp * C) W2p[j] = (j / C) < H ? W2[j] : 0.f;
 }
 
+// GCN3's six tensors in one launch: the segment table and the copies b1p [Hp1], b2p [Hp2], W3p [Hp2, C].
+struct lt_tr3_tensors {
+    lt_snap_segs s;
+    float *b1p, *b2p, *W3p;
+};
+
+__global__ void k_tr3_adam(lt_tr3_tensors T, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                           lt_adam_scalars s) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T.s.o[5]) return;
+    const int k = i < T.s.o[0] ? 0 : i < T.s.o[1] ? 1 : i < T.s.o[2] ? 2 : i < T.s.o[3] ? 3 : i < T.s.o[4] ? 4 : 5;
+    const int64_t j = k ? i - T.s.o[k - 1] : i;
+    float *p;      // a switch over constant indices: T.s.p[k] with a run-time k would move the argument struct to scratch
+    switch (k) {
+        case 0: p = T.s.p[0]; break;
+        case 1: p = T.s.p[1]; break;
+        case 2: p = T.s.p[2]; break;
+        case 3: p = T.s.p[3]; break;
+        case 4: p = T.s.p[4]; break;
+        default: p = T.s.p[5]; break;
+    }
+    float mi = m[i], vi = v[i];
+    const float np = adam_elem(p[j], g[i], mi, vi, s);
+    p[j] = np;
+    m[i] = mi;
+    v[i] = vi;
+    if (k == 1) T.b1p[j] = np;
+    else if (k == 3) T.b2p[j] = np;
+    else if (k == 4) T.W3p[j] = np;
+}
+
+__global__ void k_tr3_pad(const float *__restrict__ b1, int H1, int Hp1, const float *__restrict__ b2, int H2, int Hp2,
+                          const float *__restrict__ W3, int C, float *__restrict__ b1p, float *__restrict__ b2p,
+                          float *__restrict__ W3p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < Hp1) b1p[i] = i < H1 ? b1[i] : 0.f;
+    if (i < Hp2) b2p[i] = i < H2 ? b2[i] : 0.f;
+    if (i < Hp2 * C) W3p[i] = (i / C) < H2 ? W3[i] : 0.f;
+}
+
 extern "C" int lt_adam_step(int64_t n, float *p, const float *g, float *m, float *v, int64_t step, double lr,
                             double beta1, double beta2, double eps, double weight_decay, void *stream) {
     LT_REQUIRE(n >= 0, "lt_adam_step: n=%lld", (long long)n);
@@ -501,18 +563,34 @@ extern "C" int lt_adam_step(int64_t n, float *p, const float *g, float *m, float
 // Row stage: k_tr_ce's per-row arithmetic (the same operations in the same order: the same row losses and argmax), one
 // thread per row.  Block b leaves the tree sum of its 256 row losses in part_loss[b] and its C x C confusion cells
 // (true class, predicted class) in part_cnt[b, C * C]; a label outside [0, C) counts in no cell.
-template <int CP>
-__global__ __launch_bounds__(TR_BLOCK) void k_val_rows(int n, const float *__restrict__ Z, long ldz, int C,
+// LIST: entry i = blockIdx.x * 256 + t scores logits row rows[i] against labels[rows[i]], i < m, so the list 0 .. n - 1
+// leaves the bits of the launch without one.  An id outside [0, n) is never dereferenced: its entry adds 0 to the loss and
+// counts in no cell; each block adds its number of such entries to *n_bad (an integer atomic: the total does not depend on
+// order).  Without LIST, m, rows and n_bad are not read.
+template <int CP, bool LIST>
+__global__ __launch_bounds__(TR_BLOCK) void k_val_rows(int n, int m, const int32_t *__restrict__ rows,
+                                                       const float *__restrict__ Z, long ldz, int C,
                                                        const int32_t *__restrict__ labels, float *__restrict__ part_loss,
-                                                       int32_t *__restrict__ part_cnt) {
+                                                       int32_t *__restrict__ part_cnt, int32_t *n_bad) {
     __shared__ float sl[TR_BLOCK];
     __shared__ int sc[CP * CP];
+    __shared__ int sbad;
     const int t = threadIdx.x;
-    const int r = blockIdx.x * TR_BLOCK + t;
+    int r = blockIdx.x * TR_BLOCK + t;
     if (t < CP * CP) sc[t] = 0;
+    if constexpr (LIST)
+        if (t == 0) sbad = 0;
     __syncthreads();
+    bool scored = r < (LIST ? m : n);
+    if constexpr (LIST) {
+        if (scored) {
+            r = rows[r];
+            scored = (unsigned)r < (unsigned)n;
+            if (!scored && n_bad) atomicAdd(&sbad, 1);
+        }
+    }
     float l = 0.f;
-    if (r < n) {
+    if (scored) {
         const int y = labels[r];
         float z[CP];
 #pragma unroll
@@ -540,60 +618,8 @@ __global__ __launch_bounds__(TR_BLOCK) void k_val_rows(int n, const float *__res
     }
     if (t == 0) part_loss[blockIdx.x] = sl[0];
     if (t < C * C) part_cnt[(size_t)blockIdx.x * (C * C) + t] = sc[t];
-}
-
-// Row stage over a list: entry i = blockIdx.x * 256 + t scores logits row rows[i] against labels[rows[i]] with k_val_rows'
-// per-row arithmetic (the same operations in the same order), the same block tree and the same partials, so the list
-// 0 .. n - 1 leaves k_val_rows' bits.  An id outside [0, n) is never dereferenced: its entry adds 0 to the loss and counts in
-// no cell; each block adds its number of such entries to *n_bad (an integer atomic: the total does not depend on order).
-template <int CP>
-__global__ __launch_bounds__(TR_BLOCK) void k_val_rows_list(int n, int m, const int32_t *__restrict__ rows,
-                                                            const float *__restrict__ Z, long ldz, int C,
-                                                            const int32_t *__restrict__ labels, float *__restrict__ part_loss,
-                                                            int32_t *__restrict__ part_cnt, int32_t *n_bad) {
-    __shared__ float sl[TR_BLOCK];
-    __shared__ int sc[CP * CP];
-    __shared__ int sbad;
-    const int t = threadIdx.x;
-    const int i = blockIdx.x * TR_BLOCK + t;
-    if (t < CP * CP) sc[t] = 0;
-    if (t == 0) sbad = 0;
-    __syncthreads();
-    float l = 0.f;
-    if (i < m) {
-        const int r = rows[i];
-        if ((unsigned)r < (unsigned)n) {
-            const int y = labels[r];
-            float z[CP];
-#pragma unroll
-            for (int c = 0; c < CP; ++c) z[c] = c < C ? Z[(size_t)r * ldz + c] : -INFINITY;
-            float mx = z[0];
-            int arg = 0;
-#pragma unroll
-            for (int c = 1; c < CP; ++c)
-                if (c < C && z[c] > mx) { mx = z[c]; arg = c; }
-            float s = 0.f, zy = 0.f;
-#pragma unroll
-            for (int c = 0; c < CP; ++c) {
-                const float e = c < C ? expf(z[c] - mx) : 0.f;
-                s += e;
-                if (c == y) zy = z[c];
-            }
-            l = (mx + logf(s)) - zy;
-            if ((unsigned)y < (unsigned)C) atomicAdd(&sc[y * C + arg], 1);
-        } else if (n_bad) {
-            atomicAdd(&sbad, 1);
-        }
-    }
-    sl[t] = l;
-    __syncthreads();
-    for (int w = TR_BLOCK / 2; w >= 1; w >>= 1) {
-        if (t < w) sl[t] += sl[t + w];
-        __syncthreads();
-    }
-    if (t == 0) part_loss[blockIdx.x] = sl[0];
-    if (t < C * C) part_cnt[(size_t)blockIdx.x * (C * C) + t] = sc[t];
-    if (t == 0 && n_bad && sbad) atomicAdd(n_bad, sbad);
+    if constexpr (LIST)
+        if (t == 0 && n_bad && sbad) atomicAdd(n_bad, sbad);
 }
 
 // The early-stopping state: 8 words of device memory.
@@ -666,11 +692,6 @@ __global__ void k_val_state_reset(int32_t *state) {
 // contiguous snapshot: every thread reads *flag, a word an earlier launch on the stream wrote, and returns when it is 0.
 // V floats per thread: the host picks the widest V for which every pointer is V * 4-byte aligned and every segment starts
 // at a multiple of V; a vector that would cross its segment's end (the last one only, then) is copied element by element.
-struct lt_snap_segs {
-    float *p[6];
-    int64_t o[6];
-};
-
 template <int V>
 __global__ __launch_bounds__(256) void k_val_snapshot(lt_snap_segs T, float *__restrict__ snap,
                                                       const int32_t *__restrict__ flag, int to_live) {
@@ -736,11 +757,10 @@ struct lt_val {
     int32_t m = 0;
     int32_t keep_best = 0, patience = 0;
     int32_t kslice = 0;           // split-K slicing of X2 W1, chosen for n2 (the forward's choice at that size)
-    int32_t n_blk = 0;            // blocks of k_val_rows (of k_val_rows_list with a row list)
-    float *S1 = nullptr, *Z1 = nullptr;    // [n2, Hp1]; Z1 only feeds the tiled layer-1 route (2-layer model)
-    float *H1 = nullptr;                   // [n2, Hp1] 3-layer model: relu(A S1 + b1)
-    float *S2 = nullptr, *Z2 = nullptr;    // [n2, Hp2] 3-layer model
-    float *Sc = nullptr, *Z = nullptr;     // [n2, C]: the last product and the validation logits
+    int32_t n_blk = 0;            // blocks of k_val_rows
+    float *fS = nullptr, *fH = nullptr;    // [n2, Hp of the front layer] GCN3: X2 W1 and relu(A fS + b1)
+    float *S = nullptr, *Z = nullptr;      // [n2, Hp of the top chain]; without a front layer Z only feeds the tiled layer-1 route
+    float *Sc = nullptr, *Zc = nullptr;    // [n2, C]: the last product and the validation logits
     float *slabs = nullptr, *seg_part = nullptr;
     float *part_loss = nullptr;            // [n_blk]
     int32_t *part_cnt = nullptr;           // [n_blk, C * C]
@@ -750,7 +770,7 @@ struct lt_val {
 
 static void free_val(lt_val *v) {
     if (!v) return;
-    float *bufs[] = {v->S1, v->Z1, v->H1, v->S2, v->Z2, v->Sc, v->Z, v->slabs, v->seg_part, v->part_loss, v->snap};
+    float *bufs[] = {v->fS, v->fH, v->S, v->Z, v->Sc, v->Zc, v->slabs, v->seg_part, v->part_loss, v->snap};
     for (float *b : bufs) (void)hipFree(b);
     (void)hipFree(v->part_cnt);
     (void)hipFree(v->state);
@@ -762,281 +782,30 @@ static size_t val_head_bytes(int n, int C) {
     return n_blk * (1 + (size_t)C * C) * sizeof(float);
 }
 
-static int launch_val_head(const float *Z, long ldz, const int32_t *labels, int n, int C, float *part_loss,
-                           int32_t *part_cnt, float *loss_out, int32_t *conf_out, int32_t *state, int patience, int epoch,
-                           hipStream_t st) {
-    const int n_blk = (n + TR_BLOCK - 1) / TR_BLOCK;
-    LT_DISPATCH_CP(lt_cp_for(C), hipLaunchKernelGGL((k_val_rows<CP_>), dim3((unsigned)n_blk), dim3(TR_BLOCK), 0, st, n, Z, ldz,
-                                                    C, labels, part_loss, part_cnt));
+// The head: the row stage over all n rows (rows == NULL) or over the m listed ones, then the finish stage with the number
+// of scored entries as the divisor.
+static int launch_val_head(const float *Z, long ldz, const int32_t *labels, int n, int C, const int32_t *rows, int m,
+                           float *part_loss, int32_t *part_cnt, float *loss_out, int32_t *conf_out, int32_t *n_bad,
+                           int32_t *state, int patience, int epoch, hipStream_t st) {
+    const int cnt = rows ? m : n, n_blk = (cnt + TR_BLOCK - 1) / TR_BLOCK;
+    const dim3 grid((unsigned)n_blk), block(TR_BLOCK);
+    if (rows) {
+        LT_DISPATCH_CP(lt_cp_for(C), hipLaunchKernelGGL((k_val_rows<CP_, true>), grid, block, 0, st, n, m, rows, Z, ldz, C, labels,
+                                                        part_loss, part_cnt, n_bad));
+    } else {
+        LT_DISPATCH_CP(lt_cp_for(C), hipLaunchKernelGGL((k_val_rows<CP_, false>), grid, block, 0, st, n, m, rows, Z, ldz, C, labels,
+                                                        part_loss, part_cnt, n_bad));
+    }
     LT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_val_finish, dim3(1), dim3(TR_BLOCK), 0, st, n_blk, n, C, part_loss, part_cnt, loss_out, conf_out,
-                       state, patience, epoch);
-    LT_CHECK_LAUNCH();
-    return LT_OK;
-}
-
-// the head over a row list: k_val_rows_list over ceil(m / 256) blocks, then the finish stage with m as the divisor
-static int launch_val_head_rows(const float *Z, long ldz, const int32_t *labels, int n, int C, const int32_t *rows, int m,
-                                float *part_loss, int32_t *part_cnt, float *loss_out, int32_t *conf_out, int32_t *n_bad,
-                                int32_t *state, int patience, int epoch, hipStream_t st) {
-    const int n_blk = (m + TR_BLOCK - 1) / TR_BLOCK;
-    LT_DISPATCH_CP(lt_cp_for(C), hipLaunchKernelGGL((k_val_rows_list<CP_>), dim3((unsigned)n_blk), dim3(TR_BLOCK), 0, st, n, m,
-                                                    rows, Z, ldz, C, labels, part_loss, part_cnt, n_bad));
-    LT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_val_finish, dim3(1), dim3(TR_BLOCK), 0, st, n_blk, m, C, part_loss, part_cnt, loss_out, conf_out,
+    hipLaunchKernelGGL(k_val_finish, dim3(1), dim3(TR_BLOCK), 0, st, n_blk, cnt, C, part_loss, part_cnt, loss_out, conf_out,
                        state, patience, epoch);
     LT_CHECK_LAUNCH();
     return LT_OK;
 }
 
 // --------------------------------------------------------------------------------------------
-// trainer state
+// The front layer of GCN3 and its backward
 // --------------------------------------------------------------------------------------------
-struct lt_gcn2_trainer {
-    const lt_graph *g = nullptr;
-    int32_t n = 0, F = 0, H = 0, C = 0, Hp = 0;
-    const float *X = nullptr;
-    int64_t ldx = 0;
-    const int32_t *labels = nullptr;
-    float *W1 = nullptr, *b1 = nullptr, *W2 = nullptr, *b2 = nullptr;
-    double lr = 0, wd = 0, p = 0;
-    uint64_t seed = 0;
-    int64_t epoch = 0;            // epochs run since creation (= Adam's step count)
-    int32_t kslice = 0;           // split-K slicing of X W1 (the forward's)
-    int32_t tn_kslice = 0, tn_splits = 0;
-    int32_t n_part = 0;           // row blocks of k_tr_bwd_rows
-    float *S1 = nullptr, *Z1 = nullptr, *H1d = nullptr, *dZ1 = nullptr, *dS1 = nullptr;   // [n, Hp]
-    float *S2 = nullptr, *Z2 = nullptr, *dZ2 = nullptr, *dS2 = nullptr;                   // [n, C]
-    float *loss_r = nullptr;
-    int32_t *corr_r = nullptr;
-    float *b1p = nullptr, *W2p = nullptr;
-    float *slabs = nullptr, *tn_slabs = nullptr, *part = nullptr, *seg_part = nullptr;
-    float *grad = nullptr, *m = nullptr, *v = nullptr;   // [F*H | H | H*C | C]
-    int64_t n_param = 0;
-    lt_val *val = nullptr;        // lt_gcn2_trainer_attach_validation (owned)
-};
-
-static void free_trainer(lt_gcn2_trainer *t) {
-    if (!t) return;
-    free_val(t->val);
-    float *bufs[] = {t->S1, t->Z1, t->H1d, t->dZ1, t->dS1, t->S2, t->Z2, t->dZ2, t->dS2, t->loss_r, t->b1p, t->W2p,
-                     t->slabs, t->tn_slabs, t->part, t->seg_part, t->grad, t->m, t->v};
-    for (float *b : bufs) (void)hipFree(b);
-    (void)hipFree(t->corr_r);
-    delete t;
-}
-
-static int tn_pick_splits(int M, int N, int K) {
-    // about two blocks per CU over the 256 CUs, slices of at least 256 rows
-    const long tiles = (long)((M + TN_BM - 1) / TN_BM) * ((N + TN_BN - 1) / TN_BN);
-    long s = (512 + tiles - 1) / tiles;
-    s = s < 1 ? 1 : s > 16 ? 16 : s;
-    while (s > 1 && (K + s - 1) / s < 256) --s;
-    return (int)s;
-}
-
-extern "C" int lt_gcn2_trainer_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const int32_t *labels,
-                                      int32_t H, int32_t C, float *W1, float *b1, float *W2, float *b2, double lr,
-                                      double weight_decay, double dropout, uint64_t seed, void *stream,
-                                      lt_gcn2_trainer **out) {
-    LT_REQUIRE(out != nullptr, "lt_gcn2_trainer_create: out is NULL");
-    *out = nullptr;
-    LT_REQUIRE(g != nullptr, "lt_gcn2_trainer_create: graph is NULL");
-    LT_REQUIRE(F > 0 && H > 0 && C > 0, "lt_gcn2_trainer_create: F=%d H=%d C=%d must be positive", F, H, C);
-    LT_REQUIRE(H <= LT_MAX_H && C <= LT_MAX_C, "lt_gcn2_trainer_create: H=%d C=%d (supported: H <= %d, C <= %d)", H, C,
-               LT_MAX_H, LT_MAX_C);
-    LT_REQUIRE(X && labels && W1 && b1 && W2 && b2, "lt_gcn2_trainer_create: NULL tensor pointer");
-    LT_REQUIRE(ldx >= F, "lt_gcn2_trainer_create: ldx=%lld < F=%d", (long long)ldx, F);
-    LT_REQUIRE(dropout >= 0.0 && dropout <= 1.0, "lt_gcn2_trainer_create: dropout=%g outside [0, 1]", dropout);
-    LT_REQUIRE(lr >= 0.0 && weight_decay >= 0.0, "lt_gcn2_trainer_create: lr=%g weight_decay=%g", lr, weight_decay);
-    LT_REQUIRE(g->n > 0, "lt_gcn2_trainer_create: empty graph");
-    lt_gcn2_trainer *t = new (std::nothrow) lt_gcn2_trainer();
-    if (!t) return lt_set_error(LT_ERR_NOMEM, "lt_gcn2_trainer_create: out of host memory");
-    t->g = g; t->n = g->n; t->F = F; t->H = H; t->C = C; t->Hp = lt_round_up(H, 4);
-    t->X = X; t->ldx = ldx; t->labels = labels;
-    t->W1 = W1; t->b1 = b1; t->W2 = W2; t->b2 = b2;
-    t->lr = lr; t->wd = weight_decay; t->p = dropout; t->seed = seed;
-    t->kslice = lt_gemm_pick_kslice(t->n, H, F);
-    t->tn_splits = tn_pick_splits(F, H, t->n);
-    t->tn_kslice = lt_round_up((t->n + t->tn_splits - 1) / t->tn_splits, TN_BK);
-    t->tn_splits = (t->n + t->tn_kslice - 1) / t->tn_kslice;
-    t->n_part = (t->n + TR_ROWS_PER_BLOCK - 1) / TR_ROWS_PER_BLOCK;
-    t->n_param = (int64_t)F * H + H + (int64_t)H * C + C;
-    const size_t nh = (size_t)t->n * t->Hp * sizeof(float), nc = (size_t)t->n * C * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-#define T_HIP(call)                                                                         \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            free_trainer(t);                                                                \
-            return lt_set_error(LT_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-        }                                                                                   \
-    } while (0)
-    float **hbufs[] = {&t->S1, &t->Z1, &t->H1d, &t->dZ1, &t->dS1};
-    for (float **b : hbufs) T_HIP(hipMalloc((void **)b, nh));
-    float **cbufs[] = {&t->S2, &t->Z2, &t->dZ2, &t->dS2};
-    for (float **b : cbufs) T_HIP(hipMalloc((void **)b, nc));
-    T_HIP(hipMalloc((void **)&t->loss_r, (size_t)t->n * sizeof(float)));
-    T_HIP(hipMalloc((void **)&t->corr_r, (size_t)t->n * sizeof(int32_t)));
-    T_HIP(hipMalloc((void **)&t->b1p, (size_t)t->Hp * sizeof(float)));
-    T_HIP(hipMalloc((void **)&t->W2p, (size_t)t->Hp * C * sizeof(float)));
-    const size_t sb = lt_gemm_splitk_slab_bytes(t->n, H, F, t->kslice);
-    if (sb) T_HIP(hipMalloc((void **)&t->slabs, sb));
-    if (t->tn_splits > 1) T_HIP(hipMalloc((void **)&t->tn_slabs, (size_t)t->tn_splits * F * H * sizeof(float)));
-    T_HIP(hipMalloc((void **)&t->part, (size_t)t->n_part * ((size_t)H + (size_t)H * C) * sizeof(float)));
-    if (g->p_n_seg > 0) T_HIP(hipMalloc((void **)&t->seg_part, (size_t)g->p_n_seg * t->Hp * sizeof(float)));
-    float **pbufs[] = {&t->grad, &t->m, &t->v};
-    for (float **b : pbufs) T_HIP(hipMalloc((void **)b, (size_t)t->n_param * sizeof(float)));
-    // pad columns of S1 (the GEMM writes H of them) and the moments start at zero
-    T_HIP(hipMemsetAsync(t->S1, 0, nh, st));
-    T_HIP(hipMemsetAsync(t->m, 0, (size_t)t->n_param * sizeof(float), st));
-    T_HIP(hipMemsetAsync(t->v, 0, (size_t)t->n_param * sizeof(float), st));
-#undef T_HIP
-    *out = t;
-    return LT_OK;
-}
-
-extern "C" int lt_gcn2_trainer_destroy(lt_gcn2_trainer *t) {
-    free_trainer(t);
-    return LT_OK;
-}
-
-extern "C" int lt_gcn2_trainer_epoch(const lt_gcn2_trainer *t, int64_t *epoch) {
-    LT_REQUIRE(t != nullptr && epoch != nullptr, "lt_gcn2_trainer_epoch: NULL argument");
-    *epoch = t->epoch;
-    return LT_OK;
-}
-
-static unsigned rows_grid(int n, int rows_per_block) { return (unsigned)((n + rows_per_block - 1) / rows_per_block); }
-
-static int run_epoch(lt_gcn2_trainer *t, float *record, hipStream_t st) {
-    const lt_graph *g = t->g;
-    const int n = t->n, F = t->F, H = t->H, C = t->C, Hp = t->Hp;
-    const int lpr = lt_lpr_for(Hp), cp = lt_cp_for(C);
-    const int rpb = (TR_BLOCK / 64) * (64 / lpr);
-    int rc;
-    // forward: the launches of lt_gcn2_forward
-    if (t->slabs)
-        rc = lt_launch_gemm_splitk(t->X, t->ldx, t->W1, H, t->S1, Hp, n, H, F, t->kslice, t->slabs, st);
-    else
-        rc = lt_launch_gemm(t->X, t->ldx, t->W1, H, t->S1, Hp, n, H, F, st);
-    if (rc) return rc;
-    rc = lt_launch_layer1(g, t->S1, Hp, t->b1p, t->W2p, C, t->Z1, t->S2, st, t->seg_part);
-    if (rc) return rc;
-    lt_drop_args d;
-    d.on = t->p > 0.0;
-    d.thresh = (uint64_t)floor(t->p * 4294967296.0);
-    d.scale = t->p < 1.0 ? (float)(1.0 / (1.0 - t->p)) : 0.f;
-    d.epoch = (uint32_t)t->epoch;
-    d.seed = t->seed;
-    LT_DISPATCH_LPR(lpr, LT_DISPATCH_CP(cp,
-        hipLaunchKernelGGL((k_tr_dropout<LPR_, CP_>), dim3(rows_grid(n, rpb)), dim3(TR_BLOCK), 0, st, n, t->Z1, Hp, H, t->W2p,
-                           C, d, t->H1d, t->S2)));
-    LT_CHECK_LAUNCH();
-    rc = lt_launch_layer2(g, t->S2, C, t->b2, t->Z2, st);
-    if (rc) return rc;
-    // loss head
-    float *gW1 = t->grad, *gb1 = gW1 + (size_t)F * H, *gW2 = gb1 + H, *gb2 = gW2 + (size_t)H * C;
-    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_ce<CP_>), dim3(rows_grid(n, TR_BLOCK)), dim3(TR_BLOCK), 0, st, n, t->Z2, C,
-                                          t->labels, 1.0f / (float)n, t->loss_r, t->corr_r, t->dZ2));
-    LT_CHECK_LAUNCH();
-    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_ce_reduce<CP_>), dim3(1), dim3(TR_BLOCK), 0, st, n, C, t->loss_r, t->corr_r,
-                                          t->dZ2, record, gb2));
-    LT_CHECK_LAUNCH();
-    // backward
-    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_spmm_t_narrow<CP_>), dim3(rows_grid(n, TR_BLOCK / LT_L2_LANES)),
-                                          dim3(TR_BLOCK), 0, st, n, g->tptr, g->trow, g->tval, t->dZ2, C, t->dS2));
-    LT_CHECK_LAUNCH();
-    int W = 1;
-    while (W < Hp) W <<= 1;
-    const float scale = t->p > 0.0 ? (t->p < 1.0 ? (float)(1.0 / (1.0 - t->p)) : 0.f) : 1.f;
-    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_bwd_rows<CP_>), dim3((unsigned)t->n_part), dim3(TR_BLOCK), 0, st, n, H, Hp, W,
-                                          C, t->H1d, t->dS2, t->W2p, scale, t->dZ1, t->part));
-    LT_CHECK_LAUNCH();
-    const int L = H + H * C;   // db1 | dW2: adjacent in the gradient buffer
-    hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((L + 63) / 64)), dim3(TR_BLOCK), 0, st, t->part, t->n_part, L, gb1);
-    LT_CHECK_LAUNCH();
-    LT_DISPATCH_LPR(lpr, hipLaunchKernelGGL((k_tr_spmm_t_wide<LPR_>), dim3(rows_grid(n, rpb)), dim3(TR_BLOCK), 0, st, n,
-                                            g->tptr, g->trow, g->tval, t->dZ1, Hp, t->dS1));
-    LT_CHECK_LAUNCH();
-    {
-        const bool split = t->tn_splits > 1;
-        dim3 grid((unsigned)((F + TN_BM - 1) / TN_BM), (unsigned)((H + TN_BN - 1) / TN_BN), (unsigned)t->tn_splits);
-        hipLaunchKernelGGL(k_gemm_tn_mfma, grid, dim3(256), 0, st, t->X, (long)t->ldx, t->dS1, (long)Hp,
-                           split ? t->tn_slabs : gW1, (long)H, F, H, n, t->tn_kslice, (long)F * H);
-        LT_CHECK_LAUNCH();
-        if (split) {
-            rc = lt_launch_sum_slabs(t->tn_slabs, (long)F * H, t->tn_splits, F, H, (long)H, gW1, (long)H, st);
-            if (rc) return rc;
-        }
-    }
-    // Adam
-    const int64_t step = t->epoch + 1;
-    const int64_t o1 = (int64_t)F * H, o2 = o1 + H, o3 = o2 + (int64_t)H * C;
-    hipLaunchKernelGGL(k_tr_adam, dim3((unsigned)((t->n_param + 255) / 256)), dim3(256), 0, st, t->n_param, o1, o2, o3,
-                       t->W1, t->b1, t->W2, t->b2, t->grad, t->m, t->v, t->b1p, t->W2p,
-                       adam_scalars(step, t->lr, 0.9, 0.999, 1e-8, t->wd));
-    LT_CHECK_LAUNCH();
-    t->epoch = step;
-    return LT_OK;
-}
-
-extern "C" int lt_gcn2_trainer_run(lt_gcn2_trainer *t, int32_t n_epochs, float *record, void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_run: trainer is NULL");
-    LT_REQUIRE(n_epochs >= 0, "lt_gcn2_trainer_run: n_epochs=%d", n_epochs);
-    if (n_epochs == 0) return LT_OK;
-    LT_REQUIRE(record != nullptr, "lt_gcn2_trainer_run: record is NULL");
-    LT_REQUIRE(t->epoch + n_epochs <= (int64_t)UINT32_MAX, "lt_gcn2_trainer_run: epoch counter would pass 2^32");
-    hipStream_t st = (hipStream_t)stream;
-    // the borrowed parameters may have changed since the last run: b1p / W2p from them (Adam keeps them current after that)
-    hipLaunchKernelGGL(k_tr_pad, dim3((t->Hp * (t->C + 1) + 255) / 256), dim3(256), 0, st, t->b1, t->W2, t->H, t->Hp, t->C,
-                       t->b1p, t->W2p);
-    LT_CHECK_LAUNCH();
-    for (int32_t j = 0; j < n_epochs; ++j) {
-        const int rc = run_epoch(t, record + 2 * (size_t)j, st);
-        if (rc) return rc;
-    }
-    return LT_OK;
-}
-
-extern "C" int lt_gcn2_trainer_grads(const lt_gcn2_trainer *t, float *dW1, float *db1, float *dW2, float *db2, void *stream) {
-    LT_REQUIRE(t != nullptr && dW1 && db1 && dW2 && db2, "lt_gcn2_trainer_grads: NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t fh = (size_t)t->F * t->H, hc = (size_t)t->H * t->C;
-    LT_HIP(hipMemcpyAsync(dW1, t->grad, fh * sizeof(float), hipMemcpyDeviceToDevice, st));
-    LT_HIP(hipMemcpyAsync(db1, t->grad + fh, (size_t)t->H * sizeof(float), hipMemcpyDeviceToDevice, st));
-    LT_HIP(hipMemcpyAsync(dW2, t->grad + fh + t->H, hc * sizeof(float), hipMemcpyDeviceToDevice, st));
-    LT_HIP(hipMemcpyAsync(db2, t->grad + fh + t->H + hc, (size_t)t->C * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return LT_OK;
-}
-
-extern "C" int lt_gcn2_trainer_logits(const lt_gcn2_trainer *t, float *Z2, int64_t ldz, void *stream) {
-    LT_REQUIRE(t != nullptr && Z2 != nullptr, "lt_gcn2_trainer_logits: NULL argument");
-    LT_REQUIRE(ldz >= t->C, "lt_gcn2_trainer_logits: ldz=%lld < C=%d", (long long)ldz, t->C);
-    LT_HIP(hipMemcpy2DAsync(Z2, (size_t)ldz * sizeof(float), t->Z2, (size_t)t->C * sizeof(float), (size_t)t->C * sizeof(float),
-                            (size_t)t->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return LT_OK;
-}
-
-// ============================================================================================
-// Training of the 3-layer GCN (reference gcn/models.py:28-46): the 2-layer epoch one layer up.
-//
-//   S1 = X W1                      lt_launch_gemm(_splitk)        the 2-layer trainer's product
-//   H1d = drop_0(relu(A S1 + b1))  k_tr3_layer1 (+ _long)         row_dot chains from the bias, ReLU and the Philox mask (layer
-//                                                                 word 0) as the epilogue: Z1 never exists in memory
-//   S2 = H1d W2                    lt_launch_gemm
-//   Z2 = A S2 + b2                 lt_launch_layer1 (Z2 stored)
-//   H2d = drop_1(relu(Z2)), S3     k_tr_dropout, layer word 1
-//   Z3 = A S3 + b3                 lt_launch_layer2
-//   loss, dZ3, db3, correct        k_tr_ce, k_tr_ce_reduce
-//   dS3 = A^T dZ3                  k_tr_spmm_t_narrow
-//   dZ2, db2 | dW3                 k_tr_bwd_rows(H2d, dS3, W3p) + k_tr_colsum
-//   dS2 = A^T dZ2                  k_tr_spmm_t_wide
-//   dW2 = H1d^T dS2                k_gemm_tn_mfma + k_sum_slabs
-//   dZ1 = [H1d > 0] scale (dS2 W2^T), db1 slabs     k_tr3_dz_mfma, then k_tr_colsum
-//   dS1 = A^T dZ1; dW1 = X^T dS1   k_tr_spmm_t_wide, k_gemm_tn_mfma + k_sum_slabs
-//   Adam                           k_tr3_adam                     one launch over W1 | b1 | W2 | b2 | W3 | b3 and the padded copies
-// ============================================================================================
 
 // H1d[r] = drop(relu(A[r, :] S + bias)) for every row.  The launch's first seg_blocks blocks take the SEGMENTS of the hub rows
 // (k_layer1's scheme: row_dot's canonical order, the first segment's chain started from the bias); k_tr3_layer1_long adds
@@ -1209,333 +978,334 @@ __global__ __launch_bounds__(256) void k_tr3_dz_mfma(const float *__restrict__ A
     if (tid < TN_BN && n0 + tid < N) part[(size_t)blockIdx.x * N + n0 + tid] = red[0][tid] + red[1][tid];
 }
 
-// The six parameter tensors in one launch: index i of the concatenation W1 | b1 | W2 | b2 | W3 | b3 (o[k] = where tensor
-// k ends).  The copies the row kernels read follow the update: b1p [Hp1], b2p [Hp2], W3p [Hp2, C] (zero-padded).
-struct lt_tr3_tensors {
-    float *p[6];
-    int64_t o[6];
-    float *b1p, *b2p, *W3p;
+// --------------------------------------------------------------------------------------------
+// trainer state: one struct behind both public handles
+// --------------------------------------------------------------------------------------------
+struct lt_tn {                    // one dW = A^T B product over K = n rows
+    int32_t kslice = 0, splits = 0;
+    float *slabs = nullptr;       // [splits, M, N] when splits > 1
 };
 
-__global__ void k_tr3_adam(lt_tr3_tensors T, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
-                           lt_adam_scalars s) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= T.o[5]) return;
-    const int k = i < T.o[0] ? 0 : i < T.o[1] ? 1 : i < T.o[2] ? 2 : i < T.o[3] ? 3 : i < T.o[4] ? 4 : 5;
-    const int64_t j = k ? i - T.o[k - 1] : i;
-    float *p;      // a switch over constant indices: T.p[k] with a run-time k would move the argument struct to scratch
-    switch (k) {
-        case 0: p = T.p[0]; break;
-        case 1: p = T.p[1]; break;
-        case 2: p = T.p[2]; break;
-        case 3: p = T.p[3]; break;
-        case 4: p = T.p[4]; break;
-        default: p = T.p[5]; break;
-    }
-    float mi = m[i], vi = v[i];
-    const float np = adam_elem(p[j], g[i], mi, vi, s);
-    p[j] = np;
-    m[i] = mi;
-    v[i] = vi;
-    if (k == 1) T.b1p[j] = np;
-    else if (k == 3) T.b2p[j] = np;
-    else if (k == 4) T.W3p[j] = np;
-}
-
-__global__ void k_tr3_pad(const float *__restrict__ b1, int H1, int Hp1, const float *__restrict__ b2, int H2, int Hp2, const float *__restrict__ W3, int C,
-                          float *__restrict__ b1p, float *__restrict__ b2p, float *__restrict__ W3p) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < Hp1) b1p[i] = i < H1 ? b1[i] : 0.f;
-    if (i < Hp2) b2p[i] = i < H2 ? b2[i] : 0.f;
-    if (i < Hp2 * C) W3p[i] = (i / C) < H2 ? W3[i] : 0.f;
-}
-
-struct lt_gcn3_trainer {
+struct lt_trainer {
     const lt_graph *g = nullptr;
-    int32_t n = 0, F = 0, H1 = 0, H2 = 0, C = 0, Hp1 = 0, Hp2 = 0;
+    int32_t layers = 0;           // 2 (GCN) or 3 (GCN3); top = layers - 2 is the number of hidden layers in front of the top chain
+    int32_t n = 0, F = 0, C = 0;
+    int32_t H[2] = {0, 0}, Hp[2] = {0, 0};   // hidden widths in model order, and rounded up to 4; the top chain's is [top]
     const float *X = nullptr;
     int64_t ldx = 0;
     const int32_t *labels = nullptr;
     float *P[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // W1, b1, W2, b2, W3, b3 (borrowed)
-    int64_t off[6] = {0, 0, 0, 0, 0, 0};                                    // where each ends in grad / m / v
+    int64_t off[6] = {0, 0, 0, 0, 0, 0};                                    // where each ends in grad / m / v; off[5]: all of them
     double lr = 0, wd = 0, p = 0;
     uint64_t seed = 0;
-    int64_t epoch = 0;
-    int32_t kslice = 0;                       // split-K slicing of X W1 (the forward's)
-    int32_t tn1_kslice = 0, tn1_splits = 0;   // dW1 = X^T dS1
-    int32_t tn2_kslice = 0, tn2_splits = 0;   // dW2 = H1d^T dS2
-    int32_t n_part = 0;                       // row blocks of k_tr_bwd_rows (layer 2)
-    int32_t n_mblk = 0;                       // row blocks of k_tr3_dz_mfma
-    float *S1 = nullptr, *H1d = nullptr, *dZ1 = nullptr, *dS1 = nullptr;                        // [n, Hp1]
-    float *S2 = nullptr, *Z2 = nullptr, *H2d = nullptr, *dZ2 = nullptr, *dS2 = nullptr;         // [n, Hp2]
-    float *S3 = nullptr, *Z3 = nullptr, *dZ3 = nullptr, *dS3 = nullptr;                         // [n, C]
+    int64_t epoch = 0;            // epochs run since creation (= Adam's step count)
+    int32_t kslice = 0;           // split-K slicing of X W1 (the forward's)
+    lt_tn tn[2];                  // dW1 = X^T dS1; GCN3: dW2 = Hf^T dS
+    int32_t n_part = 0;           // row blocks of k_tr_bwd_rows
+    int32_t n_mblk = 0;           // row blocks of k_tr3_dz_mfma
+    int32_t n_seg = 0;            // the graph's hub-row segments at creation (g->p_n_seg): the rows of seg_part
+    float *S = nullptr, *Z = nullptr, *Hd = nullptr, *dZ = nullptr, *dS = nullptr;    // top chain, [n, Hp[top]]
+    float *Sc = nullptr, *Zc = nullptr, *dZc = nullptr, *dSc = nullptr;               // top chain, [n, C]
+    float *fS = nullptr, *fHd = nullptr, *fdZ = nullptr, *fdS = nullptr;              // front layer (GCN3), [n, Hp[0]]
     float *loss_r = nullptr;
     int32_t *corr_r = nullptr;
-    float *b1p = nullptr, *b2p = nullptr, *W3p = nullptr;
-    float *slabs = nullptr, *tn1_slabs = nullptr, *tn2_slabs = nullptr, *part = nullptr, *part1 = nullptr, *seg_part = nullptr;
-    float *grad = nullptr, *m = nullptr, *v = nullptr;
-    lt_val *val = nullptr;                    // lt_gcn3_trainer_attach_validation (owned)
+    // owned: mir[k] is the zero-padded copy of segment k the row kernels read, mir_len[k] floats (b1, and the top chain's
+    // b and Wc); NULL / 0 for the other segments
+    float *mir[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int32_t mir_len[6] = {0, 0, 0, 0, 0, 0};
+    float *slabs = nullptr, *part = nullptr, *part1 = nullptr, *seg_part = nullptr;
+    float *grad = nullptr, *m = nullptr, *v = nullptr;   // [off[5]]
+    lt_val *val = nullptr;        // lt_gcn*_trainer_attach_validation (owned)
 };
+struct lt_gcn2_trainer : lt_trainer {};
+struct lt_gcn3_trainer : lt_trainer {};
 
-static void free_trainer3(lt_gcn3_trainer *t) {
-    if (!t) return;
-    free_val(t->val);
-    float *bufs[] = {t->S1, t->H1d, t->dZ1, t->dS1, t->S2, t->Z2, t->H2d, t->dZ2, t->dS2, t->S3, t->Z3, t->dZ3, t->dS3,
-                     t->loss_r, t->b1p, t->b2p, t->W3p, t->slabs, t->tn1_slabs, t->tn2_slabs, t->part, t->part1,
-                     t->seg_part, t->grad, t->m, t->v};
-    for (float *b : bufs) (void)hipFree(b);
-    (void)hipFree(t->corr_r);
-    delete t;
+// Every device buffer a trainer owns: where its pointer lives, its size (0: not allocated) and whether it starts at zero.
+// create walks the table to allocate, free to release.
+struct lt_buf {
+    void **slot;
+    size_t bytes;
+    bool zero;
+};
+#define TR_MAX_BUFS 32
+
+// Fills b[TR_MAX_BUFS] from the trainer's own fields (the borrowed graph is not read: destroy may come after the graph's) and
+// returns the number of entries, -1 if the table does not hold them all.
+static int trainer_bufs(lt_trainer *t, lt_buf *b) {
+    const int top = t->layers - 2, C = t->C, hpm = t->Hp[0] > t->Hp[1] ? t->Hp[0] : t->Hp[1];
+    const size_t f4 = sizeof(float), n = (size_t)t->n;
+    const size_t nt = n * t->Hp[top] * f4, nf = top ? n * t->Hp[0] * f4 : 0, nc = n * C * f4, np = (size_t)t->off[5] * f4;
+    int k = 0;
+    auto add = [&](auto *slot, size_t bytes, bool zero = false) {
+        if (k < TR_MAX_BUFS) b[k] = lt_buf{(void **)slot, bytes, zero};
+        ++k;
+    };
+    // pad columns of the products (the GEMMs write H of them) and of the front layer's dZ (its product writes H of them) stay
+    // zero; the moments start at zero
+    add(&t->fS, nf, true); add(&t->S, nt, true); add(&t->fdZ, nf, true);
+    add(&t->fHd, nf); add(&t->fdS, nf);
+    add(&t->Z, nt); add(&t->Hd, nt); add(&t->dZ, nt); add(&t->dS, nt);
+    add(&t->Sc, nc); add(&t->Zc, nc); add(&t->dZc, nc); add(&t->dSc, nc);
+    add(&t->loss_r, n * f4); add(&t->corr_r, n * sizeof(int32_t));
+    for (int s = 0; s < 6; ++s) add(&t->mir[s], (size_t)t->mir_len[s] * f4);
+    add(&t->slabs, lt_gemm_splitk_slab_bytes(t->n, t->H[0], t->F, t->kslice));
+    add(&t->tn[0].slabs, t->tn[0].splits > 1 ? (size_t)t->tn[0].splits * t->F * t->H[0] * f4 : 0);
+    add(&t->tn[1].slabs, t->tn[1].splits > 1 ? (size_t)t->tn[1].splits * t->H[0] * t->H[1] * f4 : 0);
+    add(&t->part, (size_t)t->n_part * ((size_t)t->H[top] + (size_t)t->H[top] * C) * f4);
+    add(&t->part1, top ? (size_t)t->n_mblk * t->H[0] * f4 : 0);
+    add(&t->seg_part, (size_t)t->n_seg * hpm * f4);
+    add(&t->grad, np); add(&t->m, np, true); add(&t->v, np, true);
+    return k <= TR_MAX_BUFS ? k : -1;
 }
 
-extern "C" int lt_gcn3_trainer_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const int32_t *labels,
-                                      int32_t H1, int32_t H2, int32_t C, float *W1, float *b1, float *W2, float *b2,
-                                      float *W3, float *b3, double lr, double weight_decay, double dropout, uint64_t seed,
-                                      void *stream, lt_gcn3_trainer **out) {
-    LT_REQUIRE(out != nullptr, "lt_gcn3_trainer_create: out is NULL");
-    *out = nullptr;
-    LT_REQUIRE(g != nullptr, "lt_gcn3_trainer_create: graph is NULL");
-    LT_REQUIRE(F > 0 && H1 > 0 && H2 > 0 && C > 0, "lt_gcn3_trainer_create: F=%d H1=%d H2=%d C=%d must be positive", F, H1,
-               H2, C);
-    LT_REQUIRE(H1 <= LT_MAX_H && H2 <= LT_MAX_H && C <= LT_MAX_C,
-               "lt_gcn3_trainer_create: H1=%d H2=%d C=%d (supported: H1, H2 <= %d, C <= %d)", H1, H2, C, LT_MAX_H, LT_MAX_C);
-    LT_REQUIRE(X && labels && W1 && b1 && W2 && b2 && W3 && b3, "lt_gcn3_trainer_create: NULL tensor pointer");
-    LT_REQUIRE(ldx >= F, "lt_gcn3_trainer_create: ldx=%lld < F=%d", (long long)ldx, F);
-    LT_REQUIRE(dropout >= 0.0 && dropout <= 1.0, "lt_gcn3_trainer_create: dropout=%g outside [0, 1]", dropout);
-    LT_REQUIRE(lr >= 0.0 && weight_decay >= 0.0, "lt_gcn3_trainer_create: lr=%g weight_decay=%g", lr, weight_decay);
-    LT_REQUIRE(g->n > 0, "lt_gcn3_trainer_create: empty graph");
-    lt_gcn3_trainer *t = new (std::nothrow) lt_gcn3_trainer();
-    if (!t) return lt_set_error(LT_ERR_NOMEM, "lt_gcn3_trainer_create: out of host memory");
-    const int n = g->n;
-    t->g = g; t->n = n; t->F = F; t->H1 = H1; t->H2 = H2; t->C = C;
-    t->Hp1 = lt_round_up(H1, 4); t->Hp2 = lt_round_up(H2, 4);
+static void free_trainer(lt_trainer *t) {
+    if (!t) return;
+    free_val(t->val);
+    lt_buf b[TR_MAX_BUFS];
+    const int nb = trainer_bufs(t, b);
+    for (int k = 0; k < nb; ++k) (void)hipFree(*b[k].slot);
+    if (t->layers == 3) delete static_cast<lt_gcn3_trainer *>(t);
+    else delete static_cast<lt_gcn2_trainer *>(t);
+}
+
+static int tn_pick_splits(int M, int N, int K) {
+    // about two blocks per CU over the 256 CUs, slices of at least 256 rows
+    const long tiles = (long)((M + TN_BM - 1) / TN_BM) * ((N + TN_BN - 1) / TN_BN);
+    long s = (512 + tiles - 1) / tiles;
+    s = s < 1 ? 1 : s > 16 ? 16 : s;
+    while (s > 1 && (K + s - 1) / s < 256) --s;
+    return (int)s;
+}
+
+static void tn_plan(lt_tn *tn, int M, int N, int K) {
+    tn->splits = tn_pick_splits(M, N, K);
+    tn->kslice = lt_round_up((K + tn->splits - 1) / tn->splits, TN_BK);
+    tn->splits = (K + tn->kslice - 1) / tn->kslice;
+}
+
+// What both lt_gcn*_trainer_create share, behind the checks whose wording names the model's widths.  Hs: the hidden widths
+// (Hs[1] = 0 for the 2-layer model), ps: the 2 * layers parameter tensors.
+static int trainer_create(const char *who, int layers, const lt_graph *g, const float *X, int64_t ldx, int32_t F,
+                          const int32_t *labels, const int32_t *Hs, int32_t C, float *const *ps, double lr, double weight_decay,
+                          double dropout, uint64_t seed, void *stream, lt_trainer **out) {
+    LT_REQUIRE(ldx >= F, "%s: ldx=%lld < F=%d", who, (long long)ldx, F);
+    LT_REQUIRE(dropout >= 0.0 && dropout <= 1.0, "%s: dropout=%g outside [0, 1]", who, dropout);
+    LT_REQUIRE(lr >= 0.0 && weight_decay >= 0.0, "%s: lr=%g weight_decay=%g", who, lr, weight_decay);
+    LT_REQUIRE(g->n > 0, "%s: empty graph", who);
+    lt_trainer *t = layers == 3 ? static_cast<lt_trainer *>(new (std::nothrow) lt_gcn3_trainer())
+                                : static_cast<lt_trainer *>(new (std::nothrow) lt_gcn2_trainer());
+    if (!t) return lt_set_error(LT_ERR_NOMEM, "%s: out of host memory", who);
+    const int n = g->n, top = layers - 2;
+    t->g = g; t->layers = layers; t->n = n; t->F = F; t->C = C;
     t->X = X; t->ldx = ldx; t->labels = labels;
-    float *ps[6] = {W1, b1, W2, b2, W3, b3};
-    const int64_t sizes[6] = {(int64_t)F * H1, H1, (int64_t)H1 * H2, H2, (int64_t)H2 * C, C};
+    const int dims[4] = {F, Hs[0], top ? Hs[1] : C, C};      // layer l maps dims[l] to dims[l + 1] columns
     int64_t end = 0;
-    for (int k = 0; k < 6; ++k) { t->P[k] = ps[k]; end += sizes[k]; t->off[k] = end; }
+    for (int l = 0; l < 3; ++l) {
+        const bool have = l < layers;
+        if (l <= top) { t->H[l] = dims[l + 1]; t->Hp[l] = lt_round_up(dims[l + 1], 4); }
+        t->P[2 * l] = have ? ps[2 * l] : nullptr;
+        t->off[2 * l] = end += have ? (int64_t)dims[l] * dims[l + 1] : 0;
+        t->P[2 * l + 1] = have ? ps[2 * l + 1] : nullptr;
+        t->off[2 * l + 1] = end += have ? dims[l + 1] : 0;
+    }
     t->lr = lr; t->wd = weight_decay; t->p = dropout; t->seed = seed;
-    t->kslice = lt_gemm_pick_kslice(n, H1, F);
-    t->tn1_splits = tn_pick_splits(F, H1, n);
-    t->tn1_kslice = lt_round_up((n + t->tn1_splits - 1) / t->tn1_splits, TN_BK);
-    t->tn1_splits = (n + t->tn1_kslice - 1) / t->tn1_kslice;
-    t->tn2_splits = tn_pick_splits(H1, H2, n);
-    t->tn2_kslice = lt_round_up((n + t->tn2_splits - 1) / t->tn2_splits, TN_BK);
-    t->tn2_splits = (n + t->tn2_kslice - 1) / t->tn2_kslice;
+    t->kslice = lt_gemm_pick_kslice(n, t->H[0], F);
+    tn_plan(&t->tn[0], F, t->H[0], n);
+    if (top) tn_plan(&t->tn[1], t->H[0], t->H[1], n);
     t->n_part = (n + TR_ROWS_PER_BLOCK - 1) / TR_ROWS_PER_BLOCK;
     t->n_mblk = (n + TN_BM - 1) / TN_BM;
-    const size_t nh1 = (size_t)n * t->Hp1 * sizeof(float), nh2 = (size_t)n * t->Hp2 * sizeof(float);
-    const size_t nc = (size_t)n * C * sizeof(float), np_bytes = (size_t)end * sizeof(float);
-    const int hpm = t->Hp1 > t->Hp2 ? t->Hp1 : t->Hp2;
+    t->n_seg = g->p_n_seg > 0 ? g->p_n_seg : 0;
+    t->mir_len[1] = t->Hp[0];
+    t->mir_len[2 * top + 1] = t->Hp[top];
+    t->mir_len[2 * top + 2] = t->Hp[top] * C;
     hipStream_t st = (hipStream_t)stream;
-#define T_HIP(call)                                                                         \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            free_trainer3(t);                                                               \
-            return lt_set_error(LT_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-        }                                                                                   \
-    } while (0)
-    float **h1bufs[] = {&t->S1, &t->H1d, &t->dZ1, &t->dS1};
-    for (float **b : h1bufs) T_HIP(hipMalloc((void **)b, nh1));
-    float **h2bufs[] = {&t->S2, &t->Z2, &t->H2d, &t->dZ2, &t->dS2};
-    for (float **b : h2bufs) T_HIP(hipMalloc((void **)b, nh2));
-    float **cbufs[] = {&t->S3, &t->Z3, &t->dZ3, &t->dS3};
-    for (float **b : cbufs) T_HIP(hipMalloc((void **)b, nc));
-    T_HIP(hipMalloc((void **)&t->loss_r, (size_t)n * sizeof(float)));
-    T_HIP(hipMalloc((void **)&t->corr_r, (size_t)n * sizeof(int32_t)));
-    T_HIP(hipMalloc((void **)&t->b1p, (size_t)t->Hp1 * sizeof(float)));
-    T_HIP(hipMalloc((void **)&t->b2p, (size_t)t->Hp2 * sizeof(float)));
-    T_HIP(hipMalloc((void **)&t->W3p, (size_t)t->Hp2 * C * sizeof(float)));
-    const size_t sb = lt_gemm_splitk_slab_bytes(n, H1, F, t->kslice);
-    if (sb) T_HIP(hipMalloc((void **)&t->slabs, sb));
-    if (t->tn1_splits > 1) T_HIP(hipMalloc((void **)&t->tn1_slabs, (size_t)t->tn1_splits * F * H1 * sizeof(float)));
-    if (t->tn2_splits > 1) T_HIP(hipMalloc((void **)&t->tn2_slabs, (size_t)t->tn2_splits * H1 * H2 * sizeof(float)));
-    T_HIP(hipMalloc((void **)&t->part, (size_t)t->n_part * ((size_t)H2 + (size_t)H2 * C) * sizeof(float)));
-    T_HIP(hipMalloc((void **)&t->part1, (size_t)t->n_mblk * H1 * sizeof(float)));
-    if (g->p_n_seg > 0) T_HIP(hipMalloc((void **)&t->seg_part, (size_t)g->p_n_seg * hpm * sizeof(float)));
-    float **pbufs[] = {&t->grad, &t->m, &t->v};
-    for (float **b : pbufs) T_HIP(hipMalloc((void **)b, np_bytes));
-    // pad columns of S1 / S2 (the GEMMs write H of them) and of dZ1 (its product writes H1 of them) stay zero
-    T_HIP(hipMemsetAsync(t->S1, 0, nh1, st));
-    T_HIP(hipMemsetAsync(t->S2, 0, nh2, st));
-    T_HIP(hipMemsetAsync(t->dZ1, 0, nh1, st));
-    T_HIP(hipMemsetAsync(t->m, 0, np_bytes, st));
-    T_HIP(hipMemsetAsync(t->v, 0, np_bytes, st));
-#undef T_HIP
+    lt_buf b[TR_MAX_BUFS];
+    const int nb = trainer_bufs(t, b);
+    if (nb < 0) {      // nothing is allocated yet
+        free_trainer(t);
+        return lt_set_error(LT_ERR_INVALID, "%s: the buffer table holds %d entries, the trainer has more", who, TR_MAX_BUFS);
+    }
+    hipError_t e = hipSuccess;
+    const char *what = "hipMalloc";
+    for (int k = 0; k < nb && e == hipSuccess; ++k)
+        if (b[k].bytes) e = hipMalloc(b[k].slot, b[k].bytes);
+    if (e == hipSuccess) what = "hipMemsetAsync";
+    for (int k = 0; k < nb && e == hipSuccess; ++k)
+        if (b[k].bytes && b[k].zero) e = hipMemsetAsync(*b[k].slot, 0, b[k].bytes, st);
+    if (e != hipSuccess) {
+        free_trainer(t);
+        return lt_set_error(LT_ERR_HIP, "%s: %s failed: %s", who, what, hipGetErrorString(e));
+    }
     *out = t;
     return LT_OK;
 }
 
-extern "C" int lt_gcn3_trainer_destroy(lt_gcn3_trainer *t) {
-    free_trainer3(t);
-    return LT_OK;
-}
+// --------------------------------------------------------------------------------------------
+// the launches of one epoch, in pieces the validation forward shares
+// --------------------------------------------------------------------------------------------
+static unsigned rows_grid(int n, int rows_per_block) { return (unsigned)((n + rows_per_block - 1) / rows_per_block); }
+static int wide_rows_per_block(int Hp) { return (TR_BLOCK / 64) * (64 / lt_lpr_for(Hp)); }
 
-extern "C" int lt_gcn3_trainer_epoch(const lt_gcn3_trainer *t, int64_t *epoch) {
-    LT_REQUIRE(t != nullptr && epoch != nullptr, "lt_gcn3_trainer_epoch: NULL argument");
-    *epoch = t->epoch;
-    return LT_OK;
-}
-
-static int launch_tn(const float *A, long lda, const float *B, long ldb, float *C, int M, int N, int K, int kslice, int splits,
-                     float *slabs, hipStream_t st) {
-    const bool split = splits > 1;
-    dim3 grid((unsigned)((M + TN_BM - 1) / TN_BM), (unsigned)((N + TN_BN - 1) / TN_BN), (unsigned)splits);
-    hipLaunchKernelGGL(k_gemm_tn_mfma, grid, dim3(256), 0, st, A, lda, B, ldb, split ? slabs : C, (long)N, M, N, K, kslice,
-                       (long)M * N);
-    LT_CHECK_LAUNCH();
-    if (split) return lt_launch_sum_slabs(slabs, (long)M * N, splits, M, N, (long)N, C, (long)N, st);
-    return LT_OK;
-}
-
-static int run_epoch3(lt_gcn3_trainer *t, float *record, hipStream_t st) {
-    const lt_graph *g = t->g;
-    const int n = t->n, F = t->F, H1 = t->H1, H2 = t->H2, C = t->C, Hp1 = t->Hp1, Hp2 = t->Hp2;
-    const int lpr1 = lt_lpr_for(Hp1), lpr2 = lt_lpr_for(Hp2), cp = lt_cp_for(C);
-    const int rpb1 = (TR_BLOCK / 64) * (64 / lpr1), rpb2 = (TR_BLOCK / 64) * (64 / lpr2);
-    float *W1 = t->P[0], *W2 = t->P[2], *b3 = t->P[5];
-    float *gW1 = t->grad, *gb1 = t->grad + t->off[0], *gW2 = t->grad + t->off[1], *gb2 = t->grad + t->off[2],
-          *gb3 = t->grad + t->off[4];
-    int rc;
+// the mask of the epoch about to run (layer word 0)
+static lt_drop_args drop_args(const lt_trainer *t) {
     lt_drop_args d;
     d.on = t->p > 0.0;
     d.thresh = (uint64_t)floor(t->p * 4294967296.0);
     d.scale = t->p < 1.0 ? (float)(1.0 / (1.0 - t->p)) : 0.f;
     d.epoch = (uint32_t)t->epoch;
     d.seed = t->seed;
-    const float scale = t->p > 0.0 ? d.scale : 1.f;
-    // layer 1
-    if (t->slabs)
-        rc = lt_launch_gemm_splitk(t->X, t->ldx, W1, H1, t->S1, Hp1, n, H1, F, t->kslice, t->slabs, st);
-    else
-        rc = lt_launch_gemm(t->X, t->ldx, W1, H1, t->S1, Hp1, n, H1, F, st);
-    if (rc) return rc;
-    {
-        const int have_long = g->p_n_long > 0 ? 1 : 0;
-        const unsigned seg_blocks = have_long ? rows_grid(g->p_n_seg, rpb1) : 0u;
-        d.layer = 0;
-        LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k_tr3_layer1<LPR_>), dim3(rows_grid(n, rpb1) + seg_blocks), dim3(TR_BLOCK), 0,
-                                                 st, n, g->rowptr, g->col, g->val, t->S1, Hp1, H1, t->b1p, d, t->H1d, have_long,
-                                                 (int)seg_blocks, g->p_n_seg, g->p_seg_long, g->p_seg_begin, g->p_long_row,
-                                                 t->seg_part));
-        LT_CHECK_LAUNCH();
-        if (have_long) {
-            LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k_tr3_layer1_long<LPR_>), dim3(rows_grid(g->p_n_long, rpb1)),
-                                                     dim3(TR_BLOCK), 0, st, g->p_n_long, g->p_long_row, g->p_long_segptr,
-                                                     t->seg_part, Hp1, H1, d, t->H1d));
-            LT_CHECK_LAUNCH();
-        }
-    }
-    // layers 2 and 3: the 2-layer trainer's chain
-    rc = lt_launch_gemm(t->H1d, Hp1, W2, H2, t->S2, Hp2, n, H2, H1, st);
-    if (rc) return rc;
-    rc = lt_launch_layer1(g, t->S2, Hp2, t->b2p, t->W3p, C, t->Z2, t->S3, st, t->seg_part);
-    if (rc) return rc;
-    d.layer = 1;
-    LT_DISPATCH_LPR(lpr2, LT_DISPATCH_CP(cp,
-        hipLaunchKernelGGL((k_tr_dropout<LPR_, CP_>), dim3(rows_grid(n, rpb2)), dim3(TR_BLOCK), 0, st, n, t->Z2, Hp2, H2, t->W3p,
-                           C, d, t->H2d, t->S3)));
+    return d;
+}
+
+// S1 = X W1 over the n rows of X, through split-K slabs where the forward slices
+static int launch_xw1(const lt_trainer *t, const float *X, int64_t ldx, int n, int kslice, float *slabs, float *S1,
+                      hipStream_t st) {
+    const int H = t->H[0];
+    if (slabs) return lt_launch_gemm_splitk(X, ldx, t->P[0], H, S1, t->Hp[0], n, H, t->F, kslice, slabs, st);
+    return lt_launch_gemm(X, ldx, t->P[0], H, S1, t->Hp[0], n, H, t->F, st);
+}
+
+// GCN3's front layer on graph g: Hf = drop(relu(A S1 + b1)), then the top chain's input S = Hf W2
+static int launch_front(const lt_trainer *t, const lt_graph *g, const float *S1, const lt_drop_args &d, float *Hf,
+                        float *seg_part, float *S, hipStream_t st) {
+    const int n = g->n, H = t->H[0], Hp = t->Hp[0], lpr = lt_lpr_for(Hp), rpb = wide_rows_per_block(Hp);
+    const int have_long = g->p_n_long > 0 ? 1 : 0;
+    const unsigned seg_blocks = have_long ? rows_grid(g->p_n_seg, rpb) : 0u;
+    LT_DISPATCH_LPR(lpr, hipLaunchKernelGGL((k_tr3_layer1<LPR_>), dim3(rows_grid(n, rpb) + seg_blocks), dim3(TR_BLOCK), 0, st, n,
+                                            g->rowptr, g->col, g->val, S1, Hp, H, t->mir[1], d, Hf, have_long, (int)seg_blocks,
+                                            g->p_n_seg, g->p_seg_long, g->p_seg_begin, g->p_long_row, seg_part));
     LT_CHECK_LAUNCH();
-    rc = lt_launch_layer2(g, t->S3, C, b3, t->Z3, st);
+    if (have_long) {
+        LT_DISPATCH_LPR(lpr, hipLaunchKernelGGL((k_tr3_layer1_long<LPR_>), dim3(rows_grid(g->p_n_long, rpb)), dim3(TR_BLOCK), 0,
+                                                st, g->p_n_long, g->p_long_row, g->p_long_segptr, seg_part, Hp, H, d, Hf));
+        LT_CHECK_LAUNCH();
+    }
+    return lt_launch_gemm(Hf, Hp, t->P[2], t->H[1], S, t->Hp[1], n, t->H[1], H, st);
+}
+
+// The top chain's forward on graph g: Z = A S + b with layer 1's own Sc = relu(Z) Wc, then (d != NULL) Hd = drop(relu(Z)) and
+// Sc = Hd Wc, then Zc = A Sc + bc.  d == NULL, the validation forward: with no mask k_tr_dropout would only repeat layer 1's
+// Sc bits, so it is not launched.  Z may be NULL where layer 1 does not need it.
+static int launch_top_forward(const lt_trainer *t, const lt_graph *g, const float *S, float *Z, const lt_drop_args *d, float *Hd,
+                              float *Sc, float *Zc, float *seg_part, hipStream_t st) {
+    const int top = t->layers - 2, n = g->n, H = t->H[top], Hp = t->Hp[top], C = t->C;
+    const float *bp = t->mir[2 * top + 1], *Wcp = t->mir[2 * top + 2];
+    int rc = lt_launch_layer1(g, S, Hp, bp, Wcp, C, Z, Sc, st, seg_part);
     if (rc) return rc;
-    // loss head
-    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_ce<CP_>), dim3(rows_grid(n, TR_BLOCK)), dim3(TR_BLOCK), 0, st, n, t->Z3, C,
-                                          t->labels, 1.0f / (float)n, t->loss_r, t->corr_r, t->dZ3));
+    if (d) {
+        LT_DISPATCH_LPR(lt_lpr_for(Hp), LT_DISPATCH_CP(lt_cp_for(C),
+            hipLaunchKernelGGL((k_tr_dropout<LPR_, CP_>), dim3(rows_grid(n, wide_rows_per_block(Hp))), dim3(TR_BLOCK), 0, st, n, Z,
+                               Hp, H, Wcp, C, *d, Hd, Sc)));
+        LT_CHECK_LAUNCH();
+    }
+    return lt_launch_layer2(g, Sc, C, t->P[2 * top + 3], Zc, st);
+}
+
+// loss head: the epoch's record, dZc and dbc
+static int launch_loss_head(const lt_trainer *t, float *record, hipStream_t st) {
+    const int n = t->n, C = t->C, cp = lt_cp_for(C);
+    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_ce<CP_>), dim3(rows_grid(n, TR_BLOCK)), dim3(TR_BLOCK), 0, st, n, t->Zc, C,
+                                          t->labels, 1.0f / (float)n, t->loss_r, t->corr_r, t->dZc));
     LT_CHECK_LAUNCH();
     LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_ce_reduce<CP_>), dim3(1), dim3(TR_BLOCK), 0, st, n, C, t->loss_r, t->corr_r,
-                                          t->dZ3, record, gb3));
+                                          t->dZc, record, t->grad + t->off[2 * (t->layers - 2) + 2]));
     LT_CHECK_LAUNCH();
-    // backward through layer 3
+    return LT_OK;
+}
+
+// The top chain's backward: dSc = A^T dZc, dZ and the gradients of the hidden layer's bias and of Wc (adjacent in the
+// gradient buffer), dS = A^T dZ.
+static int launch_top_backward(const lt_trainer *t, float scale, hipStream_t st) {
+    const lt_graph *g = t->g;
+    const int top = t->layers - 2, n = t->n, H = t->H[top], Hp = t->Hp[top], C = t->C, cp = lt_cp_for(C);
+    const float *Wcp = t->mir[2 * top + 2];
     LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_spmm_t_narrow<CP_>), dim3(rows_grid(n, TR_BLOCK / LT_L2_LANES)),
-                                          dim3(TR_BLOCK), 0, st, n, g->tptr, g->trow, g->tval, t->dZ3, C, t->dS3));
+                                          dim3(TR_BLOCK), 0, st, n, g->tptr, g->trow, g->tval, t->dZc, C, t->dSc));
     LT_CHECK_LAUNCH();
     int W = 1;
-    while (W < Hp2) W <<= 1;
-    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_bwd_rows<CP_>), dim3((unsigned)t->n_part), dim3(TR_BLOCK), 0, st, n, H2, Hp2, W,
-                                          C, t->H2d, t->dS3, t->W3p, scale, t->dZ2, t->part));
+    while (W < Hp) W <<= 1;
+    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_bwd_rows<CP_>), dim3((unsigned)t->n_part), dim3(TR_BLOCK), 0, st, n, H, Hp, W,
+                                          C, t->Hd, t->dSc, Wcp, scale, t->dZ, t->part));
     LT_CHECK_LAUNCH();
-    const int L = H2 + H2 * C;   // db2 | dW3: adjacent in the gradient buffer
-    hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((L + 63) / 64)), dim3(TR_BLOCK), 0, st, t->part, t->n_part, L, gb2);
+    const int L = H + H * C;
+    hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((L + 63) / 64)), dim3(TR_BLOCK), 0, st, t->part, t->n_part, L,
+                       t->grad + t->off[2 * top]);
     LT_CHECK_LAUNCH();
-    // backward through layer 2
-    LT_DISPATCH_LPR(lpr2, hipLaunchKernelGGL((k_tr_spmm_t_wide<LPR_>), dim3(rows_grid(n, rpb2)), dim3(TR_BLOCK), 0, st, n,
-                                             g->tptr, g->trow, g->tval, t->dZ2, Hp2, t->dS2));
+    LT_DISPATCH_LPR(lt_lpr_for(Hp), hipLaunchKernelGGL((k_tr_spmm_t_wide<LPR_>), dim3(rows_grid(n, wide_rows_per_block(Hp))),
+                                                       dim3(TR_BLOCK), 0, st, n, g->tptr, g->trow, g->tval, t->dZ, Hp, t->dS));
     LT_CHECK_LAUNCH();
-    rc = launch_tn(t->H1d, (long)Hp1, t->dS2, (long)Hp2, gW2, H1, H2, n, t->tn2_kslice, t->tn2_splits, t->tn2_slabs, st);
+    return LT_OK;
+}
+
+// C [M, N] = A^T B over K rows, through the product's slabs when it is split
+static int launch_tn(const float *A, long lda, const float *B, long ldb, float *C, int M, int N, int K, const lt_tn &tn,
+                     hipStream_t st) {
+    const bool split = tn.splits > 1;
+    dim3 grid((unsigned)((M + TN_BM - 1) / TN_BM), (unsigned)((N + TN_BN - 1) / TN_BN), (unsigned)tn.splits);
+    hipLaunchKernelGGL(k_gemm_tn_mfma, grid, dim3(256), 0, st, A, lda, B, ldb, split ? tn.slabs : C, (long)N, M, N, K, tn.kslice,
+                       (long)M * N);
+    LT_CHECK_LAUNCH();
+    if (split) return lt_launch_sum_slabs(tn.slabs, (long)M * N, tn.splits, M, N, (long)N, C, (long)N, st);
+    return LT_OK;
+}
+
+static lt_snap_segs snap_segs(const lt_trainer *t) {
+    lt_snap_segs T;
+    for (int k = 0; k < 6; ++k) { T.p[k] = t->P[k]; T.o[k] = t->off[k]; }
+    return T;
+}
+
+static int run_epoch(lt_trainer *t, float *record, hipStream_t st) {
+    const lt_graph *g = t->g;
+    const int n = t->n, F = t->F, top = t->layers - 2, H1 = t->H[0], Hp1 = t->Hp[0];
+    lt_drop_args d = drop_args(t);
+    const float scale = t->p > 0.0 ? d.scale : 1.f;
+    // forward
+    int rc = launch_xw1(t, t->X, t->ldx, n, t->kslice, t->slabs, top ? t->fS : t->S, st);
     if (rc) return rc;
-    {
+    if (top) {
+        rc = launch_front(t, g, t->fS, d, t->fHd, t->seg_part, t->S, st);
+        if (rc) return rc;
+    }
+    d.layer = (uint32_t)top;
+    rc = launch_top_forward(t, g, t->S, t->Z, &d, t->Hd, t->Sc, t->Zc, t->seg_part, st);
+    if (rc) return rc;
+    rc = launch_loss_head(t, record, st);
+    if (rc) return rc;
+    // backward
+    rc = launch_top_backward(t, scale, st);
+    if (rc) return rc;
+    if (top) {      // through the middle weight and the front layer: dW2, dZ1 and db1, dS1
+        const int H2 = t->H[1], Hp2 = t->Hp[1];
+        rc = launch_tn(t->fHd, (long)Hp1, t->dS, (long)Hp2, t->grad + t->off[1], H1, H2, n, t->tn[1], st);
+        if (rc) return rc;
         dim3 grid((unsigned)t->n_mblk, (unsigned)((H1 + TN_BN - 1) / TN_BN));
-        hipLaunchKernelGGL(k_tr3_dz_mfma, grid, dim3(256), 0, st, t->dS2, (long)Hp2, W2, (long)H2, t->H1d, t->dZ1, (long)Hp1, n,
-                           H1, H2, scale, t->part1);
+        hipLaunchKernelGGL(k_tr3_dz_mfma, grid, dim3(256), 0, st, t->dS, (long)Hp2, t->P[2], (long)H2, t->fHd, t->fdZ, (long)Hp1,
+                           n, H1, H2, scale, t->part1);
+        LT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((H1 + 63) / 64)), dim3(TR_BLOCK), 0, st, t->part1, t->n_mblk, H1,
+                           t->grad + t->off[0]);
+        LT_CHECK_LAUNCH();
+        LT_DISPATCH_LPR(lt_lpr_for(Hp1), hipLaunchKernelGGL((k_tr_spmm_t_wide<LPR_>), dim3(rows_grid(n, wide_rows_per_block(Hp1))),
+                                                            dim3(TR_BLOCK), 0, st, n, g->tptr, g->trow, g->tval, t->fdZ, Hp1,
+                                                            t->fdS));
         LT_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((H1 + 63) / 64)), dim3(TR_BLOCK), 0, st, t->part1, t->n_mblk, H1, gb1);
-    LT_CHECK_LAUNCH();
-    // backward through layer 1
-    LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k_tr_spmm_t_wide<LPR_>), dim3(rows_grid(n, rpb1)), dim3(TR_BLOCK), 0, st, n,
-                                             g->tptr, g->trow, g->tval, t->dZ1, Hp1, t->dS1));
-    LT_CHECK_LAUNCH();
-    rc = launch_tn(t->X, (long)t->ldx, t->dS1, (long)Hp1, gW1, F, H1, n, t->tn1_kslice, t->tn1_splits, t->tn1_slabs, st);
+    rc = launch_tn(t->X, (long)t->ldx, top ? t->fdS : t->dS, (long)Hp1, t->grad, F, H1, n, t->tn[0], st);
     if (rc) return rc;
     // Adam
     const int64_t step = t->epoch + 1;
-    lt_tr3_tensors T;
-    for (int k = 0; k < 6; ++k) { T.p[k] = t->P[k]; T.o[k] = t->off[k]; }
-    T.b1p = t->b1p; T.b2p = t->b2p; T.W3p = t->W3p;
-    hipLaunchKernelGGL(k_tr3_adam, dim3((unsigned)((t->off[5] + 255) / 256)), dim3(256), 0, st, T, t->grad, t->m, t->v,
-                       adam_scalars(step, t->lr, 0.9, 0.999, 1e-8, t->wd));
+    const lt_adam_scalars s = adam_scalars(step, t->lr, 0.9, 0.999, 1e-8, t->wd);
+    const dim3 adam_grid((unsigned)((t->off[5] + 255) / 256));
+    if (top) {
+        const lt_tr3_tensors T = {snap_segs(t), t->mir[1], t->mir[3], t->mir[4]};
+        hipLaunchKernelGGL(k_tr3_adam, adam_grid, dim3(256), 0, st, T, t->grad, t->m, t->v, s);
+    } else {
+        hipLaunchKernelGGL(k_tr_adam, adam_grid, dim3(256), 0, st, t->off[5], t->off[0], t->off[1], t->off[2], t->P[0], t->P[1],
+                           t->P[2], t->P[3], t->grad, t->m, t->v, t->mir[1], t->mir[2], s);
+    }
     LT_CHECK_LAUNCH();
     t->epoch = step;
-    return LT_OK;
-}
-
-extern "C" int lt_gcn3_trainer_run(lt_gcn3_trainer *t, int32_t n_epochs, float *record, void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_run: trainer is NULL");
-    LT_REQUIRE(n_epochs >= 0, "lt_gcn3_trainer_run: n_epochs=%d", n_epochs);
-    if (n_epochs == 0) return LT_OK;
-    LT_REQUIRE(record != nullptr, "lt_gcn3_trainer_run: record is NULL");
-    LT_REQUIRE(t->epoch + n_epochs <= (int64_t)UINT32_MAX, "lt_gcn3_trainer_run: epoch counter would pass 2^32");
-    hipStream_t st = (hipStream_t)stream;
-    // the borrowed parameters may have changed since the last run: the mirrors from them (Adam keeps them current after that)
-    const int mx = t->Hp1 > t->Hp2 * t->C ? t->Hp1 : t->Hp2 * t->C;
-    hipLaunchKernelGGL(k_tr3_pad, dim3((mx + 255) / 256), dim3(256), 0, st, t->P[1], t->H1, t->Hp1, t->P[3], t->H2, t->Hp2,
-                       t->P[4], t->C, t->b1p, t->b2p, t->W3p);
-    LT_CHECK_LAUNCH();
-    for (int32_t j = 0; j < n_epochs; ++j) {
-        const int rc = run_epoch3(t, record + 2 * (size_t)j, st);
-        if (rc) return rc;
-    }
-    return LT_OK;
-}
-
-extern "C" int lt_gcn3_trainer_grads(const lt_gcn3_trainer *t, float *dW1, float *db1, float *dW2, float *db2, float *dW3,
-                                     float *db3, void *stream) {
-    LT_REQUIRE(t != nullptr && dW1 && db1 && dW2 && db2 && dW3 && db3, "lt_gcn3_trainer_grads: NULL argument");
-    float *dst[6] = {dW1, db1, dW2, db2, dW3, db3};
-    for (int k = 0; k < 6; ++k) {
-        const int64_t b = k ? t->off[k - 1] : 0;
-        LT_HIP(hipMemcpyAsync(dst[k], t->grad + b, (size_t)(t->off[k] - b) * sizeof(float), hipMemcpyDeviceToDevice,
-                              (hipStream_t)stream));
-    }
-    return LT_OK;
-}
-
-extern "C" int lt_gcn3_trainer_logits(const lt_gcn3_trainer *t, float *Z3, int64_t ldz, void *stream) {
-    LT_REQUIRE(t != nullptr && Z3 != nullptr, "lt_gcn3_trainer_logits: NULL argument");
-    LT_REQUIRE(ldz >= t->C, "lt_gcn3_trainer_logits: ldz=%lld < C=%d", (long long)ldz, t->C);
-    LT_HIP(hipMemcpy2DAsync(Z3, (size_t)ldz * sizeof(float), t->Z3, (size_t)t->C * sizeof(float), (size_t)t->C * sizeof(float),
-                            (size_t)t->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return LT_OK;
-}
-
-extern "C" int lt_gcn3_trainer_hidden(const lt_gcn3_trainer *t, int32_t layer, float *dst, int64_t ld, void *stream) {
-    LT_REQUIRE(t != nullptr && dst != nullptr, "lt_gcn3_trainer_hidden: NULL argument");
-    LT_REQUIRE(layer == 1 || layer == 2, "lt_gcn3_trainer_hidden: layer=%d, must be 1 or 2", layer);
-    const int H = layer == 1 ? t->H1 : t->H2, Hp = layer == 1 ? t->Hp1 : t->Hp2;
-    LT_REQUIRE(ld >= H, "lt_gcn3_trainer_hidden: ld=%lld < H%d=%d", (long long)ld, layer, H);
-    LT_HIP(hipMemcpy2DAsync(dst, (size_t)ld * sizeof(float), layer == 1 ? t->H1d : t->H2d, (size_t)Hp * sizeof(float),
-                            (size_t)H * sizeof(float), (size_t)t->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return LT_OK;
 }
 
@@ -1557,8 +1327,8 @@ extern "C" int lt_eval_head(const float *Z, int64_t ldz, const int32_t *labels, 
         return lt_set_error(LT_ERR_WORKSPACE, "lt_eval_head: workspace needs %zu bytes, 4-byte aligned", val_head_bytes(n, C));
     const int n_blk = (n + TR_BLOCK - 1) / TR_BLOCK;
     float *part_loss = (float *)workspace;
-    return launch_val_head(Z, (long)ldz, labels, n, C, part_loss, (int32_t *)(part_loss + n_blk), loss, confusion, nullptr, 0, 0,
-                           (hipStream_t)stream);
+    return launch_val_head(Z, (long)ldz, labels, n, C, nullptr, 0, part_loss, (int32_t *)(part_loss + n_blk), loss, confusion,
+                           nullptr, nullptr, 0, 0, (hipStream_t)stream);
 }
 
 extern "C" size_t lt_eval_head_rows_workspace_bytes(int32_t m, int32_t C) {
@@ -1581,8 +1351,8 @@ extern "C" int lt_eval_head_rows(const float *Z, int64_t ldz, const int32_t *lab
     if (n_bad) LT_HIP(hipMemsetAsync(n_bad, 0, sizeof(int32_t), st));
     const int n_blk = (m + TR_BLOCK - 1) / TR_BLOCK;
     float *part_loss = (float *)workspace;
-    return launch_val_head_rows(Z, (long)ldz, labels, n, C, rows, m, part_loss, (int32_t *)(part_loss + n_blk), loss, confusion,
-                                n_bad, nullptr, 0, 0, st);
+    return launch_val_head(Z, (long)ldz, labels, n, C, rows, m, part_loss, (int32_t *)(part_loss + n_blk), loss, confusion, n_bad,
+                           nullptr, 0, 0, st);
 }
 
 extern "C" int lt_early_stop_reset(int32_t *state, void *stream) {
@@ -1611,19 +1381,21 @@ static int ptr_device(const void *p) {
     return at.type == hipMemoryTypeDevice ? at.device : -1;
 }
 
-// Everything lt_gcn*_trainer_attach_validation checks and allocates.  Hp2 = 0: the 2-layer model.
-static int val_attach(const char *who, lt_val **slot, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
-                      const int32_t *labels2, int32_t keep_best, int32_t patience, const float *X, int F, int H1, int Hp1,
-                      int Hp2, int C, int64_t n_param, hipStream_t st, int with_rows = 0, const int32_t *rows = nullptr,
-                      int32_t m = 0) {
-    LT_REQUIRE(*slot == nullptr, "%s: validation is already attached to this trainer", who);
+// Everything lt_gcn*_trainer_attach_validation(_rows) checks and allocates.
+static int val_attach(const char *who, lt_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
+                      const int32_t *labels2, int32_t keep_best, int32_t patience, void *stream, int with_rows = 0,
+                      const int32_t *rows = nullptr, int32_t m = 0) {
+    LT_REQUIRE(t != nullptr, "%s: trainer is NULL", who);
+    const int F = t->F, C = t->C, top = t->layers - 2;
+    hipStream_t st = (hipStream_t)stream;
+    LT_REQUIRE(t->val == nullptr, "%s: validation is already attached to this trainer", who);
     LT_REQUIRE(g2 != nullptr && X2 != nullptr && labels2 != nullptr, "%s: NULL argument", who);
     LT_REQUIRE(g2->n > 0, "%s: empty graph", who);
     LT_REQUIRE(n2 == g2->n, "%s: X2 has %d rows, the graph %d nodes", who, n2, g2->n);
     LT_REQUIRE(ldx2 >= F, "%s: ldx2=%lld < F=%d", who, (long long)ldx2, F);
     LT_REQUIRE(keep_best == 0 || keep_best == 1, "%s: keep_best=%d, must be 0 or 1", who, keep_best);
     LT_REQUIRE(patience >= 0, "%s: patience=%d, must be >= 0 (0: never stop)", who, patience);
-    const int dev = ptr_device(X);
+    const int dev = ptr_device(t->X);
     LT_REQUIRE(dev >= 0 && ptr_device(X2) == dev && ptr_device(g2->rowptr) == dev && ptr_device(labels2) == dev,
                "%s: the validation graph, X2 and labels2 must live on the trainer's device (%d)", who, dev);
     if (with_rows) {
@@ -1663,13 +1435,13 @@ static int val_attach(const char *who, lt_val **slot, const lt_graph *g2, const 
     if (!v) return lt_set_error(LT_ERR_NOMEM, "%s: out of host memory", who);
     v->g = g2; v->n = n2; v->X = X2; v->ldx = ldx2; v->labels = labels2;
     v->keep_best = keep_best; v->patience = patience;
-    v->kslice = lt_gemm_pick_kslice(n2, H1, F);
+    v->kslice = lt_gemm_pick_kslice(n2, t->H[0], F);
     v->rows = with_rows ? rows : nullptr;
     v->m = with_rows ? m : 0;
     v->n_blk = ((with_rows ? m : n2) + TR_BLOCK - 1) / TR_BLOCK;
-    const size_t nh1 = (size_t)n2 * Hp1 * sizeof(float), nh2 = (size_t)n2 * Hp2 * sizeof(float);
+    const size_t nf = (size_t)n2 * t->Hp[0] * sizeof(float), nt = (size_t)n2 * t->Hp[top] * sizeof(float);
     const size_t nc = (size_t)n2 * C * sizeof(float);
-    const int hpm = Hp1 > Hp2 ? Hp1 : Hp2;
+    const int hpm = t->Hp[0] > t->Hp[1] ? t->Hp[0] : t->Hp[1];
 #define V_HIP(call)                                                                         \
     do {                                                                                    \
         hipError_t e_ = (call);                                                             \
@@ -1678,25 +1450,23 @@ static int val_attach(const char *who, lt_val **slot, const lt_graph *g2, const 
             return lt_set_error(LT_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
         }                                                                                   \
     } while (0)
-    V_HIP(hipMalloc((void **)&v->S1, nh1));
-    V_HIP(hipMemsetAsync(v->S1, 0, nh1, st));      // the GEMM writes H of the Hp columns
-    if (Hp2 == 0) {
-        V_HIP(hipMalloc((void **)&v->Z1, nh1));
-    } else {
-        V_HIP(hipMalloc((void **)&v->H1, nh1));
-        V_HIP(hipMalloc((void **)&v->S2, nh2));
-        V_HIP(hipMalloc((void **)&v->Z2, nh2));
-        V_HIP(hipMemsetAsync(v->S2, 0, nh2, st));
+    if (top) {
+        V_HIP(hipMalloc((void **)&v->fS, nf));
+        V_HIP(hipMemsetAsync(v->fS, 0, nf, st));      // the GEMMs write H of the Hp columns
+        V_HIP(hipMalloc((void **)&v->fH, nf));
     }
+    V_HIP(hipMalloc((void **)&v->S, nt));
+    V_HIP(hipMemsetAsync(v->S, 0, nt, st));
+    V_HIP(hipMalloc((void **)&v->Z, nt));
     V_HIP(hipMalloc((void **)&v->Sc, nc));
-    V_HIP(hipMalloc((void **)&v->Z, nc));
-    const size_t sb = lt_gemm_splitk_slab_bytes(n2, H1, F, v->kslice);
+    V_HIP(hipMalloc((void **)&v->Zc, nc));
+    const size_t sb = lt_gemm_splitk_slab_bytes(n2, t->H[0], F, v->kslice);
     if (sb) V_HIP(hipMalloc((void **)&v->slabs, sb));
     if (g2->p_n_seg > 0) V_HIP(hipMalloc((void **)&v->seg_part, (size_t)g2->p_n_seg * hpm * sizeof(float)));
     V_HIP(hipMalloc((void **)&v->part_loss, (size_t)v->n_blk * sizeof(float)));
     V_HIP(hipMalloc((void **)&v->part_cnt, (size_t)v->n_blk * C * C * sizeof(int32_t)));
     V_HIP(hipMalloc((void **)&v->state, VAL_STATE_WORDS * sizeof(int32_t)));
-    if (keep_best) V_HIP(hipMalloc((void **)&v->snap, (size_t)n_param * sizeof(float)));
+    if (keep_best) V_HIP(hipMalloc((void **)&v->snap, (size_t)t->off[5] * sizeof(float)));
 #undef V_HIP
     hipLaunchKernelGGL(k_val_state_reset, dim3(1), dim3(64), 0, st, v->state);
     {
@@ -1706,221 +1476,287 @@ static int val_attach(const char *who, lt_val **slot, const lt_graph *g2, const 
             return lt_set_error(LT_ERR_HIP, "%s: kernel launch failed: %s", who, hipGetErrorString(e_));
         }
     }
-    *slot = v;
+    t->val = v;
     return LT_OK;
+}
+
+// The epoch's forward on the validation graph with dropout off: the forward's launches at n2, its logits' bits.
+static int val_forward(lt_trainer *t, hipStream_t st) {
+    lt_val *v = t->val;
+    const bool front = t->layers == 3;
+    int rc = launch_xw1(t, v->X, v->ldx, v->n, v->kslice, v->slabs, front ? v->fS : v->S, st);
+    if (rc) return rc;
+    float *Z = v->Z;
+    if (front) {
+        lt_drop_args off;
+        off.on = 0; off.thresh = 0; off.scale = 1.f; off.epoch = 0; off.seed = 0;
+        rc = launch_front(t, v->g, v->fS, off, v->fH, v->seg_part, v->S, st);
+        if (rc) return rc;
+    } else if (!lt_tiled_wanted(v->g, t->Hp[0])) {
+        Z = nullptr;      // only the tiled layer-1 route needs it
+    }
+    return launch_top_forward(t, v->g, v->S, Z, nullptr, nullptr, v->Sc, v->Zc, v->seg_part, st);
 }
 
 // head, state and snapshot behind a validation forward; e = the epoch just trained (0-based, since creation)
 static int val_finish_epoch(lt_val *v, int C, const lt_snap_segs &T, int64_t e, float *val_loss, int32_t *val_counts,
                             hipStream_t st) {
-    int rc = v->rows ? launch_val_head_rows(v->Z, (long)C, v->labels, v->n, C, v->rows, v->m, v->part_loss, v->part_cnt, val_loss,
-                                            val_counts, nullptr, v->state, v->patience, (int)e, st)
-                     : launch_val_head(v->Z, (long)C, v->labels, v->n, C, v->part_loss, v->part_cnt, val_loss, val_counts,
-                                       v->state, v->patience, (int)e, st);
+    const int rc = launch_val_head(v->Zc, (long)C, v->labels, v->n, C, v->rows, v->m, v->part_loss, v->part_cnt, val_loss,
+                                   val_counts, nullptr, v->state, v->patience, (int)e, st);
     if (rc) return rc;
     if (v->keep_best) return launch_snapshot(T, v->snap, v->state + VS_IMPROVED, 0, st);
     return LT_OK;
 }
 
-static int val_read_state(const char *who, const lt_val *v, int32_t *state_host, hipStream_t st) {
-    LT_REQUIRE(v != nullptr, "%s: no validation attached", who);
+// --------------------------------------------------------------------------------------------
+// the entry points' bodies; `who` is the public name the messages carry
+// --------------------------------------------------------------------------------------------
+// lt_gcn*_trainer_run (val_loss == val_counts == NULL, validated = false) and _run_validated
+static int trainer_run(const char *who, lt_trainer *t, int32_t n_epochs, float *record, bool validated, float *val_loss,
+                       int32_t *val_counts, void *stream) {
+    LT_REQUIRE(t != nullptr, "%s: trainer is NULL", who);
+    if (validated) {
+        LT_REQUIRE(t->val != nullptr, "%s: no validation attached", who);
+    }
+    LT_REQUIRE(n_epochs >= 0, "%s: n_epochs=%d", who, n_epochs);
+    if (n_epochs == 0) return LT_OK;
+    if (validated) {
+        LT_REQUIRE(record && val_loss && val_counts, "%s: NULL output", who);
+        LT_REQUIRE(t->epoch + n_epochs <= (int64_t)INT32_MAX, "%s: epoch counter would pass 2^31", who);
+    } else {
+        LT_REQUIRE(record != nullptr, "%s: record is NULL", who);
+        LT_REQUIRE(t->epoch + n_epochs <= (int64_t)UINT32_MAX, "%s: epoch counter would pass 2^32", who);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const lt_snap_segs T = snap_segs(t);
+    // the borrowed parameters may have changed since the last run: the padded copies from them (Adam keeps them current after that)
+    if (t->layers == 3) {
+        const int mx = t->Hp[0] > t->Hp[1] * t->C ? t->Hp[0] : t->Hp[1] * t->C;
+        hipLaunchKernelGGL(k_tr3_pad, dim3((mx + 255) / 256), dim3(256), 0, st, t->P[1], t->H[0], t->Hp[0], t->P[3], t->H[1],
+                           t->Hp[1], t->P[4], t->C, t->mir[1], t->mir[3], t->mir[4]);
+    } else {
+        hipLaunchKernelGGL(k_tr_pad, dim3((t->Hp[0] * (t->C + 1) + 255) / 256), dim3(256), 0, st, t->P[1], t->P[2], t->H[0],
+                           t->Hp[0], t->C, t->mir[1], t->mir[2]);
+    }
+    LT_CHECK_LAUNCH();
+    const size_t cc = (size_t)t->C * t->C;
+    for (int32_t j = 0; j < n_epochs; ++j) {
+        const int64_t e = t->epoch;
+        int rc = run_epoch(t, record + 2 * (size_t)j, st);
+        if (rc == LT_OK && validated) rc = val_forward(t, st);
+        if (rc == LT_OK && validated) rc = val_finish_epoch(t->val, t->C, T, e, val_loss + j, val_counts + cc * (size_t)j, st);
+        if (rc) return rc;
+    }
+    return LT_OK;
+}
+
+// the last epoch's gradients: dst[k] takes segment k of the gradient buffer
+static int trainer_grads(const lt_trainer *t, float *const *dst, void *stream) {
+    for (int k = 0; k < 2 * t->layers; ++k) {
+        const int64_t b = k ? t->off[k - 1] : 0;
+        LT_HIP(hipMemcpyAsync(dst[k], t->grad + b, (size_t)(t->off[k] - b) * sizeof(float), hipMemcpyDeviceToDevice,
+                              (hipStream_t)stream));
+    }
+    return LT_OK;
+}
+
+// rows of width floats from a trainer buffer of leading dimension lds into dst [n, ld]
+static int copy_rows(float *dst, int64_t ld, const float *src, int lds, int width, int n, void *stream) {
+    LT_HIP(hipMemcpy2DAsync(dst, (size_t)ld * sizeof(float), src, (size_t)lds * sizeof(float), (size_t)width * sizeof(float),
+                            (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return LT_OK;
+}
+
+static int trainer_logits(const char *who, const lt_trainer *t, float *Z, int64_t ldz, void *stream) {
+    LT_REQUIRE(t != nullptr && Z != nullptr, "%s: NULL argument", who);
+    LT_REQUIRE(ldz >= t->C, "%s: ldz=%lld < C=%d", who, (long long)ldz, t->C);
+    return copy_rows(Z, ldz, t->Zc, t->C, t->C, t->n, stream);
+}
+
+static int trainer_epoch(const char *who, const lt_trainer *t, int64_t *epoch) {
+    LT_REQUIRE(t != nullptr && epoch != nullptr, "%s: NULL argument", who);
+    *epoch = t->epoch;
+    return LT_OK;
+}
+
+static int trainer_val_state(const char *who, const lt_trainer *t, int32_t *state_host, void *stream) {
+    LT_REQUIRE(t != nullptr, "%s: trainer is NULL", who);
+    LT_REQUIRE(t->val != nullptr, "%s: no validation attached", who);
     LT_REQUIRE(state_host != nullptr, "%s: state is NULL", who);
-    LT_HIP(hipMemcpyAsync(state_host, v->state, VAL_STATE_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    hipStream_t st = (hipStream_t)stream;
+    LT_HIP(hipMemcpyAsync(state_host, t->val->state, VAL_STATE_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     LT_HIP(hipStreamSynchronize(st));
     return LT_OK;
 }
 
-static int val_copy_logits(const char *who, const lt_val *v, int C, float *Z, int64_t ldz, hipStream_t st) {
-    LT_REQUIRE(v != nullptr, "%s: no validation attached", who);
+static int trainer_restore_best(const char *who, lt_trainer *t, void *stream) {
+    LT_REQUIRE(t != nullptr, "%s: trainer is NULL", who);
+    LT_REQUIRE(t->val != nullptr && t->val->keep_best, "%s: no validation with keep_best attached", who);
+    return launch_snapshot(snap_segs(t), t->val->snap, t->val->state + VS_SEEN, 1, (hipStream_t)stream);
+}
+
+static int trainer_val_logits(const char *who, const lt_trainer *t, float *Z, int64_t ldz, void *stream) {
+    LT_REQUIRE(t != nullptr, "%s: trainer is NULL", who);
+    LT_REQUIRE(t->val != nullptr, "%s: no validation attached", who);
     LT_REQUIRE(Z != nullptr, "%s: Z is NULL", who);
-    LT_REQUIRE(ldz >= C, "%s: ldz=%lld < C=%d", who, (long long)ldz, C);
-    LT_HIP(hipMemcpy2DAsync(Z, (size_t)ldz * sizeof(float), v->Z, (size_t)C * sizeof(float), (size_t)C * sizeof(float),
-                            (size_t)v->n, hipMemcpyDeviceToDevice, st));
-    return LT_OK;
+    LT_REQUIRE(ldz >= t->C, "%s: ldz=%lld < C=%d", who, (long long)ldz, t->C);
+    return copy_rows(Z, ldz, t->val->Zc, t->C, t->C, t->val->n, stream);
 }
 
 // ---- the 2-layer trainer ----
-static lt_snap_segs snap_segs2(const lt_gcn2_trainer *t) {
-    lt_snap_segs T;
-    const int64_t o1 = (int64_t)t->F * t->H, o2 = o1 + t->H, o3 = o2 + (int64_t)t->H * t->C;
-    float *ps[6] = {t->W1, t->b1, t->W2, t->b2, nullptr, nullptr};
-    const int64_t os[6] = {o1, o2, o3, t->n_param, t->n_param, t->n_param};
-    for (int k = 0; k < 6; ++k) { T.p[k] = ps[k]; T.o[k] = os[k]; }
-    return T;
+extern "C" int lt_gcn2_trainer_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const int32_t *labels,
+                                      int32_t H, int32_t C, float *W1, float *b1, float *W2, float *b2, double lr,
+                                      double weight_decay, double dropout, uint64_t seed, void *stream,
+                                      lt_gcn2_trainer **out) {
+    LT_REQUIRE(out != nullptr, "lt_gcn2_trainer_create: out is NULL");
+    *out = nullptr;
+    LT_REQUIRE(g != nullptr, "lt_gcn2_trainer_create: graph is NULL");
+    LT_REQUIRE(F > 0 && H > 0 && C > 0, "lt_gcn2_trainer_create: F=%d H=%d C=%d must be positive", F, H, C);
+    LT_REQUIRE(H <= LT_MAX_H && C <= LT_MAX_C, "lt_gcn2_trainer_create: H=%d C=%d (supported: H <= %d, C <= %d)", H, C,
+               LT_MAX_H, LT_MAX_C);
+    LT_REQUIRE(X && labels && W1 && b1 && W2 && b2, "lt_gcn2_trainer_create: NULL tensor pointer");
+    const int32_t Hs[2] = {H, 0};
+    float *const ps[4] = {W1, b1, W2, b2};
+    lt_trainer *t = nullptr;
+    const int rc = trainer_create("lt_gcn2_trainer_create", 2, g, X, ldx, F, labels, Hs, C, ps, lr, weight_decay, dropout, seed,
+                                  stream, &t);
+    *out = static_cast<lt_gcn2_trainer *>(t);
+    return rc;
 }
 
-// the forward of run_epoch on the validation graph, dropout off: lt_gcn2_forward's launches at n2 (its logits' bits)
-static int val_forward2(lt_gcn2_trainer *t, hipStream_t st) {
-    lt_val *v = t->val;
-    const int F = t->F, H = t->H, C = t->C, Hp = t->Hp;
-    int rc;
-    if (v->slabs)
-        rc = lt_launch_gemm_splitk(v->X, v->ldx, t->W1, H, v->S1, Hp, v->n, H, F, v->kslice, v->slabs, st);
-    else
-        rc = lt_launch_gemm(v->X, v->ldx, t->W1, H, v->S1, Hp, v->n, H, F, st);
-    if (rc) return rc;
-    rc = lt_launch_layer1(v->g, v->S1, Hp, t->b1p, t->W2p, C, lt_tiled_wanted(v->g, Hp) ? v->Z1 : nullptr, v->Sc, st,
-                          v->seg_part);
-    if (rc) return rc;
-    return lt_launch_layer2(v->g, v->Sc, C, t->b2, v->Z, st);
+extern "C" int lt_gcn2_trainer_destroy(lt_gcn2_trainer *t) {
+    free_trainer(t);
+    return LT_OK;
+}
+
+extern "C" int lt_gcn2_trainer_epoch(const lt_gcn2_trainer *t, int64_t *epoch) {
+    return trainer_epoch("lt_gcn2_trainer_epoch", t, epoch);
+}
+
+extern "C" int lt_gcn2_trainer_run(lt_gcn2_trainer *t, int32_t n_epochs, float *record, void *stream) {
+    return trainer_run("lt_gcn2_trainer_run", t, n_epochs, record, false, nullptr, nullptr, stream);
+}
+
+extern "C" int lt_gcn2_trainer_grads(const lt_gcn2_trainer *t, float *dW1, float *db1, float *dW2, float *db2, void *stream) {
+    LT_REQUIRE(t != nullptr && dW1 && db1 && dW2 && db2, "lt_gcn2_trainer_grads: NULL argument");
+    float *const dst[4] = {dW1, db1, dW2, db2};
+    return trainer_grads(t, dst, stream);
+}
+
+extern "C" int lt_gcn2_trainer_logits(const lt_gcn2_trainer *t, float *Z2, int64_t ldz, void *stream) {
+    return trainer_logits("lt_gcn2_trainer_logits", t, Z2, ldz, stream);
 }
 
 extern "C" int lt_gcn2_trainer_attach_validation(lt_gcn2_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2,
                                                  int32_t n2, const int32_t *labels2, int32_t keep_best, int32_t patience,
                                                  void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_attach_validation: trainer is NULL");
-    return val_attach("lt_gcn2_trainer_attach_validation", &t->val, g2, X2, ldx2, n2, labels2, keep_best, patience, t->X, t->F,
-                      t->H, t->Hp, 0, t->C, t->n_param, (hipStream_t)stream);
+    return val_attach("lt_gcn2_trainer_attach_validation", t, g2, X2, ldx2, n2, labels2, keep_best, patience, stream);
 }
 
 extern "C" int lt_gcn2_trainer_attach_validation_rows(lt_gcn2_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2,
                                                       int32_t n2, const int32_t *labels2, int32_t keep_best, int32_t patience,
                                                       const int32_t *rows, int32_t m, void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_attach_validation_rows: trainer is NULL");
-    return val_attach("lt_gcn2_trainer_attach_validation_rows", &t->val, g2, X2, ldx2, n2, labels2, keep_best, patience, t->X,
-                      t->F, t->H, t->Hp, 0, t->C, t->n_param, (hipStream_t)stream, 1, rows, m);
+    return val_attach("lt_gcn2_trainer_attach_validation_rows", t, g2, X2, ldx2, n2, labels2, keep_best, patience, stream, 1, rows,
+                      m);
 }
 
 extern "C" int lt_gcn2_trainer_run_validated(lt_gcn2_trainer *t, int32_t n_epochs, float *record, float *val_loss,
                                              int32_t *val_counts, void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_run_validated: trainer is NULL");
-    LT_REQUIRE(t->val != nullptr, "lt_gcn2_trainer_run_validated: no validation attached");
-    LT_REQUIRE(n_epochs >= 0, "lt_gcn2_trainer_run_validated: n_epochs=%d", n_epochs);
-    if (n_epochs == 0) return LT_OK;
-    LT_REQUIRE(record && val_loss && val_counts, "lt_gcn2_trainer_run_validated: NULL output");
-    LT_REQUIRE(t->epoch + n_epochs <= (int64_t)INT32_MAX, "lt_gcn2_trainer_run_validated: epoch counter would pass 2^31");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_tr_pad, dim3((t->Hp * (t->C + 1) + 255) / 256), dim3(256), 0, st, t->b1, t->W2, t->H, t->Hp, t->C,
-                       t->b1p, t->W2p);
-    LT_CHECK_LAUNCH();
-    const lt_snap_segs T = snap_segs2(t);
-    const size_t cc = (size_t)t->C * t->C;
-    for (int32_t j = 0; j < n_epochs; ++j) {
-        const int64_t e = t->epoch;
-        int rc = run_epoch(t, record + 2 * (size_t)j, st);
-        if (rc) return rc;
-        rc = val_forward2(t, st);
-        if (rc) return rc;
-        rc = val_finish_epoch(t->val, t->C, T, e, val_loss + j, val_counts + cc * (size_t)j, st);
-        if (rc) return rc;
-    }
-    return LT_OK;
+    return trainer_run("lt_gcn2_trainer_run_validated", t, n_epochs, record, true, val_loss, val_counts, stream);
 }
 
 extern "C" int lt_gcn2_trainer_val_state(const lt_gcn2_trainer *t, int32_t *state, void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_val_state: trainer is NULL");
-    return val_read_state("lt_gcn2_trainer_val_state", t->val, state, (hipStream_t)stream);
+    return trainer_val_state("lt_gcn2_trainer_val_state", t, state, stream);
 }
 
 extern "C" int lt_gcn2_trainer_restore_best(lt_gcn2_trainer *t, void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_restore_best: trainer is NULL");
-    LT_REQUIRE(t->val != nullptr && t->val->keep_best, "lt_gcn2_trainer_restore_best: no validation with keep_best attached");
-    return launch_snapshot(snap_segs2(t), t->val->snap, t->val->state + VS_SEEN, 1, (hipStream_t)stream);
+    return trainer_restore_best("lt_gcn2_trainer_restore_best", t, stream);
 }
 
 extern "C" int lt_gcn2_trainer_val_logits(const lt_gcn2_trainer *t, float *Z, int64_t ldz, void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn2_trainer_val_logits: trainer is NULL");
-    return val_copy_logits("lt_gcn2_trainer_val_logits", t->val, t->C, Z, ldz, (hipStream_t)stream);
+    return trainer_val_logits("lt_gcn2_trainer_val_logits", t, Z, ldz, stream);
 }
 
 // ---- the 3-layer trainer ----
-static lt_snap_segs snap_segs3(const lt_gcn3_trainer *t) {
-    lt_snap_segs T;
-    for (int k = 0; k < 6; ++k) { T.p[k] = t->P[k]; T.o[k] = t->off[k]; }
-    return T;
+extern "C" int lt_gcn3_trainer_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const int32_t *labels,
+                                      int32_t H1, int32_t H2, int32_t C, float *W1, float *b1, float *W2, float *b2,
+                                      float *W3, float *b3, double lr, double weight_decay, double dropout, uint64_t seed,
+                                      void *stream, lt_gcn3_trainer **out) {
+    LT_REQUIRE(out != nullptr, "lt_gcn3_trainer_create: out is NULL");
+    *out = nullptr;
+    LT_REQUIRE(g != nullptr, "lt_gcn3_trainer_create: graph is NULL");
+    LT_REQUIRE(F > 0 && H1 > 0 && H2 > 0 && C > 0, "lt_gcn3_trainer_create: F=%d H1=%d H2=%d C=%d must be positive", F, H1,
+               H2, C);
+    LT_REQUIRE(H1 <= LT_MAX_H && H2 <= LT_MAX_H && C <= LT_MAX_C,
+               "lt_gcn3_trainer_create: H1=%d H2=%d C=%d (supported: H1, H2 <= %d, C <= %d)", H1, H2, C, LT_MAX_H, LT_MAX_C);
+    LT_REQUIRE(X && labels && W1 && b1 && W2 && b2 && W3 && b3, "lt_gcn3_trainer_create: NULL tensor pointer");
+    const int32_t Hs[2] = {H1, H2};
+    float *const ps[6] = {W1, b1, W2, b2, W3, b3};
+    lt_trainer *t = nullptr;
+    const int rc = trainer_create("lt_gcn3_trainer_create", 3, g, X, ldx, F, labels, Hs, C, ps, lr, weight_decay, dropout, seed,
+                                  stream, &t);
+    *out = static_cast<lt_gcn3_trainer *>(t);
+    return rc;
 }
 
-// the forward of run_epoch3 on the validation graph, dropout off (k_tr_dropout with no mask only repeats layer 1's S3 bits,
-// so it is not launched)
-static int val_forward3(lt_gcn3_trainer *t, hipStream_t st) {
-    lt_val *v = t->val;
-    const lt_graph *g = v->g;
-    const int n = v->n, F = t->F, H1 = t->H1, H2 = t->H2, C = t->C, Hp1 = t->Hp1, Hp2 = t->Hp2;
-    const int lpr1 = lt_lpr_for(Hp1);
-    const int rpb1 = (TR_BLOCK / 64) * (64 / lpr1);
-    int rc;
-    if (v->slabs)
-        rc = lt_launch_gemm_splitk(v->X, v->ldx, t->P[0], H1, v->S1, Hp1, n, H1, F, v->kslice, v->slabs, st);
-    else
-        rc = lt_launch_gemm(v->X, v->ldx, t->P[0], H1, v->S1, Hp1, n, H1, F, st);
-    if (rc) return rc;
-    lt_drop_args d;
-    d.on = 0; d.thresh = 0; d.scale = 1.f; d.epoch = 0; d.seed = 0; d.layer = 0;
-    const int have_long = g->p_n_long > 0 ? 1 : 0;
-    const unsigned seg_blocks = have_long ? rows_grid(g->p_n_seg, rpb1) : 0u;
-    LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k_tr3_layer1<LPR_>), dim3(rows_grid(n, rpb1) + seg_blocks), dim3(TR_BLOCK), 0, st,
-                                             n, g->rowptr, g->col, g->val, v->S1, Hp1, H1, t->b1p, d, v->H1, have_long,
-                                             (int)seg_blocks, g->p_n_seg, g->p_seg_long, g->p_seg_begin, g->p_long_row,
-                                             v->seg_part));
-    LT_CHECK_LAUNCH();
-    if (have_long) {
-        LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k_tr3_layer1_long<LPR_>), dim3(rows_grid(g->p_n_long, rpb1)), dim3(TR_BLOCK),
-                                                 0, st, g->p_n_long, g->p_long_row, g->p_long_segptr, v->seg_part, Hp1, H1, d,
-                                                 v->H1));
-        LT_CHECK_LAUNCH();
-    }
-    rc = lt_launch_gemm(v->H1, Hp1, t->P[2], H2, v->S2, Hp2, n, H2, H1, st);
-    if (rc) return rc;
-    rc = lt_launch_layer1(g, v->S2, Hp2, t->b2p, t->W3p, C, v->Z2, v->Sc, st, v->seg_part);
-    if (rc) return rc;
-    return lt_launch_layer2(g, v->Sc, C, t->P[5], v->Z, st);
+extern "C" int lt_gcn3_trainer_destroy(lt_gcn3_trainer *t) {
+    free_trainer(t);
+    return LT_OK;
+}
+
+extern "C" int lt_gcn3_trainer_epoch(const lt_gcn3_trainer *t, int64_t *epoch) {
+    return trainer_epoch("lt_gcn3_trainer_epoch", t, epoch);
+}
+
+extern "C" int lt_gcn3_trainer_run(lt_gcn3_trainer *t, int32_t n_epochs, float *record, void *stream) {
+    return trainer_run("lt_gcn3_trainer_run", t, n_epochs, record, false, nullptr, nullptr, stream);
+}
+
+extern "C" int lt_gcn3_trainer_grads(const lt_gcn3_trainer *t, float *dW1, float *db1, float *dW2, float *db2, float *dW3,
+                                     float *db3, void *stream) {
+    LT_REQUIRE(t != nullptr && dW1 && db1 && dW2 && db2 && dW3 && db3, "lt_gcn3_trainer_grads: NULL argument");
+    float *const dst[6] = {dW1, db1, dW2, db2, dW3, db3};
+    return trainer_grads(t, dst, stream);
+}
+
+extern "C" int lt_gcn3_trainer_logits(const lt_gcn3_trainer *t, float *Z3, int64_t ldz, void *stream) {
+    return trainer_logits("lt_gcn3_trainer_logits", t, Z3, ldz, stream);
+}
+
+extern "C" int lt_gcn3_trainer_hidden(const lt_gcn3_trainer *t, int32_t layer, float *dst, int64_t ld, void *stream) {
+    LT_REQUIRE(t != nullptr && dst != nullptr, "lt_gcn3_trainer_hidden: NULL argument");
+    LT_REQUIRE(layer == 1 || layer == 2, "lt_gcn3_trainer_hidden: layer=%d, must be 1 or 2", layer);
+    const int H = t->H[layer - 1];
+    LT_REQUIRE(ld >= H, "lt_gcn3_trainer_hidden: ld=%lld < H%d=%d", (long long)ld, layer, H);
+    return copy_rows(dst, ld, layer == 1 ? t->fHd : t->Hd, t->Hp[layer - 1], H, t->n, stream);
 }
 
 extern "C" int lt_gcn3_trainer_attach_validation(lt_gcn3_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2,
                                                  int32_t n2, const int32_t *labels2, int32_t keep_best, int32_t patience,
                                                  void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_attach_validation: trainer is NULL");
-    return val_attach("lt_gcn3_trainer_attach_validation", &t->val, g2, X2, ldx2, n2, labels2, keep_best, patience, t->X, t->F,
-                      t->H1, t->Hp1, t->Hp2, t->C, t->off[5], (hipStream_t)stream);
+    return val_attach("lt_gcn3_trainer_attach_validation", t, g2, X2, ldx2, n2, labels2, keep_best, patience, stream);
 }
 
 extern "C" int lt_gcn3_trainer_attach_validation_rows(lt_gcn3_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2,
                                                       int32_t n2, const int32_t *labels2, int32_t keep_best, int32_t patience,
                                                       const int32_t *rows, int32_t m, void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_attach_validation_rows: trainer is NULL");
-    return val_attach("lt_gcn3_trainer_attach_validation_rows", &t->val, g2, X2, ldx2, n2, labels2, keep_best, patience, t->X,
-                      t->F, t->H1, t->Hp1, t->Hp2, t->C, t->off[5], (hipStream_t)stream, 1, rows, m);
+    return val_attach("lt_gcn3_trainer_attach_validation_rows", t, g2, X2, ldx2, n2, labels2, keep_best, patience, stream, 1, rows,
+                      m);
 }
 
 extern "C" int lt_gcn3_trainer_run_validated(lt_gcn3_trainer *t, int32_t n_epochs, float *record, float *val_loss,
                                              int32_t *val_counts, void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_run_validated: trainer is NULL");
-    LT_REQUIRE(t->val != nullptr, "lt_gcn3_trainer_run_validated: no validation attached");
-    LT_REQUIRE(n_epochs >= 0, "lt_gcn3_trainer_run_validated: n_epochs=%d", n_epochs);
-    if (n_epochs == 0) return LT_OK;
-    LT_REQUIRE(record && val_loss && val_counts, "lt_gcn3_trainer_run_validated: NULL output");
-    LT_REQUIRE(t->epoch + n_epochs <= (int64_t)INT32_MAX, "lt_gcn3_trainer_run_validated: epoch counter would pass 2^31");
-    hipStream_t st = (hipStream_t)stream;
-    const int mx = t->Hp1 > t->Hp2 * t->C ? t->Hp1 : t->Hp2 * t->C;
-    hipLaunchKernelGGL(k_tr3_pad, dim3((mx + 255) / 256), dim3(256), 0, st, t->P[1], t->H1, t->Hp1, t->P[3], t->H2, t->Hp2,
-                       t->P[4], t->C, t->b1p, t->b2p, t->W3p);
-    LT_CHECK_LAUNCH();
-    const lt_snap_segs T = snap_segs3(t);
-    const size_t cc = (size_t)t->C * t->C;
-    for (int32_t j = 0; j < n_epochs; ++j) {
-        const int64_t e = t->epoch;
-        int rc = run_epoch3(t, record + 2 * (size_t)j, st);
-        if (rc) return rc;
-        rc = val_forward3(t, st);
-        if (rc) return rc;
-        rc = val_finish_epoch(t->val, t->C, T, e, val_loss + j, val_counts + cc * (size_t)j, st);
-        if (rc) return rc;
-    }
-    return LT_OK;
+    return trainer_run("lt_gcn3_trainer_run_validated", t, n_epochs, record, true, val_loss, val_counts, stream);
 }
 
 extern "C" int lt_gcn3_trainer_val_state(const lt_gcn3_trainer *t, int32_t *state, void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_val_state: trainer is NULL");
-    return val_read_state("lt_gcn3_trainer_val_state", t->val, state, (hipStream_t)stream);
+    return trainer_val_state("lt_gcn3_trainer_val_state", t, state, stream);
 }
 
 extern "C" int lt_gcn3_trainer_restore_best(lt_gcn3_trainer *t, void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_restore_best: trainer is NULL");
-    LT_REQUIRE(t->val != nullptr && t->val->keep_best, "lt_gcn3_trainer_restore_best: no validation with keep_best attached");
-    return launch_snapshot(snap_segs3(t), t->val->snap, t->val->state + VS_SEEN, 1, (hipStream_t)stream);
+    return trainer_restore_best("lt_gcn3_trainer_restore_best", t, stream);
 }
 
 extern "C" int lt_gcn3_trainer_val_logits(const lt_gcn3_trainer *t, float *Z, int64_t ldz, void *stream) {
-    LT_REQUIRE(t != nullptr, "lt_gcn3_trainer_val_logits: trainer is NULL");
-    return val_copy_logits("lt_gcn3_trainer_val_logits", t->val, t->C, Z, ldz, (hipStream_t)stream);
+    return trainer_val_logits("lt_gcn3_trainer_val_logits", t, Z, ldz, stream);
 }

@@ -834,35 +834,36 @@ class EarlyStopState:
         return self.words.cpu().numpy()
 
 
-class GCN2Trainer(_ValidationMixin):
-    """Training of the 2-layer GCN on the GPU (lt_gcn2_trainer_*): one epoch is the reference's ``train_one_epoch`` on a
-    transfer dataset (gcn_trainer.py:144-170) -- forward with dropout, mean cross-entropy, backward, ``optim.Adam`` with
-    weight decay -- as ~15 stream-ordered launches on torch's current stream and no host synchronisation.  ``w1, b1, w2, b2``
-    are updated IN PLACE (their version counters are bumped after every ``run``); the trainer owns the Adam moments.
-    Dropout is a Philox4x32-10 mask keyed by ``seed`` and the epoch counter (include/linkteller_hip.h), so it can be
-    rebuilt exactly; it is not torch's generator.  Limits: hidden width <= 256, classes <= 8.  Validation every epoch,
-    best-model snapshot and early stopping: ``attach_validation`` / ``run_validated`` (_ValidationMixin)."""
+class _GCNTrainer(_ValidationMixin):
+    """What ``GCN2Trainer`` and ``GCN3Trainer`` share: the constructor's checks, driven by the class's parameter names, and the
+    accessors, which reach the C entry points through ``_PREFIX``.  The parameters are updated IN PLACE (their version counters
+    are bumped after every ``run``); the trainer owns the Adam moments.  Dropout is a Philox4x32-10 mask keyed by ``seed``, the
+    epoch counter and the hidden layer (include/linkteller_hip.h), so it can be rebuilt exactly; it is not torch's generator.
+    Limits: hidden widths <= 256, classes <= 8."""
 
-    _PREFIX = "lt_gcn2_trainer"
+    _NAMES = ()       # the parameter tensors in model order; each becomes the attribute of its lower-case name
+    _MODEL = ""       # the model's name in the shape error
 
-    def __init__(self, adj, x, labels, w1, b1, w2, b2, *, lr, weight_decay, dropout, seed):
+    def __init__(self, adj, x, labels, params, *, lr, weight_decay, dropout, seed):
         if not 0.0 <= float(dropout) <= 1.0:      # F.dropout's message
             raise ValueError(f"dropout probability has to be between 0 and 1, but got {dropout}")
         self.graph: HipGraph = as_hip_graph(adj)
         self.x = _f32(x, "x")
-        self.params = [_f32(t, n) for t, n in ((w1, "W1"), (b1, "b1"), (w2, "W2"), (b2, "b2"))]
-        for t, src in zip(self.params, (w1, b1, w2, b2)):
+        self.params = [_f32(t, n) for t, n in zip(params, self._NAMES)]
+        for t, src in zip(self.params, params):
             if t.data_ptr() != src.data_ptr():
                 raise ValueError("the parameters are updated in place: pass contiguous float32 device tensors")
-        self.w1, self.b1, self.w2, self.b2 = self.params
+        for name, t in zip(self._NAMES, self.params):
+            setattr(self, name.lower(), t)
         n, f = self.x.shape
-        self.n, self.f, self.h, self.c = n, f, self.w1.shape[1], self.w2.shape[1]
-        if (n != self.graph.n or self.w1.shape != (f, self.h) or self.b1.shape != (self.h,)
-                or self.w2.shape != (self.h, self.c) or self.b2.shape != (self.c,)):
-            raise ValueError("inconsistent GCN shapes")
+        dims = [f] + [w.shape[1] for w in self.params[0::2]]      # layer l maps dims[l] to dims[l + 1] columns
+        self.n, self.f, self.c = n, f, dims[-1]
+        if n != self.graph.n or any(w.shape != (dims[l], dims[l + 1]) or b.shape != (dims[l + 1],)
+                                    for l, (w, b) in enumerate(zip(self.params[0::2], self.params[1::2]))):
+            raise ValueError(f"inconsistent {self._MODEL} shapes")
         if self.graph.device_index != self.x.device.index:
             raise ValueError(f"the graph lives on cuda:{self.graph.device_index}, the features on {self.x.device}")
-        _require_finite(features=self.x, W1=self.w1, b1=self.b1, W2=self.w2, b2=self.b2)
+        _require_finite(features=self.x, **dict(zip(self._NAMES, self.params)))
         if not isinstance(labels, torch.Tensor):
             labels = torch.as_tensor(labels)
         labels = labels.reshape(-1)
@@ -872,24 +873,23 @@ class GCN2Trainer(_ValidationMixin):
             raise ValueError(f"labels outside [0, {self.c})")
         self.labels = labels.to(device=self.x.device, dtype=torch.int32).contiguous()
         h = C.c_void_p()
-        _lib.check(_lib.lib().lt_gcn2_trainer_create(self.graph.handle, self.x.data_ptr(), f, f, self.labels.data_ptr(),
-                                                     self.h, self.c, self.w1.data_ptr(), self.b1.data_ptr(),
-                                                     self.w2.data_ptr(), self.b2.data_ptr(), float(lr), float(weight_decay),
-                                                     float(dropout), int(seed) & (2**64 - 1), _stream(), C.byref(h)),
-                   "lt_gcn2_trainer_create")
+        fn = f"{self._PREFIX}_create"
+        _lib.check(getattr(_lib.lib(), fn)(self.graph.handle, self.x.data_ptr(), f, f, self.labels.data_ptr(), *dims[1:],
+                                           *[t.data_ptr() for t in self.params], float(lr), float(weight_decay),
+                                           float(dropout), int(seed) & (2**64 - 1), _stream(), C.byref(h)), fn)
         self._h = h
-        self._finalizer = weakref.finalize(self, _lib.lib().lt_gcn2_trainer_destroy, h)
+        self._finalizer = weakref.finalize(self, getattr(_lib.lib(), f"{self._PREFIX}_destroy"), h)
 
     @property
     def epoch(self) -> int:
         e = C.c_int64()
-        _lib.check(_lib.lib().lt_gcn2_trainer_epoch(self._h, C.byref(e)), "lt_gcn2_trainer_epoch")
+        self._call("epoch", C.byref(e))
         return e.value
 
     def run_async(self, epochs: int) -> torch.Tensor:
         """Enqueue ``epochs`` epochs; returns the device record [epochs, 2] (mean loss, correct count) without syncing."""
         record = torch.empty((max(int(epochs), 0), 2), dtype=torch.float32, device=self.x.device)
-        _lib.check(_lib.lib().lt_gcn2_trainer_run(self._h, int(epochs), record.data_ptr(), _stream()), "lt_gcn2_trainer_run")
+        self._call("run", int(epochs), record.data_ptr(), _stream())
         for p in self.params:
             torch.autograd.graph.increment_version(p)
         return record
@@ -900,95 +900,43 @@ class GCN2Trainer(_ValidationMixin):
         return rec[:, 0].copy(), rec[:, 1].astype("int64")
 
     def grads(self):
-        """(dW1, db1, dW2, db2) of the last epoch (before weight decay)."""
-        dev = self.x.device
-        out = [torch.empty_like(p, device=dev) for p in self.params]
-        _lib.check(_lib.lib().lt_gcn2_trainer_grads(self._h, *[t.data_ptr() for t in out], _stream()), "lt_gcn2_trainer_grads")
+        """The last epoch's gradients (before weight decay), one per parameter in the constructor's order."""
+        out = [torch.empty_like(p) for p in self.params]
+        self._call("grads", *[t.data_ptr() for t in out], _stream())
         return tuple(out)
 
     def logits(self) -> torch.Tensor:
         """The last epoch's train-mode logits (dropout applied, before that epoch's update)."""
         out = torch.empty((self.n, self.c), dtype=torch.float32, device=self.x.device)
-        _lib.check(_lib.lib().lt_gcn2_trainer_logits(self._h, out.data_ptr(), self.c, _stream()), "lt_gcn2_trainer_logits")
+        self._call("logits", out.data_ptr(), self.c, _stream())
         return out
 
 
-class GCN3Trainer(_ValidationMixin):
-    """Training of the 3-layer GCN3 on the GPU (lt_gcn3_trainer_*): the epoch of ``GCN2Trainer`` one layer up -- two hidden
-    layers with independent Philox masks (the counter's layer word), the backward through the middle layer on the matrix
-    cores, one Adam launch over the six tensors -- as stream-ordered launches on torch's current stream and no host
-    synchronisation.  ``w1 .. b3`` are updated IN PLACE (version counters bumped after every ``run``).  Limits: hidden
-    widths <= 256, classes <= 8.  Validation as for ``GCN2Trainer`` (_ValidationMixin)."""
+class GCN2Trainer(_GCNTrainer):
+    """Training of the 2-layer GCN on the GPU (lt_gcn2_trainer_*): one epoch is the reference's ``train_one_epoch`` on a
+    transfer dataset (gcn_trainer.py:144-170) -- forward with dropout, mean cross-entropy, backward, ``optim.Adam`` with
+    weight decay -- as ~15 stream-ordered launches on torch's current stream and no host synchronisation.  ``w1, b1, w2, b2``
+    are updated in place.  Validation every epoch, best-model snapshot and early stopping: ``attach_validation`` /
+    ``run_validated`` (_ValidationMixin)."""
 
-    _PREFIX = "lt_gcn3_trainer"
+    _PREFIX, _NAMES, _MODEL = "lt_gcn2_trainer", ("W1", "b1", "W2", "b2"), "GCN"
+
+    def __init__(self, adj, x, labels, w1, b1, w2, b2, *, lr, weight_decay, dropout, seed):
+        super().__init__(adj, x, labels, (w1, b1, w2, b2), lr=lr, weight_decay=weight_decay, dropout=dropout, seed=seed)
+        self.h = self.w1.shape[1]
+
+
+class GCN3Trainer(_GCNTrainer):
+    """Training of the 3-layer GCN3 on the GPU (lt_gcn3_trainer_*): the epoch of ``GCN2Trainer`` behind one more hidden layer
+    -- two hidden layers with independent Philox masks (the counter's layer word), the backward through the middle layer on
+    the matrix cores, one Adam launch over the six tensors.  ``w1 .. b3`` are updated in place.  Validation as for
+    ``GCN2Trainer`` (_ValidationMixin)."""
+
+    _PREFIX, _NAMES, _MODEL = "lt_gcn3_trainer", ("W1", "b1", "W2", "b2", "W3", "b3"), "GCN3"
 
     def __init__(self, adj, x, labels, w1, b1, w2, b2, w3, b3, *, lr, weight_decay, dropout, seed):
-        if not 0.0 <= float(dropout) <= 1.0:      # F.dropout's message
-            raise ValueError(f"dropout probability has to be between 0 and 1, but got {dropout}")
-        self.graph: HipGraph = as_hip_graph(adj)
-        self.x = _f32(x, "x")
-        names = ("W1", "b1", "W2", "b2", "W3", "b3")
-        self.params = [_f32(t, n) for t, n in zip((w1, b1, w2, b2, w3, b3), names)]
-        for t, src in zip(self.params, (w1, b1, w2, b2, w3, b3)):
-            if t.data_ptr() != src.data_ptr():
-                raise ValueError("the parameters are updated in place: pass contiguous float32 device tensors")
-        self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = self.params
-        n, f = self.x.shape
-        self.n, self.f, self.h1, self.h2, self.c = n, f, self.w1.shape[1], self.w2.shape[1], self.w3.shape[1]
-        if (n != self.graph.n or self.w1.shape != (f, self.h1) or self.b1.shape != (self.h1,)
-                or self.w2.shape != (self.h1, self.h2) or self.b2.shape != (self.h2,)
-                or self.w3.shape != (self.h2, self.c) or self.b3.shape != (self.c,)):
-            raise ValueError("inconsistent GCN3 shapes")
-        if self.graph.device_index != self.x.device.index:
-            raise ValueError(f"the graph lives on cuda:{self.graph.device_index}, the features on {self.x.device}")
-        _require_finite(features=self.x, **dict(zip(names, self.params)))
-        if not isinstance(labels, torch.Tensor):
-            labels = torch.as_tensor(labels)
-        labels = labels.reshape(-1)
-        if labels.numel() != n:
-            raise ValueError(f"labels: {labels.numel()} entries for {n} nodes")
-        if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= self.c):
-            raise ValueError(f"labels outside [0, {self.c})")
-        self.labels = labels.to(device=self.x.device, dtype=torch.int32).contiguous()
-        h = C.c_void_p()
-        _lib.check(_lib.lib().lt_gcn3_trainer_create(self.graph.handle, self.x.data_ptr(), f, f, self.labels.data_ptr(),
-                                                     self.h1, self.h2, self.c, *[t.data_ptr() for t in self.params],
-                                                     float(lr), float(weight_decay), float(dropout),
-                                                     int(seed) & (2**64 - 1), _stream(), C.byref(h)),
-                   "lt_gcn3_trainer_create")
-        self._h = h
-        self._finalizer = weakref.finalize(self, _lib.lib().lt_gcn3_trainer_destroy, h)
-
-    @property
-    def epoch(self) -> int:
-        e = C.c_int64()
-        _lib.check(_lib.lib().lt_gcn3_trainer_epoch(self._h, C.byref(e)), "lt_gcn3_trainer_epoch")
-        return e.value
-
-    def run_async(self, epochs: int) -> torch.Tensor:
-        """Enqueue ``epochs`` epochs; returns the device record [epochs, 2] (mean loss, correct count) without syncing."""
-        record = torch.empty((max(int(epochs), 0), 2), dtype=torch.float32, device=self.x.device)
-        _lib.check(_lib.lib().lt_gcn3_trainer_run(self._h, int(epochs), record.data_ptr(), _stream()), "lt_gcn3_trainer_run")
-        for p in self.params:
-            torch.autograd.graph.increment_version(p)
-        return record
-
-    def run(self, epochs: int):
-        """Run ``epochs`` epochs; returns (loss [epochs] float32, correct [epochs] int64) as CPU arrays (one read at the end)."""
-        rec = self.run_async(epochs).cpu().numpy()
-        return rec[:, 0].copy(), rec[:, 1].astype("int64")
-
-    def grads(self):
-        """(dW1, db1, dW2, db2, dW3, db3) of the last epoch (before weight decay)."""
-        out = [torch.empty_like(p) for p in self.params]
-        _lib.check(_lib.lib().lt_gcn3_trainer_grads(self._h, *[t.data_ptr() for t in out], _stream()), "lt_gcn3_trainer_grads")
-        return tuple(out)
-
-    def logits(self) -> torch.Tensor:
-        """The last epoch's train-mode logits (both dropouts applied, before that epoch's update)."""
-        out = torch.empty((self.n, self.c), dtype=torch.float32, device=self.x.device)
-        _lib.check(_lib.lib().lt_gcn3_trainer_logits(self._h, out.data_ptr(), self.c, _stream()), "lt_gcn3_trainer_logits")
-        return out
+        super().__init__(adj, x, labels, (w1, b1, w2, b2, w3, b3), lr=lr, weight_decay=weight_decay, dropout=dropout, seed=seed)
+        self.h1, self.h2 = self.w1.shape[1], self.w2.shape[1]
 
     def hidden(self, layer: int) -> torch.Tensor:
         """The last epoch's hidden activations after ReLU and dropout: layer 1 -> H1d [n, H1], layer 2 -> H2d [n, H2]."""

@@ -110,22 +110,26 @@ class GCNTrainer:
         keep = validate in ("best", "early")
         tr.attach_validation(w.adj_2, w.features_2, w.labels_2, keep_best=keep,
                              patience=int(self.args.patience) if validate == "early" else 0)
-        r = tr.run_validated(n_epochs)
+        self._log_validated(tr.run_validated(n_epochs), t_total, tr.n2, restore=keep)
+
+    def _log_validated(self, r, t_total, n_val, restore):
+        """The log lines of a validated run ``r`` (``run_validated``'s dict) whose head scored ``n_val`` rows; with ``restore``
+        the parameters of the best validation loss are put back."""
+        tr = self.gpu_trainer
         done = len(r["loss"])
         per_epoch = (time.time() - t_total) / max(done, 1)
-        n, n2 = tr.n, tr.n2
         for epoch in range(done):
             logging.info("[epoch {}]".format(epoch))
             output_info = "Epoch: {:04d}".format(epoch + 1), \
                 "loss_train: {:.4f}".format(float(r["loss"][epoch])), \
-                "acc_train: {:.4f}".format(int(r["correct"][epoch]) / n), \
+                "acc_train: {:.4f}".format(int(r["correct"][epoch]) / tr.n), \
                 "loss_val: {:.4f}".format(float(r["val_loss"][epoch])), \
-                "acc_val: {:.4f}".format(int(r["val_counts"][epoch].trace()) / n2), \
+                "acc_val: {:.4f}".format(int(r["val_counts"][epoch].trace()) / n_val), \
                 "time: {:.4f}s".format(per_epoch)
             logging.info(output_info)
-        if validate == "early" and r["stop_epoch"] >= 0:
+        if r["stop_epoch"] >= 0:      # (only a run with a patience stops)
             logging.info(f"early stop at epoch {r['stop_epoch']}")
-        if keep and done:
+        if done and restore:
             tr.restore_best()
             info = f"best validation loss {float(r['val_loss'][r['best_epoch']]):.4f} at epoch {r['best_epoch']}: that model is saved"
             print(info)
@@ -143,26 +147,7 @@ class GCNTrainer:
         tr.attach_validation(w.adj_full, w.features, w.labels, rows=w.idx_val, keep_best=keep,
                              patience=int(a.patience) if (early or validate == "early") else 0)
         r = tr.run_validated(n_epochs)
-        done = len(r["loss"])
-        per_epoch = (time.time() - t_total) / max(done, 1)
-        n, n_val = tr.n, len(w.idx_val)
-        for epoch in range(done):
-            logging.info("[epoch {}]".format(epoch))
-            output_info = "Epoch: {:04d}".format(epoch + 1), \
-                "loss_train: {:.4f}".format(float(r["loss"][epoch])), \
-                "acc_train: {:.4f}".format(int(r["correct"][epoch]) / n), \
-                "loss_val: {:.4f}".format(float(r["val_loss"][epoch])), \
-                "acc_val: {:.4f}".format(int(r["val_counts"][epoch].trace()) / n_val), \
-                "time: {:.4f}s".format(per_epoch)
-            logging.info(output_info)
-        stopped = r["stop_epoch"] >= 0
-        if stopped:
-            logging.info(f"early stop at epoch {r['stop_epoch']}")
-        if done and (validate in ("best", "early") or (early and stopped)):
-            tr.restore_best()
-            info = f"best validation loss {float(r['val_loss'][r['best_epoch']]):.4f} at epoch {r['best_epoch']}: that model is saved"
-            print(info)
-            logging.info(info)
+        self._log_validated(r, t_total, len(w.idx_val), restore=validate in ("best", "early") or (early and r["stop_epoch"] >= 0))
 
     def forward(self, mode="train"):
         w = self.worker
