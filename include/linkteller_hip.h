@@ -45,7 +45,9 @@ extern "C" {
                             Additive within 5: validation every epoch (lt_eval_head, lt_early_stop_*, lt_gcn*_trainer_attach_validation /
                             _run_validated / _val_state / _restore_best / _val_logits); no entry point changed.
                             Additive within 5: evaluation over a row list (lt_eval_head_rows, lt_eval_head_rows_workspace_bytes,
-                            lt_gcn*_trainer_attach_validation_rows); no entry point changed */
+                            lt_gcn*_trainer_attach_validation_rows); no entry point changed.
+                            Additive within 5: the wide head of the 2-layer trainer (lt_gcn2_trainer_create_wide, _counts, _hidden,
+                            _attach_validation_wide, lt_eval_head_wide, lt_eval_head_wide_workspace_bytes); no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -970,6 +972,45 @@ int lt_gcn2_trainer_attach_validation_rows(lt_gcn2_trainer *t, const lt_graph *g
 int lt_gcn3_trainer_attach_validation_rows(lt_gcn3_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
                                            const int32_t *labels2, int32_t keep_best, int32_t patience, const int32_t *rows,
                                            int32_t m, void *stream);
+
+/* ---- the wide head of the 2-layer trainer: class width 1 <= C <= 256, cross-entropy or multi-label BCE (reference
+ * gcn_trainer.py:27-28, 41-45, 258-262) ----
+ * lt_gcn2_trainer_create_wide is lt_gcn2_trainer_create with the class layer run as matrix products at the padded width and
+ * the loss head of lt_train_wide.hip.h.  loss_kind LT_LOSS_CE: labels int32 [n] (ldy is not read), mean cross-entropy;
+ * LT_LOSS_BCE: labels uint8 [n, ldy] holding 0 / 1 (any other byte counts as 1), loss = sum over all n C elements of
+ * max(z, 0) - z y + log1p(exp(-|z|)), divided by n C (F.binary_cross_entropy_with_logits, mean).  The handle is a
+ * lt_gcn2_trainer: _run, _grads, _logits, _epoch, _destroy, _run_validated, _val_state, _restore_best and _val_logits work on
+ * it.  record [n_epochs, 2] = (loss, sum over the classes of tp): for CE the correct count, as lt_gcn2_trainer_run's.  The
+ * mask contract is the 2-layer trainer's (layer word 0).  No float atomics, every reduction in a fixed order: run(a + b)
+ * equals run(a); run(b) and two trainers agree bit for bit.  Against lt_gcn2_trainer_create at C <= 8 the results agree to
+ * rounding, not bit for bit: the class layer's sums are associated differently.  LT_ERR_INVALID with a message naming the
+ * value, nothing allocated: H > 256, C > 256, an unknown loss_kind, ldy < C for LT_LOSS_BCE.
+ * lt_gcn2_trainer_counts: the LAST epoch's counts, int32 [C, 3] = (tp, fp, fn) per class (device); wide trainers only.  CE: a
+ * row with first argmax a and label y adds tp[y] when a == y, else fp[a] and fn[y].  BCE: element (r, c) is predicted positive
+ * iff z > 0 (the reference's sigmoid(z) > 0.5 in fp32 differs only where |z| < 2^-22).
+ * lt_gcn2_trainer_hidden: test accessor, the last epoch's H1d = drop(relu(A X W1 + b1)) [n, H] with leading dimension ld >= H;
+ * any 2-layer trainer.
+ * lt_gcn2_trainer_attach_validation_wide: lt_gcn2_trainer_attach_validation(_rows) for a wide trainer; labels2 as the
+ * trainer's labels (ldy2 for BCE), rows may be NULL (all n2 rows).  lt_gcn2_trainer_run_validated then writes val_counts as
+ * [n_epochs, C, 3]; the state rule, the snapshot and the accessors keep their meaning.  The attach entry points of the narrow
+ * head called on a wide trainer, and this one on a narrow trainer, are LT_ERR_INVALID.
+ * lt_eval_head_wide: the head's loss and counts [C, 3] of logits Z [n, ldz] over all rows (rows == NULL; m is not read) or
+ * the m listed ones, with lt_eval_head_rows' rules: repeats count, an id outside [0, n) is never dereferenced and is counted
+ * in *n_bad (may be NULL), the divisor stays m (times C for BCE); with rows = 0 .. n - 1 the bits of the call without a list.
+ * Workspace: lt_eval_head_wide_workspace_bytes(entries scored, C) (0 for unsupported values). */
+enum { LT_LOSS_CE = 0, LT_LOSS_BCE = 1 };
+int lt_gcn2_trainer_create_wide(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const void *labels, int64_t ldy,
+                                int32_t loss_kind, int32_t H, int32_t C, float *W1, float *b1, float *W2, float *b2, double lr,
+                                double weight_decay, double dropout, uint64_t seed, void *stream, lt_gcn2_trainer **out);
+int lt_gcn2_trainer_counts(const lt_gcn2_trainer *t, int32_t *counts, void *stream);
+int lt_gcn2_trainer_hidden(const lt_gcn2_trainer *t, float *H1d, int64_t ld, void *stream);
+int lt_gcn2_trainer_attach_validation_wide(lt_gcn2_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
+                                           const void *labels2, int64_t ldy2, int32_t keep_best, int32_t patience,
+                                           const int32_t *rows, int32_t m, void *stream);
+size_t lt_eval_head_wide_workspace_bytes(int32_t m, int32_t C);
+int lt_eval_head_wide(const float *Z, int64_t ldz, const void *labels, int64_t ldy, int32_t n, int32_t C, int32_t loss_kind,
+                      const int32_t *rows, int32_t m, float *loss, int32_t *counts, int32_t *n_bad, void *workspace,
+                      size_t workspace_bytes, void *stream);
 
 /* ---- per-kernel timing (used by bench.py for the roofline object) --------------------------
  * lt_profile_enable(mask): bit k of mask set = launches of kernel class k are bracketed by a pair of

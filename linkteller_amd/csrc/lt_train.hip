@@ -755,6 +755,7 @@ struct lt_val {
     const int32_t *labels = nullptr;
     const int32_t *rows = nullptr;         // attach_validation_rows: the head scores these m rows (borrowed); NULL: all n
     int32_t m = 0;
+    int64_t ldy = 0;                       // wide BCE head: leading dimension of the uint8 labels
     int32_t keep_best = 0, patience = 0;
     int32_t kslice = 0;           // split-K slicing of X2 W1, chosen for n2 (the forward's choice at that size)
     int32_t n_blk = 0;            // blocks of k_val_rows
@@ -809,8 +810,9 @@ static int launch_val_head(const float *Z, long ldz, const int32_t *labels, int 
 
 // H1d[r] = drop(relu(A[r, :] S + bias)) for every row.  The launch's first seg_blocks blocks take the SEGMENTS of the hub rows
 // (k_layer1's scheme: row_dot's canonical order, the first segment's chain started from the bias); k_tr3_layer1_long adds
-// them in segment order and applies the same epilogue.
-template <int LPR>
+// them in segment order and applies the same epilogue.  ACT = false: no ReLU and no mask, the row is stored as it is summed (the
+// wide head's class layer Z2 = A S2 + b2).
+template <int LPR, bool ACT = true>
 __global__ __launch_bounds__(TR_BLOCK) void k_tr3_layer1(
     int n, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
     const float *__restrict__ S, int Hp, int H, const float *__restrict__ biasp, lt_drop_args d, float *__restrict__ Hd,
@@ -840,13 +842,16 @@ __global__ __launch_bounds__(TR_BLOCK) void k_tr3_layer1(
     const f32x4 bv = active ? ld4(biasp + coff) : f32x4{0.f, 0.f, 0.f, 0.f};
     const f32x4 z = row_dot<8>(col, val, rowptr[r], rowptr[r + 1], S, Hp, coff, active, -1, nullptr, bv);
     if (active) {
-        f32x4 h = {fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f)};
-        if (d.on) h = lt_drop4(h, r, coff, H, d);
+        f32x4 h = z;
+        if constexpr (ACT) {
+            h = f32x4{fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f)};
+            if (d.on) h = lt_drop4(h, r, coff, H, d);
+        }
         *reinterpret_cast<f32x4 *>(Hd + (size_t)r * Hp + coff) = h;
     }
 }
 
-template <int LPR>
+template <int LPR, bool ACT = true>
 __global__ __launch_bounds__(TR_BLOCK) void k_tr3_layer1_long(int n_long, const int32_t *__restrict__ long_row,
                                                               const int32_t *__restrict__ long_segptr,
                                                               const float *__restrict__ part, int Hp, int H, lt_drop_args d,
@@ -867,8 +872,11 @@ __global__ __launch_bounds__(TR_BLOCK) void k_tr3_layer1_long(int n_long, const 
         const f32x4 t = ld4(part + (size_t)s * Hp + coff);
         z.x += t.x; z.y += t.y; z.z += t.z; z.w += t.w;
     }
-    f32x4 h = {fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f)};
-    if (d.on) h = lt_drop4(h, r, coff, H, d);
+    f32x4 h = z;
+    if constexpr (ACT) {
+        h = f32x4{fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f)};
+        if (d.on) h = lt_drop4(h, r, coff, H, d);
+    }
     *reinterpret_cast<f32x4 *>(Hd + (size_t)r * Hp + coff) = h;
 }
 
@@ -978,6 +986,10 @@ __global__ __launch_bounds__(256) void k_tr3_dz_mfma(const float *__restrict__ A
     if (tid < TN_BN && n0 + tid < N) part[(size_t)blockIdx.x * N + n0 + tid] = red[0][tid] + red[1][tid];
 }
 
+// The wide head's kernels and launcher.  Included here, not at the top: it uses TR_BLOCK, val_state_update and the row helpers
+// of lt_rows.hip.h defined above, and the trainer below uses its trw_plan / trw_parts / launch_trw_head.
+#include "lt_train_wide.hip.h"
+
 // --------------------------------------------------------------------------------------------
 // trainer state: one struct behind both public handles
 // --------------------------------------------------------------------------------------------
@@ -1016,7 +1028,21 @@ struct lt_trainer {
     float *slabs = nullptr, *part = nullptr, *part1 = nullptr, *seg_part = nullptr;
     float *grad = nullptr, *m = nullptr, *v = nullptr;   // [off[5]]
     lt_val *val = nullptr;        // lt_gcn*_trainer_attach_validation (owned)
+    // The wide head (lt_gcn2_trainer_create_wide; lt_train_wide.hip.h): the class layer as matrix products at the padded width
+    // Cp, Sc / Zc / dZc / dSc [n, Cp] with zero pad columns, `labels` int32 [n] (CE) or uint8 [n, ldy] (BCE), mir[3] = b2 at Cp.
+    int32_t wide = 0, loss_kind = 0, Cp = 0;
+    int64_t ldy = 0;
+    float *whead = nullptr;       // the head's partials (trw_part_bytes) and, behind them, the last epoch's counts [C, 3]
 };
+// widest padded row a segment scratch holds: the hidden widths and, for the wide head, the class layer's Cp
+static inline int trainer_hpm(const lt_trainer *t) {
+    const int h = t->Hp[0] > t->Hp[1] ? t->Hp[0] : t->Hp[1];
+    return t->wide && t->Cp > h ? t->Cp : h;
+}
+static inline int trainer_ldc(const lt_trainer *t) { return t->wide ? t->Cp : t->C; }      // leading dimension of the [n, C] buffers
+static inline int32_t *trainer_counts(const lt_trainer *t) {      // behind the training head's partials
+    return (int32_t *)((char *)t->whead + trw_parts(t->whead, t->n, t->C, true).bytes);
+}
 struct lt_gcn2_trainer : lt_trainer {};
 struct lt_gcn3_trainer : lt_trainer {};
 
@@ -1032,9 +1058,10 @@ struct lt_buf {
 // Fills b[TR_MAX_BUFS] from the trainer's own fields (the borrowed graph is not read: destroy may come after the graph's) and
 // returns the number of entries, -1 if the table does not hold them all.
 static int trainer_bufs(lt_trainer *t, lt_buf *b) {
-    const int top = t->layers - 2, C = t->C, hpm = t->Hp[0] > t->Hp[1] ? t->Hp[0] : t->Hp[1];
+    const int top = t->layers - 2, C = t->C, hpm = trainer_hpm(t);
     const size_t f4 = sizeof(float), n = (size_t)t->n;
-    const size_t nt = n * t->Hp[top] * f4, nf = top ? n * t->Hp[0] * f4 : 0, nc = n * C * f4, np = (size_t)t->off[5] * f4;
+    const bool w = t->wide != 0;      // the wide head: no Z, no row-loss arrays, no k_tr_bwd_rows slabs; its own partials
+    const size_t nt = n * t->Hp[top] * f4, nf = top ? n * t->Hp[0] * f4 : 0, nc = n * trainer_ldc(t) * f4, np = (size_t)t->off[5] * f4;
     int k = 0;
     auto add = [&](auto *slot, size_t bytes, bool zero = false) {
         if (k < TR_MAX_BUFS) b[k] = lt_buf{(void **)slot, bytes, zero};
@@ -1044,15 +1071,17 @@ static int trainer_bufs(lt_trainer *t, lt_buf *b) {
     // zero; the moments start at zero
     add(&t->fS, nf, true); add(&t->S, nt, true); add(&t->fdZ, nf, true);
     add(&t->fHd, nf); add(&t->fdS, nf);
-    add(&t->Z, nt); add(&t->Hd, nt); add(&t->dZ, nt); add(&t->dS, nt);
-    add(&t->Sc, nc); add(&t->Zc, nc); add(&t->dZc, nc); add(&t->dSc, nc);
-    add(&t->loss_r, n * f4); add(&t->corr_r, n * sizeof(int32_t));
+    // (wide: the class product writes C of the Cp columns of Sc, the dZ product H of the Hp columns of dZ)
+    add(&t->Z, w ? 0 : nt); add(&t->Hd, nt); add(&t->dZ, nt, w); add(&t->dS, nt);
+    add(&t->Sc, nc, w); add(&t->Zc, nc); add(&t->dZc, nc); add(&t->dSc, nc);
+    add(&t->loss_r, w ? 0 : n * f4); add(&t->corr_r, w ? 0 : n * sizeof(int32_t));
     for (int s = 0; s < 6; ++s) add(&t->mir[s], (size_t)t->mir_len[s] * f4);
     add(&t->slabs, lt_gemm_splitk_slab_bytes(t->n, t->H[0], t->F, t->kslice));
     add(&t->tn[0].slabs, t->tn[0].splits > 1 ? (size_t)t->tn[0].splits * t->F * t->H[0] * f4 : 0);
-    add(&t->tn[1].slabs, t->tn[1].splits > 1 ? (size_t)t->tn[1].splits * t->H[0] * t->H[1] * f4 : 0);
-    add(&t->part, (size_t)t->n_part * ((size_t)t->H[top] + (size_t)t->H[top] * C) * f4);
-    add(&t->part1, top ? (size_t)t->n_mblk * t->H[0] * f4 : 0);
+    add(&t->tn[1].slabs, t->tn[1].splits > 1 ? (size_t)t->tn[1].splits * t->H[0] * (w ? C : t->H[1]) * f4 : 0);
+    add(&t->part, w ? 0 : (size_t)t->n_part * ((size_t)t->H[top] + (size_t)t->H[top] * C) * f4);
+    add(&t->part1, top || w ? (size_t)t->n_mblk * t->H[0] * f4 : 0);
+    add(&t->whead, w ? trw_part_bytes(t->n, C, true) + 3 * (size_t)C * sizeof(int32_t) : 0);
     add(&t->seg_part, (size_t)t->n_seg * hpm * f4);
     add(&t->grad, np); add(&t->m, np, true); add(&t->v, np, true);
     return k <= TR_MAX_BUFS ? k : -1;
@@ -1087,7 +1116,8 @@ static void tn_plan(lt_tn *tn, int M, int N, int K) {
 // (Hs[1] = 0 for the 2-layer model), ps: the 2 * layers parameter tensors.
 static int trainer_create(const char *who, int layers, const lt_graph *g, const float *X, int64_t ldx, int32_t F,
                           const int32_t *labels, const int32_t *Hs, int32_t C, float *const *ps, double lr, double weight_decay,
-                          double dropout, uint64_t seed, void *stream, lt_trainer **out) {
+                          double dropout, uint64_t seed, void *stream, lt_trainer **out, int wide = 0, int loss_kind = 0,
+                          int64_t ldy = 0) {
     LT_REQUIRE(ldx >= F, "%s: ldx=%lld < F=%d", who, (long long)ldx, F);
     LT_REQUIRE(dropout >= 0.0 && dropout <= 1.0, "%s: dropout=%g outside [0, 1]", who, dropout);
     LT_REQUIRE(lr >= 0.0 && weight_decay >= 0.0, "%s: lr=%g weight_decay=%g", who, lr, weight_decay);
@@ -1098,6 +1128,7 @@ static int trainer_create(const char *who, int layers, const lt_graph *g, const 
     const int n = g->n, top = layers - 2;
     t->g = g; t->layers = layers; t->n = n; t->F = F; t->C = C;
     t->X = X; t->ldx = ldx; t->labels = labels;
+    t->wide = wide; t->loss_kind = loss_kind; t->ldy = ldy; t->Cp = lt_round_up(C, 4);
     const int dims[4] = {F, Hs[0], top ? Hs[1] : C, C};      // layer l maps dims[l] to dims[l + 1] columns
     int64_t end = 0;
     for (int l = 0; l < 3; ++l) {
@@ -1112,12 +1143,17 @@ static int trainer_create(const char *who, int layers, const lt_graph *g, const 
     t->kslice = lt_gemm_pick_kslice(n, t->H[0], F);
     tn_plan(&t->tn[0], F, t->H[0], n);
     if (top) tn_plan(&t->tn[1], t->H[0], t->H[1], n);
+    if (wide) tn_plan(&t->tn[1], t->H[0], C, n);      // dW2 = H1d^T dS2
     t->n_part = (n + TR_ROWS_PER_BLOCK - 1) / TR_ROWS_PER_BLOCK;
     t->n_mblk = (n + TN_BM - 1) / TN_BM;
     t->n_seg = g->p_n_seg > 0 ? g->p_n_seg : 0;
     t->mir_len[1] = t->Hp[0];
-    t->mir_len[2 * top + 1] = t->Hp[top];
-    t->mir_len[2 * top + 2] = t->Hp[top] * C;
+    if (wide) {
+        t->mir_len[3] = t->Cp;      // W2 is read as it lies by the products
+    } else {
+        t->mir_len[2 * top + 1] = t->Hp[top];
+        t->mir_len[2 * top + 2] = t->Hp[top] * C;
+    }
     hipStream_t st = (hipStream_t)stream;
     lt_buf b[TR_MAX_BUFS];
     const int nb = trainer_bufs(t, b);
@@ -1165,22 +1201,79 @@ static int launch_xw1(const lt_trainer *t, const float *X, int64_t ldx, int n, i
     return lt_launch_gemm(X, ldx, t->P[0], H, S1, t->Hp[0], n, H, t->F, st);
 }
 
-// GCN3's front layer on graph g: Hf = drop(relu(A S1 + b1)), then the top chain's input S = Hf W2
-static int launch_front(const lt_trainer *t, const lt_graph *g, const float *S1, const lt_drop_args &d, float *Hf,
-                        float *seg_part, float *S, hipStream_t st) {
-    const int n = g->n, H = t->H[0], Hp = t->Hp[0], lpr = lt_lpr_for(Hp), rpb = wide_rows_per_block(Hp);
+// out = A S + bias for every row of g at the padded width Hp, through k_tr3_layer1 (+ _long for the hub rows); ACT: with the
+// ReLU and the mask d
+template <bool ACT>
+static int launch_rows_layer(const lt_graph *g, const float *S, int Hp, int H, const float *biasp, const lt_drop_args &d,
+                             float *out, float *seg_part, hipStream_t st) {
+    const int n = g->n, lpr = lt_lpr_for(Hp), rpb = wide_rows_per_block(Hp);
     const int have_long = g->p_n_long > 0 ? 1 : 0;
     const unsigned seg_blocks = have_long ? rows_grid(g->p_n_seg, rpb) : 0u;
-    LT_DISPATCH_LPR(lpr, hipLaunchKernelGGL((k_tr3_layer1<LPR_>), dim3(rows_grid(n, rpb) + seg_blocks), dim3(TR_BLOCK), 0, st, n,
-                                            g->rowptr, g->col, g->val, S1, Hp, H, t->mir[1], d, Hf, have_long, (int)seg_blocks,
+    LT_DISPATCH_LPR(lpr, hipLaunchKernelGGL((k_tr3_layer1<LPR_, ACT>), dim3(rows_grid(n, rpb) + seg_blocks), dim3(TR_BLOCK), 0, st,
+                                            n, g->rowptr, g->col, g->val, S, Hp, H, biasp, d, out, have_long, (int)seg_blocks,
                                             g->p_n_seg, g->p_seg_long, g->p_seg_begin, g->p_long_row, seg_part));
     LT_CHECK_LAUNCH();
     if (have_long) {
-        LT_DISPATCH_LPR(lpr, hipLaunchKernelGGL((k_tr3_layer1_long<LPR_>), dim3(rows_grid(g->p_n_long, rpb)), dim3(TR_BLOCK), 0,
-                                                st, g->p_n_long, g->p_long_row, g->p_long_segptr, seg_part, Hp, H, d, Hf));
+        LT_DISPATCH_LPR(lpr, hipLaunchKernelGGL((k_tr3_layer1_long<LPR_, ACT>), dim3(rows_grid(g->p_n_long, rpb)), dim3(TR_BLOCK),
+                                                0, st, g->p_n_long, g->p_long_row, g->p_long_segptr, seg_part, Hp, H, d, out));
         LT_CHECK_LAUNCH();
     }
-    return lt_launch_gemm(Hf, Hp, t->P[2], t->H[1], S, t->Hp[1], n, t->H[1], H, st);
+    return LT_OK;
+}
+
+// GCN3's front layer on graph g: Hf = drop(relu(A S1 + b1)), then the top chain's input S = Hf W2
+static int launch_front(const lt_trainer *t, const lt_graph *g, const float *S1, const lt_drop_args &d, float *Hf,
+                        float *seg_part, float *S, hipStream_t st) {
+    const int rc = launch_rows_layer<true>(g, S1, t->Hp[0], t->H[0], t->mir[1], d, Hf, seg_part, st);
+    if (rc) return rc;
+    return lt_launch_gemm(Hf, t->Hp[0], t->P[2], t->H[1], S, t->Hp[1], g->n, t->H[1], t->H[0], st);
+}
+
+static lt_drop_args drop_off() {
+    lt_drop_args off;
+    off.on = 0; off.thresh = 0; off.scale = 1.f; off.epoch = 0; off.seed = 0;
+    return off;
+}
+
+// The wide route's forward on graph g from S1 = X W1: Hd = drop_0(relu(A S1 + b1)), Sc = Hd W2 (C of the Cp columns; the
+// others stay zero), Zc = A Sc + b2 at width Cp.
+static int launch_wide_forward(const lt_trainer *t, const lt_graph *g, const float *S1, const lt_drop_args &d, float *Hd,
+                               float *Sc, float *Zc, float *seg_part, hipStream_t st) {
+    const int H = t->H[0], Hp = t->Hp[0], C = t->C, Cp = t->Cp;
+    int rc = launch_rows_layer<true>(g, S1, Hp, H, t->mir[1], d, Hd, seg_part, st);
+    if (rc) return rc;
+    rc = lt_launch_gemm(Hd, Hp, t->P[2], C, Sc, Cp, g->n, C, H, st);
+    if (rc) return rc;
+    return launch_rows_layer<false>(g, Sc, Cp, C, t->mir[3], drop_off(), Zc, seg_part, st);
+}
+
+static int launch_tn(const float *A, long lda, const float *B, long ldb, float *C, int M, int N, int K, const lt_tn &tn,
+                     hipStream_t st);
+
+// The wide route's backward from dZc down to dS (= dS1): every gradient but dW1.
+static int launch_wide_backward(const lt_trainer *t, float scale, hipStream_t st) {
+    const lt_graph *g = t->g;
+    const int n = t->n, H = t->H[0], Hp = t->Hp[0], C = t->C, Cp = t->Cp;
+    const lt_trw_parts parts = trw_parts(t->whead, n, C, true);
+    hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((C + 63) / 64)), dim3(TR_BLOCK), 0, st, parts.db, parts.n_blk, C,
+                       t->grad + t->off[2]);                                                      // db2
+    LT_CHECK_LAUNCH();
+    LT_DISPATCH_LPR(lt_lpr_for(Cp), hipLaunchKernelGGL((k_tr_spmm_t_wide<LPR_>), dim3(rows_grid(n, wide_rows_per_block(Cp))),
+                                                       dim3(TR_BLOCK), 0, st, n, g->tptr, g->trow, g->tval, t->dZc, Cp, t->dSc));
+    LT_CHECK_LAUNCH();
+    int rc = launch_tn(t->Hd, (long)Hp, t->dSc, (long)Cp, t->grad + t->off[1], H, C, n, t->tn[1], st);      // dW2
+    if (rc) return rc;
+    dim3 grid((unsigned)t->n_mblk, (unsigned)((H + TN_BN - 1) / TN_BN));
+    hipLaunchKernelGGL(k_tr3_dz_mfma, grid, dim3(256), 0, st, t->dSc, (long)Cp, t->P[2], (long)C, t->Hd, t->dZ, (long)Hp, n, H, C,
+                       scale, t->part1);
+    LT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((H + 63) / 64)), dim3(TR_BLOCK), 0, st, t->part1, t->n_mblk, H,
+                       t->grad + t->off[0]);                                                      // db1
+    LT_CHECK_LAUNCH();
+    LT_DISPATCH_LPR(lt_lpr_for(Hp), hipLaunchKernelGGL((k_tr_spmm_t_wide<LPR_>), dim3(rows_grid(n, wide_rows_per_block(Hp))),
+                                                       dim3(TR_BLOCK), 0, st, n, g->tptr, g->trow, g->tval, t->dZ, Hp, t->dS));
+    LT_CHECK_LAUNCH();
+    return LT_OK;
 }
 
 // The top chain's forward on graph g: Z = A S + b with layer 1's own Sc = relu(Z) Wc, then (d != NULL) Hd = drop(relu(Z)) and
@@ -1268,13 +1361,23 @@ static int run_epoch(lt_trainer *t, float *record, hipStream_t st) {
         if (rc) return rc;
     }
     d.layer = (uint32_t)top;
-    rc = launch_top_forward(t, g, t->S, t->Z, &d, t->Hd, t->Sc, t->Zc, t->seg_part, st);
-    if (rc) return rc;
-    rc = launch_loss_head(t, record, st);
-    if (rc) return rc;
-    // backward
-    rc = launch_top_backward(t, scale, st);
-    if (rc) return rc;
+    if (t->wide) {      // the class layer as matrix products, the wide head, and their backward
+        rc = launch_wide_forward(t, g, t->S, d, t->Hd, t->Sc, t->Zc, t->seg_part, st);
+        if (rc) return rc;
+        rc = launch_trw_head(t->loss_kind, t->Zc, (long)t->Cp, t->labels, (long)t->ldy, n, t->C, nullptr, 0, t->dZc, t->whead,
+                             record, record + 1, trainer_counts(t), nullptr, nullptr, 0, 0, st);
+        if (rc) return rc;
+        rc = launch_wide_backward(t, scale, st);
+        if (rc) return rc;
+    } else {
+        rc = launch_top_forward(t, g, t->S, t->Z, &d, t->Hd, t->Sc, t->Zc, t->seg_part, st);
+        if (rc) return rc;
+        rc = launch_loss_head(t, record, st);
+        if (rc) return rc;
+        // backward
+        rc = launch_top_backward(t, scale, st);
+        if (rc) return rc;
+    }
     if (top) {      // through the middle weight and the front layer: dW2, dZ1 and db1, dS1
         const int H2 = t->H[1], Hp2 = t->Hp[1];
         rc = launch_tn(t->fHd, (long)Hp1, t->dS, (long)Hp2, t->grad + t->off[1], H1, H2, n, t->tn[1], st);
@@ -1297,7 +1400,7 @@ static int run_epoch(lt_trainer *t, float *record, hipStream_t st) {
     const int64_t step = t->epoch + 1;
     const lt_adam_scalars s = adam_scalars(step, t->lr, 0.9, 0.999, 1e-8, t->wd);
     const dim3 adam_grid((unsigned)((t->off[5] + 255) / 256));
-    if (top) {
+    if (top || t->wide) {      // (wide: segments W1 | b1 | W2 | b2, the mirrors b1p and b2p; no fifth segment, so no W3p)
         const lt_tr3_tensors T = {snap_segs(t), t->mir[1], t->mir[3], t->mir[4]};
         hipLaunchKernelGGL(k_tr3_adam, adam_grid, dim3(256), 0, st, T, t->grad, t->m, t->v, s);
     } else {
@@ -1384,9 +1487,13 @@ static int ptr_device(const void *p) {
 // Everything lt_gcn*_trainer_attach_validation(_rows) checks and allocates.
 static int val_attach(const char *who, lt_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
                       const int32_t *labels2, int32_t keep_best, int32_t patience, void *stream, int with_rows = 0,
-                      const int32_t *rows = nullptr, int32_t m = 0) {
+                      const int32_t *rows = nullptr, int32_t m = 0, int want_wide = 0, int64_t ldy2 = 0) {
     LT_REQUIRE(t != nullptr, "%s: trainer is NULL", who);
+    LT_REQUIRE(t->wide == want_wide, "%s: the trainer has the %s head; attach with lt_gcn2_trainer_attach_validation%s", who,
+               t->wide ? "wide" : "narrow", t->wide ? "_wide" : " or _attach_validation_rows");
     const int F = t->F, C = t->C, top = t->layers - 2;
+    const bool bce = t->wide && t->loss_kind == TRW_BCE;
+    if (bce) LT_REQUIRE(ldy2 >= C, "%s: ldy2=%lld < C=%d", who, (long long)ldy2, C);
     hipStream_t st = (hipStream_t)stream;
     LT_REQUIRE(t->val == nullptr, "%s: validation is already attached to this trainer", who);
     LT_REQUIRE(g2 != nullptr && X2 != nullptr && labels2 != nullptr, "%s: NULL argument", who);
@@ -1403,7 +1510,7 @@ static int val_attach(const char *who, lt_trainer *t, const lt_graph *g2, const 
         LT_REQUIRE(m > 0, "%s: m=%d, must be positive", who, m);
         LT_REQUIRE(ptr_device(rows) == dev, "%s: rows must live on the trainer's device (%d)", who, dev);
     }
-    {
+    if (!bce) {      // (the BCE head reads bytes: any value other than 0 is a 1)
         int32_t *host = new (std::nothrow) int32_t[(size_t)n2];
         if (!host) return lt_set_error(LT_ERR_NOMEM, "%s: out of host memory", who);
         hipError_t e = hipMemcpyAsync(host, labels2, (size_t)n2 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
@@ -1439,9 +1546,10 @@ static int val_attach(const char *who, lt_trainer *t, const lt_graph *g2, const 
     v->rows = with_rows ? rows : nullptr;
     v->m = with_rows ? m : 0;
     v->n_blk = ((with_rows ? m : n2) + TR_BLOCK - 1) / TR_BLOCK;
+    v->ldy = ldy2;
     const size_t nf = (size_t)n2 * t->Hp[0] * sizeof(float), nt = (size_t)n2 * t->Hp[top] * sizeof(float);
-    const size_t nc = (size_t)n2 * C * sizeof(float);
-    const int hpm = t->Hp[0] > t->Hp[1] ? t->Hp[0] : t->Hp[1];
+    const size_t nc = (size_t)n2 * trainer_ldc(t) * sizeof(float);
+    const int hpm = trainer_hpm(t);
 #define V_HIP(call)                                                                         \
     do {                                                                                    \
         hipError_t e_ = (call);                                                             \
@@ -1459,12 +1567,17 @@ static int val_attach(const char *who, lt_trainer *t, const lt_graph *g2, const 
     V_HIP(hipMemsetAsync(v->S, 0, nt, st));
     V_HIP(hipMalloc((void **)&v->Z, nt));
     V_HIP(hipMalloc((void **)&v->Sc, nc));
+    if (t->wide) V_HIP(hipMemsetAsync(v->Sc, 0, nc, st));      // the class product writes C of the Cp columns
     V_HIP(hipMalloc((void **)&v->Zc, nc));
     const size_t sb = lt_gemm_splitk_slab_bytes(n2, t->H[0], F, v->kslice);
     if (sb) V_HIP(hipMalloc((void **)&v->slabs, sb));
     if (g2->p_n_seg > 0) V_HIP(hipMalloc((void **)&v->seg_part, (size_t)g2->p_n_seg * hpm * sizeof(float)));
-    V_HIP(hipMalloc((void **)&v->part_loss, (size_t)v->n_blk * sizeof(float)));
-    V_HIP(hipMalloc((void **)&v->part_cnt, (size_t)v->n_blk * C * C * sizeof(int32_t)));
+    if (t->wide) {      // the wide head's partials in one block (launch_trw_head)
+        V_HIP(hipMalloc((void **)&v->part_loss, trw_part_bytes(with_rows ? m : n2, C, false)));
+    } else {
+        V_HIP(hipMalloc((void **)&v->part_loss, (size_t)v->n_blk * sizeof(float)));
+        V_HIP(hipMalloc((void **)&v->part_cnt, (size_t)v->n_blk * C * C * sizeof(int32_t)));
+    }
     V_HIP(hipMalloc((void **)&v->state, VAL_STATE_WORDS * sizeof(int32_t)));
     if (keep_best) V_HIP(hipMalloc((void **)&v->snap, (size_t)t->off[5] * sizeof(float)));
 #undef V_HIP
@@ -1486,6 +1599,7 @@ static int val_forward(lt_trainer *t, hipStream_t st) {
     const bool front = t->layers == 3;
     int rc = launch_xw1(t, v->X, v->ldx, v->n, v->kslice, v->slabs, front ? v->fS : v->S, st);
     if (rc) return rc;
+    if (t->wide) return launch_wide_forward(t, v->g, v->S, drop_off(), v->Z, v->Sc, v->Zc, v->seg_part, st);      // v->Z: the hidden layer
     float *Z = v->Z;
     if (front) {
         lt_drop_args off;
@@ -1499,10 +1613,13 @@ static int val_forward(lt_trainer *t, hipStream_t st) {
 }
 
 // head, state and snapshot behind a validation forward; e = the epoch just trained (0-based, since creation)
-static int val_finish_epoch(lt_val *v, int C, const lt_snap_segs &T, int64_t e, float *val_loss, int32_t *val_counts,
-                            hipStream_t st) {
-    const int rc = launch_val_head(v->Zc, (long)C, v->labels, v->n, C, v->rows, v->m, v->part_loss, v->part_cnt, val_loss,
-                                   val_counts, nullptr, v->state, v->patience, (int)e, st);
+static int val_finish_epoch(const lt_trainer *t, lt_val *v, int C, const lt_snap_segs &T, int64_t e, float *val_loss,
+                            int32_t *val_counts, hipStream_t st) {
+    const int rc = t->wide ? launch_trw_head(t->loss_kind, v->Zc, (long)t->Cp, v->labels, (long)v->ldy, v->n, C, v->rows, v->m,
+                                             nullptr, v->part_loss, val_loss, nullptr, val_counts, nullptr, v->state, v->patience,
+                                             (int)e, st)
+                           : launch_val_head(v->Zc, (long)C, v->labels, v->n, C, v->rows, v->m, v->part_loss, v->part_cnt, val_loss,
+                                             val_counts, nullptr, v->state, v->patience, (int)e, st);
     if (rc) return rc;
     if (v->keep_best) return launch_snapshot(T, v->snap, v->state + VS_IMPROVED, 0, st);
     return LT_OK;
@@ -1530,7 +1647,11 @@ static int trainer_run(const char *who, lt_trainer *t, int32_t n_epochs, float *
     hipStream_t st = (hipStream_t)stream;
     const lt_snap_segs T = snap_segs(t);
     // the borrowed parameters may have changed since the last run: the padded copies from them (Adam keeps them current after that)
-    if (t->layers == 3) {
+    if (t->wide) {      // b1 at Hp and b2 at Cp: k_tr3_pad's first two copies (its third, over Hp2 * 0 elements, is empty)
+        const int mx = t->Hp[0] > t->Cp ? t->Hp[0] : t->Cp;
+        hipLaunchKernelGGL(k_tr3_pad, dim3((mx + 255) / 256), dim3(256), 0, st, t->P[1], t->H[0], t->Hp[0], t->P[3], t->C, t->Cp,
+                           nullptr, 0, t->mir[1], t->mir[3], nullptr);
+    } else if (t->layers == 3) {
         const int mx = t->Hp[0] > t->Hp[1] * t->C ? t->Hp[0] : t->Hp[1] * t->C;
         hipLaunchKernelGGL(k_tr3_pad, dim3((mx + 255) / 256), dim3(256), 0, st, t->P[1], t->H[0], t->Hp[0], t->P[3], t->H[1],
                            t->Hp[1], t->P[4], t->C, t->mir[1], t->mir[3], t->mir[4]);
@@ -1539,12 +1660,12 @@ static int trainer_run(const char *who, lt_trainer *t, int32_t n_epochs, float *
                            t->Hp[0], t->C, t->mir[1], t->mir[2]);
     }
     LT_CHECK_LAUNCH();
-    const size_t cc = (size_t)t->C * t->C;
+    const size_t cc = t->wide ? 3 * (size_t)t->C : (size_t)t->C * t->C;      // an epoch's val_counts
     for (int32_t j = 0; j < n_epochs; ++j) {
         const int64_t e = t->epoch;
         int rc = run_epoch(t, record + 2 * (size_t)j, st);
         if (rc == LT_OK && validated) rc = val_forward(t, st);
-        if (rc == LT_OK && validated) rc = val_finish_epoch(t->val, t->C, T, e, val_loss + j, val_counts + cc * (size_t)j, st);
+        if (rc == LT_OK && validated) rc = val_finish_epoch(t, t->val, t->C, T, e, val_loss + j, val_counts + cc * (size_t)j, st);
         if (rc) return rc;
     }
     return LT_OK;
@@ -1570,7 +1691,7 @@ static int copy_rows(float *dst, int64_t ld, const float *src, int lds, int widt
 static int trainer_logits(const char *who, const lt_trainer *t, float *Z, int64_t ldz, void *stream) {
     LT_REQUIRE(t != nullptr && Z != nullptr, "%s: NULL argument", who);
     LT_REQUIRE(ldz >= t->C, "%s: ldz=%lld < C=%d", who, (long long)ldz, t->C);
-    return copy_rows(Z, ldz, t->Zc, t->C, t->C, t->n, stream);
+    return copy_rows(Z, ldz, t->Zc, trainer_ldc(t), t->C, t->n, stream);
 }
 
 static int trainer_epoch(const char *who, const lt_trainer *t, int64_t *epoch) {
@@ -1600,7 +1721,7 @@ static int trainer_val_logits(const char *who, const lt_trainer *t, float *Z, in
     LT_REQUIRE(t->val != nullptr, "%s: no validation attached", who);
     LT_REQUIRE(Z != nullptr, "%s: Z is NULL", who);
     LT_REQUIRE(ldz >= t->C, "%s: ldz=%lld < C=%d", who, (long long)ldz, t->C);
-    return copy_rows(Z, ldz, t->val->Zc, t->C, t->C, t->val->n, stream);
+    return copy_rows(Z, ldz, t->val->Zc, trainer_ldc(t), t->C, t->val->n, stream);
 }
 
 // ---- the 2-layer trainer ----
@@ -1675,6 +1796,77 @@ extern "C" int lt_gcn2_trainer_restore_best(lt_gcn2_trainer *t, void *stream) {
 
 extern "C" int lt_gcn2_trainer_val_logits(const lt_gcn2_trainer *t, float *Z, int64_t ldz, void *stream) {
     return trainer_val_logits("lt_gcn2_trainer_val_logits", t, Z, ldz, stream);
+}
+
+// ---- the 2-layer trainer with the wide head ----
+extern "C" int lt_gcn2_trainer_create_wide(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const void *labels,
+                                           int64_t ldy, int32_t loss_kind, int32_t H, int32_t C, float *W1, float *b1, float *W2,
+                                           float *b2, double lr, double weight_decay, double dropout, uint64_t seed, void *stream,
+                                           lt_gcn2_trainer **out) {
+    LT_REQUIRE(out != nullptr, "lt_gcn2_trainer_create_wide: out is NULL");
+    *out = nullptr;
+    LT_REQUIRE(g != nullptr, "lt_gcn2_trainer_create_wide: graph is NULL");
+    LT_REQUIRE(F > 0 && H > 0 && C > 0, "lt_gcn2_trainer_create_wide: F=%d H=%d C=%d must be positive", F, H, C);
+    LT_REQUIRE(H <= LT_MAX_H, "lt_gcn2_trainer_create_wide: H=%d (supported: H <= %d)", H, LT_MAX_H);
+    LT_REQUIRE(C <= LT_MAX_H, "lt_gcn2_trainer_create_wide: C=%d (supported: C <= %d)", C, LT_MAX_H);
+    LT_REQUIRE(loss_kind == LT_LOSS_CE || loss_kind == LT_LOSS_BCE,
+               "lt_gcn2_trainer_create_wide: loss_kind=%d, must be LT_LOSS_CE (0) or LT_LOSS_BCE (1)", loss_kind);
+    if (loss_kind == LT_LOSS_BCE) LT_REQUIRE(ldy >= C, "lt_gcn2_trainer_create_wide: ldy=%lld < C=%d", (long long)ldy, C);
+    LT_REQUIRE(X && labels && W1 && b1 && W2 && b2, "lt_gcn2_trainer_create_wide: NULL tensor pointer");
+    const int32_t Hs[2] = {H, 0};
+    float *const ps[4] = {W1, b1, W2, b2};
+    lt_trainer *t = nullptr;
+    const int rc = trainer_create("lt_gcn2_trainer_create_wide", 2, g, X, ldx, F, static_cast<const int32_t *>(labels), Hs, C, ps, lr,
+                                  weight_decay, dropout, seed, stream, &t, 1, loss_kind, ldy);
+    *out = static_cast<lt_gcn2_trainer *>(t);
+    return rc;
+}
+
+extern "C" int lt_gcn2_trainer_counts(const lt_gcn2_trainer *t, int32_t *counts, void *stream) {
+    LT_REQUIRE(t != nullptr && counts != nullptr, "lt_gcn2_trainer_counts: NULL argument");
+    LT_REQUIRE(t->wide, "lt_gcn2_trainer_counts: the trainer has the narrow head, which keeps no per-class counts");
+    LT_REQUIRE(t->epoch > 0, "lt_gcn2_trainer_counts: no epoch has run");
+    LT_HIP(hipMemcpyAsync(counts, trainer_counts(t), 3 * (size_t)t->C * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                          (hipStream_t)stream));
+    return LT_OK;
+}
+
+extern "C" int lt_gcn2_trainer_hidden(const lt_gcn2_trainer *t, float *H1d, int64_t ld, void *stream) {
+    LT_REQUIRE(t != nullptr && H1d != nullptr, "lt_gcn2_trainer_hidden: NULL argument");
+    LT_REQUIRE(ld >= t->H[0], "lt_gcn2_trainer_hidden: ld=%lld < H=%d", (long long)ld, t->H[0]);
+    return copy_rows(H1d, ld, t->Hd, t->Hp[0], t->H[0], t->n, stream);
+}
+
+extern "C" int lt_gcn2_trainer_attach_validation_wide(lt_gcn2_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2,
+                                                      int32_t n2, const void *labels2, int64_t ldy2, int32_t keep_best,
+                                                      int32_t patience, const int32_t *rows, int32_t m, void *stream) {
+    return val_attach("lt_gcn2_trainer_attach_validation_wide", t, g2, X2, ldx2, n2, static_cast<const int32_t *>(labels2),
+                      keep_best, patience, stream, rows != nullptr, rows, m, 1, ldy2);
+}
+
+extern "C" size_t lt_eval_head_wide_workspace_bytes(int32_t m, int32_t C) {
+    if (m <= 0 || C <= 0 || C > LT_MAX_H) return 0;
+    return trw_part_bytes(m, C, false);
+}
+
+extern "C" int lt_eval_head_wide(const float *Z, int64_t ldz, const void *labels, int64_t ldy, int32_t n, int32_t C,
+                                 int32_t loss_kind, const int32_t *rows, int32_t m, float *loss, int32_t *counts, int32_t *n_bad,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+    LT_REQUIRE(n > 0, "lt_eval_head_wide: n=%d, must be positive", n);
+    LT_REQUIRE(C > 0 && C <= LT_MAX_H, "lt_eval_head_wide: C=%d (supported: 1 .. %d)", C, LT_MAX_H);
+    LT_REQUIRE(loss_kind == LT_LOSS_CE || loss_kind == LT_LOSS_BCE,
+               "lt_eval_head_wide: loss_kind=%d, must be LT_LOSS_CE (0) or LT_LOSS_BCE (1)", loss_kind);
+    LT_REQUIRE(Z && labels && loss && counts, "lt_eval_head_wide: NULL pointer");
+    LT_REQUIRE(ldz >= C, "lt_eval_head_wide: ldz=%lld < C=%d", (long long)ldz, C);
+    if (loss_kind == LT_LOSS_BCE) LT_REQUIRE(ldy >= C, "lt_eval_head_wide: ldy=%lld < C=%d", (long long)ldy, C);
+    if (rows) LT_REQUIRE(m > 0, "lt_eval_head_wide: m=%d, must be positive", m);
+    const size_t need = trw_part_bytes(rows ? m : n, C, false);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % sizeof(float)))
+        return lt_set_error(LT_ERR_WORKSPACE, "lt_eval_head_wide: workspace needs %zu bytes, 4-byte aligned", need);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_bad) LT_HIP(hipMemsetAsync(n_bad, 0, sizeof(int32_t), st));
+    return launch_trw_head(loss_kind, Z, (long)ldz, labels, (long)ldy, n, C, rows, m, nullptr, (float *)workspace, loss, nullptr,
+                           counts, n_bad, nullptr, 0, 0, st);
 }
 
 // ---- the 3-layer trainer ----

@@ -640,6 +640,10 @@ class _ValidationMixin:
 
     _PREFIX = ""
     _val = None
+    _WIDE = False     # GCN2Trainer(head="wide"): val_counts are [C, 3] = (tp, fp, fn) per class instead of the C x C confusion
+
+    def _count_cols(self):
+        return 3 if self._WIDE else self.c
 
     def _call(self, name, *args):
         fn = f"{self._PREFIX}_{name}"
@@ -665,15 +669,16 @@ class _ValidationMixin:
             raise ValueError(f"the trainer lives on {self.x.device}: the validation graph is on cuda:{g2.device_index}, "
                              f"x2 on {x2.device}")
         _require_finite(features_2=x2)
-        if not isinstance(labels2, torch.Tensor):
-            labels2 = torch.as_tensor(labels2)
-        labels2 = labels2.reshape(-1)
-        if labels2.numel() != g2.n:
-            raise ValueError(f"labels2: {labels2.numel()} entries for {g2.n} nodes")
-        if labels2.numel() and (int(labels2.min()) < 0 or int(labels2.max()) >= self.c):
-            raise ValueError(f"labels2 outside [0, {self.c})")
-        labels2 = labels2.to(device=self.x.device, dtype=torch.int32).contiguous()
-        if rows is None:
+        labels2 = self._prepare_labels(labels2, g2.n, "labels2")
+        if self._WIDE:
+            if rows is not None:
+                rows = _as_rows(rows, g2.n, self.x.device, "rows")
+                if rows.numel() == 0:
+                    raise ValueError("rows is empty: a validation loss over no row is undefined")
+            self._call("attach_validation_wide", g2.handle, x2.data_ptr(), x2.shape[1], x2.shape[0], labels2.data_ptr(),
+                       labels2.shape[1] if labels2.dim() == 2 else 0, int(bool(keep_best)), int(patience),
+                       None if rows is None else rows.data_ptr(), 0 if rows is None else rows.numel(), _stream())
+        elif rows is None:
             self._call("attach_validation", g2.handle, x2.data_ptr(), x2.shape[1], x2.shape[0], labels2.data_ptr(),
                        int(bool(keep_best)), int(patience), _stream())
         else:
@@ -691,12 +696,12 @@ class _ValidationMixin:
 
     def run_validated_async(self, epochs: int):
         """Enqueue ``epochs`` validated epochs without syncing; returns the device tensors (record [epochs, 2], val_loss
-        [epochs], val_counts [epochs, C, C])."""
+        [epochs], val_counts [epochs, C, C]; [epochs, C, 3] = (tp, fp, fn) per class with the wide head)."""
         self._require_val()
         k, dev = max(int(epochs), 0), self.x.device
         record = torch.empty((k, 2), dtype=torch.float32, device=dev)
         val_loss = torch.empty((k,), dtype=torch.float32, device=dev)
-        val_counts = torch.empty((k, self.c, self.c), dtype=torch.int32, device=dev)
+        val_counts = torch.empty((k, self.c, self._count_cols()), dtype=torch.int32, device=dev)
         self._call("run_validated", int(epochs), record.data_ptr(), val_loss.data_ptr(), val_counts.data_ptr(), _stream())
         for p in self.params:
             torch.autograd.graph.increment_version(p)
@@ -730,7 +735,7 @@ class _ValidationMixin:
                else torch.empty(shape, dtype=dt).numpy())
         rec = cat(0, (0, 2), torch.float32)
         return {"loss": rec[:, 0].copy(), "correct": rec[:, 1].astype("int64"), "val_loss": cat(1, (0,), torch.float32),
-                "val_counts": cat(2, (0, self.c, self.c), torch.int32), "best_epoch": state["best_epoch"],
+                "val_counts": cat(2, (0, self.c, self._count_cols()), torch.int32), "best_epoch": state["best_epoch"],
                 "stop_epoch": state["stop_epoch"]}
 
     def val_state(self) -> dict:
@@ -812,6 +817,69 @@ def f1_from_confusion(conf):
     return micro, macro, weighted
 
 
+def eval_head_wide(output: torch.Tensor, labels: torch.Tensor, rows=None, loss="ce"):
+    """Loss (device float32 scalar tensor) and counts (int32 [C, 3] = (tp, fp, fn) per class) of ``output`` [n, C], C <= 256
+    (lt_eval_head_wide).  ``loss="ce"``: ``labels`` [n], mean cross-entropy, prediction = first argmax; ``loss="bce"``:
+    ``labels`` [n, C] of 0 / 1, mean binary cross-entropy with logits over all elements, predicted positive iff the logit
+    is > 0.  ``rows``: only the listed rows, repeats counting (an id outside [0, n) raises ``IndexError``).  Enqueue-only."""
+    if not (isinstance(output, torch.Tensor) and output.is_cuda and output.dtype == torch.float32 and output.dim() == 2):
+        raise ValueError("output must be a 2-d float32 device tensor")
+    if loss not in GCN2Trainer._LOSSES:
+        raise ValueError(f"loss must be 'ce' or 'bce', got {loss!r}")
+    n, c = output.shape
+    if n and (output.stride(1) != 1 or output.stride(0) < c):
+        output = output.contiguous()
+    if not isinstance(labels, torch.Tensor):
+        labels = torch.as_tensor(labels)
+    if loss == "bce":
+        if labels.dim() != 2 or labels.shape[0] != n or labels.shape[1] != c:
+            raise ValueError(f"labels must be [{n}, {c}] for loss='bce', got {tuple(labels.shape)}")
+        labels = labels.to(device=output.device)
+        if labels.dtype != torch.uint8 or labels.stride(1) != 1 or labels.stride(0) < c:
+            labels = labels.to(torch.uint8).contiguous()
+        ldy = labels.stride(0)
+    else:
+        labels = labels.reshape(-1).to(device=output.device, dtype=torch.int32).contiguous()
+        if labels.numel() != n:
+            raise ValueError(f"labels: {labels.numel()} entries for {n} rows")
+        ldy = 0
+    out_loss = torch.empty((), dtype=torch.float32, device=output.device)
+    counts = torch.empty((c, 3), dtype=torch.int32, device=output.device)
+    m = 0
+    if rows is not None:
+        rows = _as_rows(rows, n, output.device, "rows")
+        m = rows.numel()
+    ws = _workspace(_lib.lib().lt_eval_head_wide_workspace_bytes(m if rows is not None else n, c), output.device)
+    _lib.check(_lib.lib().lt_eval_head_wide(output.data_ptr(), output.stride(0) if n else c, labels.data_ptr(), ldy, n, c,
+                                            GCN2Trainer._LOSSES[loss], None if rows is None else rows.data_ptr(), m,
+                                            out_loss.data_ptr(), counts.data_ptr(), None, ws.data_ptr(), ws.numel(), _stream()),
+               "lt_eval_head_wide")
+    return out_loss, counts
+
+
+def f1_from_counts(counts, present_only=False):
+    """(micro, macro, weighted) F1 as Python floats from integer counts [C, 3] = (tp, fp, fn) per class, single- or
+    multi-label, with ``sklearn.metrics.f1_score``'s arithmetic over all C classes: per class 2 tp / (2 tp + fp + fn), 0 where
+    that denominator is 0; macro their mean; weighted by the supports tp + fn (0 when there is none); micro from the summed
+    counts.  ``present_only``: the macro mean leaves out the classes that are neither a label nor a prediction, as
+    ``f1_score`` does on single-label inputs when it is not told the class list (reference gcn_trainer.py:246-252)."""
+    import numpy as np
+    k = counts.detach().cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    if k.ndim != 2 or k.shape[1] != 3:
+        raise ValueError(f"counts must be [C, 3], got {k.shape}")
+    k = k.astype(np.int64)
+    tp, fp, fn = k[:, 0], k[:, 1], k[:, 2]
+    den = 2 * tp + fp + fn
+    f1 = np.where(den > 0, 2.0 * tp / np.maximum(den, 1), 0.0)
+    support = tp + fn
+    den_all = int(den.sum())
+    micro = 2.0 * int(tp.sum()) / den_all if den_all else 0.0
+    in_mean = f1[den > 0] if present_only else f1
+    macro = float(in_mean.mean()) if in_mean.size else 0.0
+    weighted = float((f1 * support).sum() / support.sum()) if support.sum() else 0.0
+    return float(micro), macro, weighted
+
+
 class EarlyStopState:
     """The early-stopping state block on its own (lt_early_stop_reset / lt_early_stop_update): 8 int32 words of device memory."""
 
@@ -864,21 +932,29 @@ class _GCNTrainer(_ValidationMixin):
         if self.graph.device_index != self.x.device.index:
             raise ValueError(f"the graph lives on cuda:{self.graph.device_index}, the features on {self.x.device}")
         _require_finite(features=self.x, **dict(zip(self._NAMES, self.params)))
-        if not isinstance(labels, torch.Tensor):
-            labels = torch.as_tensor(labels)
-        labels = labels.reshape(-1)
-        if labels.numel() != n:
-            raise ValueError(f"labels: {labels.numel()} entries for {n} nodes")
-        if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= self.c):
-            raise ValueError(f"labels outside [0, {self.c})")
-        self.labels = labels.to(device=self.x.device, dtype=torch.int32).contiguous()
+        self.labels = self._prepare_labels(labels, n, "labels")
         h = C.c_void_p()
-        fn = f"{self._PREFIX}_create"
-        _lib.check(getattr(_lib.lib(), fn)(self.graph.handle, self.x.data_ptr(), f, f, self.labels.data_ptr(), *dims[1:],
+        fn, label_args = self._create_call()
+        _lib.check(getattr(_lib.lib(), fn)(self.graph.handle, self.x.data_ptr(), f, f, *label_args, *dims[1:],
                                            *[t.data_ptr() for t in self.params], float(lr), float(weight_decay),
                                            float(dropout), int(seed) & (2**64 - 1), _stream(), C.byref(h)), fn)
         self._h = h
         self._finalizer = weakref.finalize(self, getattr(_lib.lib(), f"{self._PREFIX}_destroy"), h)
+
+    def _prepare_labels(self, labels, n, name):
+        """One class id per node as the int32 device tensor the library borrows."""
+        if not isinstance(labels, torch.Tensor):
+            labels = torch.as_tensor(labels)
+        labels = labels.reshape(-1)
+        if labels.numel() != n:
+            raise ValueError(f"{name}: {labels.numel()} entries for {n} nodes")
+        if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= self.c):
+            raise ValueError(f"{name} outside [0, {self.c})")
+        return labels.to(device=self.x.device, dtype=torch.int32).contiguous()
+
+    def _create_call(self):
+        """The create entry point's name and its arguments between ``F`` and the widths."""
+        return f"{self._PREFIX}_create", (self.labels.data_ptr(),)
 
     @property
     def epoch(self) -> int:
@@ -920,10 +996,55 @@ class GCN2Trainer(_GCNTrainer):
     ``run_validated`` (_ValidationMixin)."""
 
     _PREFIX, _NAMES, _MODEL = "lt_gcn2_trainer", ("W1", "b1", "W2", "b2"), "GCN"
+    _LOSSES = {"ce": 0, "bce": 1}      # LT_LOSS_CE, LT_LOSS_BCE
 
-    def __init__(self, adj, x, labels, w1, b1, w2, b2, *, lr, weight_decay, dropout, seed):
+    def __init__(self, adj, x, labels, w1, b1, w2, b2, *, lr, weight_decay, dropout, seed, head="narrow", loss="ce"):
+        """``head="wide"`` (lt_gcn2_trainer_create_wide): up to 256 classes, the class layer as matrix products and the wide loss
+        head; ``loss="ce"`` takes ``labels`` [n] (mean cross-entropy), ``loss="bce"`` takes ``labels`` [n, C] of 0 / 1 in any
+        integer or bool dtype (mean binary cross-entropy with logits over all n C elements; kept as uint8 on the device).
+        ``run`` then returns (loss, sum over the classes of tp): the correct count for ce.  ``head="narrow"`` (default) is the
+        fused class layer for at most 8 classes with cross-entropy."""
+        if head not in ("narrow", "wide"):
+            raise ValueError(f"head must be 'narrow' or 'wide', got {head!r}")
+        if loss not in self._LOSSES:
+            raise ValueError(f"loss must be 'ce' or 'bce', got {loss!r}")
+        if head == "narrow" and loss != "ce":
+            raise ValueError("the narrow head has the cross-entropy loss only: pass head='wide' for loss='bce'")
+        self._WIDE, self.head, self.loss = head == "wide", head, loss
         super().__init__(adj, x, labels, (w1, b1, w2, b2), lr=lr, weight_decay=weight_decay, dropout=dropout, seed=seed)
         self.h = self.w1.shape[1]
+
+    def _prepare_labels(self, labels, n, name):
+        if not (self._WIDE and self.loss == "bce"):
+            return super()._prepare_labels(labels, n, name)
+        if not isinstance(labels, torch.Tensor):
+            labels = torch.as_tensor(labels)
+        if labels.dim() != 2 or tuple(labels.shape) != (n, self.c):
+            raise ValueError(f"{name} must be [{n}, {self.c}] for loss='bce', got {tuple(labels.shape)}")
+        if labels.is_floating_point() or labels.is_complex():
+            raise ValueError(f"{name} must have an integer or bool dtype, got {labels.dtype}")
+        if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) > 1):
+            raise ValueError(f"{name} must hold 0 / 1")
+        return labels.to(device=self.x.device, dtype=torch.uint8).contiguous()
+
+    def _create_call(self):
+        if not self._WIDE:
+            return super()._create_call()
+        return "lt_gcn2_trainer_create_wide", (self.labels.data_ptr(), self.c, self._LOSSES[self.loss])
+
+    def counts(self) -> torch.Tensor:
+        """The last epoch's int32 [C, 3] = (tp, fp, fn) per class on the training rows (wide head only)."""
+        if not self._WIDE:
+            raise ValueError("counts() needs head='wide'")
+        out = torch.empty((self.c, 3), dtype=torch.int32, device=self.x.device)
+        self._call("counts", out.data_ptr(), _stream())
+        return out
+
+    def hidden(self) -> torch.Tensor:
+        """The last epoch's hidden activations after ReLU and dropout, H1d [n, H]."""
+        out = torch.empty((self.n, self.h), dtype=torch.float32, device=self.x.device)
+        self._call("hidden", out.data_ptr(), self.h, _stream())
+        return out
 
 
 class GCN3Trainer(_GCNTrainer):

@@ -14,8 +14,8 @@ Every flag of the reference is accepted with its default.  ``--test`` runs infer
 Without either switch the run is refused (a default run does not start a 500-epoch job by itself).  With ``--train``,
 ``--validate log | best | early`` (an addition, default ``off``) validates on the held-out graph after every epoch on the GPU:
 ``loss_val`` / ``acc_val`` in the log, the model of the best validation loss saved, and a stop after ``--patience`` epochs
-without improvement.  ``--dataset flickr`` (one graph with a train / validation / test split of its nodes; also ``reddit``,
-``ppi``, ``ppi-large`` with ``--test``) trains on the induced training subgraph, is validated on ``idx_val`` of the full graph
+without improvement.  ``--dataset flickr`` (one graph with a train / validation / test split of its nodes; ``reddit``,
+``ppi``, ``ppi-large`` with ``--train-head wide``) trains on the induced training subgraph, is validated on ``idx_val`` of the full graph
 after every epoch -- ``--early`` stops it as in the reference -- and is tested on ``idx_test`` with micro / macro / weighted F1.
 """
 from __future__ import annotations
@@ -76,12 +76,18 @@ _OPTIONS = {
     # validation loss is restored and saved; 'early': as best, and the run stops after --patience epochs without improvement
     # (utils/early_stopping.py, 'early stop at epoch {e}').  'off' (default): every record, log line and bit as without it
     "validate": (str, "off", ["off", "log", "best", "early"]),
+    # addition: which class layer and loss head --train runs.  'narrow' (default): the fused class layer for a single label and
+    # at most 8 classes, every check and every bit as before the flag existed; 'wide': up to 256 classes with cross-entropy or,
+    # for a multi-label dataset, binary cross-entropy with logits (engine.GCN2Trainer(head="wide")): reddit, ppi, ppi-large
+    "train-head": (str, "narrow", ["narrow", "wide"]),
 }
 _HELP = {
     "validate": "with --train: validate on the held-out graph after every epoch on the GPU.  log: loss_val / acc_val in the log; "
                 "best: also restore and save the model of the best validation loss; early: also stop after --patience epochs "
                 "without improvement.  Default off.",
     "patience": "epochs without improvement before --validate early stops (default 10)",
+    "train-head": "with --train: narrow (default) trains a single label with at most 8 classes; wide trains up to 256 classes, "
+                  "single- or multi-label (reddit, ppi, ppi-large), with the 2-layer GCN.",
     "early": "with --train on flickr / reddit / ppi / ppi-large (one graph with a split of its nodes): stop after --patience "
              "epochs without improvement of the validation loss over idx_val and save the best model, as the reference does; a "
              "run that never stops saves the last model.  On transfer datasets (twitch/<A>/<B>) accepted and inert, as in the "
@@ -243,14 +249,27 @@ def check_split_dataset(args):
                                   "subgraph's logits with ids of the full graph)")
     if args.early and args.patience < 1:
         raise ValueError(f"--early needs --patience >= 1 (got {args.patience})")
-    if args.dataset in _SPLIT_MULTI_LABEL:
+    if args.dataset in _SPLIT_MULTI_LABEL and getattr(args, "train_head", "narrow") != "wide":
         raise NotImplementedError(f"--train on --dataset {args.dataset}: training is implemented for a single label and at most 8 "
                                   "classes (flickr); this dataset loads, tests and attacks from a saved model (--test --model-path)")
+
+
+def check_train_head(args):
+    """``--train-head wide`` selects the wide class layer of ``--train``: it is refused here, before a Worker is built or the GPU
+    is touched, without a training run and with ``--n-layer 3`` (a wide head on GCN3 needs a second stage of the hidden
+    layer's backward product, which does not exist)."""
+    if getattr(args, "train_head", "narrow") != "wide":
+        return
+    if not args.train or args.test:
+        raise NotImplementedError("--train-head wide needs --train without --test (it selects the class layer of a training run)")
+    if args.n_layer != 2:
+        raise NotImplementedError(f"--train-head wide is implemented for the 2-layer GCN only (got --n-layer {args.n_layer})")
 
 
 def main(argv=None):
     args = get_arguments(argv)
     check_validate(args)
+    check_train_head(args)
     check_split_dataset(args)
     check_baseline_scores(args)
     check_recover(args)

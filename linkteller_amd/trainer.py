@@ -52,21 +52,28 @@ class GCNTrainer:
             # the optimizer state of gcn_trainer.py:106-108: Adam's moments live in the GPU trainer, which updates the
             # model's parameters in place
             from .engine import GCN2Trainer, GCN3Trainer
+            wide = getattr(a, "train_head", "narrow") == "wide"
+            if wide and a.n_layer != 2:
+                raise NotImplementedError(f"--train-head wide is implemented for the 2-layer GCN only (got --n-layer {a.n_layer})")
             if w.transfer:
                 train_on = (w.adj_1, w.features_1, w.labels_1)
             else:                                              # gcn_trainer.py:131, 154: the induced training subgraph
                 if getattr(a, "fastmode", False):
                     raise NotImplementedError(f"dataset = {self.dataset}: --fastmode is refused (the reference then indexes the "
                                               "training subgraph's logits with ids of the full graph)")
-                if w.multi_label > 1 or w.n_classes > 8:
+                if wide and w.n_classes > 256:
+                    raise NotImplementedError(f"dataset = {self.dataset}: the wide head trains at most 256 classes (got "
+                                              f"n_classes = {w.n_classes})")
+                if not wide and (w.multi_label > 1 or w.n_classes > 8):
                     raise NotImplementedError(
                         f"dataset = {self.dataset}: training is implemented for a single label and at most 8 classes (got "
                         f"multi_label = {w.multi_label}, n_classes = {w.n_classes}); load a trained model with --test --model-path")
                 train_on = (w.adj_train, w.features_train, w.labels[torch.as_tensor(w.idx_train, device=w.labels.device)])
             layers = [self.model.gc1, self.model.gc2] + ([self.model.gc3] if a.n_layer == 3 else [])
             params = [t.detach() for g in layers for t in (g.weight, g.bias)]
+            head = dict(head="wide", loss="bce" if getattr(w, "multi_label", 1) > 1 else "ce") if wide else {}
             self.gpu_trainer = (GCN3Trainer if a.n_layer == 3 else GCN2Trainer)(
-                *train_on, *params, lr=a.lr, weight_decay=a.weight_decay, dropout=a.dropout, seed=a.seed)
+                *train_on, *params, lr=a.lr, weight_decay=a.weight_decay, dropout=a.dropout, seed=a.seed, **head)
 
     def train(self):
         """gcn_trainer.py:200-243 on a transfer dataset: ``num_epochs`` epochs on (features_1, adj_1, labels_1), the
@@ -118,13 +125,17 @@ class GCNTrainer:
         tr = self.gpu_trainer
         done = len(r["loss"])
         per_epoch = (time.time() - t_total) / max(done, 1)
+        # the record's second word is the sum of tp over the classes: the correct rows of a single-label trainer; of a multi-label
+        # one the (node, label) pairs that are true positives, printed as their share of all n C pairs (never above 1; the
+        # training rows' (fp, fn) are kept for the last epoch only, so a per-epoch F1 as acc_val's cannot be formed)
+        train_terms = tr.n * (tr.c if getattr(tr, "loss", "ce") == "bce" else 1)
         for epoch in range(done):
             logging.info("[epoch {}]".format(epoch))
             output_info = "Epoch: {:04d}".format(epoch + 1), \
                 "loss_train: {:.4f}".format(float(r["loss"][epoch])), \
-                "acc_train: {:.4f}".format(int(r["correct"][epoch]) / tr.n), \
+                "acc_train: {:.4f}".format(int(r["correct"][epoch]) / train_terms), \
                 "loss_val: {:.4f}".format(float(r["val_loss"][epoch])), \
-                "acc_val: {:.4f}".format(int(r["val_counts"][epoch].trace()) / n_val), \
+                "acc_val: {:.4f}".format(self._acc_val(r["val_counts"][epoch], n_val)), \
                 "time: {:.4f}s".format(per_epoch)
             logging.info(output_info)
         if r["stop_epoch"] >= 0:      # (only a run with a patience stops)
@@ -134,6 +145,14 @@ class GCNTrainer:
             info = f"best validation loss {float(r['val_loss'][r['best_epoch']]):.4f} at epoch {r['best_epoch']}: that model is saved"
             print(info)
             logging.info(info)
+
+    def _acc_val(self, counts, n_val):
+        """An epoch's ``acc_val``: the confusion's trace over the rows scored; with the wide head the micro F1 of its (tp, fp, fn)
+        counts -- for a single label the accuracy, as the reference's ``f1_score(...)[0]`` (gcn_trainer.py:246-252)."""
+        if getattr(self.gpu_trainer, "head", "narrow") == "wide":
+            from .engine import f1_from_counts
+            return f1_from_counts(counts)[0]
+        return int(counts.trace()) / n_val
 
     def _train_split(self, n_epochs, validate, t_total):
         """gcn_trainer.py:183-206, 229-238 on a dataset with one graph and a split of its nodes: always validated -- every epoch
@@ -158,9 +177,17 @@ class GCNTrainer:
     def _eval_split(self, output, mode):
         """gcn_trainer.py:341-384 for a dataset with a split: validation loss / F1 over ``idx_val``, test loss and micro / macro /
         weighted F1 over ``idx_test``.  Single label with at most 8 classes: the evaluation head over the row list on the
-        device and ``f1_from_confusion``; multi-label or wider: host torch / sklearn, as the reference does."""
+        device and ``f1_from_confusion``; multi-label or wider: host torch / sklearn, as the reference does -- or, in a run with
+        ``--train-head wide``, ``eval_head_wide`` and ``f1_from_counts`` on the device."""
         w = self.worker
-        if w.multi_label == 1 and w.n_classes <= 8:
+        if getattr(self.args, "train_head", "narrow") == "wide":      # any width up to 256, either label kind, on the device
+            from .engine import eval_head_wide, f1_from_counts
+            kind = "bce" if w.multi_label > 1 else "ce"
+
+            def score(rows):
+                loss, counts = eval_head_wide(output, w.labels, rows=rows, loss=kind)
+                return float(loss), f1_from_counts(counts, present_only=kind == "ce")
+        elif w.multi_label == 1 and w.n_classes <= 8:
             from .engine import eval_head, f1_from_confusion
 
             def score(rows):
