@@ -153,7 +153,14 @@ int lt_device_count(int *count);
  *                         never waiting) for the index run the GPU publishes early in the step and, if it is there, walks it and asks
  *                         for the destination lines before the stream wait, 0 = everything after the wait (default: the look
  *                         shortens the section behind the wait by 1.6 us and costs the twitch-RU step 2.4), 2 = as 1, and the
- *                         indices the early look saw are compared with the finished run (lt_host_landing_stats).  Bit-identical
+ *                         indices the early look saw are compared with the finished run (lt_host_landing_stats).  Bit-identical.
+ *                         Under "host_poll" = 1 the indices are always consumed before any wait; 1 then adds the walk ahead that
+ *                         asks for the destination lines while the values are still out, 2 the comparison (and its wait)
+ *   "host_poll"           ... packed calls of one probe chunk: 1 = the host places every value as soon as its word in the staging
+ *                         block stops reading as the sentinel, and a call that consumed them all returns without the stream wait
+ *                         (default; see lt_influence_matrix_host), 0 = the values are placed behind the wait.  Bit-identical
+ *   "host_poll_sentinel"  the sentinel's 32-bit pattern (default 0xFFFFFFFF, a NaN no score is).  For tests: with the pattern of a
+ *                         score the matrix holds, the call runs out of stall budget, waits for the stream and is still exact
  *   "feature_stagger"     feature-difference route, one wave per row: the row blocks start in (value & 255) groups, (value >> 8) x 10 ns
  *                         apart, so that a group walks its lists while the next one's rows arrive; 0 = all together.  Bit-identical
  *   "xf64_blocks"         aggregate-first route: blocks per XCD that walk the compacted work items of the rows a call reaches (default 96;
@@ -444,9 +451,19 @@ int lt_influence_rows_f64(const lt_baseline *b, const int32_t *probe_nodes, int3
  * ("export_compact") the matrix's zeros do not cross PCIe: the touched values travel packed into a pinned staging block the
  * baseline owns (allocated on first use, worst-case size, freed by lt_baseline_destroy) -- 4 bytes of index per value early in
  * the step, as soon as the probes' records are matched, 4 bytes of value from the probes' blocks at its end -- the host zero-fills
- * dst while the GPU computes, may walk the index run before the stream wait ("export_early") and places the values after it.
- * Every other call is lt_influence_rows_f64 followed by the wait.  Same values, bit for bit.  Like every call on a baseline
- * handle, not thread-safe. */
+ * dst while the GPU computes and, in a call of one probe chunk ("host_poll"), places each value as it lands: the value words of
+ * the staging block hold a sentinel between calls, every touched position gets exactly one 4-byte store, so a word that no
+ * longer reads as the sentinel is final.  A call that consumed the whole run this way returns WITHOUT waiting for the stream:
+ *   - dst holds the complete matrix, and a node-id flag raised by the call's lists is in host memory (lt_node_check may follow);
+ *   - the stream may still be retiring the last launch's tail: `out` is ordered for later users by the stream, as after
+ *     lt_influence_rows, and an asynchronous error of that tail surfaces at the stream's next wait, not from this call.
+ *   - so what was safe only because the call used to be fully synchronous no longer is: the next call on this baseline must go
+ *     to the SAME stream (or behind a wait of the caller's own), and `out` or the workspace may be freed only by a stream-ordered
+ *     allocator or behind such a wait -- else it races with the last launch's tail.  "host_poll" = 0 restores the old behaviour.
+ * The host's stalls are bounded (200 us in all, counted in looks and clock reads): beyond that the call waits for the stream
+ * once, reports its error, and places the rest behind the wait -- so does a call of several chunks or with "host_poll" = 0, and a
+ * score that happens to equal the sentinel costs that one wait and nothing else.  Every call that is not packed is
+ * lt_influence_rows_f64 followed by the wait.  Same values, bit for bit.  Like every call on a baseline handle, not thread-safe. */
 int lt_influence_matrix_host(const lt_baseline *b, const int32_t *probe_nodes, int32_t n_probe,
                              const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode,
                              float *out, int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
@@ -461,7 +478,8 @@ int lt_influence_matrix_host(const lt_baseline *b, const int32_t *probe_nodes, i
  *                LT_STEP_DST_PINNED: the caller vouches that dst is pinned host memory it allocated.  On the packed route only
  *                the host touches dst, and the runtime is then not asked what kind of pointer it is; on every route where
  *                the GPU writes dst it is resolved as lt_influence_matrix_host resolves it, flag or no flag.
- *   bad_probe, bad_observe   optional: behind the wait the node-id flag is read and cleared as by lt_node_check.  A flag raised
+ *   bad_probe, bad_observe   optional: behind the wait (or, in a call that placed its values by look and did not wait, behind the
+ *                last value: the launches that raise the flag had ended by then) the node-id flag is read and cleared as by lt_node_check.  A flag raised
  *                by THIS call's lists returns LT_ERR_INDEX from this call with the two words filled (1 = that list held an id
  *                outside [0, n)); the matrix of such a call is meaningless.  Both are 0 after any other return -- also when
  *                the call is refused on entry with LT_ERR_INDEX because an EARLIER call left its flag uncollected (that
@@ -475,11 +493,18 @@ int lt_influence_step_host(const lt_baseline *b, const int32_t *probe_nodes, int
                            float *out, int64_t ldo, double *dst, int64_t ldd, void *workspace, size_t workspace_bytes,
                            void *stream, int32_t flags, int32_t *bad_probe, int32_t *bad_observe);
 
-/* The packed calls of lt_influence_matrix_host / lt_influence_step_host on this baseline so far: out4[0] = calls whose index run the host consumed before
- * the stream wait, [1] = calls that did everything after it, [2] = nanoseconds spent between the wait's return and the matrix
- * being complete, summed over both, [3] = ("export_early" = 2) index words the early look saw differently from the finished
- * run -- anything but 0 means the publication is broken.  Additive in ABI 5. */
+/* The packed calls of lt_influence_matrix_host / lt_influence_step_host on this baseline so far: out4[0] = calls that made the
+ * "export_early" look (the index run walked ahead of its values), [1] = the other packed calls, [2] = nanoseconds the host spent
+ * placing -- between the wait's return and the matrix being complete, or, for a call that placed by look ("host_poll"), from the
+ * end of its zero-fill to the complete matrix -- summed over both, [3] = ("export_early" = 2) index words the early look saw
+ * differently from the finished run -- anything but 0 means the publication is broken.  Additive in ABI 5. */
 int lt_host_landing_stats(const lt_baseline *b, int64_t *out4);
+/* ... and of those calls: out4[0] = calls that placed their values by look ("host_poll"), [1] = those of them that ran out of
+ * stall budget and finished behind the stream wait, [2] = stalled looks (loads that found the ready word or a value word not
+ * yet there; in the rounds over the entries passed over: every entry a round rescanned and left pending), [3] = entries whose
+ * first look found them not yet there.  The stall budget is coarse: the clock is read every 1 024 looks, and while entries are
+ * pending it runs on all time, placing included -- about 250 us pass before a fallback.  Additive in ABI 5. */
+int lt_host_landing_stats2(const lt_baseline *b, int64_t *out4);
 
 /* ---- measurement support: the gather ceiling of the tiled SpMM ------------------------------------------------------
  * The tiled (column-sliced work-item) kernel of lt_spmm_csr_f32 with everything but its gathers removed: the same work

@@ -69,6 +69,8 @@ static lt_tuning tuning_defaults() {
     t.export_zero_share = (int)std::min<long long>(100, std::max<long long>(0, env_ll("LT_EXPORT_ZERO_SHARE", 35)));
     t.export_compact = (int)std::min<long long>(2, std::max<long long>(0, env_ll("LT_EXPORT_COMPACT", 1)));
     t.export_early = (int)std::min<long long>(2, std::max<long long>(0, env_ll("LT_EXPORT_EARLY", 0)));
+    t.host_poll = env_ll("LT_HOST_POLL", 1) != 0 ? 1 : 0;
+    t.host_poll_sentinel = (long long)LT_LANDING_SENTINEL;
     t.feature_stagger = (int)env_ll("LT_FEATURE_STAGGER", 0);
     const long long xb = env_ll("LT_XF64_BLOCKS", 96);
     t.xf64_blocks = xb > 0 && xb <= 4096 ? (int)xb : 96;
@@ -131,6 +133,14 @@ extern "C" int lt_set_tuning(const char *key, long long value) {
     else if (!strcmp(key, "export_early")) {
         LT_REQUIRE(reset || (value >= 0 && value <= 2), "lt_set_tuning: export_early must be 0, 1 or 2");
         t.export_early = reset ? d.export_early : (int)value;
+    }
+    else if (!strcmp(key, "host_poll")) {
+        LT_REQUIRE(reset || value == 0 || value == 1, "lt_set_tuning: host_poll must be 0 or 1");
+        t.host_poll = reset ? d.host_poll : (int)value;
+    }
+    else if (!strcmp(key, "host_poll_sentinel")) {
+        LT_REQUIRE(reset || (value >= 0 && value <= 0xffffffffLL), "lt_set_tuning: host_poll_sentinel must be a 32-bit pattern");
+        t.host_poll_sentinel = reset ? d.host_poll_sentinel : value;
     }
     else if (!strcmp(key, "export_zero_blocks")) t.export_zero_blocks = reset ? d.export_zero_blocks : (int)std::min<long long>(4096, std::max<long long>(1, value));
     else if (!strcmp(key, "feature_stagger")) {
@@ -683,7 +693,11 @@ extern "C" int lt_graph_reached_rows(const lt_graph *g, const int32_t *probes, i
 
 // ---- node ids out of range: the flag words the kernels raise (include/linkteller_hip.h, lt_node_check) -------------------------
 // Two words of mapped host memory per process (portable: every device writes through its own alias): [0] a probe list,
-// [1] an observed list held an id outside [0, n).
+// [1] an observed list held an id outside [0, n).  Coherent, said explicitly (what the default means depends on the environment):
+// a host-landed call that placed its values by look reads the words WITHOUT a stream wait, on the argument that the launches
+// that raise them had ended before the finish launch began.  That holds only if a kernel's plain store to this memory is in host
+// memory when the kernel has ended -- true of fine-grained memory (never cached in the L2 past the end-of-kernel release), not
+// promised for coarse-grained memory between two kernels of one stream.
 namespace {
 int32_t *g_node_err_host = nullptr;
 bool g_node_err_tried = false;
@@ -691,7 +705,7 @@ bool g_node_err_tried = false;
 int32_t *lt_node_err_dev() {
     if (!g_node_err_tried) {
         g_node_err_tried = true;
-        if (hipHostMalloc((void **)&g_node_err_host, 2 * sizeof(int32_t), hipHostMallocMapped | hipHostMallocPortable) == hipSuccess)
+        if (hipHostMalloc((void **)&g_node_err_host, 2 * sizeof(int32_t), hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent) == hipSuccess)
             g_node_err_host[0] = g_node_err_host[1] = 0;
         else { g_node_err_host = nullptr; (void)hipGetLastError(); }
     }

@@ -412,6 +412,7 @@ static void free_baseline(lt_baseline *b) {
     if (b->stage_host) (void)hipHostFree(b->stage_host);
     (void)hipFree(b->stage_cur);
     free(b->stage_copy);
+    free(b->stage_pending);
     delete b;
 }
 

@@ -1563,7 +1563,8 @@ __global__ __launch_bounds__(LT_BLOCK) void k_delta_probe_finish(
     auto put = [&](int pos, int k, float v) __attribute__((always_inline)) {
         orow[pos] = v;
         if (srow) srow[pos] = (double)v;
-        if (cval && cbase + k < ccap) cval[cbase + k] = v;
+        // (a system-scope atomic store, like the indices: written through, never torn -- the host may be looking at the word)
+        if (cval && cbase + k < ccap) __hip_atomic_store(cval + cbase + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     };
     const int cnt = hdr.x & 0xffff, n_short = hdr.y & 0xffff, n_long = (int)((unsigned)hdr.y >> 16), v = (int)((unsigned)hdr.x >> 16);
     const lt_df_inc *ent = reinterpret_cast<const lt_df_inc *>(dl_src + hdr.w);
@@ -2533,31 +2534,96 @@ extern "C" int lt_influence_rows_f64(const lt_baseline *b, const int32_t *probe_
 // values travel as one dense run in the baseline's pinned staging block, in two halves of the same numbering -- the indices into
 // dst, which depend on the graph and the lists alone, early in the step (lt_items.hip.h: delta_index_group in the pre-activation's
 // launch when the records rode behind the product rows, else the record blocks' own tail), the fp32 values from the finish kernel
-// -- next to one 64-byte line with the ready word.  The host zero-fills dst while the GPU computes and places the values behind
-// the stream wait.  With "export_early" a single-chunk call looks in between, without ever waiting for it, whether the index run
-// has been published and if so walks it once -- the indices are then in this core's cache, the destination lines asked for.  What
-// orders that look is the ready word (delta_index_publish); everything else is program order and the wait.  (Off by default: it
-// shortens the section behind the wait and costs the step more, profiles/host_early_ab.txt.)  Every other call:
-// lt_influence_rows_f64 and the wait.
+// -- next to one 64-byte line with the ready word.  The block: index run from 0 | value region from the block's midpoint
+// (stage_val_off, fixed per allocation) | the ready line, last.  The host zero-fills dst while the GPU computes.  Then:
+//   "host_poll" = 1 (default), single-chunk calls: the host waits for the ready word (delta_index_publish; acquire), takes the run's
+//   length and walks the run front to back (lt_host_landing.h): a value word that no longer reads as the sentinel is final -- every
+//   entry gets exactly one 4-byte value store (put() in k_delta_probe_finish, short and long positions, repeated observed nodes
+//   alike: one store per touched POSITION) -- so it is placed at once and its word armed again.  A call that consumed every entry
+//   this way returns WITHOUT the stream wait: the matrix is complete in dst, the stream may still be retiring the finish launch's
+//   tail (its fp32 mirror `out` is ordered for every later user by the stream).  Stalls are bounded by a budget of looks and clock
+//   reads, no runtime call in the loop; when it runs out the call waits for the stream once and places the rest in the late form
+//   (counted as a fallback: a faulted stream, a value that equals the sentinel, a finish launch that simply comes later).
+//   "export_early" >= 1 there: while the values are still out the host walks the index run once and asks for the destination
+//   lines (2: and compares the indices it consumed with the finished run, which needs the wait: tests).
+//   "host_poll" = 0, and every multi-chunk call -- the late form: the stream wait, then the values are placed; with "export_early" a
+//   single-chunk call looks in between, bounded by hipStreamQuery, whether the index run has been published and if so walks it
+//   (off by default: it shortens the section behind the wait and costs the step more, profiles/host_early_ab.txt).
+// The invariant -- outside a call every word of the value region holds the sentinel -- is kept by whoever consumes a word: both
+// forms store the sentinel back into each word they read.  A path that leaves without having consumed the run (a refused or
+// failed call behind its launches) waits for the stream first and arms the whole region, in program order before anything else
+// is enqueued.  Every call that does not pack: lt_influence_rows_f64 and the wait.
 #define LT_COMPACT_MAX_FRAC 0.25              // mean touched share of a row up to which "export_compact" = 1 packs (see NOTES.md)
 #define LT_COMPACT_MAX_BYTES ((size_t)256 << 20)   // pinned staging beyond this: whole rows
-#define LT_EARLY_QUERY_EVERY 256              // looks at the ready word between two hipStreamQuery calls
-#ifdef LT_HOST_LAB
-#include <vector>
-static volatile uint32_t g_host_lab_sink;
-static int lt_host_lab_env(const char *name) { const char *e = getenv(name); return (e && *e) ? atoi(e) : 0; }
-#endif
+#define LT_STAGE_PENDING 65536                // entries a polled call may pass over and come back to (the headline's run has 17 250); beyond: it stalls
+#define LT_EARLY_QUERY_EVERY 256              // late form: looks at the ready word between two hipStreamQuery calls
 extern "C" int lt_host_landing_stats(const lt_baseline *b, int64_t *out4) {
     LT_REQUIRE(b != nullptr, "lt_host_landing_stats: baseline is NULL");
     LT_REQUIRE(out4 != nullptr, "lt_host_landing_stats: out is NULL");
     out4[0] = b->stage_early; out4[1] = b->stage_late; out4[2] = b->stage_post_ns; out4[3] = b->stage_mismatch;
     return LT_OK;
 }
+extern "C" int lt_host_landing_stats2(const lt_baseline *b, int64_t *out4) {
+    LT_REQUIRE(b != nullptr, "lt_host_landing_stats2: baseline is NULL");
+    LT_REQUIRE(out4 != nullptr, "lt_host_landing_stats2: out is NULL");
+    out4[0] = b->stage_polled; out4[1] = b->stage_fallback; out4[2] = b->stage_looks; out4[3] = b->stage_late_entries;
+    return LT_OK;
+}
+// every word of the staging block's value region <- the sentinel (the caller knows that nothing in flight still stores there)
+static void lt_stage_arm(const lt_baseline *b, uint32_t sentinel) {
+    if (b->stage_host && b->stage_bytes >= 64 + b->stage_val_off)
+        lt_landing_arm(reinterpret_cast<uint32_t *>(static_cast<char *>(b->stage_host) + b->stage_val_off),
+                       (b->stage_bytes - 64 - b->stage_val_off) / sizeof(uint32_t), sentinel);
+    b->stage_sentinel = sentinel;
+}
+// lt_landing::settle of a host-landed call: the stream wait
+struct lt_host_settle { hipStream_t st; hipError_t err; };
+static int lt_host_settle_fn(void *p) {
+    lt_host_settle *s = static_cast<lt_host_settle *>(p);
+    s->err = hipStreamSynchronize(s->st);
+    return s->err == hipSuccess ? 0 : 1;
+}
+#ifdef LT_HOST_LAB
+#include <vector>
+static volatile uint32_t g_host_lab_sink;
+static int lt_host_lab_env(const char *name) { const char *e = getenv(name); return (e && *e) ? atoi(e) : 0; }
+#endif
+// The look ahead of "export_early": the published index run walked once, while its values are still out -- its lines come into
+// this core's cache, and each destination line is asked for, for writing (2: the indices kept as they were seen)
+struct lt_host_ahead { const lt_baseline *b; const uint32_t *idx; double *dst; uint64_t lim; int early; size_t seen; };
+static void lt_host_ahead_fn(void *p, size_t total) {
+    lt_host_ahead *a = static_cast<lt_host_ahead *>(p);
+    const lt_baseline *b = a->b;
+    a->seen = total + 1;
+    if (a->early == 2) {
+        if (b->stage_copy_words < total) {
+            free(b->stage_copy);
+            b->stage_copy = static_cast<uint32_t *>(malloc(std::max<size_t>(total, 1) * sizeof(uint32_t)));
+            b->stage_copy_words = b->stage_copy ? total : 0;
+        }
+        if (b->stage_copy_words >= total) memcpy(b->stage_copy, a->idx, total * sizeof(uint32_t));
+    }
+#ifdef LT_HOST_LAB
+    if (lt_host_lab_env("LT_HOST_LAB_NOPF")) {
+        uint32_t acc = 0;
+        for (size_t e = 0; e < total; ++e) acc += a->idx[e];
+        g_host_lab_sink = acc;
+        return;
+    }
+#endif
+    for (size_t e = 0; e < total; ++e) {
+        const uint32_t x = a->idx[e];
+        if (x < a->lim) __builtin_prefetch(a->dst + x, 1, 3);
+    }
+}
 #ifdef LT_HOST_LAB
 // tools/host_lab/step_parts.py: monotonic nanoseconds of the last host-landed call -- [0] entry, [1] first launch returned,
-// [2] last launch returned, [3] zero-fill done, [4] wait returned, [5] matrix placed (node check included)
-int64_t g_lt_lab_stamp[6];
+// [2] last launch returned, [3] zero-fill done, [4] wait returned (a polled call that did not wait: the run consumed), [5] matrix
+// placed (node check included); of a polled call also [6] ready word seen, [7] first value seen, [8] last value seen, [9] the
+// nanoseconds of stall the budget saw
+int64_t g_lt_lab_stamp[10];
 extern "C" void lt_host_lab_stamps(int64_t *out6) { for (int i = 0; i < 6; ++i) out6[i] = g_lt_lab_stamp[i]; }
+extern "C" void lt_host_lab_stamps10(int64_t *out10) { for (int i = 0; i < 10; ++i) out10[i] = g_lt_lab_stamp[i]; }
 #define LT_LAB_STAMP(i) (g_lt_lab_stamp[i] = lt_now_ns())
 #else
 #define LT_LAB_STAMP(i) ((void)0)
@@ -2603,8 +2669,10 @@ static int influence_host_impl(const lt_baseline *b, const int32_t *probe_nodes,
         }
         b->stage_parity = 0;
     }
+    const uint32_t sentinel = (uint32_t)lt_tune().host_poll_sentinel;
     if (want && b->stage_bytes < need) {
-        // (worst case: every pair touched; this call is synchronous, so nothing of an earlier one still writes the old block.)
+        // (worst case: every pair touched; every earlier call returned with all of its stores to the old block landed -- behind the
+        // stream wait, or because the host had read every one of them.)
         // Coherent, said explicitly: the host reads the block while a kernel may still be running, and what the default means for
         // that depends on the environment.  The device-side alias is asked once, here.
         if (b->stage_host) (void)hipHostFree(b->stage_host);
@@ -2612,14 +2680,20 @@ static int influence_host_impl(const lt_baseline *b, const int32_t *probe_nodes,
         b->stage_dev = nullptr;
         b->stage_bytes = 0;
         if (hipHostMalloc(&b->stage_host, need, hipHostMallocCoherent) == hipSuccess &&
-            hipHostGetDevicePointer(&b->stage_dev, b->stage_host, 0) == hipSuccess) b->stage_bytes = need;
-        else {
+            hipHostGetDevicePointer(&b->stage_dev, b->stage_host, 0) == hipSuccess) {
+            b->stage_bytes = need;
+            if (!b->stage_pending) b->stage_pending = static_cast<uint32_t *>(malloc(LT_STAGE_PENDING * sizeof(uint32_t)));
+            b->stage_val_off = run_bytes;       // (the block's midpoint: index words never land in the value region, whatever a later call's size)
+            lt_stage_arm(b, sentinel);
+        } else {
             (void)hipGetLastError();
             if (b->stage_host) (void)hipHostFree(b->stage_host);
             b->stage_host = nullptr; b->stage_dev = nullptr; want = false;
         }
     }
-    // (the block may be larger than this call needs: the ready word's line is its last one, wherever the runs end)
+    if (want && b->stage_sentinel != sentinel) lt_stage_arm(b, sentinel);      // ("host_poll_sentinel" changed: tests)
+    // (the block may be larger than this call needs: the value region starts at its midpoint and the ready word's line is its last
+    // one, wherever the runs end)
     const size_t ready_off = b->stage_bytes >= 64 ? b->stage_bytes - 64 : 0;
     char *const hs = static_cast<char *>(b->stage_host);
     unsigned *const h_ready = want ? reinterpret_cast<unsigned *>(hs + ready_off) : nullptr;
@@ -2627,7 +2701,7 @@ static int influence_host_impl(const lt_baseline *b, const int32_t *probe_nodes,
     if (want) {
         char *d = static_cast<char *>(b->stage_dev);
         cmp.idx = reinterpret_cast<uint32_t *>(d);
-        cmp.val = reinterpret_cast<float *>(d + run_bytes);
+        cmp.val = reinterpret_cast<float *>(d + b->stage_val_off);
         cmp.ready = reinterpret_cast<unsigned *>(d + ready_off);
         cmp.cur = b->stage_cur + b->stage_parity;
         cmp.cur_next = b->stage_cur + (b->stage_parity ^ 1);
@@ -2646,6 +2720,7 @@ static int influence_host_impl(const lt_baseline *b, const int32_t *probe_nodes,
         if (cmp.taken) {       // (launches already queued may still write the staging block; cursors and ticket may be left dirty)
             (void)hipStreamSynchronize(st);
             (void)hipMemset(b->stage_cur, 0, 4 * sizeof(int));
+            lt_stage_arm(b, sentinel);      // (behind the wait: whatever those launches stored is gone before the next call enqueues)
         }
         return rc;
     }
@@ -2661,8 +2736,59 @@ static int influence_host_impl(const lt_baseline *b, const int32_t *probe_nodes,
         for (int32_t i = 0; i < n_probe; ++i) memset(dst + (size_t)i * ldd, 0, (size_t)n_obs * sizeof(double));
     LT_LAB_STAMP(3);
     const uint32_t *idx = reinterpret_cast<const uint32_t *>(hs);
-    const float *val = reinterpret_cast<const float *>(hs + run_bytes);
+    uint32_t *const valw = reinterpret_cast<uint32_t *>(hs + b->stage_val_off);
+#ifdef LT_HOST_LAB
+    const float *val = reinterpret_cast<const float *>(valw);
+#endif
     const uint64_t lim = (uint64_t)n_probe * (uint64_t)ldd;
+    // ---- "host_poll": the values are placed as they land (lt_host_landing.h), and a call that consumed them all does not wait
+    if (lt_tune().host_poll != 0 && cmp.chunks == 1) {
+        lt_host_settle hs_ctx = {st, hipSuccess};
+        lt_host_ahead ha_ctx = {b, idx, dst, lim, early, 0};
+        lt_landing L = {};
+        L.idx = idx; L.val = valw; L.ready = h_ready; L.dst = dst; L.lim = lim; L.cap = cells;
+        L.sentinel = sentinel;
+        L.budget_ns = LT_LANDING_BUDGET_NS;
+        L.settle = lt_host_settle_fn; L.settle_arg = &hs_ctx;
+        if (b->stage_pending) { L.pending = b->stage_pending; L.pending_cap = LT_STAGE_PENDING; }
+        if (early >= 1) { L.on_ready = lt_host_ahead_fn; L.on_ready_arg = &ha_ctx; }
+#ifdef LT_HOST_LAB
+        L.stamps = true;
+        if (lt_host_lab_env("LT_HOST_LAB_INORDER")) L.pending = nullptr;      // (the strict front-to-back walk, for comparison)
+#endif
+        const int64_t t0 = lt_now_ns();
+        const int lrc = lt_landing_consume(L);
+        b->stage_looks += L.looks;
+        b->stage_late_entries += L.late_entries;
+        if (lrc || !L.published) {      // (the wait failed, or behind it the run is still not published: nothing is known about the block)
+            lt_stage_arm(b, sentinel);
+            return lrc ? lt_set_error(LT_ERR_HIP, "hipStreamSynchronize(st) failed: %s (%s)", hipGetErrorString(hs_ctx.err), who)
+                       : lt_set_error(LT_ERR_HIP, "%s: the packed run was not published", who);
+        }
+#ifdef LT_HOST_LAB
+        g_lt_lab_stamp[6] = L.t_ready; g_lt_lab_stamp[7] = L.t_first; g_lt_lab_stamp[8] = L.t_last; g_lt_lab_stamp[9] = L.idle_ns;
+        // Step 0 of profiles/host_poll_ab.txt: what the wait would still have cost behind the last value (not the product)
+        if (lt_host_lab_env("LT_HOST_LAB_WAIT")) LT_HIP(hipStreamSynchronize(st));
+#endif
+        // Without the wait: the host has read every value of the finish launch, so that launch had begun, and every earlier launch
+        // of the call -- the record blocks that raise the node-id flag words among them -- had ended, its stores in host memory
+        // (the consumer's acquire fence orders the caller's reads of those words behind the values').  A run of no entries proves
+        // nothing of the kind, and "export_early" = 2 compares with the finished run: both wait.
+        if (!L.settled && (L.total == 0 || early == 2)) LT_HIP(hipStreamSynchronize(st));
+        LT_LAB_STAMP(4);
+        ++b->stage_polled;
+        if (L.settled) ++b->stage_fallback;
+        if (early >= 1 && ha_ctx.seen) {
+            ++b->stage_early;
+            if (early == 2) {
+                if (ha_ctx.seen != L.total + 1 || b->stage_copy_words < L.total) ++b->stage_mismatch;
+                else
+                    for (size_t e = 0; e < L.total; ++e) b->stage_mismatch += b->stage_copy[e] != idx[e];
+            }
+        } else ++b->stage_late;
+        b->stage_post_ns += lt_now_ns() - t0;
+        return LT_OK;
+    }
     // The opportunistic look: bounded by the stream -- it leaves when the word is there OR the stream is no longer busy (done or
     // failed), and never waits on GPU-written memory alone.  Not seen: nothing early happens, the call is the late form.
     size_t seen = 0;        // entries of the run the early look walked
@@ -2680,29 +2806,17 @@ static int influence_host_impl(const lt_baseline *b, const int32_t *probe_nodes,
         if (queried) (void)hipGetLastError();      // (hipErrorNotReady is an answer, not an error to be found by a later check)
         if (r != 0u && (size_t)(r - 1u) <= cells) {
             seen = (size_t)(r - 1u);
-            if (early == 2) {
-                if (b->stage_copy_words < seen) {
-                    free(b->stage_copy);
-                    b->stage_copy = static_cast<uint32_t *>(malloc(std::max<size_t>(seen, 1) * sizeof(uint32_t)));
-                    b->stage_copy_words = b->stage_copy ? seen : 0;
-                }
-                if (b->stage_copy_words >= seen) memcpy(b->stage_copy, idx, seen * sizeof(uint32_t));
-            }
-            // one pass over the run: its lines come into this core's cache, and each destination line is asked for, for writing
-#ifdef LT_HOST_LAB
-            if (lt_host_lab_env("LT_HOST_LAB_NOPF")) {
-                uint32_t acc = 0;
-                for (size_t e = 0; e < seen; ++e) acc += idx[e];
-                g_host_lab_sink = acc;
-            } else
-#endif
-            for (size_t e = 0; e < seen; ++e) {
-                const uint32_t x = idx[e];
-                if (x < lim) __builtin_prefetch(dst + x, 1, 3);
-            }
+            lt_host_ahead ha_ctx = {b, idx, dst, lim, early, 0};
+            lt_host_ahead_fn(&ha_ctx, seen);
         }
     }
-    LT_HIP(hipStreamSynchronize(st));
+    {
+        const hipError_t e_ = hipStreamSynchronize(st);
+        if (e_ != hipSuccess) {
+            lt_stage_arm(b, sentinel);
+            return lt_set_error(LT_ERR_HIP, "hipStreamSynchronize(st) failed: %s (%s)", hipGetErrorString(e_), who);
+        }
+    }
     LT_LAB_STAMP(4);
 #ifdef LT_HOST_LAB      // tools/host_lab/early_ab.py --forms: where the post-wait section's time goes (forms 1 and 2 are not the product)
     {
@@ -2715,6 +2829,7 @@ static int influence_host_impl(const lt_baseline *b, const int32_t *probe_nodes,
             g_host_lab_sink = acc;
             b->stage_post_ns += lt_now_ns() - t1;
             ++b->stage_late;
+            lt_stage_arm(b, sentinel);
             return LT_OK;
         }
         if (form == 2) {            // placing from a copy the host made itself: warm reads, the same stores
@@ -2727,18 +2842,20 @@ static int influence_host_impl(const lt_baseline *b, const int32_t *probe_nodes,
                 if (ci[e] < lim) dst[ci[e]] = (double)cv[e];
             b->stage_post_ns += lt_now_ns() - t1;
             ++b->stage_late;
+            lt_stage_arm(b, sentinel);
             return LT_OK;
         }
     }
 #endif
     const int64_t t0 = lt_now_ns();
     const unsigned r_end = __atomic_load_n(h_ready, __ATOMIC_ACQUIRE);
-    if (r_end == 0u) return lt_set_error(LT_ERR_HIP, "%s: the packed run was not published", who);
-    const size_t total = std::min<size_t>((size_t)__atomic_load_n(h_ready + 1, __ATOMIC_RELAXED), cells);
-    for (size_t e = 0; e < total; ++e) {
-        const uint32_t x = idx[e];
-        if (x < lim) dst[x] = (double)val[e];
+    if (r_end == 0u) {
+        lt_stage_arm(b, sentinel);
+        return lt_set_error(LT_ERR_HIP, "%s: the packed run was not published", who);
     }
+    const size_t total = std::min<size_t>((size_t)__atomic_load_n(h_ready + 1, __ATOMIC_RELAXED), cells);
+    // (every word the call's launches stored is consumed here, and armed again as it is: the region leaves the call as it entered)
+    lt_landing_place_late(idx, valw, 0, total, dst, lim, sentinel);
     b->stage_post_ns += lt_now_ns() - t0;
     if (seen > 0) {
         ++b->stage_early;
@@ -2769,7 +2886,12 @@ extern "C" int lt_influence_step_host(const lt_baseline *b, const int32_t *probe
     LT_REQUIRE((flags & ~(LT_STEP_REFRESH | LT_STEP_DST_PINNED)) == 0, "lt_influence_step_host: unknown flags 0x%x", (unsigned)flags);
     int rc = influence_host_impl(b, probe_nodes, n_probe, observe_nodes, n_obs, delta, mode, out, ldo, dst, ldd, workspace,
                                  workspace_bytes, stream, flags, "lt_influence_step_host");
-    // (behind the wait: the flag words are this call's kernels' -- a refused call launched nothing and leaves them alone)
+    // (the flag words are this call's kernels' -- a refused call launched nothing and leaves them alone.  They are read behind the
+    // stream wait, or, for a call that consumed its value run by look and did not wait, behind the values: the flags are raised by
+    // the record blocks, in launches that had ended -- their stores in host memory -- before the finish launch, whose every value
+    // the host has read, began.  The finish kernel itself reads no list and raises nothing.  This rests on the flag words being
+    // fine-grained host memory, which a kernel's plain stores have reached when the kernel has ended: lt_core.hip allocates them
+    // hipHostMallocCoherent for that reason.)
     if (!rc && n_probe > 0 && n_obs > 0) rc = lt_node_check(bad_probe, bad_observe);
     LT_LAB_STAMP(5);
     return rc;

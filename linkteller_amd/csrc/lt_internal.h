@@ -194,6 +194,14 @@ struct lt_baseline {
     mutable int64_t stage_early = 0, stage_late = 0, stage_post_ns = 0, stage_mismatch = 0;
     mutable uint32_t *stage_copy = nullptr;   // "export_early" = 2: the indices as the early look saw them
     mutable size_t stage_copy_words = 0;
+    // The value region of the staging block: [stage_val_off, stage_bytes - 64), fixed when the block is allocated (the index run
+    // grows from 0 and never reaches it), every word of it holding stage_sentinel outside a call (lt_host_landing.h)
+    mutable size_t stage_val_off = 0;
+    mutable uint32_t stage_sentinel = 0;
+    mutable uint32_t *stage_pending = nullptr;   // LT_STAGE_PENDING words: entries the walk passed over (lt_landing::pending), allocated with the block
+    // lt_host_landing_stats2: calls that consumed the value run by look ("host_poll"), those of them that fell back to the stream
+    // wait, stalled looks, entries whose first look found them not yet there
+    mutable int64_t stage_polled = 0, stage_fallback = 0, stage_looks = 0, stage_late_entries = 0;
 };
 // what lt_baseline_refresh marks stale (lt_influence_step_host does the same inside its call)
 static inline void lt_baseline_mark_stale(const lt_baseline *b) {
@@ -268,6 +276,10 @@ struct lt_tuning {
                                  // before the stream wait, 0 everything after the wait (default: the look costs the step more than it
                                  // saves behind the wait, profiles/host_early_ab.txt), 2 as 1 and the early look is compared with the
                                  // finished run (LT_EXPORT_EARLY)
+    int host_poll;               // ... packed, single-chunk calls: 1 the host places each value as its word in the staging block stops reading
+                                 // as the sentinel and returns without the stream wait (default), 0 everything behind the wait
+                                 // (LT_HOST_POLL)
+    long long host_poll_sentinel;   // the sentinel's bit pattern (tests: a value the matrix holds; default 0xFFFFFFFF)
     int feature_stagger;         // the row-per-wave kernel's blocks start in (value & 255) groups, (value >> 8) ticks of 10 ns apart; 0 = together
                                  // (LT_FEATURE_STAGGER)
     int feature_ring_min_rows;   // (LT_FEATURE_RING_MIN_ROWS, default 1024: below it the CUs' waves have no row each)
@@ -287,16 +299,12 @@ int lt_export_rows_dev(const float *src, int64_t lds, int32_t rows, int32_t cols
                                 hipGetErrorString(e_), __FILE__, __LINE__);                \
     } while (0)
 
-static inline int64_t lt_now_ns() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (int64_t)ts.tv_sec * 1000000000ll + ts.tv_nsec;
-}
+#include "lt_host_landing.h"      // lt_now_ns, and the consumer of the packed value run
 // -DLT_HOST_LAB only (tools/host_lab/step_parts.py; nothing of it is in a product build): stamp [1] of a host-landed call, the
 // moment its first launch has returned.  "Launch" = the first KERNEL launch checked with LT_CHECK_LAUNCH in any translation unit
 // (at the headline shape the product rows'); a hipMemsetAsync / hipMemcpyAsync in front of it does not set the stamp.
 #ifdef LT_HOST_LAB
-extern int64_t g_lt_lab_stamp[6];
+extern int64_t g_lt_lab_stamp[10];
 #define LT_LAB_FIRST_LAUNCH() do { if (!g_lt_lab_stamp[1]) g_lt_lab_stamp[1] = lt_now_ns(); } while (0)
 #else
 #define LT_LAB_FIRST_LAUNCH() ((void)0)

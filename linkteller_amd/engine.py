@@ -446,12 +446,19 @@ class Baseline:
         return ws
 
     def host_landing_stats(self) -> dict:
-        """The packed ``influence_matrix_host`` calls on this baseline so far (lt_host_landing_stats): how many consumed the
-        index run before the stream wait (``early``) / after it (``late``), the nanoseconds spent behind the wait
-        (``post_ns``), and the index words an ``export_early`` = 2 look saw differently from the finished run (``mismatch``)."""
+        """The packed ``influence_matrix_host`` calls on this baseline so far (lt_host_landing_stats): how many walked the index
+        run ahead of its values (``early``, the ``export_early`` look) / did not (``late``), the nanoseconds the host spent placing
+        (``post_ns``: behind the stream wait, or, for a polled call, from the zero-fill's end to the complete matrix), and the
+        index words an ``export_early`` = 2 look saw differently from the finished run (``mismatch``).  And, of those calls
+        (lt_host_landing_stats2): how many placed their values as they landed, by look (``polled``, the ``host_poll`` path), how
+        many of these ran out of stall budget and fell back to the stream wait (``fallback``), the stalled looks (``looks``) and
+        the entries whose first look found them not yet there (``late_entries``)."""
         o = (C.c_int64 * 4)()
         _lib.check(_lib.lib().lt_host_landing_stats(self._h, o), "lt_host_landing_stats")
-        return {"early": int(o[0]), "late": int(o[1]), "post_ns": int(o[2]), "mismatch": int(o[3])}
+        p = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().lt_host_landing_stats2(self._h, p), "lt_host_landing_stats2")
+        return {"early": int(o[0]), "late": int(o[1]), "post_ns": int(o[2]), "mismatch": int(o[3]),
+                "polled": int(p[0]), "fallback": int(p[1]), "looks": int(p[2]), "late_entries": int(p[3])}
 
     def influence_rows_vec(self, probes: torch.Tensor, obs: torch.Tensor, delta: float, m: int, out: torch.Tensor,
                            vec: torch.Tensor) -> torch.Tensor:

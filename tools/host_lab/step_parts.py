@@ -7,7 +7,11 @@ and this tool puts time.perf_counter_ns (the same clock) around the Python call.
 Printed: medians over the blocks of the per-block medians, in us.  "launch..wait" is first launch returned -> wait returned: GPU span
 + launch latency + completion latency (take the GPU span from a kernel trace of its own, tools/host_lab/trace_medians.py).
 --steps-only K --form calls|step: K steps of one form and nothing else (what a kernel trace is taken of).
-python tools/host_lab/step_parts.py --lib PATH [--blocks 10] [--steps 50]"""
+A call that places its values by look ("host_poll" = 1, the default) also stamps: ready word seen, first value seen, last value
+seen, and reports the stall time its budget saw; "wait returned" is then the moment the run was consumed -- unless LT_HOST_LAB_WAIT=1
+is set, which makes the lab build still call the stream wait behind the last value: "(a) last value..wait" is then what the
+product path saves outright.  --host-poll 0 measures the late form.
+python tools/host_lab/step_parts.py --lib PATH [--blocks 10] [--steps 50] [--host-poll 0|1]"""
 import argparse, ctypes, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
@@ -19,12 +23,15 @@ ap.add_argument("--steps", type=int, default=50)
 ap.add_argument("--steps-only", type=int, default=0)
 ap.add_argument("--form", default="step", choices=["calls", "step"])
 ap.add_argument("--lib", default=None)
+ap.add_argument("--host-poll", type=int, default=None, choices=[0, 1])
 a = ap.parse_args()
 if a.lib:
     _lib.LIB_PATH = os.path.abspath(a.lib)
 from linkteller_amd import engine, graph, synth
 
 dev = torch.device("cuda:0")
+if a.host_poll is not None:
+    _lib.set_tuning("host_poll", a.host_poll)
 adj, x_np, w = synth.twitch_like_problem("twitch-RU", hidden=256, n_classes=2, seed=0)
 n = adj.shape[0]
 base = engine.Baseline(graph.HipGraph(graph.first_order_gcn(adj)), torch.from_numpy(x_np).to(dev),
@@ -66,11 +73,14 @@ if a.steps_only:
 handle = _lib.lib()
 if not hasattr(handle, "lt_host_lab_stamps"):
     sys.exit("the library was not built with -DLT_HOST_LAB")
-handle.lt_host_lab_stamps.restype = None
-handle.lt_host_lab_stamps.argtypes = [ctypes.POINTER(ctypes.c_int64)]
-stamps = (ctypes.c_int64 * 6)()
+read_stamps = handle.lt_host_lab_stamps10 if hasattr(handle, "lt_host_lab_stamps10") else handle.lt_host_lab_stamps
+read_stamps.restype = None
+read_stamps.argtypes = [ctypes.POINTER(ctypes.c_int64)]
+stamps = (ctypes.c_int64 * 10)()
 COLS = ("step", "python before", "library before 1st launch", "launches", "zero-fill", "launch..wait", "wait after zero-fill",
-        "placing + node check", "python after", "between calls")
+        "placing + node check", "python after", "between calls",
+        "1st launch..ready word", "1st launch..first value", "1st launch..last value", "(b) first..last value",
+        "(a) last value..wait", "(c) stall seen by the budget")
 
 ref = step_calls().copy()
 for fn in forms.values():
@@ -86,12 +96,14 @@ for blk in range(a.blocks):
             t0 = time.perf_counter_ns()
             fn()
             t1 = time.perf_counter_ns()
-            handle.lt_host_lab_stamps(stamps)
+            read_stamps(stamps)
             s = list(stamps)
+            polled = s[6] >= s[0] and s[8] >= s[6]      # (this call's: a call in the late form leaves an earlier call's stamps)
             rows.append((t1 - t0, s[0] - t0, s[1] - s[0], s[2] - s[1], s[3] - s[2], s[4] - s[1], s[4] - s[3], s[5] - s[4], t1 - s[5],
-                         0 if t_prev is None else t0 - t_prev))
+                         0 if t_prev is None else t0 - t_prev)
+                        + ((s[6] - s[1], s[7] - s[1], s[8] - s[1], s[8] - s[7], s[4] - s[8], s[9]) if polled else (np.nan,) * 6))
             t_prev = time.perf_counter_ns()
-        res[name].append(np.median(np.array(rows, dtype=np.float64), axis=0) / 1e3)
+        res[name].append(np.nanmedian(np.array(rows, dtype=np.float64), axis=0) / 1e3)
 for name in forms:
     m = np.median(np.array(res[name]), axis=0)
     lo, hi = np.min(np.array(res[name]), axis=0), np.max(np.array(res[name]), axis=0)
