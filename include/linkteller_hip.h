@@ -47,7 +47,9 @@ extern "C" {
                             Additive within 5: evaluation over a row list (lt_eval_head_rows, lt_eval_head_rows_workspace_bytes,
                             lt_gcn*_trainer_attach_validation_rows); no entry point changed.
                             Additive within 5: the wide head of the 2-layer trainer (lt_gcn2_trainer_create_wide, _counts, _hidden,
-                            _attach_validation_wide, lt_eval_head_wide, lt_eval_head_wide_workspace_bytes); no entry point changed */
+                            _attach_validation_wide, lt_eval_head_wide, lt_eval_head_wide_workspace_bytes); no entry point changed.
+                            Additive within 5: the wide head of the 3-layer trainer (lt_gcn3_trainer_create_wide, _counts,
+                            _attach_validation_wide); no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -1036,6 +1038,27 @@ size_t lt_eval_head_wide_workspace_bytes(int32_t m, int32_t C);
 int lt_eval_head_wide(const float *Z, int64_t ldz, const void *labels, int64_t ldy, int32_t n, int32_t C, int32_t loss_kind,
                       const int32_t *rows, int32_t m, float *loss, int32_t *counts, int32_t *n_bad, void *workspace,
                       size_t workspace_bytes, void *stream);
+
+/* ---- the wide head on the 3-layer trainer.  Additive within ABI 5. ----
+ * lt_gcn3_trainer_create_wide is lt_gcn3_trainer_create with the class layer and the loss head of
+ * lt_gcn2_trainer_create_wide behind the two hidden layers: labels, ldy and loss_kind as there, widths H1, H2 <= 256 and
+ * C <= 256.  The handle is a lt_gcn3_trainer: _run, _run_validated, _grads, _logits, _hidden, _epoch, _val_state,
+ * _restore_best, _val_logits and _destroy work on it.  record [n_epochs, 2] = (loss, sum over the classes of tp).  The mask
+ * contract is GCN3's (layer words 0 and 1): a narrow and a wide GCN3 trainer of one seed draw the same masks.  No float
+ * atomics: run(a + b) equals run(a); run(b) and two trainers agree bit for bit.  LT_ERR_INVALID with a message naming the
+ * value, nothing allocated: H1 or H2 > 256, C > 256, an unknown loss_kind, ldy < C for LT_LOSS_BCE, a NULL pointer.
+ * lt_gcn3_trainer_counts: lt_gcn2_trainer_counts for a wide 3-layer trainer.
+ * lt_gcn3_trainer_attach_validation_wide: lt_gcn2_trainer_attach_validation_wide for a wide 3-layer trainer; val_counts are
+ * [n_epochs, C, 3].  The narrow attach entry points on a wide trainer, and this one on a narrow trainer, are
+ * LT_ERR_INVALID with a message naming the right call. */
+int lt_gcn3_trainer_create_wide(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const void *labels, int64_t ldy,
+                                int32_t loss_kind, int32_t H1, int32_t H2, int32_t C, float *W1, float *b1, float *W2, float *b2,
+                                float *W3, float *b3, double lr, double weight_decay, double dropout, uint64_t seed, void *stream,
+                                lt_gcn3_trainer **out);
+int lt_gcn3_trainer_counts(const lt_gcn3_trainer *t, int32_t *counts, void *stream);
+int lt_gcn3_trainer_attach_validation_wide(lt_gcn3_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
+                                           const void *labels2, int64_t ldy2, int32_t keep_best, int32_t patience,
+                                           const int32_t *rows, int32_t m, void *stream);
 
 /* ---- per-kernel timing (used by bench.py for the roofline object) --------------------------
  * lt_profile_enable(mask): bit k of mask set = launches of kernel class k are bracketed by a pair of

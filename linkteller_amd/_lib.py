@@ -196,6 +196,13 @@ SIGNATURES = {
     "lt_eval_head_wide_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lt_eval_head_wide": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lt_gcn3_trainer_create_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_void_p,
+                                              C.POINTER(C.c_void_p)]),
+    "lt_gcn3_trainer_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_gcn3_trainer_attach_validation_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                                         C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "lt_profile_enable": (C.c_int, [C.c_int]),
     "lt_profile_reset": (C.c_int, []),
     "lt_profile_summary": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

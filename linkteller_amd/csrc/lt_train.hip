@@ -27,6 +27,11 @@
 //   dW1 = X^T dS1                  k_gemm_tn_mfma + k_sum_slabs   v_mfma_f32_32x32x2_f32, A^T staged through LDS, split-K
 //   Adam                           k_tr_adam / k_tr3_adam         one launch over W1 | b1 | W2 | b2 (| W3 | b3) and the padded copies
 //
+// With the wide head (lt_gcn*_trainer_create_wide; lt_train_wide.hip.h, included below) the top chain is launch_wide_forward,
+// launch_trw_head and launch_wide_backward instead: the class layer as matrix products at the padded width, the hidden layer's
+// backward a k_tr3_dz_mfma stage (GCN3 then runs two: dZ2 here, dZ1 in the front layer's backward), Adam by k_tr3_adam over
+// four segments or, for GCN3, k_tr3w_adam over six.
+//
 // Every reduction has a fixed order (no float atomics): two trainings with the same inputs give the same bits.
 // Built with -ffp-contract=off: the only fused operations are explicit fmaf calls and the MFMAs.
 #include <math.h>
@@ -544,6 +549,47 @@ __global__ void k_tr3_pad(const float *__restrict__ b1, int H1, int Hp1, const f
     if (i < Hp2 * C) W3p[i] = (i / C) < H2 ? W3[i] : 0.f;
 }
 
+// GCN3 with the wide head: the six segments and the three bias copies b1p [Hp1], b2p [Hp2], b3p [Cp].  No W3p: both products
+// read W3 as it lies.  A sibling of k_tr3_adam / k_tr3_pad, not a generalisation of them (NOTES.md, 2026-10-20, "Left out").
+struct lt_tr3w_tensors {
+    lt_snap_segs s;
+    float *b1p, *b2p, *b3p;
+};
+
+__global__ void k_tr3w_adam(lt_tr3w_tensors T, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                            lt_adam_scalars s) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T.s.o[5]) return;
+    const int k = i < T.s.o[0] ? 0 : i < T.s.o[1] ? 1 : i < T.s.o[2] ? 2 : i < T.s.o[3] ? 3 : i < T.s.o[4] ? 4 : 5;
+    const int64_t j = k ? i - T.s.o[k - 1] : i;
+    float *p;      // a switch over constant indices, as in k_tr3_adam
+    switch (k) {
+        case 0: p = T.s.p[0]; break;
+        case 1: p = T.s.p[1]; break;
+        case 2: p = T.s.p[2]; break;
+        case 3: p = T.s.p[3]; break;
+        case 4: p = T.s.p[4]; break;
+        default: p = T.s.p[5]; break;
+    }
+    float mi = m[i], vi = v[i];
+    const float np = adam_elem(p[j], g[i], mi, vi, s);
+    p[j] = np;
+    m[i] = mi;
+    v[i] = vi;
+    if (k == 1) T.b1p[j] = np;
+    else if (k == 3) T.b2p[j] = np;
+    else if (k == 5) T.b3p[j] = np;
+}
+
+__global__ void k_tr3w_pad(const float *__restrict__ b1, int H1, int Hp1, const float *__restrict__ b2, int H2, int Hp2,
+                           const float *__restrict__ b3, int C, int Cp, float *__restrict__ b1p, float *__restrict__ b2p,
+                           float *__restrict__ b3p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < Hp1) b1p[i] = i < H1 ? b1[i] : 0.f;
+    if (i < Hp2) b2p[i] = i < H2 ? b2[i] : 0.f;
+    if (i < Cp) b3p[i] = i < C ? b3[i] : 0.f;
+}
+
 extern "C" int lt_adam_step(int64_t n, float *p, const float *g, float *m, float *v, int64_t step, double lr,
                             double beta1, double beta2, double eps, double weight_decay, void *stream) {
     LT_REQUIRE(n >= 0, "lt_adam_step: n=%lld", (long long)n);
@@ -1012,7 +1058,7 @@ struct lt_trainer {
     uint64_t seed = 0;
     int64_t epoch = 0;            // epochs run since creation (= Adam's step count)
     int32_t kslice = 0;           // split-K slicing of X W1 (the forward's)
-    lt_tn tn[2];                  // dW1 = X^T dS1; GCN3: dW2 = Hf^T dS
+    lt_tn tn[3];                  // dW1 = X^T dS1; GCN3: dW2 = Hf^T dS; the wide head: tn[top + 1], dWc = Hd^T dSc
     int32_t n_part = 0;           // row blocks of k_tr_bwd_rows
     int32_t n_mblk = 0;           // row blocks of k_tr3_dz_mfma
     int32_t n_seg = 0;            // the graph's hub-row segments at creation (g->p_n_seg): the rows of seg_part
@@ -1026,10 +1072,12 @@ struct lt_trainer {
     float *mir[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int32_t mir_len[6] = {0, 0, 0, 0, 0, 0};
     float *slabs = nullptr, *part = nullptr, *part1 = nullptr, *seg_part = nullptr;
+    float *part2 = nullptr;       // GCN3 with the wide head: the db2 slabs [n_mblk, H2] of the top chain's k_tr3_dz_mfma stage
     float *grad = nullptr, *m = nullptr, *v = nullptr;   // [off[5]]
     lt_val *val = nullptr;        // lt_gcn*_trainer_attach_validation (owned)
-    // The wide head (lt_gcn2_trainer_create_wide; lt_train_wide.hip.h): the class layer as matrix products at the padded width
-    // Cp, Sc / Zc / dZc / dSc [n, Cp] with zero pad columns, `labels` int32 [n] (CE) or uint8 [n, ldy] (BCE), mir[3] = b2 at Cp.
+    // The wide head (lt_gcn*_trainer_create_wide; lt_train_wide.hip.h): the class layer as matrix products at the padded width
+    // Cp, Sc / Zc / dZc / dSc [n, Cp] with zero pad columns, `labels` int32 [n] (CE) or uint8 [n, ldy] (BCE), mir[2 top + 3] = the
+    // class bias at Cp (b2 of the 2-layer model, b3 of GCN3, whose mir[3] is b2 at Hp2).
     int32_t wide = 0, loss_kind = 0, Cp = 0;
     int64_t ldy = 0;
     float *whead = nullptr;       // the head's partials (trw_part_bytes) and, behind them, the last epoch's counts [C, 3]
@@ -1053,7 +1101,7 @@ struct lt_buf {
     size_t bytes;
     bool zero;
 };
-#define TR_MAX_BUFS 32
+#define TR_MAX_BUFS 40
 
 // Fills b[TR_MAX_BUFS] from the trainer's own fields (the borrowed graph is not read: destroy may come after the graph's) and
 // returns the number of entries, -1 if the table does not hold them all.
@@ -1078,9 +1126,11 @@ static int trainer_bufs(lt_trainer *t, lt_buf *b) {
     for (int s = 0; s < 6; ++s) add(&t->mir[s], (size_t)t->mir_len[s] * f4);
     add(&t->slabs, lt_gemm_splitk_slab_bytes(t->n, t->H[0], t->F, t->kslice));
     add(&t->tn[0].slabs, t->tn[0].splits > 1 ? (size_t)t->tn[0].splits * t->F * t->H[0] * f4 : 0);
-    add(&t->tn[1].slabs, t->tn[1].splits > 1 ? (size_t)t->tn[1].splits * t->H[0] * (w ? C : t->H[1]) * f4 : 0);
+    add(&t->tn[1].slabs, t->tn[1].splits > 1 ? (size_t)t->tn[1].splits * t->H[0] * (top ? t->H[1] : C) * f4 : 0);
+    add(&t->tn[2].slabs, t->tn[2].splits > 1 ? (size_t)t->tn[2].splits * t->H[1] * C * f4 : 0);
     add(&t->part, w ? 0 : (size_t)t->n_part * ((size_t)t->H[top] + (size_t)t->H[top] * C) * f4);
     add(&t->part1, top || w ? (size_t)t->n_mblk * t->H[0] * f4 : 0);
+    add(&t->part2, top && w ? (size_t)t->n_mblk * t->H[1] * f4 : 0);
     add(&t->whead, w ? trw_part_bytes(t->n, C, true) + 3 * (size_t)C * sizeof(int32_t) : 0);
     add(&t->seg_part, (size_t)t->n_seg * hpm * f4);
     add(&t->grad, np); add(&t->m, np, true); add(&t->v, np, true);
@@ -1143,13 +1193,14 @@ static int trainer_create(const char *who, int layers, const lt_graph *g, const 
     t->kslice = lt_gemm_pick_kslice(n, t->H[0], F);
     tn_plan(&t->tn[0], F, t->H[0], n);
     if (top) tn_plan(&t->tn[1], t->H[0], t->H[1], n);
-    if (wide) tn_plan(&t->tn[1], t->H[0], C, n);      // dW2 = H1d^T dS2
+    if (wide) tn_plan(&t->tn[top + 1], t->H[top], C, n);      // dWc = Hd^T dSc (dW2 of the 2-layer model, dW3 of GCN3)
     t->n_part = (n + TR_ROWS_PER_BLOCK - 1) / TR_ROWS_PER_BLOCK;
     t->n_mblk = (n + TN_BM - 1) / TN_BM;
     t->n_seg = g->p_n_seg > 0 ? g->p_n_seg : 0;
     t->mir_len[1] = t->Hp[0];
-    if (wide) {
-        t->mir_len[3] = t->Cp;      // W2 is read as it lies by the products
+    if (wide) {      // the class weight is read as it lies by the products
+        t->mir_len[2 * top + 1] = t->Hp[top];
+        t->mir_len[2 * top + 3] = t->Cp;
     } else {
         t->mir_len[2 * top + 1] = t->Hp[top];
         t->mir_len[2 * top + 2] = t->Hp[top] * C;
@@ -1235,40 +1286,44 @@ static lt_drop_args drop_off() {
     return off;
 }
 
-// The wide route's forward on graph g from S1 = X W1: Hd = drop_0(relu(A S1 + b1)), Sc = Hd W2 (C of the Cp columns; the
-// others stay zero), Zc = A Sc + b2 at width Cp.
-static int launch_wide_forward(const lt_trainer *t, const lt_graph *g, const float *S1, const lt_drop_args &d, float *Hd,
+// The wide route's forward on graph g from the top chain's product S (X W1; GCN3: Hf W2): Hd = drop(relu(A S + b)) with the
+// mask d, Sc = Hd Wc (C of the Cp columns; the others stay zero), Zc = A Sc + bc at width Cp.  The chain's tensors by the
+// trainer's depth: top = layers - 2 hidden layers lie in front of it.
+static int launch_wide_forward(const lt_trainer *t, const lt_graph *g, const float *S, const lt_drop_args &d, float *Hd,
                                float *Sc, float *Zc, float *seg_part, hipStream_t st) {
-    const int H = t->H[0], Hp = t->Hp[0], C = t->C, Cp = t->Cp;
-    int rc = launch_rows_layer<true>(g, S1, Hp, H, t->mir[1], d, Hd, seg_part, st);
+    const int top = t->layers - 2, H = t->H[top], Hp = t->Hp[top], C = t->C, Cp = t->Cp;
+    int rc = launch_rows_layer<true>(g, S, Hp, H, t->mir[2 * top + 1], d, Hd, seg_part, st);
     if (rc) return rc;
-    rc = lt_launch_gemm(Hd, Hp, t->P[2], C, Sc, Cp, g->n, C, H, st);
+    rc = lt_launch_gemm(Hd, Hp, t->P[2 * top + 2], C, Sc, Cp, g->n, C, H, st);
     if (rc) return rc;
-    return launch_rows_layer<false>(g, Sc, Cp, C, t->mir[3], drop_off(), Zc, seg_part, st);
+    return launch_rows_layer<false>(g, Sc, Cp, C, t->mir[2 * top + 3], drop_off(), Zc, seg_part, st);
 }
 
 static int launch_tn(const float *A, long lda, const float *B, long ldb, float *C, int M, int N, int K, const lt_tn &tn,
                      hipStream_t st);
 
-// The wide route's backward from dZc down to dS (= dS1): every gradient but dW1.
+// The wide route's backward from dZc down to the top chain's dS: the gradients of the class layer and of the hidden layer's
+// bias.  The hidden layer's k_tr3_dz_mfma stage leaves its bias slabs in part1, or, behind a front layer whose own stage
+// uses part1, in part2.
 static int launch_wide_backward(const lt_trainer *t, float scale, hipStream_t st) {
     const lt_graph *g = t->g;
-    const int n = t->n, H = t->H[0], Hp = t->Hp[0], C = t->C, Cp = t->Cp;
+    const int top = t->layers - 2, n = t->n, H = t->H[top], Hp = t->Hp[top], C = t->C, Cp = t->Cp;
+    float *bslabs = top ? t->part2 : t->part1;
     const lt_trw_parts parts = trw_parts(t->whead, n, C, true);
     hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((C + 63) / 64)), dim3(TR_BLOCK), 0, st, parts.db, parts.n_blk, C,
-                       t->grad + t->off[2]);                                                      // db2
+                       t->grad + t->off[2 * top + 2]);                                            // dbc
     LT_CHECK_LAUNCH();
     LT_DISPATCH_LPR(lt_lpr_for(Cp), hipLaunchKernelGGL((k_tr_spmm_t_wide<LPR_>), dim3(rows_grid(n, wide_rows_per_block(Cp))),
                                                        dim3(TR_BLOCK), 0, st, n, g->tptr, g->trow, g->tval, t->dZc, Cp, t->dSc));
     LT_CHECK_LAUNCH();
-    int rc = launch_tn(t->Hd, (long)Hp, t->dSc, (long)Cp, t->grad + t->off[1], H, C, n, t->tn[1], st);      // dW2
+    int rc = launch_tn(t->Hd, (long)Hp, t->dSc, (long)Cp, t->grad + t->off[2 * top + 1], H, C, n, t->tn[top + 1], st);      // dWc
     if (rc) return rc;
     dim3 grid((unsigned)t->n_mblk, (unsigned)((H + TN_BN - 1) / TN_BN));
-    hipLaunchKernelGGL(k_tr3_dz_mfma, grid, dim3(256), 0, st, t->dSc, (long)Cp, t->P[2], (long)C, t->Hd, t->dZ, (long)Hp, n, H, C,
-                       scale, t->part1);
+    hipLaunchKernelGGL(k_tr3_dz_mfma, grid, dim3(256), 0, st, t->dSc, (long)Cp, t->P[2 * top + 2], (long)C, t->Hd, t->dZ, (long)Hp,
+                       n, H, C, scale, bslabs);
     LT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((H + 63) / 64)), dim3(TR_BLOCK), 0, st, t->part1, t->n_mblk, H,
-                       t->grad + t->off[0]);                                                      // db1
+    hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((H + 63) / 64)), dim3(TR_BLOCK), 0, st, bslabs, t->n_mblk, H,
+                       t->grad + t->off[2 * top]);                                                // db of the hidden layer
     LT_CHECK_LAUNCH();
     LT_DISPATCH_LPR(lt_lpr_for(Hp), hipLaunchKernelGGL((k_tr_spmm_t_wide<LPR_>), dim3(rows_grid(n, wide_rows_per_block(Hp))),
                                                        dim3(TR_BLOCK), 0, st, n, g->tptr, g->trow, g->tval, t->dZ, Hp, t->dS));
@@ -1400,7 +1455,10 @@ static int run_epoch(lt_trainer *t, float *record, hipStream_t st) {
     const int64_t step = t->epoch + 1;
     const lt_adam_scalars s = adam_scalars(step, t->lr, 0.9, 0.999, 1e-8, t->wd);
     const dim3 adam_grid((unsigned)((t->off[5] + 255) / 256));
-    if (top || t->wide) {      // (wide: segments W1 | b1 | W2 | b2, the mirrors b1p and b2p; no fifth segment, so no W3p)
+    if (top && t->wide) {
+        const lt_tr3w_tensors T = {snap_segs(t), t->mir[1], t->mir[3], t->mir[5]};
+        hipLaunchKernelGGL(k_tr3w_adam, adam_grid, dim3(256), 0, st, T, t->grad, t->m, t->v, s);
+    } else if (top || t->wide) {      // (wide: segments W1 | b1 | W2 | b2, the mirrors b1p and b2p; no fifth segment, so no W3p)
         const lt_tr3_tensors T = {snap_segs(t), t->mir[1], t->mir[3], t->mir[4]};
         hipLaunchKernelGGL(k_tr3_adam, adam_grid, dim3(256), 0, st, T, t->grad, t->m, t->v, s);
     } else {
@@ -1489,8 +1547,8 @@ static int val_attach(const char *who, lt_trainer *t, const lt_graph *g2, const 
                       const int32_t *labels2, int32_t keep_best, int32_t patience, void *stream, int with_rows = 0,
                       const int32_t *rows = nullptr, int32_t m = 0, int want_wide = 0, int64_t ldy2 = 0) {
     LT_REQUIRE(t != nullptr, "%s: trainer is NULL", who);
-    LT_REQUIRE(t->wide == want_wide, "%s: the trainer has the %s head; attach with lt_gcn2_trainer_attach_validation%s", who,
-               t->wide ? "wide" : "narrow", t->wide ? "_wide" : " or _attach_validation_rows");
+    LT_REQUIRE(t->wide == want_wide, "%s: the trainer has the %s head; attach with lt_gcn%d_trainer_attach_validation%s", who,
+               t->wide ? "wide" : "narrow", t->layers, t->wide ? "_wide" : " or _attach_validation_rows");
     const int F = t->F, C = t->C, top = t->layers - 2;
     const bool bce = t->wide && t->loss_kind == TRW_BCE;
     if (bce) LT_REQUIRE(ldy2 >= C, "%s: ldy2=%lld < C=%d", who, (long long)ldy2, C);
@@ -1599,7 +1657,13 @@ static int val_forward(lt_trainer *t, hipStream_t st) {
     const bool front = t->layers == 3;
     int rc = launch_xw1(t, v->X, v->ldx, v->n, v->kslice, v->slabs, front ? v->fS : v->S, st);
     if (rc) return rc;
-    if (t->wide) return launch_wide_forward(t, v->g, v->S, drop_off(), v->Z, v->Sc, v->Zc, v->seg_part, st);      // v->Z: the hidden layer
+    if (t->wide) {      // v->Z: the top chain's hidden layer
+        if (front) {
+            rc = launch_front(t, v->g, v->fS, drop_off(), v->fH, v->seg_part, v->S, st);
+            if (rc) return rc;
+        }
+        return launch_wide_forward(t, v->g, v->S, drop_off(), v->Z, v->Sc, v->Zc, v->seg_part, st);
+    }
     float *Z = v->Z;
     if (front) {
         lt_drop_args off;
@@ -1647,7 +1711,11 @@ static int trainer_run(const char *who, lt_trainer *t, int32_t n_epochs, float *
     hipStream_t st = (hipStream_t)stream;
     const lt_snap_segs T = snap_segs(t);
     // the borrowed parameters may have changed since the last run: the padded copies from them (Adam keeps them current after that)
-    if (t->wide) {      // b1 at Hp and b2 at Cp: k_tr3_pad's first two copies (its third, over Hp2 * 0 elements, is empty)
+    if (t->wide && t->layers == 3) {
+        const int mh = t->Hp[0] > t->Hp[1] ? t->Hp[0] : t->Hp[1], mx = mh > t->Cp ? mh : t->Cp;
+        hipLaunchKernelGGL(k_tr3w_pad, dim3((mx + 255) / 256), dim3(256), 0, st, t->P[1], t->H[0], t->Hp[0], t->P[3], t->H[1],
+                           t->Hp[1], t->P[5], t->C, t->Cp, t->mir[1], t->mir[3], t->mir[5]);
+    } else if (t->wide) {      // b1 at Hp and b2 at Cp: k_tr3_pad's first two copies (its third, over Hp2 * 0 elements, is empty)
         const int mx = t->Hp[0] > t->Cp ? t->Hp[0] : t->Cp;
         hipLaunchKernelGGL(k_tr3_pad, dim3((mx + 255) / 256), dim3(256), 0, st, t->P[1], t->H[0], t->Hp[0], t->P[3], t->C, t->Cp,
                            nullptr, 0, t->mir[1], t->mir[3], nullptr);
@@ -1822,13 +1890,17 @@ extern "C" int lt_gcn2_trainer_create_wide(const lt_graph *g, const float *X, in
     return rc;
 }
 
-extern "C" int lt_gcn2_trainer_counts(const lt_gcn2_trainer *t, int32_t *counts, void *stream) {
-    LT_REQUIRE(t != nullptr && counts != nullptr, "lt_gcn2_trainer_counts: NULL argument");
-    LT_REQUIRE(t->wide, "lt_gcn2_trainer_counts: the trainer has the narrow head, which keeps no per-class counts");
-    LT_REQUIRE(t->epoch > 0, "lt_gcn2_trainer_counts: no epoch has run");
+static int trainer_counts_out(const char *who, const lt_trainer *t, int32_t *counts, void *stream) {
+    LT_REQUIRE(t != nullptr && counts != nullptr, "%s: NULL argument", who);
+    LT_REQUIRE(t->wide, "%s: the trainer has the narrow head, which keeps no per-class counts", who);
+    LT_REQUIRE(t->epoch > 0, "%s: no epoch has run", who);
     LT_HIP(hipMemcpyAsync(counts, trainer_counts(t), 3 * (size_t)t->C * sizeof(int32_t), hipMemcpyDeviceToDevice,
                           (hipStream_t)stream));
     return LT_OK;
+}
+
+extern "C" int lt_gcn2_trainer_counts(const lt_gcn2_trainer *t, int32_t *counts, void *stream) {
+    return trainer_counts_out("lt_gcn2_trainer_counts", t, counts, stream);
 }
 
 extern "C" int lt_gcn2_trainer_hidden(const lt_gcn2_trainer *t, float *H1d, int64_t ld, void *stream) {
@@ -1889,6 +1961,43 @@ extern "C" int lt_gcn3_trainer_create(const lt_graph *g, const float *X, int64_t
                                   stream, &t);
     *out = static_cast<lt_gcn3_trainer *>(t);
     return rc;
+}
+
+// ---- the 3-layer trainer with the wide head ----
+extern "C" int lt_gcn3_trainer_create_wide(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const void *labels,
+                                           int64_t ldy, int32_t loss_kind, int32_t H1, int32_t H2, int32_t C, float *W1, float *b1,
+                                           float *W2, float *b2, float *W3, float *b3, double lr, double weight_decay,
+                                           double dropout, uint64_t seed, void *stream, lt_gcn3_trainer **out) {
+    LT_REQUIRE(out != nullptr, "lt_gcn3_trainer_create_wide: out is NULL");
+    *out = nullptr;
+    LT_REQUIRE(g != nullptr, "lt_gcn3_trainer_create_wide: graph is NULL");
+    LT_REQUIRE(F > 0 && H1 > 0 && H2 > 0 && C > 0, "lt_gcn3_trainer_create_wide: F=%d H1=%d H2=%d C=%d must be positive", F, H1,
+               H2, C);
+    LT_REQUIRE(H1 <= LT_MAX_H && H2 <= LT_MAX_H, "lt_gcn3_trainer_create_wide: H1=%d H2=%d (supported: H1, H2 <= %d)", H1, H2,
+               LT_MAX_H);
+    LT_REQUIRE(C <= LT_MAX_H, "lt_gcn3_trainer_create_wide: C=%d (supported: C <= %d)", C, LT_MAX_H);
+    LT_REQUIRE(loss_kind == LT_LOSS_CE || loss_kind == LT_LOSS_BCE,
+               "lt_gcn3_trainer_create_wide: loss_kind=%d, must be LT_LOSS_CE (0) or LT_LOSS_BCE (1)", loss_kind);
+    if (loss_kind == LT_LOSS_BCE) LT_REQUIRE(ldy >= C, "lt_gcn3_trainer_create_wide: ldy=%lld < C=%d", (long long)ldy, C);
+    LT_REQUIRE(X && labels && W1 && b1 && W2 && b2 && W3 && b3, "lt_gcn3_trainer_create_wide: NULL tensor pointer");
+    const int32_t Hs[2] = {H1, H2};
+    float *const ps[6] = {W1, b1, W2, b2, W3, b3};
+    lt_trainer *t = nullptr;
+    const int rc = trainer_create("lt_gcn3_trainer_create_wide", 3, g, X, ldx, F, static_cast<const int32_t *>(labels), Hs, C, ps, lr,
+                                  weight_decay, dropout, seed, stream, &t, 1, loss_kind, ldy);
+    *out = static_cast<lt_gcn3_trainer *>(t);
+    return rc;
+}
+
+extern "C" int lt_gcn3_trainer_counts(const lt_gcn3_trainer *t, int32_t *counts, void *stream) {
+    return trainer_counts_out("lt_gcn3_trainer_counts", t, counts, stream);
+}
+
+extern "C" int lt_gcn3_trainer_attach_validation_wide(lt_gcn3_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2,
+                                                      int32_t n2, const void *labels2, int64_t ldy2, int32_t keep_best,
+                                                      int32_t patience, const int32_t *rows, int32_t m, void *stream) {
+    return val_attach("lt_gcn3_trainer_attach_validation_wide", t, g2, X2, ldx2, n2, static_cast<const int32_t *>(labels2),
+                      keep_best, patience, stream, rows != nullptr, rows, m, 1, ldy2);
 }
 
 extern "C" int lt_gcn3_trainer_destroy(lt_gcn3_trainer *t) {

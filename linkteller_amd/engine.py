@@ -647,7 +647,7 @@ class _ValidationMixin:
 
     _PREFIX = ""
     _val = None
-    _WIDE = False     # GCN2Trainer(head="wide"): val_counts are [C, 3] = (tp, fp, fn) per class instead of the C x C confusion
+    _WIDE = False     # GCN2Trainer / GCN3Trainer(head="wide"): val_counts are [C, 3] = (tp, fp, fn) per class instead of the C x C confusion
 
     def _count_cols(self):
         return 3 if self._WIDE else self.c
@@ -914,10 +914,22 @@ class _GCNTrainer(_ValidationMixin):
     accessors, which reach the C entry points through ``_PREFIX``.  The parameters are updated IN PLACE (their version counters
     are bumped after every ``run``); the trainer owns the Adam moments.  Dropout is a Philox4x32-10 mask keyed by ``seed``, the
     epoch counter and the hidden layer (include/linkteller_hip.h), so it can be rebuilt exactly; it is not torch's generator.
-    Limits: hidden widths <= 256, classes <= 8."""
+    Limits: hidden widths <= 256, classes <= 8 (``head="wide"``: <= 256)."""
 
     _NAMES = ()       # the parameter tensors in model order; each becomes the attribute of its lower-case name
     _MODEL = ""       # the model's name in the shape error
+    _LOSSES = {"ce": 0, "bce": 1}      # LT_LOSS_CE, LT_LOSS_BCE
+    head, loss = "narrow", "ce"
+
+    def _set_head(self, head, loss):
+        """The ``head`` / ``loss`` arguments of both trainers, checked before anything touches the device."""
+        if head not in ("narrow", "wide"):
+            raise ValueError(f"head must be 'narrow' or 'wide', got {head!r}")
+        if loss not in self._LOSSES:
+            raise ValueError(f"loss must be 'ce' or 'bce', got {loss!r}")
+        if head == "narrow" and loss != "ce":
+            raise ValueError("the narrow head has the cross-entropy loss only: pass head='wide' for loss='bce'")
+        self._WIDE, self.head, self.loss = head == "wide", head, loss
 
     def __init__(self, adj, x, labels, params, *, lr, weight_decay, dropout, seed):
         if not 0.0 <= float(dropout) <= 1.0:      # F.dropout's message
@@ -949,9 +961,18 @@ class _GCNTrainer(_ValidationMixin):
         self._finalizer = weakref.finalize(self, getattr(_lib.lib(), f"{self._PREFIX}_destroy"), h)
 
     def _prepare_labels(self, labels, n, name):
-        """One class id per node as the int32 device tensor the library borrows."""
+        """One class id per node as the int32 device tensor the library borrows; for the wide head with ``loss="bce"`` the
+        [n, C] matrix of 0 / 1 as uint8."""
         if not isinstance(labels, torch.Tensor):
             labels = torch.as_tensor(labels)
+        if self._WIDE and self.loss == "bce":
+            if labels.dim() != 2 or tuple(labels.shape) != (n, self.c):
+                raise ValueError(f"{name} must be [{n}, {self.c}] for loss='bce', got {tuple(labels.shape)}")
+            if labels.is_floating_point() or labels.is_complex():
+                raise ValueError(f"{name} must have an integer or bool dtype, got {labels.dtype}")
+            if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) > 1):
+                raise ValueError(f"{name} must hold 0 / 1")
+            return labels.to(device=self.x.device, dtype=torch.uint8).contiguous()
         labels = labels.reshape(-1)
         if labels.numel() != n:
             raise ValueError(f"{name}: {labels.numel()} entries for {n} nodes")
@@ -961,7 +982,17 @@ class _GCNTrainer(_ValidationMixin):
 
     def _create_call(self):
         """The create entry point's name and its arguments between ``F`` and the widths."""
+        if self._WIDE:
+            return f"{self._PREFIX}_create_wide", (self.labels.data_ptr(), self.c, self._LOSSES[self.loss])
         return f"{self._PREFIX}_create", (self.labels.data_ptr(),)
+
+    def counts(self) -> torch.Tensor:
+        """The last epoch's int32 [C, 3] = (tp, fp, fn) per class on the training rows (wide head only)."""
+        if not self._WIDE:
+            raise ValueError("counts() needs head='wide'")
+        out = torch.empty((self.c, 3), dtype=torch.int32, device=self.x.device)
+        self._call("counts", out.data_ptr(), _stream())
+        return out
 
     @property
     def epoch(self) -> int:
@@ -1003,7 +1034,6 @@ class GCN2Trainer(_GCNTrainer):
     ``run_validated`` (_ValidationMixin)."""
 
     _PREFIX, _NAMES, _MODEL = "lt_gcn2_trainer", ("W1", "b1", "W2", "b2"), "GCN"
-    _LOSSES = {"ce": 0, "bce": 1}      # LT_LOSS_CE, LT_LOSS_BCE
 
     def __init__(self, adj, x, labels, w1, b1, w2, b2, *, lr, weight_decay, dropout, seed, head="narrow", loss="ce"):
         """``head="wide"`` (lt_gcn2_trainer_create_wide): up to 256 classes, the class layer as matrix products and the wide loss
@@ -1011,41 +1041,9 @@ class GCN2Trainer(_GCNTrainer):
         integer or bool dtype (mean binary cross-entropy with logits over all n C elements; kept as uint8 on the device).
         ``run`` then returns (loss, sum over the classes of tp): the correct count for ce.  ``head="narrow"`` (default) is the
         fused class layer for at most 8 classes with cross-entropy."""
-        if head not in ("narrow", "wide"):
-            raise ValueError(f"head must be 'narrow' or 'wide', got {head!r}")
-        if loss not in self._LOSSES:
-            raise ValueError(f"loss must be 'ce' or 'bce', got {loss!r}")
-        if head == "narrow" and loss != "ce":
-            raise ValueError("the narrow head has the cross-entropy loss only: pass head='wide' for loss='bce'")
-        self._WIDE, self.head, self.loss = head == "wide", head, loss
+        self._set_head(head, loss)
         super().__init__(adj, x, labels, (w1, b1, w2, b2), lr=lr, weight_decay=weight_decay, dropout=dropout, seed=seed)
         self.h = self.w1.shape[1]
-
-    def _prepare_labels(self, labels, n, name):
-        if not (self._WIDE and self.loss == "bce"):
-            return super()._prepare_labels(labels, n, name)
-        if not isinstance(labels, torch.Tensor):
-            labels = torch.as_tensor(labels)
-        if labels.dim() != 2 or tuple(labels.shape) != (n, self.c):
-            raise ValueError(f"{name} must be [{n}, {self.c}] for loss='bce', got {tuple(labels.shape)}")
-        if labels.is_floating_point() or labels.is_complex():
-            raise ValueError(f"{name} must have an integer or bool dtype, got {labels.dtype}")
-        if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) > 1):
-            raise ValueError(f"{name} must hold 0 / 1")
-        return labels.to(device=self.x.device, dtype=torch.uint8).contiguous()
-
-    def _create_call(self):
-        if not self._WIDE:
-            return super()._create_call()
-        return "lt_gcn2_trainer_create_wide", (self.labels.data_ptr(), self.c, self._LOSSES[self.loss])
-
-    def counts(self) -> torch.Tensor:
-        """The last epoch's int32 [C, 3] = (tp, fp, fn) per class on the training rows (wide head only)."""
-        if not self._WIDE:
-            raise ValueError("counts() needs head='wide'")
-        out = torch.empty((self.c, 3), dtype=torch.int32, device=self.x.device)
-        self._call("counts", out.data_ptr(), _stream())
-        return out
 
     def hidden(self) -> torch.Tensor:
         """The last epoch's hidden activations after ReLU and dropout, H1d [n, H]."""
@@ -1062,7 +1060,11 @@ class GCN3Trainer(_GCNTrainer):
 
     _PREFIX, _NAMES, _MODEL = "lt_gcn3_trainer", ("W1", "b1", "W2", "b2", "W3", "b3"), "GCN3"
 
-    def __init__(self, adj, x, labels, w1, b1, w2, b2, w3, b3, *, lr, weight_decay, dropout, seed):
+    def __init__(self, adj, x, labels, w1, b1, w2, b2, w3, b3, *, lr, weight_decay, dropout, seed, head="narrow", loss="ce"):
+        """``head`` and ``loss`` as for ``GCN2Trainer``: ``head="wide"`` (lt_gcn3_trainer_create_wide) puts the wide class layer
+        and loss head, up to 256 classes with ``loss="ce"`` or ``"bce"``, behind the two hidden layers; both heads draw the
+        same two dropout masks from one seed.  ``counts()`` and the [C, 3] ``val_counts`` follow."""
+        self._set_head(head, loss)
         super().__init__(adj, x, labels, (w1, b1, w2, b2, w3, b3), lr=lr, weight_decay=weight_decay, dropout=dropout, seed=seed)
         self.h1, self.h2 = self.w1.shape[1], self.w2.shape[1]
 

@@ -256,8 +256,8 @@ def check_split_dataset(args):
 
 def check_train_head(args):
     """``--train-head wide`` selects the wide class layer of ``--train``: it is refused here, before a Worker is built or the GPU
-    is touched, without a training run and with ``--n-layer 3`` (a wide head on GCN3 needs a second stage of the hidden
-    layer's backward product, which does not exist)."""
+    is touched, without a training run and with ``--n-layer 3`` (``main`` trains the 2-layer GCN only; GCN3, with either head,
+    is trained through the in-process ``GCNTrainer`` sequence of README)."""
     if getattr(args, "train_head", "narrow") != "wide":
         return
     if not args.train or args.test:

@@ -52,9 +52,7 @@ class GCNTrainer:
             # the optimizer state of gcn_trainer.py:106-108: Adam's moments live in the GPU trainer, which updates the
             # model's parameters in place
             from .engine import GCN2Trainer, GCN3Trainer
-            wide = getattr(a, "train_head", "narrow") == "wide"
-            if wide and a.n_layer != 2:
-                raise NotImplementedError(f"--train-head wide is implemented for the 2-layer GCN only (got --n-layer {a.n_layer})")
+            wide = getattr(a, "train_head", "narrow") == "wide"      # either model: GCN3Trainer takes the wide head too
             if w.transfer:
                 train_on = (w.adj_1, w.features_1, w.labels_1)
             else:                                              # gcn_trainer.py:131, 154: the induced training subgraph
