@@ -541,7 +541,7 @@ int lt_wide_combine(const float *const *vecs, int32_t n_vec, int64_t n_pairs, in
                     float *ss, int32_t first, int32_t last, void *stream);
 
 /* ---- the same for the 3-layer model (GCN3, gcn/models.py:28-46; --n-layer 3, gcn_trainer.py:81-86) -------------
- *   logits = A (relu(A (relu(A (X W1) + b1) W2) + b2) W3) + b3,   H1, H2 <= 256, C <= 8.
+ *   logits = A (relu(A (relu(A (X W1) + b1) W2) + b2) W3) + b3,   H1, H2 <= 256, C <= 8 (C <= 256: lt_baseline3_create_wide).
  * lt_baseline3_create owns the unperturbed forward (S1, H1, S2, Z2, S3, OUT) and borrows X and the six parameter tensors;
  * lt_baseline3_refresh marks everything stale and launches nothing: the next reader recomputes what IT reads on its own stream
  * (a LT_MODE_DELTA build the fp64 pre-activations only, the fp32 modes and lt_baseline3_logits the fp32 forward).  lt_influence3_rows evaluates the
@@ -555,6 +555,23 @@ int lt_baseline3_create(const lt_graph *g, const float *X, int64_t ldx, int32_t 
                         const float *W2, const float *b2, int32_t H2,
                         const float *W3, const float *b3, int32_t C,
                         void *stream, lt_baseline3 **out);
+/* The same handle for a WIDE class layer (reddit's 41 classes, ppi's 121 labels: what lt_gcn3_trainer_create_wide trains):
+ * H1, H2 <= 256 and 1 <= C <= 256; same arguments, same handle type, LT_ERR_UNSUPPORTED beyond.  refresh, features_changed,
+ * enable_fp64 and destroy work as on a narrow handle (the fp64 pre-activations do not depend on C); lt_baseline3_logits forms
+ * the last layer by the unfused product and SpMM (lt_gemm_f32 / lt_spmm_csr_f32's kernels: fp32 rounding only).
+ * MODE RULE of a wide handle: lt_influence3_rows_mode serves LT_MODE_DELTA alone -- levels 1 and 2 of the narrow chain, then
+ * dS3x = dH2x W3 as one MFMA product over the level-2 items (their count stays on the device) and the observed rows with a
+ * lane group across the class columns.  LT_MODE_SPARSE / LT_MODE_FULL and lt_influence3_rows return LT_ERR_UNSUPPORTED and
+ * enqueue nothing: the fp32 finite difference of these shapes is the caller's loop over lt_gemm_f32 / lt_spmm_csr_f32.  A cell
+ * depends on (probe, observed, model, graph) alone, not on the chunking or the other nodes of the call; no floating-point
+ * atomics.  Everything else as for a narrow handle: enqueue only, ids checked on the device (lt_node_check), probes chunked
+ * by "chunk_budget_bytes" -- the level-2 tables are sized by n rows per probe, so a large graph gets small chunks.
+ * C <= 8 is allowed here and takes the wide kernels all the same. */
+int lt_baseline3_create_wide(const lt_graph *g, const float *X, int64_t ldx, int32_t F,
+                             const float *W1, const float *b1, int32_t H1,
+                             const float *W2, const float *b2, int32_t H2,
+                             const float *W3, const float *b3, int32_t C,
+                             void *stream, lt_baseline3 **out);
 int lt_baseline3_refresh(lt_baseline3 *b, void *stream);
 /* lt_baseline_features_changed for the inner 2-layer baseline, and everything lt_baseline3_refresh marks stale. */
 int lt_baseline3_features_changed(lt_baseline3 *b, void *stream);

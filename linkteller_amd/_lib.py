@@ -94,6 +94,9 @@ SIGNATURES = {
     "lt_baseline3_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                       C.POINTER(C.c_void_p)]),
+    "lt_baseline3_create_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.POINTER(C.c_void_p)]),
     "lt_baseline3_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lt_baseline3_features_changed": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lt_baseline3_destroy": (C.c_int, [C.c_void_p]),

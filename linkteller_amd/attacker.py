@@ -178,7 +178,8 @@ class Attacker:
 
     def _walk(self):
         """ONE ``state_dict()`` walk per attack (it costs ~10 us per call on a 2-layer module; the round-4 path made three):
-        (kind, state_dict) with kind 'gcn2' | 'gcn3' (within what lt_baseline3 serves) | 'generic'."""
+        (kind, state_dict) with kind 'gcn2' | 'gcn3' | 'gcn3w' (within what lt_baseline3 serves: up to 8 classes, 9 .. 256
+        classes) | 'generic'."""
         # (and that one walk is skipped while the model's parameters are the very objects -- and storages -- of the last walk: four
         # attribute reads instead of ~10 us of state_dict(); a load_state_dict() copies in place and is seen by the baseline's
         # refresh, a replaced parameter / a moved module changes the identity or the data pointer and walks again)
@@ -205,8 +206,9 @@ class Attacker:
         if len(keys) == 4 and all(k in sd for k in self._TWO):
             kind = "gcn2"
         elif (len(keys) == 6 and all(k in sd for k in self._THREE) and sd["gc1.weight"].shape[1] <= 256
-                and sd["gc2.weight"].shape[1] <= 256 and sd["gc3.weight"].shape[1] <= 8):
-            kind = "gcn3"          # GCN3 (gcn/models.py:28-46): hidden widths <= 256, <= 8 classes
+                and sd["gc2.weight"].shape[1] <= 256 and sd["gc3.weight"].shape[1] <= 256):
+            # GCN3 (gcn/models.py:28-46): hidden widths <= 256; <= 8 classes, or the wide class layer (reddit 41, ppi 121)
+            kind = "gcn3" if sd["gc3.weight"].shape[1] <= 8 else "gcn3w"
         else:
             kind = "generic"
         self._walk_cache = None
@@ -251,8 +253,8 @@ class Attacker:
         return out
 
     def _rows_generic(self, probe_nodes, observe_nodes, sd=None):
-        """Probe rows for GraphConvolution stacks neither probe primitive covers (more than 3 layers, or a GCN3
-        wider than 256 hidden units / 8 classes): per probe, row v of S1 = X W1 is replaced by (x_v + x_v*d) W1 and
+        """Probe rows for GraphConvolution stacks neither probe primitive covers (more than 3 layers, a GCN3 wider than
+        256 hidden units or classes, and `sparse` / `full` of a GCN3 with 9 .. 256 classes): per probe, row v of S1 = X W1 is replaced by (x_v + x_v*d) W1 and
         the remaining layers run through lt_spmm_csr_f32 / lt_gemm_f32.  Same quantity, ~2 launches per layer per
         probe; kept as the reference implementation the 3-layer primitive is tested against."""
         layers = self._layers(sd)
@@ -321,6 +323,9 @@ class Attacker:
             # the 3-hop probe primitive: `delta` (default) propagates the perturbation exactly through the three layers,
             # `sparse` / `full` are the reference's fp32 finite difference on the rows a probe can reach
             return self.baseline3(sd).influence_rows(probe_nodes, observe_nodes, float(self.args.influence), self._mode(mode))
+        if kind == "gcn3w" and self._mode(mode) == "delta":
+            # 9 .. 256 classes: `delta` through the wide handle (lt_baseline3_create_wide); `sparse` / `full` stay the loop below
+            return self.baseline3(sd).influence_rows(probe_nodes, observe_nodes, float(self.args.influence), "delta")
         return self._rows_generic(probe_nodes, observe_nodes, sd)
 
     def _device_nodes(self, nodes, b, e):

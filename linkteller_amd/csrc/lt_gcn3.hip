@@ -16,6 +16,10 @@
 // non-zero: every recomputed row goes through the SAME device functions as the baseline forward below (row_dot chains
 // started from the bias, relu_w2_partial + group_sum, row2_dot), so rows a probe cannot reach difference to exactly 0
 // and rows it can reach carry only the perturbation and fp32 rounding -- the reference's noise class.
+//
+// A WIDE class layer (lt_baseline3_create_wide: 9 .. 256 classes, reddit / ppi) is served in LT_MODE_DELTA alone: the class width
+// enters behind the layer-2 kink test, so the chain is the narrow one up to dH2 and the last two steps have wide forms (k3w_* /
+// k3dw_* below).  Its level-2 tables are sized by n rows per probe, as S3x is: large graphs get small probe chunks.
 #include <new>
 
 #include "lt_items.hip.h"
@@ -49,6 +53,11 @@ struct lt_baseline3 {
     // lt_baseline3_refresh launches nothing (round 6, as lt_baseline_refresh since ABI 2): the padded parameters and the fp32 forward
     // are recomputed on the stream of the first call that reads them -- a LT_MODE_DELTA build reads no fp32 layer at all
     bool pad_fresh = false, fp32_fresh = false;
+    // lt_baseline3_create_wide (C <= 256; LT_MODE_DELTA only): the class rows S3 / OUT have the stride Cp = C rounded up to 4 and
+    // the last layer of the fp32 forward goes through the unfused product / SpMM
+    bool wide = false;
+    int32_t Cp = 0;
+    float *b3p = nullptr;       // b3 zero-padded to Cp (an aligned bias for the SpMM's 16-byte path)
 };
 
 // h[dst] = relu(A[r,:] S + bias): all rows (items == NULL), or the level-1 items of a probe chunk, whose row reads
@@ -410,6 +419,190 @@ __global__ __launch_bounds__(LT_BLOCK) void k3d_stageC(
     if (q == 0) out[(long)b * ldo + j] = sqrtf(ss);
 }
 
+// ---- LT_MODE_DELTA with a wide class layer (lt_baseline3_create_wide, C <= 256) ------------------------------------------------------
+// The class width only enters behind the layer-2 kink test, so levels 1 and 2 are the chain above; the last two steps change:
+// k3d_stageB's  . W3  in registers (CP <= 8 columns per lane) becomes one MFMA product over the level-2 items, dS3x = dH2x W3
+// (row count on the device, as level 1), and k3d_stageC's 8 lanes x CP columns become a lane group ACROSS the class columns.
+// For the product the level-2 items need a place each, known to the readers: k3w_rank2 turns a probe's marks (k3_mark2) into
+// a bitmap row with positions, (mask, members of the probe below this word) -- what bits1 is for level 1 --, k3w_list2 adds
+// the probes' offsets (off2[b] = members of the probes before b; off2[nb] = the chunk's count, which stays on the device) and
+// lists the items: item (b, r2) sits at off2[b] + bits_pos(row_b, r2), a probe's items ascending in r2, the probes in order.
+// Nothing here depends on which thread came first: a cell's value is a function of (probe, observed, model, graph) alone.
+__global__ __launch_bounds__(LT_BLOCK) void k3w_rank2(int words, const uint32_t *__restrict__ bits2, uint2 *__restrict__ rank2,
+                                                      int32_t *__restrict__ cnt2) {
+    __shared__ int s_wave[LT_BLOCK / 64];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const uint32_t *row = bits2 + (size_t)b * words;
+    int run = 0;                                             // members in the words before this stretch (the same in every thread)
+    for (int w0 = 0; w0 < words; w0 += LT_BLOCK) {          // (block-uniform)
+        const int w = w0 + threadIdx.x;
+        const uint32_t m = w < words ? row[w] : 0u;
+        const int cnt = __popc(m);
+        int incl = cnt;                                      // inclusive prefix over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += t;
+        }
+        if (lane == 63) s_wave[wid] = incl;
+        __syncthreads();
+        int before = 0, all = 0;
+#pragma unroll
+        for (int k = 0; k < LT_BLOCK / 64; ++k) {
+            before += k < wid ? s_wave[k] : 0;
+            all += s_wave[k];
+        }
+        if (w < words) rank2[(size_t)b * words + w] = make_uint2(m, (unsigned)(run + before + incl - cnt));
+        run += all;
+        __syncthreads();                                     // (s_wave is rewritten by the next stretch)
+    }
+    if (threadIdx.x == 0) cnt2[b] = run;
+}
+// one block per probe: its offset (every block sums the counts in front of it, as k_item_bits does for level 1), its items
+__global__ __launch_bounds__(LT_BLOCK) void k3w_list2(int nb, int words, const uint2 *__restrict__ rank2,
+                                                      const int32_t *__restrict__ cnt2, int32_t *__restrict__ off2,
+                                                      int2 *__restrict__ items2) {
+    __shared__ int32_t red[LT_BLOCK / 64];
+    const int b = blockIdx.x;
+    int part = 0;
+    for (int i = threadIdx.x; i < b; i += LT_BLOCK) part += cnt2[i];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
+    __syncthreads();
+    int my_off = 0;
+#pragma unroll
+    for (int k = 0; k < LT_BLOCK / 64; ++k) my_off += red[k];
+    if (threadIdx.x == 0) {
+        off2[b] = my_off;
+        if (b == nb - 1) off2[nb] = my_off + cnt2[b];
+    }
+    for (int w = threadIdx.x; w < words; w += LT_BLOCK) {
+        const uint2 e = rank2[(size_t)b * words + w];
+        uint32_t m = e.x;
+        int pos = my_off + (int)e.y;
+        while (m) {
+            const int bit = __ffs((int)m) - 1;
+            m &= m - 1u;
+            items2[pos++] = make_int2(b, w * 32 + bit);
+        }
+    }
+}
+
+// level-2 items: k3d_stageB up to the kink test -- the same entry-order chain over the members of R1 in row q, the same
+// relu_diff on the fp64 pre-activation -- and the row dH2x[item, 0 .. Hp2) stored instead of multiplied by W3
+template <int LPR>
+__global__ __launch_bounds__(LT_BLOCK) void k3dw_stageB(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+    const double *__restrict__ Z2d, int Hp2, const int32_t *__restrict__ off, const float *__restrict__ dS2x,
+    const uint2 *__restrict__ bits1, int words, const int2 *__restrict__ items2, const int32_t *__restrict__ n_items2,
+    float *__restrict__ dH2x) {
+    constexpr int RPW = 64 / LPR;
+    const int lane = threadIdx.x & 63;
+    const int gl = lane & (LPR - 1);
+    const int coff = 4 * gl;
+    const bool active = coff < Hp2;
+    const int total = *n_items2;
+    const int wave0 = (blockIdx.x * LT_BLOCK + threadIdx.x) >> 6;
+    const int nwaves = gridDim.x * (LT_BLOCK / 64);
+    for (int base = wave0 * RPW; base < total; base += nwaves * RPW) {
+        const int it = base + lane / LPR;
+        if (it >= total) continue;      // (group-uniform: the shuffles below stay inside the group)
+        const int2 w = items2[it];
+        const int b = w.x, q = w.y;
+        const uint2 *mb = bits1 + (size_t)b * words;
+        const float *items = dS2x + (size_t)off[b] * Hp2;
+        f32x4 dz = {0.f, 0.f, 0.f, 0.f};
+        double zq[4] = {0.0, 0.0, 0.0, 0.0};
+        if (active) {
+            const double2 z01 = *reinterpret_cast<const double2 *>(Z2d + (size_t)q * Hp2 + coff);
+            const double2 z23 = *reinterpret_cast<const double2 *>(Z2d + (size_t)q * Hp2 + coff + 2);
+            zq[0] = z01.x; zq[1] = z01.y; zq[2] = z23.x; zq[3] = z23.y;
+        }
+        const int e_end = rowptr[q + 1], gbase = lane & ~(LPR - 1);
+        for (int e0 = rowptr[q]; e0 < e_end; e0 += LPR) {            // (group-uniform)
+            const int e = e0 + gl;
+            int p = -1;
+            float a = 0.f;
+            if (e < e_end) {
+                p = bits_pos(mb, col[e]);
+                a = val[e];
+            }
+            unsigned long long hits = __ballot(p >= 0) >> gbase;
+            if (LPR < 64) hits &= (1ull << LPR) - 1ull;
+            while (hits) {                                           // members of R1 only, in entry order (group-uniform)
+                const int k = __ffsll((long long)hits) - 1;
+                hits &= hits - 1ull;
+                const int pk = __shfl(p, gbase + k, 64);
+                const float ak = __shfl(a, gbase + k, 64);
+                if (active) dz = fma4(ak, ld4(items + (size_t)pk * Hp2 + coff), dz);
+            }
+        }
+        if (active) {
+            f32x4 dh;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dh[k] = relu_diff(zq[k], dz[k]);
+            *reinterpret_cast<f32x4 *>(dH2x + (size_t)it * Hp2 + coff) = dh;
+        }
+    }
+}
+
+// observed rows: one lane group per (probe, observed) cell, a lane per 4 class columns.  The entries of row u are walked in
+// entry order (the group looks LPR of them up side by side, as stage B does), the members of R2 add fma(a, dS3x[pos][c], acc);
+// then d = acc / delta, the lane's squares in column order, the lanes by the fixed butterfly, sqrt.  A cell no path reaches
+// sums nothing: 0 / delta, fma, sqrt = +0.  (Columns C .. Cp of dS3x are never written: what they hold is carried along and
+// left out of the squares.)
+template <int LPR>
+__global__ __launch_bounds__(LT_BLOCK) void k3dw_stageC(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int C, int Cp, int nb,
+    const float *__restrict__ dS3x, const uint2 *__restrict__ rank2, int words, const int32_t *__restrict__ off2,
+    const int32_t *__restrict__ observe, int n_obs, float delta, float *__restrict__ out, long ldo) {
+    const int lane = threadIdx.x & 63;
+    const int gl = lane & (LPR - 1), gbase = lane & ~(LPR - 1);
+    const int coff = 4 * gl;
+    const bool active = coff < Cp;
+    const long cell = ((long)blockIdx.x * LT_BLOCK + threadIdx.x) / LPR;
+    if (cell >= (long)nb * n_obs) return;                           // (group-uniform)
+    const int b = (int)(cell / n_obs), j = (int)(cell % n_obs);
+    const int u = observe[j];
+    const uint2 *mb = rank2 + (size_t)b * words;
+    const float *mine = dS3x + (size_t)off2[b] * Cp;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const int e_end = rowptr[u + 1];
+    for (int e0 = rowptr[u]; e0 < e_end; e0 += LPR) {               // (group-uniform)
+        const int e = e0 + gl;
+        int p = -1;
+        float a = 0.f;
+        if (e < e_end) {
+            p = bits_pos(mb, col[e]);
+            a = val[e];
+        }
+        unsigned long long hits = __ballot(p >= 0) >> gbase;
+        if (LPR < 64) hits &= (1ull << LPR) - 1ull;
+        while (hits) {                                              // members of R2 only, in entry order (group-uniform)
+            const int k = __ffsll((long long)hits) - 1;
+            hits &= hits - 1ull;
+            const int pk = __shfl(p, gbase + k, 64);
+            const float ak = __shfl(a, gbase + k, 64);
+            if (active) acc = fma4(ak, ld4(mine + (size_t)pk * Cp + coff), acc);
+        }
+    }
+    float ss = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (active && coff + k < C) {
+            const float d = acc[k] / delta;
+            ss = fmaf(d, d, ss);
+        }
+    ss = group_sum<LPR>(ss);
+    if (gl == 0) out[(long)b * ldo + j] = sqrtf(ss);
+}
+
+__global__ void k3w_pad_b3(const float *__restrict__ b3, int C, int Cp, float *__restrict__ b3p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < Cp) b3p[i] = i < C ? b3[i] : 0.f;
+}
+
 __global__ void k3_pad(const float *__restrict__ b1, int H1, int Hp1, const float *__restrict__ b2, int H2, int Hp2,
                        const float *__restrict__ W3, int C, float *__restrict__ b1p, float *__restrict__ b2p,
                        float *__restrict__ W3p) {
@@ -424,7 +617,7 @@ static void free_baseline3(lt_baseline3 *b) {
     if (!b) return;
     (void)hipFree(b->S1); (void)hipFree(b->Act1); (void)hipFree(b->S2); (void)hipFree(b->Z2); (void)hipFree(b->S3);
     (void)hipFree(b->OUT); (void)hipFree(b->b1p); (void)hipFree(b->b2p); (void)hipFree(b->W3p); (void)hipFree(b->slabs);
-    (void)hipFree(b->seg_part);
+    (void)hipFree(b->seg_part); (void)hipFree(b->b3p);
     (void)hipFree(b->S2d); (void)hipFree(b->Z2d); (void)hipFree(b->seg2d);
     if (b->l1) (void)lt_baseline_destroy(b->l1);
     delete b;
@@ -453,6 +646,10 @@ static int ensure3_pad(const lt_baseline3 *cb, hipStream_t st) {
     hipLaunchKernelGGL(k3_pad, dim3((mx + 255) / 256), dim3(256), 0, st, b->b1, b->H1, b->Hp1, b->b2, b->H2, b->Hp2, b->W3,
                        b->C, b->b1p, b->b2p, b->W3p);
     LT_CHECK_LAUNCH();
+    if (b->wide) {
+        hipLaunchKernelGGL(k3w_pad_b3, dim3((b->Cp + 255) / 256), dim3(256), 0, st, b->b3, b->C, b->Cp, b->b3p);
+        LT_CHECK_LAUNCH();
+    }
     b->pad_fresh = true;
     return LT_OK;
 }
@@ -482,6 +679,18 @@ static int ensure3_fp32(const lt_baseline3 *cb, hipStream_t st) {
     if (b->Hp2 != b->H2) LT_HIP(hipMemsetAsync(b->S2, 0, (size_t)n * b->Hp2 * sizeof(float), st));
     rc = lt_launch_gemm(b->Act1, b->Hp1, b->W2, b->H2, b->S2, b->Hp2, n, b->H2, b->H1, st);
     if (rc) return rc;
+    if (b->wide) {
+        // the class layer unfused: H2 = relu(A S2 + b2) (into Z2), S3 = H2 W3, OUT = A S3 + b3 -- the SpMM's wide row kernels,
+        // the MFMA product; rows of stride Cp
+        rc = lt_spmm_csr_f32(g, b->S2, b->Hp2, b->Hp2, b->b2p, 1, b->Z2, b->Hp2, st);
+        if (rc) return rc;
+        rc = lt_launch_gemm(b->Z2, b->Hp2, b->W3, b->C, b->S3, b->Cp, n, b->C, b->H2, st);
+        if (rc) return rc;
+        rc = lt_spmm_csr_f32(g, b->S3, b->Cp, b->C, b->b3p, 0, b->OUT, b->Cp, st);
+        if (rc) return rc;
+        b->fp32_fresh = true;
+        return LT_OK;
+    }
     // S3 = relu(A S2 + b2) W3, OUT = A S3 + b3: the fused layer kernels of the 2-layer path
     rc = lt_launch_layer1(g, b->S2, b->Hp2, b->b2p, b->W3p, b->C, b->Z2, b->S3, st, b->seg_part);
     if (rc) return rc;
@@ -491,23 +700,27 @@ static int ensure3_fp32(const lt_baseline3 *cb, hipStream_t st) {
     return LT_OK;
 }
 
-extern "C" int lt_baseline3_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const float *W1,
-                                   const float *b1, int32_t H1, const float *W2, const float *b2, int32_t H2,
-                                   const float *W3, const float *b3, int32_t C, void *stream, lt_baseline3 **out) {
-    LT_REQUIRE(out != nullptr, "lt_baseline3_create: out is NULL");
+#define LT3_WIDE_MAX_C 256     // classes of a wide handle: one lane group of k3dw_stageC (64 lanes x 4 columns)
+// `fn` = the entry point's name in the messages; max_c = LT_MAX_C (the fused class layer) or LT3_WIDE_MAX_C (a wide handle)
+static int baseline3_create(const char *fn, bool wide, const lt_graph *g, const float *X, int64_t ldx, int32_t F, const float *W1,
+                            const float *b1, int32_t H1, const float *W2, const float *b2, int32_t H2, const float *W3,
+                            const float *b3, int32_t C, void *stream, lt_baseline3 **out) {
+    const int max_c = wide ? LT3_WIDE_MAX_C : LT_MAX_C;
+    LT_REQUIRE(out != nullptr, "%s: out is NULL", fn);
     *out = nullptr;
-    LT_REQUIRE(g != nullptr, "lt_baseline3_create: graph is NULL");
-    LT_REQUIRE(F > 0 && H1 > 0 && H2 > 0 && C > 0, "lt_baseline3_create: F=%d H1=%d H2=%d C=%d must be positive", F, H1, H2, C);
-    if (H1 > LT_MAX_H || H2 > LT_MAX_H || C > LT_MAX_C)
-        return lt_set_error(LT_ERR_UNSUPPORTED, "lt_baseline3_create: H1=%d H2=%d C=%d (supported: H <= %d, C <= %d)", H1, H2, C,
-                            LT_MAX_H, LT_MAX_C);
-    LT_REQUIRE(X && W1 && b1 && W2 && b2 && W3 && b3, "lt_baseline3_create: NULL tensor pointer");
-    LT_REQUIRE(ldx >= F, "lt_baseline3_create: ldx=%lld < F=%d", (long long)ldx, F);
+    LT_REQUIRE(g != nullptr, "%s: graph is NULL", fn);
+    LT_REQUIRE(F > 0 && H1 > 0 && H2 > 0 && C > 0, "%s: F=%d H1=%d H2=%d C=%d must be positive", fn, F, H1, H2, C);
+    if (H1 > LT_MAX_H || H2 > LT_MAX_H || C > max_c)
+        return lt_set_error(LT_ERR_UNSUPPORTED, "%s: H1=%d H2=%d C=%d (supported: H <= %d, C <= %d)", fn, H1, H2, C, LT_MAX_H, max_c);
+    LT_REQUIRE(X && W1 && b1 && W2 && b2 && W3 && b3, "%s: NULL tensor pointer", fn);
+    LT_REQUIRE(ldx >= F, "%s: ldx=%lld < F=%d", fn, (long long)ldx, F);
     (void)lt_node_err_dev();      // (allocated outside any stream capture)
     lt_baseline3 *b = new (std::nothrow) lt_baseline3();
-    if (!b) return lt_set_error(LT_ERR_NOMEM, "lt_baseline3_create: out of host memory");
+    if (!b) return lt_set_error(LT_ERR_NOMEM, "%s: out of host memory", fn);
     b->g = g; b->n = g->n; b->F = F; b->H1 = H1; b->H2 = H2; b->C = C;
     b->Hp1 = lt_round_up(H1, 4); b->Hp2 = lt_round_up(H2, 4);
+    b->wide = wide; b->Cp = lt_round_up(C, 4);
+    const size_t ldc = wide ? (size_t)b->Cp : (size_t)C;      // row stride of S3 / OUT
     b->X = X; b->ldx = ldx; b->W1 = W1; b->b1 = b1; b->W2 = W2; b->b2 = b2; b->W3 = W3; b->b3 = b3;
     const size_t n1 = (size_t)(b->n > 0 ? b->n : 1);
 #define B3_HIP(call)                                                                        \
@@ -522,8 +735,9 @@ extern "C" int lt_baseline3_create(const lt_graph *g, const float *X, int64_t ld
     B3_HIP(hipMalloc((void **)&b->Act1, n1 * b->Hp1 * sizeof(float)));
     B3_HIP(hipMalloc((void **)&b->S2, n1 * b->Hp2 * sizeof(float)));
     B3_HIP(hipMalloc((void **)&b->Z2, n1 * b->Hp2 * sizeof(float)));
-    B3_HIP(hipMalloc((void **)&b->S3, n1 * C * sizeof(float)));
-    B3_HIP(hipMalloc((void **)&b->OUT, n1 * C * sizeof(float)));
+    B3_HIP(hipMalloc((void **)&b->S3, n1 * ldc * sizeof(float)));
+    B3_HIP(hipMalloc((void **)&b->OUT, n1 * ldc * sizeof(float)));
+    if (wide) B3_HIP(hipMalloc((void **)&b->b3p, (size_t)b->Cp * sizeof(float)));
     B3_HIP(hipMalloc((void **)&b->b1p, (size_t)b->Hp1 * sizeof(float)));
     B3_HIP(hipMalloc((void **)&b->b2p, (size_t)b->Hp2 * sizeof(float)));
     B3_HIP(hipMalloc((void **)&b->W3p, (size_t)b->Hp2 * C * sizeof(float)));
@@ -540,6 +754,20 @@ extern "C" int lt_baseline3_create(const lt_graph *g, const float *X, int64_t ld
     return LT_OK;
 }
 
+extern "C" int lt_baseline3_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const float *W1,
+                                   const float *b1, int32_t H1, const float *W2, const float *b2, int32_t H2,
+                                   const float *W3, const float *b3, int32_t C, void *stream, lt_baseline3 **out) {
+    return baseline3_create("lt_baseline3_create", false, g, X, ldx, F, W1, b1, H1, W2, b2, H2, W3, b3, C, stream, out);
+}
+
+// The same handle for a class layer of up to LT3_WIDE_MAX_C columns: LT_MODE_DELTA only (the wide chain above), logits through
+// the unfused class layer.  C <= LT_MAX_C is allowed and takes the wide kernels all the same.
+extern "C" int lt_baseline3_create_wide(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const float *W1,
+                                        const float *b1, int32_t H1, const float *W2, const float *b2, int32_t H2,
+                                        const float *W3, const float *b3, int32_t C, void *stream, lt_baseline3 **out) {
+    return baseline3_create("lt_baseline3_create_wide", true, g, X, ldx, F, W1, b1, H1, W2, b2, H2, W3, b3, C, stream, out);
+}
+
 extern "C" int lt_baseline3_destroy(lt_baseline3 *b) {
     free_baseline3(b);
     return LT_OK;
@@ -549,6 +777,11 @@ extern "C" int lt_baseline3_logits(const lt_baseline3 *b, float *dst, void *stre
     LT_REQUIRE(b != nullptr && dst != nullptr, "lt_baseline3_logits: NULL argument");
     if (b->n == 0) return LT_OK;
     { const int rc = ensure3_fp32(b, (hipStream_t)stream); if (rc) return rc; }
+    if (b->wide && b->Cp != b->C) {      // rows of stride Cp -> the caller's dense [n, C]
+        LT_HIP(hipMemcpy2DAsync(dst, (size_t)b->C * sizeof(float), b->OUT, (size_t)b->Cp * sizeof(float), (size_t)b->C * sizeof(float),
+                                (size_t)b->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return LT_OK;
+    }
     LT_HIP(hipMemcpyAsync(dst, b->OUT, (size_t)b->n * b->C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return LT_OK;
 }
@@ -606,6 +839,10 @@ struct infl3_ws {
     uint32_t *bits2;
     int2 *items2;
     int32_t *probes_s, *obs_s;    // the call's lists, every id checked against [0, n) (lt_items.hip.h k_check_nodes)
+    // a wide handle (delta only; S3x = dS3x [items2, Cp]): the level-2 bitmap with positions, the probes' counts and offsets, dH2x
+    uint2 *rank2;
+    int32_t *cnt2, *off2;
+    float *dH2x;
     size_t bytes;
     int chunk;
 };
@@ -618,7 +855,13 @@ static infl3_ws carve3(void *base, const lt_baseline3 *b, int n_probe, int n_obs
     const size_t maxc = (size_t)(b->g->max_col_nnz > 0 ? b->g->max_col_nnz : 1);
     const size_t words = (n + 31) / 32;
     const size_t splitk = (((size_t)b->F + probe_kslice3(b) - 1) / probe_kslice3(b)) * (size_t)b->H1;
-    const size_t per_probe = (Hp1 + splitk + maxc * (Hp1 + Hp2) + n * C) * sizeof(float) + n * sizeof(int2) +
+    // (a wide handle: no fp32 product rows, and the level-2 tables -- dH2x, dS3x, the items -- by the upper bound of n rows per
+    // probe, as S3x is for a narrow one: a large graph gets small chunks)
+    const size_t Cp = (size_t)b->Cp;
+    const size_t per_probe_wide = Hp1 * sizeof(double) + (maxc * (Hp1 + Hp2) + n * (Hp2 + Cp)) * sizeof(float) + n * sizeof(int2) +
+                                  words * (2 * sizeof(uint2) + sizeof(uint32_t)) + 3 * sizeof(int32_t);
+    const size_t per_probe = b->wide ? per_probe_wide :
+                             (Hp1 + splitk + maxc * (Hp1 + Hp2) + n * C) * sizeof(float) + n * sizeof(int2) +
                              words * (sizeof(uint2) + sizeof(uint32_t)) + sizeof(int32_t);
     size_t chunk = (size_t)lt_tune().chunk_budget / per_probe;
     if (chunk < 1) chunk = 1;
@@ -632,6 +875,25 @@ static infl3_ws carve3(void *base, const lt_baseline3 *b, int n_probe, int n_obs
         offb += lt_align_up(bytes ? bytes : 1, 256);
         return q;
     };
+    if (b->wide) {
+        w.Spd = (double *)take(chunk * Hp1 * sizeof(double));
+        w.off = (int32_t *)take((chunk + 1) * sizeof(int32_t));
+        w.n_items2 = (int32_t *)take(sizeof(int32_t));
+        w.H1x = (float *)take(chunk * maxc * Hp1 * sizeof(float));
+        w.S2x = (float *)take(chunk * maxc * Hp2 * sizeof(float));
+        w.bits1 = (uint2 *)take(chunk * words * sizeof(uint2));
+        w.bits2 = (uint32_t *)take(chunk * words * sizeof(uint32_t));
+        w.rank2 = (uint2 *)take(chunk * words * sizeof(uint2));
+        w.cnt2 = (int32_t *)take(chunk * sizeof(int32_t));
+        w.off2 = (int32_t *)take((chunk + 1) * sizeof(int32_t));
+        w.items2 = (int2 *)take(chunk * n * sizeof(int2));
+        w.dH2x = (float *)take(chunk * n * Hp2 * sizeof(float));
+        w.S3x = (float *)take(chunk * n * Cp * sizeof(float));
+        w.probes_s = (int32_t *)take((size_t)(n_probe > 0 ? n_probe : 1) * sizeof(int32_t));
+        w.obs_s = (int32_t *)take((size_t)(n_obs > 0 ? n_obs : 1) * sizeof(int32_t));
+        w.bytes = offb;
+        return w;
+    }
     w.Sp = (float *)take(chunk * Hp1 * sizeof(float));
     w.Spd = (double *)take(chunk * Hp1 * sizeof(double));
     w.slabs = (float *)take(lt_gemm_splitk_slab_bytes((int)chunk, b->H1, b->F, probe_kslice3(b)));
@@ -654,6 +916,65 @@ extern "C" size_t lt_influence3_workspace_bytes(const lt_baseline3 *b, int32_t n
     return carve3(nullptr, b, n_probe, n_obs).bytes;
 }
 
+// The probe chunks of a wide handle (LT_MODE_DELTA; the lists are the checked ones, the fp64 pre-activations are fresh): level 1
+// as for a narrow handle, then the wide forms of the last two steps (k3w_rank2 ... k3dw_stageC above).  Enqueue only.
+static int influence3_wide_chunks(const lt_baseline3 *b, const infl3_ws &w, const int32_t *probe_nodes, int n_probe,
+                                  const int32_t *observe_nodes, int n_obs, float delta, float *out, int64_t ldo, hipStream_t st) {
+    const lt_graph *g = b->g;
+    const int n = b->n, C = b->C, Cp = b->Cp, Hp1 = b->Hp1, Hp2 = b->Hp2;
+    const int lpr1 = lt_lpr_for(Hp1), lpr2 = lt_lpr_for(Hp2), lprc = lt_lpr_for(Cp);
+    const int words = (n + 31) / 32;
+    const long maxc = g->max_col_nnz > 0 ? g->max_col_nnz : 1;
+    for (int p0 = 0; p0 < n_probe; p0 += w.chunk) {
+        const int nb = (n_probe - p0) < w.chunk ? (n_probe - p0) : w.chunk;
+        const int32_t *probes = probe_nodes + p0;
+        float *orow = out + (int64_t)p0 * ldo;
+        LT_REQUIRE(((long)nb * n_obs * lprc + LT_BLOCK - 1) / LT_BLOCK < 2147483647L,
+                   "lt_influence3_rows: %d probes x %d observed nodes per chunk exceed the grid limit", nb, n_obs);
+        const long m_bound = (long)nb * maxc, m2_bound = (long)nb * n;
+        LT_REQUIRE(m_bound < 2147483647L && m2_bound < 2147483647L,
+                   "lt_influence3_rows: %d probes x %ld rows per chunk exceed the grid limit", nb, maxc > n ? maxc : (long)n);
+        // level 1 (the narrow chain's): the probes' product rows in fp64, the items, dH1 on the fp64 pre-activation, dS2x = dH1x W2
+        int rc = lt_tune().gcn3_product_gather != 0 ? lt_fp64_product_rows_gather(b->l1, probes, nb, w.Spd, (long)Hp1, st) : 1;
+        if (rc == 1) {
+            if (Hp1 != b->H1) LT_HIP(hipMemsetAsync(w.Spd, 0, (size_t)nb * Hp1 * sizeof(double), st));
+            rc = lt_launch_gemm_f64_gather(b->X, (long)b->ldx, probes, nb, b->W1, (long)b->H1, b->H1, b->F, w.Spd, (long)Hp1, st);
+        }
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_item_bits, dim3(nb), dim3(256), 0, st, g->tptr, g->trow, probes, nb, words, w.bits1, w.off, (int2 *)nullptr, (uint2 *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
+        LT_CHECK_LAUNCH();
+        LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k3d_items1<LPR_>), dim3(LT3_GRID), dim3(LT_BLOCK), 0, st, g->tptr, g->trow,
+                                                 g->tval, probes, nb, w.off, w.Spd, b->l1->Z1d, Hp1, delta, w.H1x));
+        LT_CHECK_LAUNCH();
+        if (Hp2 != b->H2) LT_HIP(hipMemsetAsync(w.S2x, 0, (size_t)m_bound * Hp2 * sizeof(float), st));
+        rc = lt_launch_gemm_mdev(w.H1x, Hp1, b->W2, b->H2, w.S2x, Hp2, (int)m_bound, w.off + nb, b->H2, b->H1, st);
+        if (rc) return rc;
+        // level 2: R2 by marking, then every member's place
+        LT_HIP(hipMemsetAsync(w.bits2, 0, (size_t)nb * words * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(k3_mark2, dim3(LT3_GRID), dim3(LT_BLOCK), 0, st, g->tptr, g->trow, probes, nb, w.off, words, w.bits2,
+                           w.n_items2);
+        LT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k3w_rank2, dim3((unsigned)nb), dim3(LT_BLOCK), 0, st, words, w.bits2, w.rank2, w.cnt2);
+        LT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k3w_list2, dim3((unsigned)nb), dim3(LT_BLOCK), 0, st, nb, words, w.rank2, w.cnt2, w.off2, w.items2);
+        LT_CHECK_LAUNCH();
+        LT_DISPATCH_LPR(lpr2, hipLaunchKernelGGL((k3dw_stageB<LPR_>), dim3(LT3_GRID), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
+                                                 b->Z2d, Hp2, w.off, w.S2x, w.bits1, words, w.items2, w.off2 + nb, w.dH2x));
+        LT_CHECK_LAUNCH();
+        // dS3x = dH2x W3 over the items (the count on the device); W3 as the caller holds it: the product reads K = H2 rows of it
+        // and N = C columns, and leaves the pad columns of both operands alone
+        rc = lt_launch_gemm_mdev(w.dH2x, Hp2, b->W3, C, w.S3x, Cp, (int)m2_bound, w.off2 + nb, C, b->H2, st);
+        if (rc) return rc;
+        // level 3: the observed rows
+        const unsigned gridC = (unsigned)(((long)nb * n_obs * lprc + LT_BLOCK - 1) / LT_BLOCK);
+        LT_DISPATCH_LPR(lprc, hipLaunchKernelGGL((k3dw_stageC<LPR_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
+                                                 C, Cp, nb, w.S3x, w.rank2, words, w.off2, observe_nodes, n_obs, delta, orow,
+                                                 (long)ldo));
+        LT_CHECK_LAUNCH();
+    }
+    return LT_OK;
+}
+
 extern "C" int lt_influence3_rows(const lt_baseline3 *b, const int32_t *probe_nodes, int32_t n_probe,
                                   const int32_t *observe_nodes, int32_t n_obs, float delta, float *out, int64_t ldo,
                                   void *workspace, size_t workspace_bytes, void *stream) {
@@ -668,6 +989,9 @@ extern "C" int lt_influence3_rows_mode(const lt_baseline3 *b, const int32_t *pro
     lt_prof_call prof_call_;
     LT_REQUIRE(mode == LT_MODE_SPARSE || mode == LT_MODE_FULL || mode == LT_MODE_DELTA, "lt_influence3_rows_mode: unknown mode %d", mode);
     const bool exact = mode == LT_MODE_DELTA;
+    if (b->wide && !exact)
+        return lt_set_error(LT_ERR_UNSUPPORTED, "lt_influence3_rows: a wide handle (lt_baseline3_create_wide, C=%d) serves LT_MODE_DELTA "
+                            "only; the fp32 finite difference of this shape is the caller's loop over the unfused layers", b->C);
     LT_REQUIRE(!exact || b->Z2d != nullptr, "lt_influence3_rows_mode: LT_MODE_DELTA needs lt_baseline3_enable_fp64");
     LT_REQUIRE(n_probe >= 0 && n_obs >= 0, "lt_influence3_rows: negative count");
     LT_REQUIRE(delta != 0.f && delta == delta, "lt_influence3_rows: delta must be a non-zero number");
@@ -698,6 +1022,7 @@ extern "C" int lt_influence3_rows_mode(const lt_baseline3 *b, const int32_t *pro
         const int rc = exact ? ensure3_fp64(b, st) : ensure3_fp32(b, st);
         if (rc) return rc;
     }
+    if (b->wide) return influence3_wide_chunks(b, w, probe_nodes, n_probe, observe_nodes, n_obs, delta, out, ldo, st);
     for (int p0 = 0; p0 < n_probe; p0 += w.chunk) {
         const int nb = (n_probe - p0) < w.chunk ? (n_probe - p0) : w.chunk;
         const int32_t *probes = probe_nodes + p0;

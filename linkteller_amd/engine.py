@@ -1092,7 +1092,10 @@ def baseline_for(adj, x, w1, b1, w2, b2):
 class Baseline3:
     """Unperturbed forward state of the 3-layer model (reference gcn/models.py:28-46) + its probe primitive
     (lt_baseline3_create / lt_influence3_rows): the reference's fp32 finite difference, evaluated on the rows a
-    probe reaches in 1 / 2 / 3 hops."""
+    probe reaches in 1 / 2 / 3 hops.  More than 8 classes (up to 256) make a WIDE handle (lt_baseline3_create_wide,
+    ``wide = True``): it serves ``mode="delta"`` alone, the fp32 finite difference of such a model is the attacker's loop."""
+
+    NARROW_MAX_C = 8
 
     def __init__(self, adj, x, w1, b1, w2, b2, w3, b3):
         self.graph: HipGraph = as_hip_graph(adj)
@@ -1108,10 +1111,12 @@ class Baseline3:
             raise ValueError(f"the graph lives on cuda:{self.graph.device_index}, the features on {self.x.device}")
         _require_finite(features=self.x, W1=self.w1, b1=self.b1, W2=self.w2, b2=self.b2, W3=self.w3, b3=self.b3)
         h = C.c_void_p()
-        _lib.check(_lib.lib().lt_baseline3_create(self.graph.handle, self.x.data_ptr(), f, f, self.w1.data_ptr(),
-                                                  self.b1.data_ptr(), self.h1, self.w2.data_ptr(), self.b2.data_ptr(),
-                                                  self.h2, self.w3.data_ptr(), self.b3.data_ptr(), self.c, _stream(),
-                                                  C.byref(h)), "lt_baseline3_create")
+        self.wide = self.c > self.NARROW_MAX_C
+        create = "lt_baseline3_create_wide" if self.wide else "lt_baseline3_create"
+        _lib.check(getattr(_lib.lib(), create)(self.graph.handle, self.x.data_ptr(), f, f, self.w1.data_ptr(),
+                                               self.b1.data_ptr(), self.h1, self.w2.data_ptr(), self.b2.data_ptr(),
+                                               self.h2, self.w3.data_ptr(), self.b3.data_ptr(), self.c, _stream(),
+                                               C.byref(h)), create)
         self._h = h
         self._x_seen = _x_version(self.x)
         self._finalizer = weakref.finalize(self, _lib.lib().lt_baseline3_destroy, h)
@@ -1144,6 +1149,9 @@ class Baseline3:
         """`sparse` (= `full`): the reference's fp32 finite difference on the rows a probe reaches in 1 / 2 / 3 hops;
         `delta`: the perturbation propagated exactly through the three layers (lt_influence3_rows_mode)."""
         m = _lib.MODES[mode or "sparse"] if isinstance(mode, str) or mode is None else int(mode)
+        if self.wide and m != _lib.MODE_DELTA:
+            raise NotImplementedError(f"a GCN3 with {self.c} classes is served in mode 'delta' only (lt_baseline3_create_wide); "
+                                      "its fp32 finite difference is Attacker._rows_generic")
         if m == _lib.MODE_DELTA:
             self.enable_fp64()
         dev = self.x.device
