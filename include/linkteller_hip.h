@@ -49,7 +49,9 @@ extern "C" {
                             Additive within 5: the wide head of the 2-layer trainer (lt_gcn2_trainer_create_wide, _counts, _hidden,
                             _attach_validation_wide, lt_eval_head_wide, lt_eval_head_wide_workspace_bytes); no entry point changed.
                             Additive within 5: the wide head of the 3-layer trainer (lt_gcn3_trainer_create_wide, _counts,
-                            _attach_validation_wide); no entry point changed */
+                            _attach_validation_wide); no entry point changed.
+                            Additive within 5: edge recovery over rows that arrive in chunks (lt_top_stream_*) and lt_pairs_present;
+                            no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -730,6 +732,52 @@ int lt_normalize_csr(int32_t n, const int32_t *rowptr, const int32_t *col, int64
 size_t lt_top_pairs_workspace_bytes(int32_t n, int64_t m);
 int lt_top_pairs_lower(const float *scores, int64_t lds, int32_t n, int64_t m, int64_t *out_idx, float *out_score,
                        int64_t *out_info, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- the same selection over rows that arrive in chunks: a whole graph's edge list without the n x n matrix ------------------
+ * A handle selects the m first cells of the strict lower triangle of an n x n score matrix that is never formed: the caller
+ * pushes rows [row_begin, row_begin + n_rows) as lt_influence_rows / lt_influence3_rows* wrote them for those probes, then
+ * finishes.  Total order, out_idx, out_score and out_info are exactly those of lt_top_pairs_lower on the assembled matrix: the
+ * result is a pure function of the matrix, whatever the cut into pushes, slack_cells, the compactions that fired or the order in
+ * which waves appended.
+ * lt_top_stream_create: n >= 2, 1 <= m <= min(n (n - 1) / 2, 2^30), max_push_rows >= 1 (the largest n_rows a push may bring; no
+ *   storage depends on it), slack_cells = 0 for the default max(2 (n - 1), 2^22) or a value in [2 (n - 1), 2^31]: the candidate
+ *   buffers hold m + slack_cells entries, and a push is cut into slabs of whole rows of at most slack_cells / 2 cells.  Allocates
+ *   lt_top_stream_bytes device bytes, A(x) = x rounded up to 256:
+ *     25600 + A(8 cap) + A(16 cap) + 4 A(4 m) + A(1024 nblk),  cap = m + slack_cells,
+ *     nblk = ceil(m / (256 r)), r the smallest of 4, 8, 16 ... with ceil(m / (256 r)) <= 4096
+ *   -- linear in m + slack_cells; nothing is O(n^2) or O(n max_push_rows).  Synchronises the device once (its header is cleared).
+ * lt_top_stream_push: rows = device [n_rows, lds] fp32.  Of row i only columns 0 .. i - 1 are read, so lds >= row_begin + n_rows - 1
+ *   is enough (a chunk may be formed against the first row_begin + n_rows observed nodes only); nothing else is touched.  Rows
+ *   arrive contiguously, in ascending order, from row 0, each once: the handle keeps the next expected row.  LT_ERR_INVALID
+ *   before anything is enqueued (the handle stays as it was): NULL, n_rows outside [1, max_push_rows], another row_begin than the
+ *   next row, rows beyond n, lds too small, a finished handle.
+ * lt_top_stream_finish: out_idx int64 [m], out_score fp32 [m], out_info int64 [4], device.  LT_ERR_INVALID before row n - 1 was
+ *   pushed, and on a handle that was finished already.
+ * push and finish only enqueue on `stream`: no synchronisation, no host read of device memory, no spinning in a kernel; all
+ *   running state (held count, threshold key, cells seen) lives in device memory and stream order is the only barrier.  In front
+ *   of every slab a predicated chain of 6 + P launches (P = bytes of n * n - 1) is enqueued; its blocks return at once unless the
+ *   held count exceeds m + slack_cells / 2, in which case exactly the m first held entries are kept and the threshold key rises.
+ *   A failed HIP call inside push / finish leaves the handle's content undefined until lt_top_stream_reset.
+ * lt_top_stream_reset: enqueues the clear of the state; the handle then takes another matrix of the same (n, m).
+ * lt_top_stream_stats: enqueues a copy of 16 state words to d_out (device int64 [16]): [0], [1] entries in the two buffers,
+ *   [2] the current buffer, [5] threshold key, [6] whether one is set, [7] cells tied at it that were dropped, [8] cells scanned,
+ *   [9] chains that fired in front of the first slab of a push (between pushes), [10] in front of a later slab (inside a push),
+ *   [11] slabs scanned; the others are internal.  One handle serves one stream at a time.  Additive in ABI 5. */
+typedef struct lt_top_stream lt_top_stream;
+int lt_top_stream_create(int32_t n, int64_t m, int32_t max_push_rows, int64_t slack_cells, lt_top_stream **out);
+int lt_top_stream_bytes(const lt_top_stream *s, size_t *device_bytes);
+int lt_top_stream_push(lt_top_stream *s, const float *rows, int64_t lds, int32_t row_begin, int32_t n_rows, void *stream);
+int lt_top_stream_finish(lt_top_stream *s, int64_t *out_idx, float *out_score, int64_t *out_info, void *stream);
+int lt_top_stream_reset(lt_top_stream *s, void *stream);
+int lt_top_stream_stats(const lt_top_stream *s, int64_t *d_out, void *stream);
+int lt_top_stream_destroy(lt_top_stream *s);
+
+/* lt_pairs_present: out[k] (uint8, device) = 1 iff column v[k] is stored in row u[k] of the device CSR pattern (sorted columns, as
+ * the attack's samplers take it), else 0: a binary search per pair.  u, v: device int32 [m].  d_info (device int64 [1]) is
+ * cleared and then counts the pairs with an id outside [0, n); such a pair gets out[k] = 0 and reads nothing.  The node-id flag of
+ * the probe primitives is not involved.  Enqueue only.  Additive in ABI 5. */
+int lt_pairs_present(int32_t n, const int32_t *d_rowptr, const int32_t *d_col, const int32_t *u, const int32_t *v, int64_t m,
+                     uint8_t *out, int64_t *d_info, void *stream);
 
 /* ---- attack metrics: the table behind roc_curve / precision_recall_curve / average_precision_score (attacker.py:378-389) --------
  * Item k (of n_items) has label labels[k] (uint8, 0 or 1) and score scores[index[k]], or scores[k] when index_or_null is NULL.

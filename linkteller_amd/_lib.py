@@ -121,6 +121,15 @@ SIGNATURES = {
     "lt_top_pairs_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "lt_top_pairs_lower": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),
+    "lt_top_stream_create": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
+    "lt_top_stream_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "lt_top_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "lt_top_stream_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_top_stream_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lt_top_stream_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_top_stream_destroy": (C.c_int, [C.c_void_p]),
+    "lt_pairs_present": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
     "lt_score_curve_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "lt_score_curve": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

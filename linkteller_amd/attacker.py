@@ -556,7 +556,94 @@ class Attacker:
         self.compute_and_save(list(s_ex[oe]), list(s_nex[on]))
 
     # ------------------------------------------------------------------------------------------
-    def recover_edges(self, beliefs=None, mode=None) -> dict:
+    # recover_edges(chunk=K) / recover_graph: chunk e's rows formed against observed[:e] only (the cells right of the diagonal are
+    # never read).  Off by default: every chunk then has an observed list of its own.  tools/recover_stream_time.py part (a) times
+    # both forms; NOTES.md (2026-10-20) records what was measured and the decision
+    recover_triangular = False
+
+    def _stream_top_pairs(self, probes, observed, m, chunk, mode=None):
+        """``engine.top_pairs_lower`` of the len(probes) x len(observed) influence rows without forming them at once: ``chunk``
+        probes at a time through an ``engine.TopPairsStream`` -> the same ``(idx, score, info)``.  Leaves the handle's counters in
+        ``self.recover_stream_stats`` (device bytes, pushes; with ``self.recover_keep_stats`` set, the compaction counts too)."""
+        n, chunk = int(observed.numel()), int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk = {chunk}: at least 1")
+        chunk = min(chunk, n)
+        sel = engine.TopPairsStream(n, m, chunk, device=observed.device)
+        try:
+            pushes = 0
+            for b in range(0, n, chunk):
+                e = min(b + chunk, n)
+                obs = observed[:e] if (self.recover_triangular and e > 1) else observed
+                sel.push(self._rows(probes[b:e], obs, mode), b)
+                pushes += 1
+            out = sel.finish()
+            self.recover_stream_stats = {"device_bytes": sel.device_bytes, "pushes": pushes, "chunk": chunk}
+            if getattr(self, "recover_keep_stats", False):      # (a copy of the handle's counters: one wait)
+                self.recover_stream_stats.update(sel.stats())
+        finally:
+            sel.close()
+        return out
+
+    def recover_graph(self, beliefs=None, mode=None, chunk=1024, nodes=None) -> dict:
+        """``recover_edges`` for the attacked graph itself: the node set is every node (or ``nodes``), each is perturbed, every
+        pair is ranked, and the m highest-scoring pairs under each density belief are the predicted edges.  Needs no
+        ``prepare_test_data()`` and no pair lists: the rows are formed ``chunk`` probes at a time and consumed by an
+        ``engine.TopPairsStream`` (O(m) device state, no n x n matrix, no label triangle); the edge count comes from
+        ``sampling.upper_edge_count`` on the device (a given ``nodes`` list: counted on the HOST in the scipy pattern restricted to
+        the list, one pass over the stored entries -- the whole graph is the case the device count serves), ``is_edge`` from
+        ``engine.pairs_present`` for the selected pairs only.  Returns and stores the ``recovered`` dict of ``recover_edges``, key
+        for key.  Serves every model kind ``_rows`` serves; with several ranks every rank forms everything itself."""
+        from . import recover, sampling
+        n_graph = int(self.features.shape[0])
+        nodes = np.arange(n_graph, dtype=np.int64) if nodes is None else np.asarray(nodes, dtype=np.int64).reshape(-1)
+        n = len(nodes)
+        if n < 2:
+            raise ValueError("recover_graph: fewer than two nodes")
+        if not self.features.is_cuda:
+            raise engine._lib.LinkTellerHipError("recover_graph: the features must live on the GPU; there is no CPU path")
+        n_total = n * (n - 1) // 2
+        probes, observed = self._device_nodes(nodes, 0, n)
+        csr = self._pattern_csr()
+        if n == n_graph and np.array_equal(nodes, np.arange(n_graph)):
+            n_edges = sampling.upper_edge_count(csr)
+        else:
+            import scipy.sparse as sp
+            adj = sp.csr_matrix(self.worker.adj_ori)
+            pattern = sp.csr_matrix((np.ones(adj.indices.shape[0], dtype=np.int8), adj.indices, adj.indptr), shape=adj.shape)
+            sub = sp.coo_matrix(pattern[nodes][:, nodes])        # positions of the node list: pair (i, j), i < j, as the samplers count
+            sub.sum_duplicates()
+            n_edges = int((sub.col > sub.row).sum())
+        beliefs = recover.density_ladder(n_edges, n) if beliefs is None else [float(b) for b in beliefs]
+        counts = recover.belief_counts(beliefs, n_total)
+        m = int(counts.max())
+        idx_d, val_d, info = self._stream_top_pairs(probes, observed, m, chunk, mode)
+        # cell (i, j), j < i: the pair (nodes[j], nodes[i]) scored by perturbing nodes[i]
+        obs64 = observed.to(torch.int64)
+        present_d = engine.pairs_present(csr, obs64[idx_d % n], obs64[idx_d // n])
+        idx, val, raw = idx_d.cpu().numpy(), val_d.cpu().numpy(), info["raw"].cpu().numpy()
+        engine.node_check()
+        order = np.lexsort((idx, -val.astype(np.float64)))      # ascending cell index -> rank order
+        idx, val = idx[order], val[order]
+        ci, cj = idx // n, idx % n
+        u, v = nodes[cj], nodes[ci]
+        present = present_d.cpu().numpy()[order] != 0
+        stats = recover.recovery_stats(present, n_edges, counts)
+        self.recovered = {
+            "pairs": np.stack([u, v], axis=1).astype(np.int64), "scores": val.astype(np.float64), "is_edge": present,
+            "beliefs": list(beliefs), "counts": counts, "precision": stats["precision"], "recall": stats["recall"],
+            "f1": stats["f1"], "tp": stats["tp"],
+            "threshold": float(np.array([raw[0]], dtype=np.int64).astype(np.uint32).view(np.float32)[0]),
+            "n_edges": n_edges, "n_total": n_total,
+            "above": int(raw[1]), "tied_taken": int(raw[2]), "tied_total": int(raw[3]),
+        }
+        return self.recovered
+
+    def recovered_all_filename(self):
+        name = self.result_filename()
+        return osp.join(osp.dirname(name), "recover_all_" + osp.basename(name))
+
+    def recover_edges(self, beliefs=None, mode=None, chunk=None) -> dict:
         """The attack's edge list (the reference's post-processing script, attack_stats_all.py:44-116): under a belief k about the
         density of the sampled subgraph, the m = ceil(k n (n - 1) / 2) highest-scoring pairs of sampled nodes are predicted as
         edges.  ``beliefs=None``: the reference's ladder r/4 .. 4r around the subgraph's true density (``recover.density_ladder``).
@@ -592,11 +679,17 @@ class Attacker:
         counts = recover.belief_counts(beliefs, n_total)
         m = int(counts.max())
         cinfo = None
-        if str(getattr(self.args, "attack_mode", "efficient")) in ("baseline", "baseline-feat") and self._baseline_route() == "device":
+        if chunk is not None:
+            # addition: the rows chunk by chunk through engine.TopPairsStream -- the same triple, no n x n matrix
+            if str(getattr(self.args, "attack_mode", "efficient")) in ("baseline", "baseline-feat"):
+                raise NotImplementedError("recover_edges(chunk=...): the baseline attacks' correlation square is formed in one piece")
+            idx_d, val_d, info = self._stream_top_pairs(probes, observed, m, chunk, mode)
+        elif str(getattr(self.args, "attack_mode", "efficient")) in ("baseline", "baseline-feat") and self._baseline_route() == "device":
             rows, cinfo = self._baseline_square_device()     # (addition: the baseline attacks' correlation square, symmetric)
+            idx_d, val_d, info = engine.top_pairs_lower(rows, m)
         else:
             rows = self._rows(probes, observed, mode)
-        idx_d, val_d, info = engine.top_pairs_lower(rows, m)
+            idx_d, val_d, info = engine.top_pairs_lower(rows, m)
         if cinfo is not None:
             cinfo.check(nan_ok=False)     # (a zero-norm row makes whole rows NaN: lt_top_pairs_lower's set would be unspecified)
         if dev_sample is not None:
@@ -631,9 +724,9 @@ class Attacker:
         name = self.result_filename()
         return osp.join(osp.dirname(name), "recover_" + osp.basename(name))
 
-    def save_recovered(self):
+    def save_recovered(self, filename=None):
         """The dict of ``recover_edges`` next to the attack's result file (``eval_<dataset>/recover_<result file>``), one printed
-        line per belief.  Rank 0 only."""
+        line per belief.  Rank 0 only.  ``filename``: another place (``recovered_all_filename()`` for ``recover_graph``)."""
         rank, _ = lt_dist.world()
         if rank != 0:
             return
@@ -641,7 +734,7 @@ class Attacker:
         for k, b in enumerate(r["beliefs"]):
             print(f"belief = {b:.6g}, m = {int(r['counts'][k])}, tp = {int(r['tp'][k])}, precision = {r['precision'][k]:.4f}, "
                   f"recall = {r['recall'][k]:.4f}, f1 = {r['f1'][k]:.4f}")
-        filename = self.recovered_filename()
+        filename = self.recovered_filename() if filename is None else filename
         os.makedirs(osp.dirname(filename), exist_ok=True)
         torch.save(r, filename)
         print(f"recovered edges saved to: {filename}")

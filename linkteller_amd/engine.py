@@ -1276,6 +1276,129 @@ def top_pairs_lower(scores: torch.Tensor, m: int):
     return idx, val, info
 
 
+class TopPairsStream:
+    """``top_pairs_lower`` over rows that arrive in chunks (lt_top_stream_*): the n x n matrix is never formed, the handle keeps
+    O(m + slack) device state.  ``push(rows, row_begin)`` takes rows [row_begin, row_begin + rows.shape[0]) -- fp32 CUDA, last
+    stride 1, at least ``row_begin + rows.shape[0] - 1`` columns; only columns 0 .. i - 1 of row i are read -- contiguously and in
+    ascending order from row 0, at most ``max_rows`` a call.  ``finish()`` returns the ``(idx, score, info)`` of
+    ``top_pairs_lower`` on the assembled matrix, byte for byte, whatever the cut into pushes or ``slack_cells`` (0 = default; at
+    least 2 (n - 1)).  ``reset()`` readies the handle for another matrix of the same (n, m).  Nothing synchronises but the
+    constructor.  ``device_bytes``: what the handle allocated (the formula stands in include/linkteller_hip.h)."""
+
+    def __init__(self, n: int, m: int, max_rows: int, slack_cells: int = 0, device=None):
+        n, m, max_rows, slack_cells = int(n), int(m), int(max_rows), int(slack_cells)
+        total = n * (n - 1) // 2
+        if n < 2 or not 1 <= m <= total:
+            raise ValueError(f"m={m} outside [1, {total}] for n={n}")
+        if max_rows < 1:
+            raise ValueError(f"max_rows={max_rows} < 1")
+        if slack_cells != 0 and slack_cells < 2 * (n - 1):
+            raise ValueError(f"slack_cells={slack_cells} below the minimum 2 (n - 1) = {2 * (n - 1)} (0 = default)")
+        _lib.require_gpu()
+        self.n, self.m, self.max_rows = n, m, max_rows
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._h = None
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().lt_top_stream_create(n, m, max_rows, slack_cells, C.byref(h)), "lt_top_stream_create")
+        self._h = h
+        nbytes = C.c_size_t()
+        _lib.check(_lib.lib().lt_top_stream_bytes(self._h, C.byref(nbytes)), "lt_top_stream_bytes")
+        self.device_bytes = int(nbytes.value)
+
+    def _handle(self):
+        if self._h is None:
+            raise _lib.LinkTellerHipError("TopPairsStream: the handle was closed")
+        return self._h
+
+    def push(self, rows: torch.Tensor, row_begin: int):
+        if not isinstance(rows, torch.Tensor):
+            raise TypeError("rows must be a torch.Tensor")
+        if not rows.is_cuda:
+            raise _lib.LinkTellerHipError(f"rows must live on the GPU (got {rows.device}); there is no CPU path")
+        if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[0] < 1:
+            raise TypeError(f"rows must be a 2-d float32 tensor of at least one row, got {rows.dtype} {tuple(rows.shape)}")
+        if rows.shape[1] > 1 and rows.stride(1) != 1:
+            raise ValueError("rows must have last-dimension stride 1 (rows may be strided)")
+        k, row_begin = int(rows.shape[0]), int(row_begin)
+        if rows.shape[1] < row_begin + k - 1:
+            raise ValueError(f"rows has {int(rows.shape[1])} columns, rows [{row_begin}, {row_begin + k}) need {row_begin + k - 1}")
+        lds = int(rows.stride(0)) if k > 1 else max(int(rows.stride(0)), int(rows.shape[1]))
+        if lds < row_begin + k - 1:
+            raise ValueError(f"row stride {lds} smaller than the {row_begin + k - 1} columns read")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().lt_top_stream_push(self._handle(), rows.data_ptr(), lds, row_begin, k, _stream()), "lt_top_stream_push")
+
+    def finish(self):
+        idx = torch.empty(self.m, dtype=torch.int64, device=self.device)
+        val = torch.empty(self.m, dtype=torch.float32, device=self.device)
+        raw = torch.empty(4, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().lt_top_stream_finish(self._handle(), idx.data_ptr(), val.data_ptr(), raw.data_ptr(), _stream()),
+                       "lt_top_stream_finish")
+        info = {"threshold_bits": raw[0], "above": raw[1], "tied_taken": raw[2], "tied_total": raw[3], "raw": raw}
+        return idx, val, info
+
+    def reset(self):
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().lt_top_stream_reset(self._handle(), _stream()), "lt_top_stream_reset")
+
+    def stats(self) -> dict:
+        """The handle's counters (one copy of 16 words, one wait): ``held``, ``seen`` cells, compactions that fired in front of
+        the first slab of a push (``fired_between``) and of a later one (``fired_inside``), ``slabs``, ``tied_dropped``."""
+        raw = torch.empty(16, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().lt_top_stream_stats(self._handle(), raw.data_ptr(), _stream()), "lt_top_stream_stats")
+        w = [int(v) for v in raw.cpu().tolist()]
+        return {"held": w[w[2] & 1], "seen": w[8], "fired_between": w[9], "fired_inside": w[10], "slabs": w[11],
+                "threshold_set": bool(w[6]), "tied_dropped": w[7]}
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            _lib.lib().lt_top_stream_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pairs_present(csr, u, v) -> torch.Tensor:
+    """uint8 CUDA tensor [len(u)]: 1 iff column ``v[k]`` is stored in row ``u[k]`` of the device pattern ``csr``
+    (``sampling.device_pattern_csr``; lt_pairs_present: a binary search per pair).  ``u``, ``v``: integer CUDA tensors of equal
+    length.  An id outside [0, n) raises ``IndexError`` (the call's own info word, read here: one wait); the node-id flag of the
+    probe primitives is not touched."""
+    rowptr, col = csr[0], csr[1]
+    for name, t in (("u", u), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if not t.is_cuda:
+            raise _lib.LinkTellerHipError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype.is_floating_point or t.dtype == torch.bool or t.is_complex() or t.dim() != 1:
+            raise TypeError(f"{name} must be a 1-d tensor of integer ids, got {t.dtype} {tuple(t.shape)}")
+    if u.numel() != v.numel():
+        raise ValueError(f"u and v differ in length: {u.numel()} and {v.numel()}")
+    _lib.require_gpu()
+    dev = rowptr.device
+    n = int(rowptr.numel()) - 1
+    lim = torch.iinfo(torch.int32)
+
+    def _ids(t):      # ids beyond int32 are out of range whatever n is: keep them out of range through the narrowing
+        return t.contiguous() if t.dtype == torch.int32 else t.clamp(min=-1, max=lim.max).to(torch.int32)
+    u32, v32 = _ids(u), _ids(v)
+    out = torch.empty(u32.numel(), dtype=torch.uint8, device=dev)
+    info = torch.empty(1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().lt_pairs_present(n, rowptr.data_ptr(), col.data_ptr(), u32.data_ptr(), v32.data_ptr(), u32.numel(),
+                                               out.data_ptr(), info.data_ptr(), _stream()), "lt_pairs_present")
+    bad = int(info.item())
+    if bad:
+        raise IndexError(f"pairs_present: {bad} pairs name a node outside [0, {n})")
+    return out
+
+
 _curve_ws = {}       # score_curve's workspace: only the latest (device, size) is kept, sizes repeat across calls
 
 

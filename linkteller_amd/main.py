@@ -80,6 +80,11 @@ _OPTIONS = {
     # at most 8 classes, every check and every bit as before the flag existed; 'wide': up to 256 classes with cross-entropy or,
     # for a multi-label dataset, binary cross-entropy with logits (engine.GCN2Trainer(head="wide")): reddit, ppi, ppi-large
     "train-head": (str, "narrow", ["narrow", "wide"]),
+    # additions: with --recover, form the score rows K probes at a time and select through engine.TopPairsStream instead of the
+    # one-shot n x n matrix (0 = one shot: the same edge list either way); and which nodes are ranked -- 'sample', the sampled
+    # subgraph as before, or 'all': every node of the attacked graph (Attacker.recover_graph; the sampled AUC attack is skipped,
+    # the list goes to eval_<dataset>/recover_all_<result file>)
+    "recover-chunk": (int, 0), "recover-nodes": (str, "sample", ["sample", "all"]),
 }
 _HELP = {
     "validate": "with --train: validate on the held-out graph after every epoch on the GPU.  log: loss_val / acc_val in the log; "
@@ -172,6 +177,22 @@ def check_recover(args):
                                   f"sample-type={args.sample_type})")
     if args.density_belief < 0:
         raise ValueError(f"--density-belief {args.density_belief}: a density belief is > 0 (0 = the ladder around the true density)")
+
+
+def check_recover_stream(args):
+    """``--recover-chunk K`` / ``--recover-nodes all`` shape what ``--recover`` does: without it they are refused here, before a
+    Worker is built or the GPU is touched; so are a negative K and, with the baseline attacks (whose correlation square is formed
+    in one piece), anything but the defaults."""
+    chunk, nodes = int(getattr(args, "recover_chunk", 0)), getattr(args, "recover_nodes", "sample")
+    if chunk == 0 and nodes == "sample":
+        return
+    if chunk < 0:
+        raise ValueError(f"--recover-chunk {chunk}: the probes per chunk, > 0 (0 = the one-shot matrix)")
+    if not getattr(args, "recover", False):
+        raise NotImplementedError(f"--recover-chunk {chunk} / --recover-nodes {nodes} need --recover (they shape the edge recovery)")
+    if args.attack_mode != "efficient":
+        raise NotImplementedError(f"--recover-chunk / --recover-nodes all need --attack-mode efficient (got {args.attack_mode}: "
+                                  "the baseline attacks' correlation square is formed in one piece)")
 
 
 def check_metrics_only(args):
@@ -273,6 +294,7 @@ def main(argv=None):
     check_split_dataset(args)
     check_baseline_scores(args)
     check_recover(args)
+    check_recover_stream(args)
     check_metrics_only(args)
     check_dp_build(args)
     check_sample_build(args)

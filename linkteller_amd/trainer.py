@@ -230,9 +230,24 @@ class GCNTrainer:
         precision, recall = tp / p, tp / t
         return 2 * precision * recall / (precision + recall), precision, recall, ap
 
+    def _recover_whole_graph(self):
+        """addition: ``--recover --recover-nodes all`` -- the attacked graph itself instead of a sample (``Attacker.recover_graph``)."""
+        a = self.args
+        if not (a.attack_mode == "efficient" and str(a.sample_type).startswith("unbalanced")):
+            raise NotImplementedError("recover: served after the efficient attack on an unbalanced* sample only")
+        self.attacker = Attacker(args=a, model=self.model, worker=self.worker)
+        print("recover-nodes = all: the sampled AUC attack is skipped, every node is perturbed and every pair ranked")
+        belief = float(getattr(a, "density_belief", 0.0) or 0.0)
+        t = time.time()
+        self.attacker.recover_graph(beliefs=[belief] if belief > 0 else None, chunk=int(getattr(a, "recover_chunk", 0) or 0) or 1024)
+        print(f"whole-graph recovery done using {time.time() - t} seconds!")
+        self.attacker.save_recovered(self.attacker.recovered_all_filename())
+
     def eval_output(self, output, mode="clean", eval_degree=False):
         a = self.args
-        if a.attack:
+        if a.attack and getattr(a, "recover", False) and getattr(a, "recover_nodes", "sample") == "all":
+            self._recover_whole_graph()
+        elif a.attack:
             # (addition: with baseline_scores = device the baseline attacks' square lives on the device and is ranked there too)
             served = ("efficient", "baseline", "baseline-feat") if getattr(a, "baseline_scores", "host") == "device" else ("efficient",)
             if getattr(a, "recover", False) and not (a.attack_mode in served and str(a.sample_type).startswith("unbalanced")):
@@ -263,7 +278,8 @@ class GCNTrainer:
             print(f"attacks done using {time.time() - t} seconds!")
             if getattr(a, "recover", False):                      # addition (main.check_recover: efficient + unbalanced* only)
                 belief = float(getattr(a, "density_belief", 0.0) or 0.0)
-                self.attacker.recover_edges(beliefs=[belief] if belief > 0 else None)
+                chunk = int(getattr(a, "recover_chunk", 0) or 0)  # addition: --recover-chunk, 0 = the one-shot matrix
+                self.attacker.recover_edges(beliefs=[belief] if belief > 0 else None, **({"chunk": chunk} if chunk > 0 else {}))
                 self.attacker.save_recovered()
         if not self.worker.transfer:
             self._eval_split(output, mode)
