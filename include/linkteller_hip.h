@@ -51,7 +51,9 @@ extern "C" {
                             Additive within 5: the wide head of the 3-layer trainer (lt_gcn3_trainer_create_wide, _counts,
                             _attach_validation_wide); no entry point changed.
                             Additive within 5: edge recovery over rows that arrive in chunks (lt_top_stream_*) and lt_pairs_present;
-                            no entry point changed */
+                            no entry point changed.
+                            Additive within 5: the pair list of the 3-layer model (lt_influence3_pairs, _workspace_bytes); no entry
+                            point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -592,6 +594,32 @@ int lt_baseline3_enable_fp64(lt_baseline3 *b, void *stream);
 int lt_influence3_rows_mode(const lt_baseline3 *b, const int32_t *probe_nodes, int32_t n_probe,
                             const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode,
                             float *out, int64_t ldo, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The probe primitive of the 3-layer model over a LIST of pairs: the contract of lt_influence_pairs for a lt_baseline3 handle.
+ * Pairs are grouped by probe: probe i = probe_nodes[i] owns pair_obs[pair_ptr[i] .. pair_ptr[i + 1]), and out[k] is the value
+ * lt_influence3_rows_mode writes at (the probe that owns k, pair_obs[k]) for the same mode, BIT FOR BIT -- levels 1 and 2 of a
+ * probe chunk are the launches of the rows call, and the observed-row kernels run the same per-cell device function for pair k
+ * that the rectangle kernels run for cell (b, j); a lane group finds its probe by a binary search in the chunk's offsets.  A
+ * probe may own no pair, probes may repeat, u == v is allowed, a pair may be listed twice.  probe_nodes / pair_obs / out are
+ * device pointers; out holds n_pairs floats.  pair_ptr is a HOST array of n_probe + 1 int64 offsets: it is validated before
+ * anything is launched (pair_ptr[0] == 0, non-decreasing, pair_ptr[n_probe] == n_pairs, not NULL unless n_pairs == 0:
+ * LT_ERR_INVALID, nothing launched or written), gives every probe chunk its range of pairs by value, and reaches the device by
+ * one stream-ordered copy: pageable memory may be released when the call returns, pinned memory once the stream has passed that
+ * copy.  Modes as in lt_influence3_rows_mode: a narrow handle serves LT_MODE_SPARSE, LT_MODE_DELTA and LT_MODE_FULL (evaluated
+ * as SPARSE: the same quantity for this model); a wide handle LT_MODE_DELTA alone (LT_ERR_UNSUPPORTED otherwise, nothing
+ * enqueued); DELTA needs lt_baseline3_enable_fp64.  n_pairs == 0 or n_probe == 0: LT_OK, nothing launched.  At most
+ * 2^31 - 65537 pairs per call.  Enqueue only, no host synchronisation; node ids checked on the device (LT_ERR_INDEX /
+ * lt_node_check; bad_observe covers pair_obs; a pending flag of an earlier call refuses this one); probes chunked by
+ * "chunk_budget_bytes" exactly as the rows call chunks them.  A chunk whose probes own no pair launches NOTHING: its levels 1
+ * and 2 are skipped with its observed rows.  The workspace holds the level-1 / level-2 tables of one probe chunk, the two checked
+ * lists and the offsets -- nothing of the size of n_probe x (nodes observed):
+ *   lt_influence3_pairs_workspace_bytes(b, P, M) <= lt_influence3_workspace_bytes(b, P, 1) + 4 M + 8 (P + 1) + 512,
+ * whatever nodes the list names.  The query returns 0 for invalid arguments. */
+size_t lt_influence3_pairs_workspace_bytes(const lt_baseline3 *b, int32_t n_probe, int64_t n_pairs);
+int lt_influence3_pairs(const lt_baseline3 *b, const int32_t *probe_nodes, int32_t n_probe,
+                        const int64_t *pair_ptr, const int32_t *pair_obs, int64_t n_pairs,
+                        float delta, int32_t mode, float *out, void *workspace, size_t workspace_bytes,
+                        void *stream);
 
 /* ---- LapGraph cell selection (worker.py:302-335: A += noise, the n_keep largest cells of the strict lower
  * triangle by a 50-way np.argpartition) --------------------------------------------------------------------------------

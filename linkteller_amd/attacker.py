@@ -63,8 +63,8 @@ class Attacker:
             numpy stream is a host loop.
           * ``rng="philox"`` with an ``unbalanced*`` type is a ``ValueError``: its node draw stays on numpy.
         Both need a GPU (``LinkTellerHipError`` without one).  Whatever the device routes do not serve -- the attack methods that
-        write a result file, the naive and baseline attacks on an ``unbalanced*`` sample, a model ``engine.Baseline`` does not
-        serve on the pair-list route, CPU features -- FALLS BACK to the host lists: ``exist_edges`` / ``nonexist_edges`` are
+        write a result file, the naive and baseline attacks on an ``unbalanced*`` sample, a model without a pair-list
+        primitive (``_pair_route``: neither ``engine.Baseline`` nor ``engine.Baseline3`` serves it), CPU features -- FALLS BACK to the host lists: ``exist_edges`` / ``nonexist_edges`` are
         materialised from one download on first access (the arrays the host route builds, element for element, for the
         ``unbalanced*`` types) and everything proceeds as on the host route, raising what it raises there."""
         st = self.args.sample_type
@@ -398,12 +398,32 @@ class Attacker:
         ``pair_scores``)."""
         return self.get_gradient_eps_mat(v)[u]
 
+    def _pair_route(self, mode=None):
+        """The object whose ``influence_pairs`` scores a LIST of pairs for this model and mode, or None where the list has no
+        primitive and the caller takes the rectangle (``_rows``).  The one place that decides it:
+          * a 2-layer model served by ``engine.Baseline`` (lt_influence_pairs), every mode;
+          * a GCN3 with up to 8 classes (``engine.Baseline3``, lt_influence3_pairs), every mode;
+          * a GCN3 with 9 .. 256 classes in ``delta`` (the wide handle; `sparse` / `full` keep the generic loop, as in ``_rows``).
+        None for ``engine.WideBaseline``, generic stacks and CPU features.  The baseline is built or refreshed on the way, as in
+        ``_rows``."""
+        if not self.features.is_cuda:
+            return None
+        kind, sd = self._walk()
+        m = self._mode(mode)
+        if kind == "gcn2":
+            base = self.baseline(m, sd)
+            return base if isinstance(base, engine.Baseline) else None
+        if kind == "gcn3" or (kind == "gcn3w" and m == "delta"):
+            return self.baseline3(sd)
+        return None
+
     def pair_scores(self, probe, observed, mode=None, chunk=1024) -> np.ndarray:
-        """||grad_mat(probe[k])[observed[k]]||_2 for a LIST of pairs, float64 [n_pairs] on the host in input order.  A 2-layer
-        model served by ``engine.Baseline`` goes through ``lt_influence_pairs``: the pairs grouped by probe
-        (``engine.group_pairs``), one call, ONE device-to-host copy of n_pairs floats.  Every other model the attacker accepts
-        (GCN3, ``engine.WideBaseline``, generic stacks) takes ``_rows`` on ``chunk`` probes x the distinct observed nodes of
-        their pairs and gathers -- the same values, through a rectangle."""
+        """||grad_mat(probe[k])[observed[k]]||_2 for a LIST of pairs, float64 [n_pairs] on the host in input order.  A model
+        with a pair-list primitive (``_pair_route``: a 2-layer model served by ``engine.Baseline``, a GCN3 within what
+        ``engine.Baseline3`` serves) goes through ``influence_pairs``: the pairs grouped by probe (``engine.group_pairs``), one
+        call, ONE device-to-host copy of n_pairs floats.  Every other model the attacker accepts (``engine.WideBaseline``,
+        generic stacks, a GCN3 with more than 8 classes outside `delta`) takes ``_pair_scores_rect``: ``_rows`` on ``chunk``
+        probes x the distinct observed nodes of their pairs, gathered -- the same values, through a rectangle."""
         probe = np.asarray(probe, dtype=np.int64).reshape(-1)
         observed = np.asarray(observed, dtype=np.int64).reshape(-1)
         if probe.shape != observed.shape:
@@ -416,15 +436,17 @@ class Attacker:
         if probe.size == 0:
             return scores
         nodes, ptr, obs, order = engine.group_pairs(probe, observed)
-        kind, sd = self._walk()
-        if kind == "gcn2" and self.features.is_cuda:
-            m = self._mode(mode)
-            base = self.baseline(m, sd)
-            if isinstance(base, engine.Baseline):
-                out = base.influence_pairs(nodes, ptr, obs, float(self.args.influence), m)
-                scores[order] = out.cpu().numpy()
-                engine.node_check()
-                return scores
+        base = self._pair_route(mode)
+        if base is not None:
+            out = base.influence_pairs(nodes, ptr, obs, float(self.args.influence), self._mode(mode))
+            scores[order] = out.cpu().numpy()
+            engine.node_check()
+            return scores
+        return self._pair_scores_rect(nodes, ptr, obs, order, scores, mode, chunk)
+
+    def _pair_scores_rect(self, nodes, ptr, obs, order, scores, mode=None, chunk=1024) -> np.ndarray:
+        """The rectangle route of ``pair_scores`` (``engine.group_pairs``' layout in, ``scores`` filled in input order): the
+        fallback of the models without a pair-list primitive, and what the list route is measured against."""
         for c0 in range(0, len(nodes), chunk):
             pc = nodes[c0:c0 + chunk]
             k0, k1 = int(ptr[c0]), int(ptr[c0 + len(pc)])
@@ -529,17 +551,25 @@ class Attacker:
         t = time.time()
         ex = np.asarray(self.exist_edges, dtype=np.int64).reshape(-1, 2)
         nex = np.asarray(self.nonexist_edges, dtype=np.int64).reshape(-1, 2)
-        n = self.worker.n_nodes
         s_ex = np.empty(len(ex)); s_nex = np.empty(len(nex))
-        kind, sd = self._walk()
-        if kind == "gcn2" and self.features.is_cuda and isinstance(self.baseline(None, sd), engine.Baseline):
-            # only the listed pairs are formed (lt_influence_pairs: probe = the first node, observed = the second), and only their
-            # scores cross PCIe -- the rows path below forms chunk x N scores to read a few dozen per row; same bits
+        if self._pair_route() is not None:
+            # only the listed pairs are formed (lt_influence_pairs / lt_influence3_pairs: probe = the first node, observed = the
+            # second), and only their scores cross PCIe -- the rows path forms chunk x N scores to read a few dozen per row; same bits
             s = self.pair_scores(np.concatenate([ex[:, 0], nex[:, 0]]), np.concatenate([ex[:, 1], nex[:, 1]]))
             s_ex[:], s_nex[:] = s[:len(ex)], s[len(ex):]
-            starts = np.empty(0, dtype=np.int64)
         else:
-            starts = np.union1d(ex[:, 0], nex[:, 0])
+            self._balanced_scores_rect(ex, nex, s_ex, s_nex, chunk)
+        print(f"time for predicting edges: {time.time() - t}")
+        # stable sort by the first node reproduces the reference's grouped emission order
+        oe, on = np.argsort(ex[:, 0], kind="stable"), np.argsort(nex[:, 0], kind="stable")
+        self.compute_and_save(list(s_ex[oe]), list(s_nex[on]))
+
+    def _balanced_scores_rect(self, ex, nex, s_ex, s_nex, chunk=1024):
+        """The rectangle route of ``link_prediction_attack_efficient_balanced``: ``chunk`` starting nodes x every node through
+        ``_rows``, each block copied to the host and read at the listed cells into ``s_ex`` / ``s_nex`` (list order).  The fallback
+        of the models without a pair-list primitive, and what the list route is measured against."""
+        n = self.worker.n_nodes
+        starts = np.union1d(ex[:, 0], nex[:, 0])
         all_nodes = np.arange(n, dtype=np.int64)
         pos = np.full(n, -1, dtype=np.int64)
         for c0 in range(0, len(starts), chunk):
@@ -550,10 +580,7 @@ class Attacker:
             for pairs, dst in ((ex, s_ex), (nex, s_nex)):
                 sel = pos[pairs[:, 0]] >= 0
                 dst[sel] = rows[pos[pairs[sel, 0]], pairs[sel, 1]]
-        print(f"time for predicting edges: {time.time() - t}")
-        # stable sort by the first node reproduces the reference's grouped emission order
-        oe, on = np.argsort(ex[:, 0], kind="stable"), np.argsort(nex[:, 0], kind="stable")
-        self.compute_and_save(list(s_ex[oe]), list(s_nex[on]))
+        return s_ex, s_nex
 
     # ------------------------------------------------------------------------------------------
     # recover_edges(chunk=K) / recover_graph: chunk e's rows formed against observed[:e] only (the cells right of the diagonal are
@@ -769,18 +796,15 @@ class Attacker:
         ``pair_scores`` takes that route (the labels permuted as ``engine.group_pairs`` orders the pairs), else from
         ``pair_scores``' host result, uploaded (fp32 values widened on the way down: the narrowing is exact)."""
         dev = self.features.device
-        kind, sd = self._walk()
-        if kind == "gcn2" and self.features.is_cuda:
-            m = self._mode(mode)
-            base = self.baseline(m, sd)
-            if isinstance(base, engine.Baseline):
-                n = int(self.features.shape[0])
-                for ids, what in ((probe, "probe"), (observed, "observed")):
-                    if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= n):
-                        raise IndexError(f"{what}: node id out of range for {n} nodes")
-                nodes, ptr, obs, order = engine.group_pairs(probe, observed)
-                out = base.influence_pairs(nodes, ptr, obs, float(self.args.influence), m)
-                return engine.score_curve(out, torch.from_numpy(np.ascontiguousarray(labels[order])).to(dev))
+        base = self._pair_route(mode)
+        if base is not None:
+            n = int(self.features.shape[0])
+            for ids, what in ((probe, "probe"), (observed, "observed")):
+                if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= n):
+                    raise IndexError(f"{what}: node id out of range for {n} nodes")
+            nodes, ptr, obs, order = engine.group_pairs(probe, observed)
+            out = base.influence_pairs(nodes, ptr, obs, float(self.args.influence), self._mode(mode))
+            return engine.score_curve(out, torch.from_numpy(np.ascontiguousarray(labels[order])).to(dev))
         s = self.pair_scores(probe, observed, mode)
         if not self.features.is_cuda:
             raise LinkTellerHipError("evaluate: the metrics run on the GPU; there is no CPU path")
@@ -789,16 +813,14 @@ class Attacker:
     def _pair_curve_device(self, probe, observed, n_edges, mode=None):
         """``_pair_curve`` for pair lists that live on the device (int32 CUDA tensors, the first ``n_edges`` pairs labelled 1):
         ``engine.group_pairs_device`` + ``Baseline.influence_pairs`` + ``engine.score_curve``, the labels permuted by the device
-        ``order``.  None when the model is not a 2-layer GCN served by ``engine.Baseline`` (the caller takes the host lists)."""
-        kind, sd = self._walk()
-        if kind != "gcn2" or not self.features.is_cuda or probe.numel() == 0:
+        ``order``.  None when the model has no pair-list primitive (``_pair_route``; the caller takes the host lists)."""
+        if not self.features.is_cuda or probe.numel() == 0:
             return None
-        m = self._mode(mode)
-        base = self.baseline(m, sd)
-        if not isinstance(base, engine.Baseline):
+        base = self._pair_route(mode)
+        if base is None:
             return None
         nodes, ptr, obs, order = engine.group_pairs_device(probe, observed, int(self.features.shape[0]))
-        out = base.influence_pairs(nodes, ptr, obs, float(self.args.influence), m)
+        out = base.influence_pairs(nodes, ptr, obs, float(self.args.influence), self._mode(mode))
         labels = torch.zeros(probe.numel(), dtype=torch.uint8, device=probe.device)
         labels[:n_edges] = 1
         return engine.score_curve(out, labels[order.long()])

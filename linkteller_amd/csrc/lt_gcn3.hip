@@ -20,6 +20,10 @@
 // A WIDE class layer (lt_baseline3_create_wide: 9 .. 256 classes, reddit / ppi) is served in LT_MODE_DELTA alone: the class width
 // enters behind the layer-2 kink test, so the chain is the narrow one up to dH2 and the last two steps have wide forms (k3w_* /
 // k3dw_* below).  Its level-2 tables are sized by n rows per probe, as S3x is: large graphs get small probe chunks.
+//
+// A LIST of (probe, observed) pairs (lt_influence3_pairs) takes the same chunk loop: only the last step reads the observed list, so
+// levels 1 and 2 are launched as above and the observed-row kernels have a list form (k*_stageC_pairs) that runs the rectangle's
+// per-cell device function (k3_cellC / k3d_cellC / k3dw_cellC) for pair k -- the bits of the rectangle by construction.
 #include <new>
 
 #include "lt_items.hip.h"
@@ -235,18 +239,27 @@ __global__ __launch_bounds__(LT_BLOCK) void k3_stageB(
     }
 }
 
-// observed rows: out[b][j] = || (A[u,:] S3' + b3 - OUT[u]) / delta ||, 8 lanes per (probe, observed node)
+// The list form of the observed-row kernels (lt_influence3_pairs): a lane group owns pair k of the chunk instead of cell (b, j).  Its
+// probe is the last b with pair_ptr[b] <= k (probes without pairs repeat an offset): a binary search in the chunk's slice of the device
+// copy of the offsets, at most 16 steps (a chunk holds up to 65 534 probes) over lines that every group of the wave shares.  k is the
+// same in all lanes of a group, so the search and everything behind it is group-uniform.
+__device__ __forceinline__ int pair_owner(const int64_t *__restrict__ pair_ptr, int nb, long k) {
+    int lo = 0, hi = nb;      // pair_ptr[lo] <= k < pair_ptr[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pair_ptr[mid] <= k) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// observed rows: out[b][j] = || (A[u,:] S3' + b3 - OUT[u]) / delta ||, 8 lanes per (probe, observed node).  The cell (probe b of the
+// chunk, observed node u) is ONE function for the rectangle and the list kernel: the two differ in how a group finds (b, u) and where
+// lane 0 stores the value, nothing else.
 template <int CP>
-__global__ __launch_bounds__(LT_BLOCK) void k3_stageC(
+__device__ __forceinline__ float k3_cellC(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
-    const float *__restrict__ S3, int C, const float *__restrict__ b3, const float *__restrict__ OUT, int nb, int n,
-    const float *__restrict__ S3x, const uint32_t *__restrict__ bits2, int words, const int32_t *__restrict__ observe,
-    int n_obs, float delta, float *__restrict__ out, long ldo) {
-    const long gid = ((long)blockIdx.x * LT_BLOCK + threadIdx.x) / LT_L2_LANES;
-    const int q = threadIdx.x & (LT_L2_LANES - 1);
-    if (gid >= (long)nb * n_obs) return;
-    const int b = (int)(gid / n_obs), j = (int)(gid % n_obs);
-    const int u = observe[j];
+    const float *__restrict__ S3, int C, const float *__restrict__ b3, const float *__restrict__ OUT, int n,
+    const float *__restrict__ S3x, const uint32_t *__restrict__ bits2, int words, float delta, int b, int u, int q) {
     const uint32_t *mb = bits2 + (size_t)b * words;
     const float *mine = S3x + (size_t)b * n * C;
     const int e0 = rowptr[u], e1 = rowptr[u + 1];
@@ -263,7 +276,34 @@ __global__ __launch_bounds__(LT_BLOCK) void k3_stageC(
                      [&](int c, int) { return member(c) ? mine + (size_t)c * C : S3 + (size_t)c * C; }, acc);
         res = diff_norm<CP>(acc, b3, OUT + (size_t)u * C, C, delta);
     }
+    return res;
+}
+template <int CP>
+__global__ __launch_bounds__(LT_BLOCK) void k3_stageC(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+    const float *__restrict__ S3, int C, const float *__restrict__ b3, const float *__restrict__ OUT, int nb, int n,
+    const float *__restrict__ S3x, const uint32_t *__restrict__ bits2, int words, const int32_t *__restrict__ observe,
+    int n_obs, float delta, float *__restrict__ out, long ldo) {
+    const long gid = ((long)blockIdx.x * LT_BLOCK + threadIdx.x) / LT_L2_LANES;
+    const int q = threadIdx.x & (LT_L2_LANES - 1);
+    if (gid >= (long)nb * n_obs) return;
+    const int b = (int)(gid / n_obs), j = (int)(gid % n_obs);
+    const float res = k3_cellC<CP>(rowptr, col, val, S3, C, b3, OUT, n, S3x, bits2, words, delta, b, observe[j], q);
     if (q == 0) out[(long)b * ldo + j] = res;
+}
+// the list form: pairs k0 .. k1 of the call are the chunk's (pair_ptr = the chunk's slice of the offsets, nb + 1 of them)
+template <int CP>
+__global__ __launch_bounds__(LT_BLOCK) void k3_stageC_pairs(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+    const float *__restrict__ S3, int C, const float *__restrict__ b3, const float *__restrict__ OUT, int nb, int n,
+    const float *__restrict__ S3x, const uint32_t *__restrict__ bits2, int words, const int64_t *__restrict__ pair_ptr, long k0,
+    long k1, const int32_t *__restrict__ pair_obs, float delta, float *__restrict__ out) {
+    const long k = k0 + ((long)blockIdx.x * LT_BLOCK + threadIdx.x) / LT_L2_LANES;
+    const int q = threadIdx.x & (LT_L2_LANES - 1);
+    if (k >= k1) return;                                            // (group-uniform)
+    const int b = pair_owner(pair_ptr, nb, k);
+    const float res = k3_cellC<CP>(rowptr, col, val, S3, C, b3, OUT, n, S3x, bits2, words, delta, b, pair_obs[k], q);
+    if (q == 0) out[k] = res;
 }
 
 // ---- exact propagation (LT_MODE_DELTA) for three layers ---------------------------------------------------------------
@@ -390,16 +430,11 @@ __global__ __launch_bounds__(LT_BLOCK) void k3d_stageB(
     }
 }
 
+// (the cell is one function for the rectangle and the list kernel, as k3_cellC)
 template <int CP>
-__global__ __launch_bounds__(LT_BLOCK) void k3d_stageC(
-    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int C, int nb, int n,
-    const float *__restrict__ dS3x, const uint32_t *__restrict__ bits2, int words, const int32_t *__restrict__ observe,
-    int n_obs, float delta, float *__restrict__ out, long ldo) {
-    const long gid = ((long)blockIdx.x * LT_BLOCK + threadIdx.x) / LT_L2_LANES;
-    const int q = threadIdx.x & (LT_L2_LANES - 1);
-    if (gid >= (long)nb * n_obs) return;
-    const int b = (int)(gid / n_obs), j = (int)(gid % n_obs);
-    const int u = observe[j];
+__device__ __forceinline__ float k3d_cellC(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int C, int n,
+    const float *__restrict__ dS3x, const uint32_t *__restrict__ bits2, int words, float delta, int b, int u, int q) {
     const uint32_t *mb = bits2 + (size_t)b * words;
     const float *mine = dS3x + (size_t)b * n * C;
     const int e0 = rowptr[u], e1 = rowptr[u + 1];
@@ -416,7 +451,31 @@ __global__ __launch_bounds__(LT_BLOCK) void k3d_stageC(
             const float d = acc[c] / delta;
             ss = fmaf(d, d, ss);
         }
-    if (q == 0) out[(long)b * ldo + j] = sqrtf(ss);
+    return sqrtf(ss);
+}
+template <int CP>
+__global__ __launch_bounds__(LT_BLOCK) void k3d_stageC(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int C, int nb, int n,
+    const float *__restrict__ dS3x, const uint32_t *__restrict__ bits2, int words, const int32_t *__restrict__ observe,
+    int n_obs, float delta, float *__restrict__ out, long ldo) {
+    const long gid = ((long)blockIdx.x * LT_BLOCK + threadIdx.x) / LT_L2_LANES;
+    const int q = threadIdx.x & (LT_L2_LANES - 1);
+    if (gid >= (long)nb * n_obs) return;
+    const int b = (int)(gid / n_obs), j = (int)(gid % n_obs);
+    const float res = k3d_cellC<CP>(rowptr, col, val, C, n, dS3x, bits2, words, delta, b, observe[j], q);
+    if (q == 0) out[(long)b * ldo + j] = res;
+}
+template <int CP>
+__global__ __launch_bounds__(LT_BLOCK) void k3d_stageC_pairs(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int C, int nb, int n,
+    const float *__restrict__ dS3x, const uint32_t *__restrict__ bits2, int words, const int64_t *__restrict__ pair_ptr, long k0,
+    long k1, const int32_t *__restrict__ pair_obs, float delta, float *__restrict__ out) {
+    const long k = k0 + ((long)blockIdx.x * LT_BLOCK + threadIdx.x) / LT_L2_LANES;
+    const int q = threadIdx.x & (LT_L2_LANES - 1);
+    if (k >= k1) return;                                            // (group-uniform)
+    const int b = pair_owner(pair_ptr, nb, k);
+    const float res = k3d_cellC<CP>(rowptr, col, val, C, n, dS3x, bits2, words, delta, b, pair_obs[k], q);
+    if (q == 0) out[k] = res;
 }
 
 // ---- LT_MODE_DELTA with a wide class layer (lt_baseline3_create_wide, C <= 256) ------------------------------------------------------
@@ -552,19 +611,14 @@ __global__ __launch_bounds__(LT_BLOCK) void k3dw_stageB(
 // then d = acc / delta, the lane's squares in column order, the lanes by the fixed butterfly, sqrt.  A cell no path reaches
 // sums nothing: 0 / delta, fma, sqrt = +0.  (Columns C .. Cp of dS3x are never written: what they hold is carried along and
 // left out of the squares.)
+// (The cell is one function for the rectangle and the list kernel, as k3_cellC; every lane of the group returns the group's value.)
 template <int LPR>
-__global__ __launch_bounds__(LT_BLOCK) void k3dw_stageC(
-    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int C, int Cp, int nb,
-    const float *__restrict__ dS3x, const uint2 *__restrict__ rank2, int words, const int32_t *__restrict__ off2,
-    const int32_t *__restrict__ observe, int n_obs, float delta, float *__restrict__ out, long ldo) {
-    const int lane = threadIdx.x & 63;
-    const int gl = lane & (LPR - 1), gbase = lane & ~(LPR - 1);
+__device__ __forceinline__ float k3dw_cellC(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int C, int Cp,
+    const float *__restrict__ dS3x, const uint2 *__restrict__ rank2, int words, const int32_t *__restrict__ off2, float delta, int b,
+    int u, int gl, int gbase) {
     const int coff = 4 * gl;
     const bool active = coff < Cp;
-    const long cell = ((long)blockIdx.x * LT_BLOCK + threadIdx.x) / LPR;
-    if (cell >= (long)nb * n_obs) return;                           // (group-uniform)
-    const int b = (int)(cell / n_obs), j = (int)(cell % n_obs);
-    const int u = observe[j];
     const uint2 *mb = rank2 + (size_t)b * words;
     const float *mine = dS3x + (size_t)off2[b] * Cp;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -595,7 +649,34 @@ __global__ __launch_bounds__(LT_BLOCK) void k3dw_stageC(
             ss = fmaf(d, d, ss);
         }
     ss = group_sum<LPR>(ss);
-    if (gl == 0) out[(long)b * ldo + j] = sqrtf(ss);
+    return sqrtf(ss);
+}
+template <int LPR>
+__global__ __launch_bounds__(LT_BLOCK) void k3dw_stageC(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int C, int Cp, int nb,
+    const float *__restrict__ dS3x, const uint2 *__restrict__ rank2, int words, const int32_t *__restrict__ off2,
+    const int32_t *__restrict__ observe, int n_obs, float delta, float *__restrict__ out, long ldo) {
+    const int lane = threadIdx.x & 63;
+    const int gl = lane & (LPR - 1), gbase = lane & ~(LPR - 1);
+    const long cell = ((long)blockIdx.x * LT_BLOCK + threadIdx.x) / LPR;
+    if (cell >= (long)nb * n_obs) return;                           // (group-uniform)
+    const int b = (int)(cell / n_obs), j = (int)(cell % n_obs);
+    const float res = k3dw_cellC<LPR>(rowptr, col, val, C, Cp, dS3x, rank2, words, off2, delta, b, observe[j], gl, gbase);
+    if (gl == 0) out[(long)b * ldo + j] = res;
+}
+template <int LPR>
+__global__ __launch_bounds__(LT_BLOCK) void k3dw_stageC_pairs(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int C, int Cp, int nb,
+    const float *__restrict__ dS3x, const uint2 *__restrict__ rank2, int words, const int32_t *__restrict__ off2,
+    const int64_t *__restrict__ pair_ptr, long k0, long k1, const int32_t *__restrict__ pair_obs, float delta,
+    float *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int gl = lane & (LPR - 1), gbase = lane & ~(LPR - 1);
+    const long k = k0 + ((long)blockIdx.x * LT_BLOCK + threadIdx.x) / LPR;
+    if (k >= k1) return;                                            // (group-uniform)
+    const int b = pair_owner(pair_ptr, nb, k);
+    const float res = k3dw_cellC<LPR>(rowptr, col, val, C, Cp, dS3x, rank2, words, off2, delta, b, pair_obs[k], gl, gbase);
+    if (gl == 0) out[k] = res;
 }
 
 __global__ void k3w_pad_b3(const float *__restrict__ b3, int C, int Cp, float *__restrict__ b3p) {
@@ -839,6 +920,7 @@ struct infl3_ws {
     uint32_t *bits2;
     int2 *items2;
     int32_t *probes_s, *obs_s;    // the call's lists, every id checked against [0, n) (lt_items.hip.h k_check_nodes)
+    int64_t *pair_ptr;            // lt_influence3_pairs: the device copy of pair_ptr [n_probe + 1] (obs_s is then [n_pairs])
     // a wide handle (delta only; S3x = dS3x [items2, Cp]): the level-2 bitmap with positions, the probes' counts and offsets, dH2x
     uint2 *rank2;
     int32_t *cnt2, *off2;
@@ -849,7 +931,9 @@ struct infl3_ws {
 
 static int probe_kslice3(const lt_baseline3 *b) { return lt_gemm_pick_kslice(b->n, b->H1, b->F); }
 
-static infl3_ws carve3(void *base, const lt_baseline3 *b, int n_probe, int n_obs) {
+// n_pairs >= 0: the carve of lt_influence3_pairs (n_obs = 0) -- the checked observed list is sized by the pair list and the offsets'
+// device copy follows it; the chunk and every per-chunk table are those of the rows call
+static infl3_ws carve3(void *base, const lt_baseline3 *b, int n_probe, int n_obs, int64_t n_pairs = -1) {
     infl3_ws w = {};
     const size_t n = (size_t)b->n, C = (size_t)b->C, Hp1 = (size_t)b->Hp1, Hp2 = (size_t)b->Hp2;
     const size_t maxc = (size_t)(b->g->max_col_nnz > 0 ? b->g->max_col_nnz : 1);
@@ -890,7 +974,8 @@ static infl3_ws carve3(void *base, const lt_baseline3 *b, int n_probe, int n_obs
         w.dH2x = (float *)take(chunk * n * Hp2 * sizeof(float));
         w.S3x = (float *)take(chunk * n * Cp * sizeof(float));
         w.probes_s = (int32_t *)take((size_t)(n_probe > 0 ? n_probe : 1) * sizeof(int32_t));
-        w.obs_s = (int32_t *)take((size_t)(n_obs > 0 ? n_obs : 1) * sizeof(int32_t));
+        w.obs_s = (int32_t *)take((n_pairs >= 0 ? (size_t)n_pairs : (size_t)(n_obs > 0 ? n_obs : 1)) * sizeof(int32_t));
+        if (n_pairs >= 0) w.pair_ptr = (int64_t *)take(((size_t)n_probe + 1) * sizeof(int64_t));
         w.bytes = offb;
         return w;
     }
@@ -906,7 +991,8 @@ static infl3_ws carve3(void *base, const lt_baseline3 *b, int n_probe, int n_obs
     w.items2 = (int2 *)take(chunk * n * sizeof(int2));
     w.S3x = (float *)take(chunk * n * C * sizeof(float));
     w.probes_s = (int32_t *)take((size_t)(n_probe > 0 ? n_probe : 1) * sizeof(int32_t));
-    w.obs_s = (int32_t *)take((size_t)(n_obs > 0 ? n_obs : 1) * sizeof(int32_t));
+    w.obs_s = (int32_t *)take((n_pairs >= 0 ? (size_t)n_pairs : (size_t)(n_obs > 0 ? n_obs : 1)) * sizeof(int32_t));
+    if (n_pairs >= 0) w.pair_ptr = (int64_t *)take(((size_t)n_probe + 1) * sizeof(int64_t));
     w.bytes = offb;
     return w;
 }
@@ -918,8 +1004,17 @@ extern "C" size_t lt_influence3_workspace_bytes(const lt_baseline3 *b, int32_t n
 
 // The probe chunks of a wide handle (LT_MODE_DELTA; the lists are the checked ones, the fp64 pre-activations are fresh): level 1
 // as for a narrow handle, then the wide forms of the last two steps (k3w_rank2 ... k3dw_stageC above).  Enqueue only.
+// The caller's pair list (lt_influence3_pairs).  A call with one has no observe list (n_obs = 0): observe_nodes is the checked pair_obs,
+// and only the last step of a chunk -- the observed rows -- reads it.
+struct lt_pairs3_job {
+    const int64_t *ptr;      // HOST [n_probe + 1], validated by the caller
+    const int32_t *obs;      // device [n_pairs]
+    int64_t n_pairs;
+};
+
 static int influence3_wide_chunks(const lt_baseline3 *b, const infl3_ws &w, const int32_t *probe_nodes, int n_probe,
-                                  const int32_t *observe_nodes, int n_obs, float delta, float *out, int64_t ldo, hipStream_t st) {
+                                  const int32_t *observe_nodes, int n_obs, float delta, float *out, int64_t ldo, hipStream_t st,
+                                  const lt_pairs3_job *pj) {
     const lt_graph *g = b->g;
     const int n = b->n, C = b->C, Cp = b->Cp, Hp1 = b->Hp1, Hp2 = b->Hp2;
     const int lpr1 = lt_lpr_for(Hp1), lpr2 = lt_lpr_for(Hp2), lprc = lt_lpr_for(Cp);
@@ -929,8 +1024,14 @@ static int influence3_wide_chunks(const lt_baseline3 *b, const infl3_ws &w, cons
         const int nb = (n_probe - p0) < w.chunk ? (n_probe - p0) : w.chunk;
         const int32_t *probes = probe_nodes + p0;
         float *orow = out + (int64_t)p0 * ldo;
-        LT_REQUIRE(((long)nb * n_obs * lprc + LT_BLOCK - 1) / LT_BLOCK < 2147483647L,
-                   "lt_influence3_rows: %d probes x %d observed nodes per chunk exceed the grid limit", nb, n_obs);
+        // (a pair list: the chunk's pairs by value; a chunk whose probes own none is skipped whole, levels 1 and 2 included)
+        const long k0 = pj ? (long)pj->ptr[p0] : 0L, k1 = pj ? (long)pj->ptr[p0 + nb] : 0L;
+        if (pj && k0 == k1) continue;
+        const long cells = pj ? k1 - k0 : (long)nb * n_obs;
+        if (pj) LT_REQUIRE((cells * lprc + LT_BLOCK - 1) / LT_BLOCK < 2147483647L,
+                           "lt_influence3_pairs: %ld pairs per chunk of %d probes exceed the grid limit", cells, nb);
+        else LT_REQUIRE((cells * lprc + LT_BLOCK - 1) / LT_BLOCK < 2147483647L,
+                        "lt_influence3_rows: %d probes x %d observed nodes per chunk exceed the grid limit", nb, n_obs);
         const long m_bound = (long)nb * maxc, m2_bound = (long)nb * n;
         LT_REQUIRE(m_bound < 2147483647L && m2_bound < 2147483647L,
                    "lt_influence3_rows: %d probes x %ld rows per chunk exceed the grid limit", nb, maxc > n ? maxc : (long)n);
@@ -966,10 +1067,16 @@ static int influence3_wide_chunks(const lt_baseline3 *b, const infl3_ws &w, cons
         rc = lt_launch_gemm_mdev(w.dH2x, Hp2, b->W3, C, w.S3x, Cp, (int)m2_bound, w.off2 + nb, C, b->H2, st);
         if (rc) return rc;
         // level 3: the observed rows
-        const unsigned gridC = (unsigned)(((long)nb * n_obs * lprc + LT_BLOCK - 1) / LT_BLOCK);
-        LT_DISPATCH_LPR(lprc, hipLaunchKernelGGL((k3dw_stageC<LPR_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
-                                                 C, Cp, nb, w.S3x, w.rank2, words, w.off2, observe_nodes, n_obs, delta, orow,
-                                                 (long)ldo));
+        const unsigned gridC = (unsigned)((cells * lprc + LT_BLOCK - 1) / LT_BLOCK);
+        if (pj) {
+            LT_DISPATCH_LPR(lprc, hipLaunchKernelGGL((k3dw_stageC_pairs<LPR_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col,
+                                                     g->val, C, Cp, nb, w.S3x, w.rank2, words, w.off2, w.pair_ptr + p0, k0, k1,
+                                                     observe_nodes, delta, out));
+        } else {
+            LT_DISPATCH_LPR(lprc, hipLaunchKernelGGL((k3dw_stageC<LPR_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
+                                                     C, Cp, nb, w.S3x, w.rank2, words, w.off2, observe_nodes, n_obs, delta, orow,
+                                                     (long)ldo));
+        }
         LT_CHECK_LAUNCH();
     }
     return LT_OK;
@@ -982,9 +1089,45 @@ extern "C" int lt_influence3_rows(const lt_baseline3 *b, const int32_t *probe_no
                                    workspace_bytes, stream);
 }
 
+static int influence3_impl(const lt_baseline3 *b, const int32_t *probe_nodes, int32_t n_probe, const int32_t *observe_nodes,
+                           int32_t n_obs, float delta, int32_t mode, float *out, int64_t ldo, void *workspace, size_t workspace_bytes,
+                           void *stream, const lt_pairs3_job *pj);
+
 extern "C" int lt_influence3_rows_mode(const lt_baseline3 *b, const int32_t *probe_nodes, int32_t n_probe,
                                        const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode, float *out,
                                        int64_t ldo, void *workspace, size_t workspace_bytes, void *stream) {
+    return influence3_impl(b, probe_nodes, n_probe, observe_nodes, n_obs, delta, mode, out, ldo, workspace, workspace_bytes, stream,
+                           nullptr);
+}
+
+// ---- lt_influence3_pairs (include/linkteller_hip.h): the scores of a LIST of (probe, observed) pairs, grouped by probe -----------
+extern "C" size_t lt_influence3_pairs_workspace_bytes(const lt_baseline3 *b, int32_t n_probe, int64_t n_pairs) {
+    if (!b || n_probe < 0 || n_pairs < 0 || n_pairs > LT_PAIRS_MAX) return 0;
+    return carve3(nullptr, b, n_probe, 0, n_pairs).bytes;
+}
+extern "C" int lt_influence3_pairs(const lt_baseline3 *b, const int32_t *probe_nodes, int32_t n_probe, const int64_t *pair_ptr,
+                                   const int32_t *pair_obs, int64_t n_pairs, float delta, int32_t mode, float *out,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+    LT_REQUIRE(b != nullptr, "lt_influence3_pairs: baseline is NULL");
+    LT_REQUIRE(n_probe >= 0 && n_pairs >= 0, "lt_influence3_pairs: negative count");
+    LT_REQUIRE(n_pairs <= LT_PAIRS_MAX, "lt_influence3_pairs: %lld pairs (at most %lld per call)", (long long)n_pairs, (long long)LT_PAIRS_MAX);
+    // the offsets, on the host, before anything is launched
+    LT_REQUIRE(pair_ptr != nullptr || n_pairs == 0, "lt_influence3_pairs: pair_ptr is NULL");
+    if (pair_ptr) {
+        LT_REQUIRE(pair_ptr[0] == 0, "lt_influence3_pairs: pair_ptr[0] = %lld, not 0", (long long)pair_ptr[0]);
+        for (int32_t i = 0; i < n_probe; ++i)
+            LT_REQUIRE(pair_ptr[i + 1] >= pair_ptr[i], "lt_influence3_pairs: pair_ptr decreases at probe %d", i);
+        LT_REQUIRE(pair_ptr[n_probe] == n_pairs, "lt_influence3_pairs: pair_ptr[n_probe] = %lld, n_pairs = %lld",
+                   (long long)pair_ptr[n_probe], (long long)n_pairs);
+    }
+    // (FULL names the quantity SPARSE computes for this model: lt_influence3_rows_mode evaluates both by the same launches)
+    const lt_pairs3_job pj = {pair_ptr, pair_obs, n_pairs};
+    return influence3_impl(b, probe_nodes, n_probe, nullptr, 0, delta, mode, out, 0, workspace, workspace_bytes, stream, &pj);
+}
+
+static int influence3_impl(const lt_baseline3 *b, const int32_t *probe_nodes, int32_t n_probe, const int32_t *observe_nodes,
+                           int32_t n_obs, float delta, int32_t mode, float *out, int64_t ldo, void *workspace, size_t workspace_bytes,
+                           void *stream, const lt_pairs3_job *pj) {
     LT_REQUIRE(b != nullptr, "lt_influence3_rows: baseline is NULL");
     lt_prof_call prof_call_;
     LT_REQUIRE(mode == LT_MODE_SPARSE || mode == LT_MODE_FULL || mode == LT_MODE_DELTA, "lt_influence3_rows_mode: unknown mode %d", mode);
@@ -995,25 +1138,34 @@ extern "C" int lt_influence3_rows_mode(const lt_baseline3 *b, const int32_t *pro
     LT_REQUIRE(!exact || b->Z2d != nullptr, "lt_influence3_rows_mode: LT_MODE_DELTA needs lt_baseline3_enable_fp64");
     LT_REQUIRE(n_probe >= 0 && n_obs >= 0, "lt_influence3_rows: negative count");
     LT_REQUIRE(delta != 0.f && delta == delta, "lt_influence3_rows: delta must be a non-zero number");
-    if (n_probe == 0 || n_obs == 0) return LT_OK;
-    LT_REQUIRE(probe_nodes && observe_nodes && out, "lt_influence3_rows: NULL pointer");
-    LT_REQUIRE(ldo >= n_obs, "lt_influence3_rows: ldo=%lld < n_obs=%d", (long long)ldo, n_obs);
+    if (n_probe == 0 || (pj ? pj->n_pairs == 0 : n_obs == 0)) return LT_OK;
+    if (pj) {
+        LT_REQUIRE(probe_nodes && pj->obs && out, "lt_influence3_pairs: NULL pointer");
+        observe_nodes = pj->obs;
+    } else {
+        LT_REQUIRE(probe_nodes && observe_nodes && out, "lt_influence3_rows: NULL pointer");
+        LT_REQUIRE(ldo >= n_obs, "lt_influence3_rows: ldo=%lld < n_obs=%d", (long long)ldo, n_obs);
+    }
     LT_REQUIRE(b->n > 0, "lt_influence3_rows: empty graph");
     { const int rc = lt_node_err_pending(); if (rc) return rc; }     // an earlier call's list held an id out of range
-    const size_t need = lt_influence3_workspace_bytes(b, n_probe, n_obs);
+    const size_t need = pj ? lt_influence3_pairs_workspace_bytes(b, n_probe, pj->n_pairs) : lt_influence3_workspace_bytes(b, n_probe, n_obs);
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 256))
-        return lt_set_error(LT_ERR_WORKSPACE, "lt_influence3_rows: workspace needs %zu bytes, 256-byte aligned", need);
+        return lt_set_error(LT_ERR_WORKSPACE, "%s: workspace needs %zu bytes, 256-byte aligned",
+                            pj ? "lt_influence3_pairs" : "lt_influence3_rows", need);
     hipStream_t st = (hipStream_t)stream;
     const lt_graph *g = b->g;
-    const infl3_ws w = carve3(workspace, b, n_probe, n_obs);
+    const infl3_ws w = carve3(workspace, b, n_probe, n_obs, pj ? pj->n_pairs : (int64_t)-1);
     const int n = b->n, C = b->C, Hp1 = b->Hp1, Hp2 = b->Hp2, cp = lt_cp_for(C);
     {   // node ids: both lists checked into the workspace (the first reader is a GEMM that gathers X[probes])
-        const long tot = (long)n_probe + n_obs;
+        // (a pair list: pair_obs is the observed list of the check -- LT_PAIRS_MAX keeps the two counts' sum an int -- and the offsets go
+        // to the device behind it by one stream-ordered copy)
+        const long n_list = pj ? (long)pj->n_pairs : (long)n_obs, tot = (long)n_probe + n_list;
         hipLaunchKernelGGL(k_check_nodes, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, probe_nodes, n_probe, observe_nodes,
-                           n_obs, n, w.probes_s, w.obs_s, lt_node_err_dev());
+                           (int)n_list, n, w.probes_s, w.obs_s, lt_node_err_dev());
         LT_CHECK_LAUNCH();
         probe_nodes = w.probes_s;
         observe_nodes = w.obs_s;
+        if (pj) LT_HIP(hipMemcpyAsync(w.pair_ptr, pj->ptr, ((size_t)n_probe + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     }
     const int lpr1 = lt_lpr_for(Hp1), lpr2 = lt_lpr_for(Hp2);
     const int words = (n + 31) / 32;
@@ -1022,13 +1174,19 @@ extern "C" int lt_influence3_rows_mode(const lt_baseline3 *b, const int32_t *pro
         const int rc = exact ? ensure3_fp64(b, st) : ensure3_fp32(b, st);
         if (rc) return rc;
     }
-    if (b->wide) return influence3_wide_chunks(b, w, probe_nodes, n_probe, observe_nodes, n_obs, delta, out, ldo, st);
+    if (b->wide) return influence3_wide_chunks(b, w, probe_nodes, n_probe, observe_nodes, n_obs, delta, out, ldo, st, pj);
     for (int p0 = 0; p0 < n_probe; p0 += w.chunk) {
         const int nb = (n_probe - p0) < w.chunk ? (n_probe - p0) : w.chunk;
         const int32_t *probes = probe_nodes + p0;
         float *orow = out + (int64_t)p0 * ldo;
-        LT_REQUIRE(((long)nb * n_obs * LT_L2_LANES + LT_BLOCK - 1) / LT_BLOCK < 2147483647L,
-                   "lt_influence3_rows: %d probes x %d observed nodes per chunk exceed the grid limit", nb, n_obs);
+        // (a pair list: the chunk's pairs by value; a chunk whose probes own none is skipped whole, levels 1 and 2 included)
+        const long k0 = pj ? (long)pj->ptr[p0] : 0L, k1 = pj ? (long)pj->ptr[p0 + nb] : 0L;
+        if (pj && k0 == k1) continue;
+        const long cells = pj ? k1 - k0 : (long)nb * n_obs;
+        if (pj) LT_REQUIRE((cells * LT_L2_LANES + LT_BLOCK - 1) / LT_BLOCK < 2147483647L,
+                           "lt_influence3_pairs: %ld pairs per chunk of %d probes exceed the grid limit", cells, nb);
+        else LT_REQUIRE((cells * LT_L2_LANES + LT_BLOCK - 1) / LT_BLOCK < 2147483647L,
+                        "lt_influence3_rows: %d probes x %d observed nodes per chunk exceed the grid limit", nb, n_obs);
         const long m_bound = (long)nb * maxc;
         LT_REQUIRE(m_bound < 2147483647L, "lt_influence3_rows: %d probes x %ld rows per chunk exceed the grid limit", nb, maxc);
         int rc;
@@ -1073,23 +1231,35 @@ extern "C" int lt_influence3_rows_mode(const lt_baseline3 *b, const int32_t *pro
         LT_CHECK_LAUNCH();
         hipLaunchKernelGGL(k3_list2, dim3((unsigned)nb), dim3(LT_BLOCK), 0, st, words, w.bits2, w.items2, w.n_items2);
         LT_CHECK_LAUNCH();
-        const unsigned gridC = (unsigned)(((long)nb * n_obs * LT_L2_LANES + LT_BLOCK - 1) / LT_BLOCK);
+        const unsigned gridC = (unsigned)((cells * LT_L2_LANES + LT_BLOCK - 1) / LT_BLOCK);
         if (!exact) {
             LT_DISPATCH_LPR(lpr2, LT_DISPATCH_CP(cp,
                 hipLaunchKernelGGL((k3_stageB<LPR_, CP_>), dim3(LT3_GRID), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val, b->S2,
                                    Hp2, b->b2p, b->W3p, C, w.off, w.S2x, w.bits1, words, w.items2, w.n_items2, n, w.S3x)));
             LT_CHECK_LAUNCH();
             // level 3: observed rows
-            LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k3_stageC<CP_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
-                                                  b->S3, C, b->b3, b->OUT, nb, n, w.S3x, w.bits2, words, observe_nodes, n_obs,
-                                                  delta, orow, (long)ldo));
+            if (pj) {
+                LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k3_stageC_pairs<CP_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col,
+                                                      g->val, b->S3, C, b->b3, b->OUT, nb, n, w.S3x, w.bits2, words, w.pair_ptr + p0,
+                                                      k0, k1, observe_nodes, delta, out));
+            } else {
+                LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k3_stageC<CP_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
+                                                      b->S3, C, b->b3, b->OUT, nb, n, w.S3x, w.bits2, words, observe_nodes, n_obs,
+                                                      delta, orow, (long)ldo));
+            }
         } else {
             LT_DISPATCH_LPR(lpr2, LT_DISPATCH_CP(cp,
                 hipLaunchKernelGGL((k3d_stageB<LPR_, CP_>), dim3(LT3_GRID), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val, b->Z2d,
                                    Hp2, b->W3p, C, w.off, w.S2x, w.bits1, words, w.items2, w.n_items2, n, w.S3x)));
             LT_CHECK_LAUNCH();
-            LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k3d_stageC<CP_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
-                                                  C, nb, n, w.S3x, w.bits2, words, observe_nodes, n_obs, delta, orow, (long)ldo));
+            if (pj) {
+                LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k3d_stageC_pairs<CP_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col,
+                                                      g->val, C, nb, n, w.S3x, w.bits2, words, w.pair_ptr + p0, k0, k1, observe_nodes,
+                                                      delta, out));
+            } else {
+                LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k3d_stageC<CP_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
+                                                      C, nb, n, w.S3x, w.bits2, words, observe_nodes, n_obs, delta, orow, (long)ldo));
+            }
         }
         LT_CHECK_LAUNCH();
     }

@@ -2489,7 +2489,7 @@ struct lt_compact_out {
 // lt_influence_pairs: the caller's pair list.  A call with one has no observe list (observe_nodes = NULL, n_obs = 0): stage A runs as
 // in every other call on the item route -- no fused records, no pair marks, no per-row stage B, no hub blocks, all of which are keyed
 // by an observe list -- and stage B is k_pair_stageB writing out[k].
-#define LT_PAIRS_MAX ((int64_t)2147483647 - 65536)      // the list's check shares a launch (and its int counts) with the probes'
+// (LT_PAIRS_MAX, lt_internal.h: the list's check shares a launch -- and its int counts -- with the probes')
 struct lt_pairs_job {
     const int64_t *ptr;      // HOST [n_probe + 1], validated by the caller
     const int32_t *obs;      // device [n_pairs]

@@ -346,6 +346,8 @@ struct lt_prof_scope {
 // clamped), and the entry check of the probe primitives (LT_ERR_INDEX when an earlier call raised a flag)
 int32_t *lt_node_err_dev();
 int lt_node_err_pending();
+// lt_influence_pairs / lt_influence3_pairs: pairs per call
+#define LT_PAIRS_MAX ((int64_t)2147483647 - 65536)      // the list's check shares a launch (and its int counts) with the probes'
 
 int lt_baseline_refresh_fp64(lt_baseline *b, hipStream_t st);
 // what a call needs of the baseline, recomputed here if lt_baseline_refresh marked it stale: need_fp32 = S1 and the

@@ -1173,6 +1173,43 @@ class Baseline3:
                    "lt_influence3_rows_mode")
         return out
 
+    def influence_pairs(self, probe_nodes, pair_ptr, pair_obs, delta: float, mode="delta", out=None) -> torch.Tensor:
+        """[n_pairs] fp32 on the device: ``Baseline.influence_pairs`` for the 3-layer model (lt_influence3_pairs).  Probe i =
+        ``probe_nodes[i]`` owns ``pair_obs[pair_ptr[i]:pair_ptr[i + 1]]`` and ``out[k]`` is what ``influence_rows`` writes at
+        (that probe, ``pair_obs[k]``) for the same mode, bit for bit -- without the rectangle: the output and the workspace are
+        sized by the list.  ``pair_ptr`` is a HOST array of n_probe + 1 int64 offsets (validated by the library before anything
+        is launched).  Modes as in ``influence_rows``: a wide handle serves ``delta`` alone."""
+        import numpy as np
+        m = _lib.MODES[mode] if isinstance(mode, str) else int(mode)
+        if self.wide and m != _lib.MODE_DELTA:
+            raise NotImplementedError(f"a GCN3 with {self.c} classes is served in mode 'delta' only (lt_baseline3_create_wide); "
+                                      "its fp32 finite difference is Attacker._rows_generic")
+        dev = self.x.device
+        probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
+        obs = _as_nodes(pair_obs, self.n, dev, "pair_obs")
+        if isinstance(pair_ptr, torch.Tensor):
+            pair_ptr = pair_ptr.cpu().numpy()
+        ptr = np.ascontiguousarray(np.asarray(pair_ptr).reshape(-1), dtype=np.int64)
+        npb, npairs = probes.numel(), obs.numel()
+        if ptr.size != npb + 1:
+            raise ValueError(f"pair_ptr must hold n_probe + 1 = {npb + 1} offsets, got {ptr.size}")
+        if m == _lib.MODE_DELTA and not self._fp64:
+            self.enable_fp64()
+        if out is None:
+            out = torch.empty((npairs,), dtype=torch.float32, device=dev)
+        elif out.shape != (npairs,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError("out must be a contiguous float32 [n_pairs] tensor on the baseline's device")
+        key = ("pairs", npb, npairs)
+        need = _lib.lib().lt_influence3_pairs_workspace_bytes(self._h, npb, npairs)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _workspace(need, dev)
+            self._ws = {key: ws}
+        _lib.check(_lib.lib().lt_influence3_pairs(self._h, probes.data_ptr(), npb, ptr.ctypes.data, obs.data_ptr(), npairs,
+                                                  float(delta), m, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                   "lt_influence3_pairs")
+        return out
+
 
 def group_pairs(probe, observed):
     """Two equal-length id arrays in any order -> ``(probe_nodes, pair_ptr, pair_obs, order)``, the grouped layout of
