@@ -53,7 +53,9 @@ extern "C" {
                             Additive within 5: edge recovery over rows that arrive in chunks (lt_top_stream_*) and lt_pairs_present;
                             no entry point changed.
                             Additive within 5: the pair list of the 3-layer model (lt_influence3_pairs, _workspace_bytes); no entry
-                            point changed */
+                            point changed.
+                            Additive within 5: the 2-layer model with a wide class layer through one handle (lt_baseline2w_*,
+                            lt_influence2w_*); no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -620,6 +622,53 @@ int lt_influence3_pairs(const lt_baseline3 *b, const int32_t *probe_nodes, int32
                         const int64_t *pair_ptr, const int32_t *pair_obs, int64_t n_pairs,
                         float delta, int32_t mode, float *out, void *workspace, size_t workspace_bytes,
                         void *stream);
+
+/* ---- the 2-layer model with a WIDE class layer (GCN, gcn/models.py:8-25, with reddit's 41 classes or ppi's 121 labels: what
+ * lt_gcn2_trainer_create_wide trains) through one handle ----------------------------------------------------------------------
+ *   logits = A (relu(A (X W1) + b1) W2) + b2,   H <= 256 and 1 <= C <= 256 (LT_ERR_UNSUPPORTED beyond, *out = NULL).
+ * C <= 8 is allowed and takes the wide kernels all the same.  The handle borrows X and the four parameter tensors and owns,
+ * from creation, the fp64 parts LT_MODE_DELTA reads: an inner lt_baseline over (X, W1, b1) whose fp64 pre-activation and product
+ * rows take the routes of lt_baseline_enable_fp64 -- there is no enable call.  lt_baseline2w_refresh marks everything stale and
+ * launches nothing: the next reader re-forms what IT reads on its own stream (the probe calls the fp64 pre-activation alone,
+ * lt_baseline2w_logits the fp32 forward: the unfused product and SpMM, lt_gemm_f32 / lt_spmm_csr_f32's kernels, allocated by
+ * its first call).  lt_baseline2w_features_changed is lt_baseline_features_changed for the inner baseline.
+ * MODE RULE: LT_MODE_DELTA alone.  For two layers the class width enters only behind the single ReLU kink test, so the chain is
+ * the wide chain of lt_baseline3_create_wide with one level removed: per probe chunk the probes' fp64 product rows, the level-1
+ * bitmap with positions, dH1 = relu(Z1 + A[r,v] d S1[v]) - relu(Z1) piecewise on the fp64 pre-activation, dS2x = dH1x W2 as ONE
+ * MFMA product over the items (their count stays on the device; rows of stride C rounded up to 4) and the observed rows with a
+ * lane group across the class columns -- the wide chain's own kernels, handed the level-1 tables: row u's entries in entry
+ * order, the members of R1 add fma(a, dS2x[pos][c], acc), / delta, the squares in one fixed order, sqrt.  No floating-point
+ * atomics; a cell no path reaches is exactly +0; the pad columns are carried along and never enter the squares.
+ * LT_MODE_SPARSE / LT_MODE_FULL return LT_ERR_UNSUPPORTED and enqueue nothing: the fp32 finite difference of these shapes
+ * stays lt_influence_rows_vec + lt_wide_combine over class slices.
+ * lt_influence2w_rows: the contract of lt_influence3_rows_mode -- enqueue only, no host synchronisation; a cell depends on
+ * (probe, observed, model, graph) alone, not on the chunking, the other nodes of the call or the run; node ids checked on the
+ * device into copies (lt_node_check / LT_ERR_INDEX; a bad id is replaced, never dereferenced); probes chunked by
+ * "chunk_budget_bytes" -- the per-probe tables are sized by the longest column of A_hat, not by n, so chunks are large;
+ * n_probe == 0 or n_obs == 0: LT_OK, nothing launched; a short or misaligned workspace: LT_ERR_WORKSPACE.
+ * lt_influence2w_pairs: the contract of lt_influence3_pairs -- out[k] is, BIT FOR BIT, what the rows call writes at (the probe
+ * that owns k, pair_obs[k]); pair_ptr is a HOST array of n_probe + 1 int64 offsets validated before anything is launched
+ * (LT_ERR_INVALID, nothing written); a chunk whose probes own no pair launches nothing; n_pairs == 0: LT_OK; and
+ *   lt_influence2w_pairs_workspace_bytes(b, P, M) <= lt_influence2w_workspace_bytes(b, P, 1) + 4 M + 8 (P + 1) + 512.
+ * The workspace queries return 0 for invalid arguments.  lt_baseline2w_logits writes a dense [n, C] matrix. */
+typedef struct lt_baseline2w lt_baseline2w;
+int lt_baseline2w_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F,
+                         const float *W1, const float *b1, int32_t H,
+                         const float *W2, const float *b2, int32_t C,
+                         void *stream, lt_baseline2w **out);
+int lt_baseline2w_refresh(lt_baseline2w *b, void *stream);
+int lt_baseline2w_features_changed(lt_baseline2w *b, void *stream);
+int lt_baseline2w_destroy(lt_baseline2w *b);
+int lt_baseline2w_logits(const lt_baseline2w *b, float *dst, void *stream);
+size_t lt_influence2w_workspace_bytes(const lt_baseline2w *b, int32_t n_probe, int32_t n_obs);
+int lt_influence2w_rows(const lt_baseline2w *b, const int32_t *probe_nodes, int32_t n_probe,
+                        const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode,
+                        float *out, int64_t ldo, void *workspace, size_t workspace_bytes, void *stream);
+size_t lt_influence2w_pairs_workspace_bytes(const lt_baseline2w *b, int32_t n_probe, int64_t n_pairs);
+int lt_influence2w_pairs(const lt_baseline2w *b, const int32_t *probe_nodes, int32_t n_probe,
+                         const int64_t *pair_ptr, const int32_t *pair_obs, int64_t n_pairs,
+                         float delta, int32_t mode, float *out, void *workspace, size_t workspace_bytes,
+                         void *stream);
 
 /* ---- LapGraph cell selection (worker.py:302-335: A += noise, the n_keep largest cells of the strict lower
  * triangle by a 50-way np.argpartition) --------------------------------------------------------------------------------

@@ -154,6 +154,18 @@ SIGNATURES = {
     "lt_influence3_pairs_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int64]),
     "lt_influence3_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lt_baseline2w_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lt_baseline2w_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lt_baseline2w_features_changed": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lt_baseline2w_destroy": (C.c_int, [C.c_void_p]),
+    "lt_baseline2w_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_influence2w_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
+    "lt_influence2w_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lt_influence2w_pairs_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int64]),
+    "lt_influence2w_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
+                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "lt_node_check": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lt_export_rows_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "lt_profile_calls": (C.c_int, [C.POINTER(C.c_int64)]),

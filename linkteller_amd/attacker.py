@@ -64,7 +64,7 @@ class Attacker:
           * ``rng="philox"`` with an ``unbalanced*`` type is a ``ValueError``: its node draw stays on numpy.
         Both need a GPU (``LinkTellerHipError`` without one).  Whatever the device routes do not serve -- the attack methods that
         write a result file, the naive and baseline attacks on an ``unbalanced*`` sample, a model without a pair-list
-        primitive (``_pair_route``: neither ``engine.Baseline`` nor ``engine.Baseline3`` serves it), CPU features -- FALLS BACK to the host lists: ``exist_edges`` / ``nonexist_edges`` are
+        primitive (``_pair_route``: none of ``engine.Baseline``, ``engine.Baseline2W`` and ``engine.Baseline3`` serves it), CPU features -- FALLS BACK to the host lists: ``exist_edges`` / ``nonexist_edges`` are
         materialised from one download on first access (the arrays the host route builds, element for element, for the
         ``unbalanced*`` types) and everything proceeds as on the host route, raising what it raises there."""
         st = self.args.sample_type
@@ -317,7 +317,9 @@ class Attacker:
         kind, sd = self._walk()
         if kind == "gcn2":
             mode = self._mode(mode)
-            base = self.baseline(mode, sd)  # (engine.WideBaseline beyond 256 hidden units / 8 classes: every mode, slice by slice)
+            # (beyond 8 classes: engine.Baseline2W in `delta`; engine.WideBaseline, slice by slice, for every other mode and beyond
+            # 256 hidden units)
+            base = self.baseline(mode, sd)
             return base.influence_rows(probe_nodes, observe_nodes, float(self.args.influence), mode)
         if kind == "gcn3":
             # the 3-hop probe primitive: `delta` (default) propagates the perturbation exactly through the three layers,
@@ -352,25 +354,32 @@ class Attacker:
         -- through a raw pointer -- are announced with ``baseline().features_changed()``.  With several ranks the product the MODE reads (fp32 X W1 for `full` /
         `sparse`, the fp64 one for `delta`) is sharded or replicated per ``dist.choose_baseline_sharding``."""
         mode = self._mode(mode)
+        # A class layer of 9 .. 256 columns behind a hidden layer of up to 256 (engine.wide_class_shapes) has two routes: the ONE
+        # handle of engine.Baseline2W, which serves `delta` alone, and the slices of engine.WideBaseline (every mode; LT_WIDE2=slices
+        # keeps it in `delta` too, with its bits).  The handle is the default: profiles/wide2_attack_time.json.  Which of the two
+        # a mode wants is part of the cache key: a switch between `delta` and `sparse` / `full` on such a model rebuilds.
+        want2w = mode == "delta" and os.environ.get("LT_WIDE2", "handle") != "slices"
         # (the very state_dict of the last call -- _walk() hands the same object back while no parameter was replaced or moved --
         # with the same adjacency and feature storage: the key below would come out the same; ~4 us of Python in front of the first
         # launch of every attack.  Parameters on another device are copies: their in-place updates need the full check.)
         same = getattr(self, "_key_same", None)
         if (sd is not None and same is not None and self._baseline is not None and same[0] is sd and same[1] is self.adj
-                and same[2] is self.features and same[3] == self.features.data_ptr()):
+                and same[2] is self.features and same[3] == self.features.data_ptr() and same[4] == want2w):
             created = False
         else:
             dev = self.features.device
             src = self._params(sd)
             off_device = any(p.device != dev for p in src)
+            use2w = want2w and engine.wide_class_shapes(src[0].shape[1], src[2].shape[1])
             # parameters held on another device are copied: then an in-place update (p._version) means a rebuild too
-            key = (id(self.adj), self.features.data_ptr(), tuple((p.data_ptr(), p._version if off_device else 0) for p in src))
+            key = (id(self.adj), self.features.data_ptr(), tuple((p.data_ptr(), p._version if off_device else 0) for p in src), use2w)
             created = self._baseline is None or self._baseline_key != key
             if created:
-                self._baseline = engine.baseline_for(self.adj, self.features, *[p.to(dev) for p in src])
+                make = engine.Baseline2W if use2w else engine.baseline_for
+                self._baseline = make(self.adj, self.features, *[p.to(dev) for p in src])
                 self._baseline_key = key
                 self._sharding_mode = None
-            self._key_same = None if (off_device or sd is None) else (sd, self.adj, self.features, self.features.data_ptr())
+            self._key_same = None if (off_device or sd is None) else (sd, self.adj, self.features, self.features.data_ptr(), want2w)
         refreshed = created and not lt_dist.collectives_on()      # a new baseline computes everything on first use
         if getattr(self, "_sharding_mode", None) != mode:
             lt_dist.choose_baseline_sharding(self._baseline, mode=mode)      # (several ranks: ends with a refresh for `mode`)
@@ -402,6 +411,8 @@ class Attacker:
         """The object whose ``influence_pairs`` scores a LIST of pairs for this model and mode, or None where the list has no
         primitive and the caller takes the rectangle (``_rows``).  The one place that decides it:
           * a 2-layer model served by ``engine.Baseline`` (lt_influence_pairs), every mode;
+          * a 2-layer model with 9 .. 256 classes in ``delta`` (``engine.Baseline2W``, lt_influence2w_pairs: what ``baseline()``
+            builds for it unless LT_WIDE2=slices);
           * a GCN3 with up to 8 classes (``engine.Baseline3``, lt_influence3_pairs), every mode;
           * a GCN3 with 9 .. 256 classes in ``delta`` (the wide handle; `sparse` / `full` keep the generic loop, as in ``_rows``).
         None for ``engine.WideBaseline``, generic stacks and CPU features.  The baseline is built or refreshed on the way, as in
@@ -412,14 +423,14 @@ class Attacker:
         m = self._mode(mode)
         if kind == "gcn2":
             base = self.baseline(m, sd)
-            return base if isinstance(base, engine.Baseline) else None
+            return base if isinstance(base, (engine.Baseline, engine.Baseline2W)) else None
         if kind == "gcn3" or (kind == "gcn3w" and m == "delta"):
             return self.baseline3(sd)
         return None
 
     def pair_scores(self, probe, observed, mode=None, chunk=1024) -> np.ndarray:
         """||grad_mat(probe[k])[observed[k]]||_2 for a LIST of pairs, float64 [n_pairs] on the host in input order.  A model
-        with a pair-list primitive (``_pair_route``: a 2-layer model served by ``engine.Baseline``, a GCN3 within what
+        with a pair-list primitive (``_pair_route``: a 2-layer model served by ``engine.Baseline`` or ``engine.Baseline2W``, a GCN3 within what
         ``engine.Baseline3`` serves) goes through ``influence_pairs``: the pairs grouped by probe (``engine.group_pairs``), one
         call, ONE device-to-host copy of n_pairs floats.  Every other model the attacker accepts (``engine.WideBaseline``,
         generic stacks, a GCN3 with more than 8 classes outside `delta`) takes ``_pair_scores_rect``: ``_rows`` on ``chunk``

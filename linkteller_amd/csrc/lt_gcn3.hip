@@ -24,6 +24,9 @@
 // A LIST of (probe, observed) pairs (lt_influence3_pairs) takes the same chunk loop: only the last step reads the observed list, so
 // levels 1 and 2 are launched as above and the observed-row kernels have a list form (k*_stageC_pairs) that runs the rectangle's
 // per-cell device function (k3_cellC / k3d_cellC / k3dw_cellC) for pair k -- the bits of the rectangle by construction.
+//
+// The 2-LAYER model with a wide class layer (lt_baseline2w, at the end of this file) is the wide chain with one level removed and
+// shares its kernels: k3d_items1, the MFMA product over the items, k3dw_stageC / k3dw_stageC_pairs over the level-1 tables.
 #include <new>
 
 #include "lt_items.hip.h"
@@ -1264,4 +1267,293 @@ static int influence3_impl(const lt_baseline3 *b, const int32_t *probe_nodes, in
         LT_CHECK_LAUNCH();
     }
     return LT_OK;
+}
+
+// ---- the 2-layer model with a wide class layer (lt_baseline2w: H <= 256, 1 <= C <= 256; LT_MODE_DELTA alone) --------------------------
+//   logits = A (relu(A (X W1) + b1) W2) + b2
+// For two layers the class width enters only behind the single kink test, so the chain is the wide chain above with one level removed:
+// the probes' fp64 product rows, the level-1 bitmap with positions (k_item_bits: bits1, off), dH1x on the fp64 pre-activation
+// (k3d_items1), dS2x = dH1x W2 as one MFMA product over the items (count on the device, rows of stride Cp) -- and the observed rows are
+// k3dw_stageC / k3dw_stageC_pairs themselves, handed the level-1 tables where the 3-layer chain hands them the level-2 ones: a probe's
+// item (b, r) sits at off[b] + bits_pos(bits1 row of b, r), which is all k3dw_cellC asks of (rank2, off2, dS3x).  No level-2 table, so
+// the per-probe tables are sized by the longest column, not by n: chunks are large.
+// The handle owns an inner 2-layer baseline over (X, W1, b1) for the fp64 pre-activation Z1d and the probes' product rows (what
+// lt_baseline3_enable_fp64 builds: C = 1, no_agg), from creation; the fp32 forward exists only for lt_baseline2w_logits and is
+// allocated by its first call.
+struct lt_baseline2w {
+    const lt_graph *g = nullptr;
+    int32_t n = 0, F = 0, H = 0, C = 0, Hp = 0, Cp = 0;
+    const float *X = nullptr;
+    int64_t ldx = 0;
+    const float *W1 = nullptr, *b1 = nullptr, *W2 = nullptr, *b2 = nullptr;
+    lt_baseline *l1 = nullptr;      // owned: Z1d, the product rows
+    // owned, lt_baseline2w_logits only
+    float *S1 = nullptr;    // [n, Hp]  X W1
+    float *Act1 = nullptr;  // [n, Hp]  relu(A S1 + b1)
+    float *S2 = nullptr;    // [n, Cp]  H1 W2
+    float *OUT = nullptr;   // [n, Cp]  A S2 + b2
+    float *b1p = nullptr, *b2p = nullptr;   // zero-padded to Hp / Cp
+    bool fp32_fresh = false;
+};
+
+static void free_baseline2w(lt_baseline2w *b) {
+    if (!b) return;
+    (void)hipFree(b->S1); (void)hipFree(b->Act1); (void)hipFree(b->S2); (void)hipFree(b->OUT); (void)hipFree(b->b1p); (void)hipFree(b->b2p);
+    if (b->l1) (void)lt_baseline_destroy(b->l1);
+    delete b;
+}
+
+extern "C" int lt_baseline2w_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const float *W1, const float *b1,
+                                    int32_t H, const float *W2, const float *b2, int32_t C, void *stream, lt_baseline2w **out) {
+    LT_REQUIRE(out != nullptr, "lt_baseline2w_create: out is NULL");
+    *out = nullptr;
+    LT_REQUIRE(g != nullptr, "lt_baseline2w_create: graph is NULL");
+    LT_REQUIRE(F > 0 && H > 0 && C > 0, "lt_baseline2w_create: F=%d H=%d C=%d must be positive", F, H, C);
+    if (H > LT_MAX_H || C > LT3_WIDE_MAX_C)
+        return lt_set_error(LT_ERR_UNSUPPORTED, "lt_baseline2w_create: H=%d C=%d (supported: H <= %d, C <= %d)", H, C, LT_MAX_H,
+                            LT3_WIDE_MAX_C);
+    LT_REQUIRE(X && W1 && b1 && W2 && b2, "lt_baseline2w_create: NULL tensor pointer");
+    LT_REQUIRE(ldx >= F, "lt_baseline2w_create: ldx=%lld < F=%d", (long long)ldx, F);
+    (void)lt_node_err_dev();      // (allocated outside any stream capture)
+    lt_baseline2w *b = new (std::nothrow) lt_baseline2w();
+    if (!b) return lt_set_error(LT_ERR_NOMEM, "lt_baseline2w_create: out of host memory");
+    b->g = g; b->n = g->n; b->F = F; b->H = H; b->C = C;
+    b->Hp = lt_round_up(H, 4); b->Cp = lt_round_up(C, 4);
+    b->X = X; b->ldx = ldx; b->W1 = W1; b->b1 = b1; b->W2 = W2; b->b2 = b2;
+    // (W2 / b2 of the inner handle are never used for arithmetic: only its fp64 pre-activation and product rows are read; C = 1
+    // keeps its padding kernel inside W2's first H floats)
+    int rc = lt_baseline_create(g, X, ldx, F, W1, b1, H, W2, b2, 1, stream, &b->l1);
+    if (rc == LT_OK) {
+        b->l1->no_agg = true;
+        rc = lt_baseline_enable_fp64(b->l1, stream);
+    }
+    if (rc) {
+        free_baseline2w(b);
+        return rc;
+    }
+    *out = b;
+    return LT_OK;
+}
+
+extern "C" int lt_baseline2w_refresh(lt_baseline2w *b, void *stream) {
+    LT_REQUIRE(b != nullptr, "lt_baseline2w_refresh: baseline is NULL");
+    b->fp32_fresh = false;
+    return lt_baseline_refresh(b->l1, stream);
+}
+
+extern "C" int lt_baseline2w_features_changed(lt_baseline2w *b, void *stream) {
+    LT_REQUIRE(b != nullptr, "lt_baseline2w_features_changed: baseline is NULL");
+    b->fp32_fresh = false;
+    return lt_baseline_features_changed(b->l1, stream);
+}
+
+extern "C" int lt_baseline2w_destroy(lt_baseline2w *b) {
+    free_baseline2w(b);
+    return LT_OK;
+}
+
+// the unperturbed fp32 forward on the unfused layers (the product, the SpMM's row kernels), rows of stride Hp / Cp
+static int ensure2w_fp32(const lt_baseline2w *cb, hipStream_t st) {
+    lt_baseline2w *b = const_cast<lt_baseline2w *>(cb);   // cache state only
+    if (b->fp32_fresh || b->n == 0) return LT_OK;
+    const size_t n = (size_t)b->n;
+    // (each buffer once: a call that failed half-way leaves what it got to the next call and to destroy)
+    if (!b->S1) LT_HIP(hipMalloc((void **)&b->S1, n * b->Hp * sizeof(float)));
+    if (!b->Act1) LT_HIP(hipMalloc((void **)&b->Act1, n * b->Hp * sizeof(float)));
+    if (!b->S2) LT_HIP(hipMalloc((void **)&b->S2, n * b->Cp * sizeof(float)));
+    if (!b->OUT) LT_HIP(hipMalloc((void **)&b->OUT, n * b->Cp * sizeof(float)));
+    if (!b->b1p) LT_HIP(hipMalloc((void **)&b->b1p, (size_t)b->Hp * sizeof(float)));
+    if (!b->b2p) LT_HIP(hipMalloc((void **)&b->b2p, (size_t)b->Cp * sizeof(float)));
+    hipLaunchKernelGGL(k3w_pad_b3, dim3((b->Hp + 255) / 256), dim3(256), 0, st, b->b1, b->H, b->Hp, b->b1p);
+    LT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k3w_pad_b3, dim3((b->Cp + 255) / 256), dim3(256), 0, st, b->b2, b->C, b->Cp, b->b2p);
+    LT_CHECK_LAUNCH();
+    if (b->Hp != b->H) LT_HIP(hipMemsetAsync(b->S1, 0, n * b->Hp * sizeof(float), st));
+    int rc = lt_launch_gemm(b->X, b->ldx, b->W1, b->H, b->S1, b->Hp, b->n, b->H, b->F, st);
+    if (rc) return rc;
+    rc = lt_spmm_csr_f32(b->g, b->S1, b->Hp, b->Hp, b->b1p, 1, b->Act1, b->Hp, st);
+    if (rc) return rc;
+    rc = lt_launch_gemm(b->Act1, b->Hp, b->W2, b->C, b->S2, b->Cp, b->n, b->C, b->H, st);
+    if (rc) return rc;
+    rc = lt_spmm_csr_f32(b->g, b->S2, b->Cp, b->C, b->b2p, 0, b->OUT, b->Cp, st);
+    if (rc) return rc;
+    b->fp32_fresh = true;
+    return LT_OK;
+}
+
+extern "C" int lt_baseline2w_logits(const lt_baseline2w *b, float *dst, void *stream) {
+    LT_REQUIRE(b != nullptr && dst != nullptr, "lt_baseline2w_logits: NULL argument");
+    if (b->n == 0) return LT_OK;
+    { const int rc = ensure2w_fp32(b, (hipStream_t)stream); if (rc) return rc; }
+    LT_HIP(hipMemcpy2DAsync(dst, (size_t)b->C * sizeof(float), b->OUT, (size_t)b->Cp * sizeof(float), (size_t)b->C * sizeof(float),
+                            (size_t)b->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return LT_OK;
+}
+
+struct infl2w_ws {
+    double *Spd;            // fp64 product rows of the chunk's probes [chunk, Hp]
+    int32_t *off;           // [chunk + 1] the probes' item offsets; off[nb] = the chunk's item count (stays on the device)
+    uint2 *bits1;           // [chunk, words] the level-1 bitmap with positions
+    float *dH1x, *dS2x;     // [chunk * maxc, Hp] / [chunk * maxc, Cp]
+    int32_t *probes_s, *obs_s;
+    int64_t *pair_ptr;      // lt_influence2w_pairs: the device copy of the offsets (obs_s is then [n_pairs])
+    size_t bytes;
+    int chunk;
+};
+
+// n_pairs >= 0: the carve of lt_influence2w_pairs (n_obs = 0); the chunk and every per-chunk table are those of the rows call
+static infl2w_ws carve2w(void *base, const lt_baseline2w *b, int n_probe, int n_obs, int64_t n_pairs = -1) {
+    infl2w_ws w = {};
+    const size_t Hp = (size_t)b->Hp, Cp = (size_t)b->Cp;
+    const size_t maxc = (size_t)(b->g->max_col_nnz > 0 ? b->g->max_col_nnz : 1);
+    const size_t words = ((size_t)b->n + 31) / 32;
+    const size_t per_probe = Hp * sizeof(double) + maxc * (Hp + Cp) * sizeof(float) + words * sizeof(uint2) + sizeof(int32_t);
+    size_t chunk = (size_t)lt_tune().chunk_budget / per_probe;
+    if (chunk > 65534) chunk = 65534;
+    if (chunk > (size_t)2147483646 / maxc) chunk = (size_t)2147483646 / maxc;      // (the items' upper bound chunk * maxc stays an int)
+    if (chunk > (size_t)(n_probe > 0 ? n_probe : 1)) chunk = (size_t)(n_probe > 0 ? n_probe : 1);
+    if (chunk < 1) chunk = 1;
+    w.chunk = (int)chunk;
+    size_t offb = 0;
+    char *p = (char *)base;
+    auto take = [&](size_t bytes) {
+        void *q = p ? (void *)(p + offb) : nullptr;
+        offb += lt_align_up(bytes ? bytes : 1, 256);
+        return q;
+    };
+    w.Spd = (double *)take(chunk * Hp * sizeof(double));
+    w.off = (int32_t *)take((chunk + 1) * sizeof(int32_t));
+    w.bits1 = (uint2 *)take(chunk * words * sizeof(uint2));
+    w.dH1x = (float *)take(chunk * maxc * Hp * sizeof(float));
+    w.dS2x = (float *)take(chunk * maxc * Cp * sizeof(float));
+    w.probes_s = (int32_t *)take((size_t)(n_probe > 0 ? n_probe : 1) * sizeof(int32_t));
+    w.obs_s = (int32_t *)take((n_pairs >= 0 ? (size_t)n_pairs : (size_t)(n_obs > 0 ? n_obs : 1)) * sizeof(int32_t));
+    if (n_pairs >= 0) w.pair_ptr = (int64_t *)take(((size_t)n_probe + 1) * sizeof(int64_t));
+    w.bytes = offb;
+    return w;
+}
+
+extern "C" size_t lt_influence2w_workspace_bytes(const lt_baseline2w *b, int32_t n_probe, int32_t n_obs) {
+    if (!b || n_probe < 0 || n_obs < 0) return 0;
+    return carve2w(nullptr, b, n_probe, n_obs).bytes;
+}
+extern "C" size_t lt_influence2w_pairs_workspace_bytes(const lt_baseline2w *b, int32_t n_probe, int64_t n_pairs) {
+    if (!b || n_probe < 0 || n_pairs < 0 || n_pairs > LT_PAIRS_MAX) return 0;
+    return carve2w(nullptr, b, n_probe, 0, n_pairs).bytes;
+}
+
+// rows (pj == NULL) and pairs: everything but the last launch of a chunk is the same
+static int influence2w_impl(const lt_baseline2w *b, const int32_t *probe_nodes, int32_t n_probe, const int32_t *observe_nodes, int32_t n_obs,
+                            float delta, int32_t mode, float *out, int64_t ldo, void *workspace, size_t workspace_bytes, void *stream,
+                            const lt_pairs3_job *pj) {
+    const char *fn = pj ? "lt_influence2w_pairs" : "lt_influence2w_rows";
+    lt_prof_call prof_call_;
+    LT_REQUIRE(mode == LT_MODE_SPARSE || mode == LT_MODE_FULL || mode == LT_MODE_DELTA, "%s: unknown mode %d", fn, mode);
+    if (mode != LT_MODE_DELTA)
+        return lt_set_error(LT_ERR_UNSUPPORTED, "%s: a lt_baseline2w handle (C=%d) serves LT_MODE_DELTA only; the fp32 finite difference "
+                            "of this shape is lt_influence_rows_vec + lt_wide_combine over class slices", fn, b->C);
+    LT_REQUIRE(n_probe >= 0 && n_obs >= 0, "%s: negative count", fn);
+    LT_REQUIRE(delta != 0.f && delta == delta, "%s: delta must be a non-zero number", fn);
+    if (n_probe == 0 || (pj ? pj->n_pairs == 0 : n_obs == 0)) return LT_OK;
+    if (pj) {
+        LT_REQUIRE(probe_nodes && pj->obs && out, "%s: NULL pointer", fn);
+        observe_nodes = pj->obs;
+    } else {
+        LT_REQUIRE(probe_nodes && observe_nodes && out, "%s: NULL pointer", fn);
+        LT_REQUIRE(ldo >= n_obs, "%s: ldo=%lld < n_obs=%d", fn, (long long)ldo, n_obs);
+    }
+    LT_REQUIRE(b->n > 0, "%s: empty graph", fn);
+    { const int rc = lt_node_err_pending(); if (rc) return rc; }     // an earlier call's list held an id out of range
+    const size_t need = pj ? lt_influence2w_pairs_workspace_bytes(b, n_probe, pj->n_pairs) : lt_influence2w_workspace_bytes(b, n_probe, n_obs);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 256))
+        return lt_set_error(LT_ERR_WORKSPACE, "%s: workspace needs %zu bytes, 256-byte aligned", fn, need);
+    hipStream_t st = (hipStream_t)stream;
+    const lt_graph *g = b->g;
+    const infl2w_ws w = carve2w(workspace, b, n_probe, n_obs, pj ? pj->n_pairs : (int64_t)-1);
+    const int n = b->n, C = b->C, Cp = b->Cp, Hp = b->Hp;
+    const int lpr1 = lt_lpr_for(Hp), lprc = lt_lpr_for(Cp);
+    const int words = (n + 31) / 32;
+    const long maxc = g->max_col_nnz > 0 ? g->max_col_nnz : 1;
+    // the grid of every chunk's last launch, before anything is enqueued
+    for (int p0 = 0; p0 < n_probe; p0 += w.chunk) {
+        const int nb = (n_probe - p0) < w.chunk ? (n_probe - p0) : w.chunk;
+        const long cells = pj ? (long)(pj->ptr[p0 + nb] - pj->ptr[p0]) : (long)nb * n_obs;
+        LT_REQUIRE((cells * lprc + LT_BLOCK - 1) / LT_BLOCK < 2147483647L, "%s: %ld cells per chunk of %d probes exceed the grid limit",
+                   fn, cells, nb);
+    }
+    {   // node ids: both lists checked into the workspace (a pair list: pair_obs is the observed list of the check, and the offsets
+        // go to the device behind it by one stream-ordered copy)
+        const long n_list = pj ? (long)pj->n_pairs : (long)n_obs, tot = (long)n_probe + n_list;
+        hipLaunchKernelGGL(k_check_nodes, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, probe_nodes, n_probe, observe_nodes,
+                           (int)n_list, n, w.probes_s, w.obs_s, lt_node_err_dev());
+        LT_CHECK_LAUNCH();
+        probe_nodes = w.probes_s;
+        observe_nodes = w.obs_s;
+        if (pj) LT_HIP(hipMemcpyAsync(w.pair_ptr, pj->ptr, ((size_t)n_probe + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    }
+    { const int rc = lt_fp64_form_all(b->l1, st); if (rc) return rc; }      // Z1d, every row (nothing when it is current)
+    for (int p0 = 0; p0 < n_probe; p0 += w.chunk) {
+        const int nb = (n_probe - p0) < w.chunk ? (n_probe - p0) : w.chunk;
+        const int32_t *probes = probe_nodes + p0;
+        // (a pair list: the chunk's pairs by value; a chunk whose probes own none launches nothing)
+        const long k0 = pj ? (long)pj->ptr[p0] : 0L, k1 = pj ? (long)pj->ptr[p0 + nb] : 0L;
+        if (pj && k0 == k1) continue;
+        const long cells = pj ? k1 - k0 : (long)nb * n_obs;
+        const long m_bound = (long)nb * maxc;       // (< 2^31: carve2w)
+        int rc = lt_tune().gcn3_product_gather != 0 ? lt_fp64_product_rows_gather(b->l1, probes, nb, w.Spd, (long)Hp, st) : 1;
+        if (rc == 1) {
+            if (Hp != b->H) LT_HIP(hipMemsetAsync(w.Spd, 0, (size_t)nb * Hp * sizeof(double), st));
+            rc = lt_launch_gemm_f64_gather(b->X, (long)b->ldx, probes, nb, b->W1, (long)b->H, b->H, b->F, w.Spd, (long)Hp, st);
+        }
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_item_bits, dim3(nb), dim3(256), 0, st, g->tptr, g->trow, probes, nb, words, w.bits1, w.off, (int2 *)nullptr, (uint2 *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
+        LT_CHECK_LAUNCH();
+        LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k3d_items1<LPR_>), dim3(LT3_GRID), dim3(LT_BLOCK), 0, st, g->tptr, g->trow, g->tval,
+                                                 probes, nb, w.off, w.Spd, b->l1->Z1d, Hp, delta, w.dH1x));
+        LT_CHECK_LAUNCH();
+        // dS2x = dH1x W2 over the items; W2 as the caller holds it (K = H rows, N = C columns: the pad columns of both operands
+        // are left alone)
+        rc = lt_launch_gemm_mdev(w.dH1x, Hp, b->W2, C, w.dS2x, Cp, (int)m_bound, w.off + nb, C, b->H, st);
+        if (rc) return rc;
+        // the observed rows: the wide chain's cell over the level-1 tables
+        const unsigned gridC = (unsigned)((cells * lprc + LT_BLOCK - 1) / LT_BLOCK);
+        if (pj) {
+            LT_DISPATCH_LPR(lprc, hipLaunchKernelGGL((k3dw_stageC_pairs<LPR_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col,
+                                                     g->val, C, Cp, nb, w.dS2x, w.bits1, words, w.off, w.pair_ptr + p0, k0, k1,
+                                                     observe_nodes, delta, out));
+        } else {
+            LT_DISPATCH_LPR(lprc, hipLaunchKernelGGL((k3dw_stageC<LPR_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
+                                                     C, Cp, nb, w.dS2x, w.bits1, words, w.off, observe_nodes, n_obs, delta,
+                                                     out + (int64_t)p0 * ldo, (long)ldo));
+        }
+        LT_CHECK_LAUNCH();
+    }
+    return LT_OK;
+}
+
+extern "C" int lt_influence2w_rows(const lt_baseline2w *b, const int32_t *probe_nodes, int32_t n_probe, const int32_t *observe_nodes,
+                                   int32_t n_obs, float delta, int32_t mode, float *out, int64_t ldo, void *workspace,
+                                   size_t workspace_bytes, void *stream) {
+    LT_REQUIRE(b != nullptr, "lt_influence2w_rows: baseline is NULL");
+    return influence2w_impl(b, probe_nodes, n_probe, observe_nodes, n_obs, delta, mode, out, ldo, workspace, workspace_bytes, stream,
+                            nullptr);
+}
+
+extern "C" int lt_influence2w_pairs(const lt_baseline2w *b, const int32_t *probe_nodes, int32_t n_probe, const int64_t *pair_ptr,
+                                    const int32_t *pair_obs, int64_t n_pairs, float delta, int32_t mode, float *out, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+    LT_REQUIRE(b != nullptr, "lt_influence2w_pairs: baseline is NULL");
+    LT_REQUIRE(n_probe >= 0 && n_pairs >= 0, "lt_influence2w_pairs: negative count");
+    LT_REQUIRE(n_pairs <= LT_PAIRS_MAX, "lt_influence2w_pairs: %lld pairs (at most %lld per call)", (long long)n_pairs, (long long)LT_PAIRS_MAX);
+    // the offsets, on the host, before anything is launched
+    LT_REQUIRE(pair_ptr != nullptr || n_pairs == 0, "lt_influence2w_pairs: pair_ptr is NULL");
+    if (pair_ptr) {
+        LT_REQUIRE(pair_ptr[0] == 0, "lt_influence2w_pairs: pair_ptr[0] = %lld, not 0", (long long)pair_ptr[0]);
+        for (int32_t i = 0; i < n_probe; ++i)
+            LT_REQUIRE(pair_ptr[i + 1] >= pair_ptr[i], "lt_influence2w_pairs: pair_ptr decreases at probe %d", i);
+        LT_REQUIRE(pair_ptr[n_probe] == n_pairs, "lt_influence2w_pairs: pair_ptr[n_probe] = %lld, n_pairs = %lld",
+                   (long long)pair_ptr[n_probe], (long long)n_pairs);
+    }
+    const lt_pairs3_job pj = {pair_ptr, pair_obs, n_pairs};
+    return influence2w_impl(b, probe_nodes, n_probe, nullptr, 0, delta, mode, out, 0, workspace, workspace_bytes, stream, &pj);
 }

@@ -117,7 +117,8 @@ def _refresh_handle(owner, name, *args):
     announced with ``features_changed()``."""
     v = _x_version(owner.x)
     if v != owner._x_seen:
-        changed = "lt_baseline3_features_changed" if isinstance(owner, Baseline3) else "lt_baseline_features_changed"
+        changed = ("lt_baseline3_features_changed" if isinstance(owner, Baseline3) else
+                   "lt_baseline2w_features_changed" if isinstance(owner, Baseline2W) else "lt_baseline_features_changed")
         _lib.check(getattr(_lib.lib(), changed)(owner._h, _stream()), changed)
         owner._x_seen = v
     _lib.check(getattr(_lib.lib(), name)(owner._h, *args, _stream()), name)
@@ -1208,6 +1209,126 @@ class Baseline3:
         _lib.check(_lib.lib().lt_influence3_pairs(self._h, probes.data_ptr(), npb, ptr.ctypes.data, obs.data_ptr(), npairs,
                                                   float(delta), m, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
                    "lt_influence3_pairs")
+        return out
+
+
+def wide_class_shapes(h: int, c: int) -> bool:
+    """What ``Baseline2W`` is for: a 2-layer model whose hidden layer fits one pass of the row kernels and whose class layer
+    does not fit the fused epilogue (reddit's 41 classes, ppi's 121 labels) but fits one lane group (lt_baseline2w_create)."""
+    return h <= 256 and 9 <= c <= 256
+
+
+class Baseline2W:
+    """The probe primitive of a 2-layer model with up to 256 classes as ONE handle (lt_baseline2w_create; H <= 256): `delta`
+    alone -- the wide GCN3 chain with one level removed, one MFMA product over a probe chunk's items and a lane group across
+    the class columns per (probe, observed) cell -- as a rectangle (``influence_rows``) and as a pair list
+    (``influence_pairs``, the rectangle's bits).  `sparse` / `full` raise ``NotImplementedError``: the fp32 finite difference
+    of these shapes is ``WideBaseline``'s.  The fp64 parts belong to the handle from creation (``enable_fp64`` is a no-op)."""
+
+    supports_sharding = False       # dist.choose_baseline_sharding: replicated on every rank, no timing loop
+
+    def __init__(self, adj, x, w1, b1, w2, b2):
+        self.graph: HipGraph = as_hip_graph(adj)
+        self.x, self.w1, self.b1, self.w2, self.b2 = (
+            _f32(t, n) for t, n in ((x, "x"), (w1, "W1"), (b1, "b1"), (w2, "W2"), (b2, "b2")))
+        n, f = self.x.shape
+        self.n, self.f, self.h, self.c = n, f, self.w1.shape[1], self.w2.shape[1]
+        if (n != self.graph.n or self.w1.shape[0] != f or self.w2.shape[0] != self.h or self.b1.numel() != self.h
+                or self.b2.numel() != self.c):
+            raise ValueError("inconsistent GCN shapes")
+        if self.graph.device_index != self.x.device.index:
+            raise ValueError(f"the graph lives on cuda:{self.graph.device_index}, the features on {self.x.device}")
+        _require_finite(features=self.x, W1=self.w1, b1=self.b1, W2=self.w2, b2=self.b2)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().lt_baseline2w_create(self.graph.handle, self.x.data_ptr(), f, f, self.w1.data_ptr(),
+                                                   self.b1.data_ptr(), self.h, self.w2.data_ptr(), self.b2.data_ptr(),
+                                                   self.c, _stream(), C.byref(h)), "lt_baseline2w_create")
+        self._h = h
+        self._x_seen = _x_version(self.x)
+        self._finalizer = weakref.finalize(self, _lib.lib().lt_baseline2w_destroy, h)
+        self._ws = {}
+
+    def refresh(self, mode=None):
+        """The borrowed inputs changed: everything derived from them is re-formed by the next call that reads it."""
+        _refresh_handle(self, "lt_baseline2w_refresh")
+
+    def features_changed(self):
+        """``Baseline.features_changed`` for this handle (lt_baseline2w_features_changed)."""
+        _lib.check(_lib.lib().lt_baseline2w_features_changed(self._h, _stream()), "lt_baseline2w_features_changed")
+        self._x_seen = _x_version(self.x)
+        return self
+
+    def enable_fp64(self):
+        return self
+
+    def fp64_route(self) -> int:
+        return -1
+
+    def shard_refresh(self, enable=True):
+        return self
+
+    shard_refresh_fp64 = shard_refresh
+
+    def logits(self) -> torch.Tensor:
+        out = torch.empty((self.n, self.c), dtype=torch.float32, device=self.x.device)
+        _lib.check(_lib.lib().lt_baseline2w_logits(self._h, out.data_ptr(), _stream()), "lt_baseline2w_logits")
+        return out
+
+    def _delta(self, mode):
+        m = _lib.MODES[mode or "delta"] if isinstance(mode, str) or mode is None else int(mode)
+        if m != _lib.MODE_DELTA:
+            raise NotImplementedError(f"a 2-layer model with {self.c} classes is served through this handle in mode 'delta' only "
+                                      "(lt_baseline2w_create); its fp32 finite difference is engine.WideBaseline")
+        return m
+
+    def _workspace(self, key, need):
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _workspace(need, self.x.device)
+            self._ws = {key: ws}
+        return ws
+
+    def influence_rows(self, probe_nodes, observe_nodes, delta: float, mode="delta", out=None) -> torch.Tensor:
+        """[n_probe, n_obs] fp32 on the device (lt_influence2w_rows): the perturbation propagated exactly through the two layers."""
+        m = self._delta(mode)
+        dev = self.x.device
+        probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
+        obs = _as_nodes(observe_nodes, self.n, dev, "observe_nodes")
+        npb, nob = probes.numel(), obs.numel()
+        if out is None:
+            out = torch.empty((npb, nob), dtype=torch.float32, device=dev)
+        elif out.shape != (npb, nob) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 [n_probe, n_obs] tensor")
+        ws = self._workspace((npb, nob), _lib.lib().lt_influence2w_workspace_bytes(self._h, npb, nob))   # (depends on the knobs too)
+        _lib.check(_lib.lib().lt_influence2w_rows(self._h, probes.data_ptr(), npb, obs.data_ptr(), nob, float(delta), m,
+                                                  out.data_ptr(), nob, ws.data_ptr(), ws.numel(), _stream()),
+                   "lt_influence2w_rows")
+        return out
+
+    def influence_pairs(self, probe_nodes, pair_ptr, pair_obs, delta: float, mode="delta", out=None) -> torch.Tensor:
+        """[n_pairs] fp32 on the device: ``Baseline.influence_pairs`` for this handle (lt_influence2w_pairs).  Probe i =
+        ``probe_nodes[i]`` owns ``pair_obs[pair_ptr[i]:pair_ptr[i + 1]]`` and ``out[k]`` is what ``influence_rows`` writes at
+        (that probe, ``pair_obs[k]``), bit for bit; ``pair_ptr`` is a HOST array of n_probe + 1 int64 offsets (validated by the
+        library before anything is launched).  The output and the workspace are sized by the list."""
+        import numpy as np
+        m = self._delta(mode)
+        dev = self.x.device
+        probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
+        obs = _as_nodes(pair_obs, self.n, dev, "pair_obs")
+        if isinstance(pair_ptr, torch.Tensor):
+            pair_ptr = pair_ptr.cpu().numpy()
+        ptr = np.ascontiguousarray(np.asarray(pair_ptr).reshape(-1), dtype=np.int64)
+        npb, npairs = probes.numel(), obs.numel()
+        if ptr.size != npb + 1:
+            raise ValueError(f"pair_ptr must hold n_probe + 1 = {npb + 1} offsets, got {ptr.size}")
+        if out is None:
+            out = torch.empty((npairs,), dtype=torch.float32, device=dev)
+        elif out.shape != (npairs,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError("out must be a contiguous float32 [n_pairs] tensor on the baseline's device")
+        ws = self._workspace(("pairs", npb, npairs), _lib.lib().lt_influence2w_pairs_workspace_bytes(self._h, npb, npairs))
+        _lib.check(_lib.lib().lt_influence2w_pairs(self._h, probes.data_ptr(), npb, ptr.ctypes.data, obs.data_ptr(), npairs,
+                                                   float(delta), m, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                   "lt_influence2w_pairs")
         return out
 
 
