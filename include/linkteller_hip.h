@@ -55,7 +55,9 @@ extern "C" {
                             Additive within 5: the pair list of the 3-layer model (lt_influence3_pairs, _workspace_bytes); no entry
                             point changed.
                             Additive within 5: the 2-layer model with a wide class layer through one handle (lt_baseline2w_*,
-                            lt_influence2w_*); no entry point changed */
+                            lt_influence2w_*); no entry point changed.
+                            Additive within 5: minibatch training of the feature-only MLP baselines (lt_mlp_trainer_*,
+                            lt_mlp_forward, lt_mlp_forward_workspace_bytes); no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -1201,6 +1203,59 @@ int lt_gcn3_trainer_counts(const lt_gcn3_trainer *t, int32_t *counts, void *stre
 int lt_gcn3_trainer_attach_validation_wide(lt_gcn3_trainer *t, const lt_graph *g2, const float *X2, int64_t ldx2, int32_t n2,
                                            const void *labels2, int64_t ldy2, int32_t keep_best, int32_t patience,
                                            const int32_t *rows, int32_t m, void *stream);
+
+/* ---- the feature-only baselines, trained in minibatches.  Additive within ABI 5. ----
+ * The reference's OneLayerMLP / SingleHiddenLayerMLP (gcn/models.py:91-120) under MLPTrainer (mlp_trainer.py): no graph.
+ *   depth 2: Z1 = X_b W1 + b1, H1d = dropout_p(relu(Z1)), Z2 = H1d W2 + b2      (W1 [F, H], b1 [H], W2 [H, C], b2 [C])
+ *   depth 1: Z = X_b W + b, no hidden layer, no dropout                                (W1 = W [F, C], b1 = b [C]; W2, b2, H not read)
+ * X_b = the rows of the borrowed X [n, ldx] one batch of the epoch's row order names; it is never materialised.
+ * lt_mlp_trainer_create borrows X, labels and the parameter tensors (device, project layout [in, out], updated in place) and
+ * owns the Adam moments and every intermediate.  loss_kind / labels / ldy as lt_gcn2_trainer_create_wide, taken over the
+ * batch's own rows: a batch of b rows divides by b (CE) or b C (BCE), the last, shorter batch of an epoch by its own size.
+ * LT_ERR_INVALID with a message naming the value, nothing allocated: depth other than 1 / 2, H outside [1, 256] (depth 2), C
+ * outside [1, 256], batch_size < 1, n < 1, F < 1, ldx < F, an unknown loss_kind, ldy < C for LT_LOSS_BCE, dropout outside
+ * [0, 1], lr or weight_decay < 0, a NULL pointer.
+ * One step (s = optimiser steps since creation): forward, loss head (the step's loss and the sum of tp: for CE the correct
+ * count), dZ2, dW2 = H1d^T dZ2, db2, dZ1 = [H1d > 0] (dZ2 W2^T) / (1 - p), db1, dW1 = X_b^T dZ1, then one Adam step under
+ * lt_adam_step's contract with step number s + 1 (betas 0.9 / 0.999, eps 1e-8, weight decay added to the gradient).
+ * Dropout: element (j, h), j = the row's position inside its batch, i = j H + h, is kept iff word (i & 3) of Philox4x32-10
+ * with counter (q lo, q hi, s, 0), q = i >> 2, key (seed lo, seed hi) is >= floor(p 2^32); kept values are scaled by
+ * (float)(1 / (1 - p)); p = 0 draws nothing, p = 1 keeps nothing.
+ * lt_mlp_trainer_run enqueues every step of n_epochs epochs on `stream`, no host synchronisation: epoch e's batches are
+ * order[e, 0 .. B), [B .. 2 B), ..., the last one n - (ceil(n / B) - 1) B rows.  order: device int32 [n_epochs, n], one
+ * permutation per epoch (not checked to be one: a repeated row counts twice), or NULL for the Philox shuffle: the key of row r
+ * in epoch e (e = epochs since creation) is word 0 of Philox4x32-10 with counter (r, 0, e, 2), key (seed lo, seed hi); the
+ * epoch's order is the rows sorted ascending by (key, r).  An id outside [0, n) is never used as an address (row 0 stands in)
+ * and raises the probe-list flag of lt_node_check: LT_ERR_INDEX from it, or from the next call that finds it.  batch_size >= n
+ * with the identity order is the reference's full-batch branch.  record: device fp32 [n_epochs ceil(n / B), 2] = (loss, sum of
+ * tp) per step, or NULL.  No float atomics, every sum in a fixed order that depends on the step's shapes alone: two trainers
+ * given the same inputs agree bit for bit and run(a + b) equals run(a); run(b).
+ * lt_mlp_trainer_step enqueues ONE step over the b rows rows[0 .. b) (device int32, 1 <= b <= min(batch_size, n), ids checked
+ * as above): the step lt_mlp_trainer_run takes for that batch, bit for bit; it advances the step count, not the epoch count.
+ * record: device fp32 [2] or NULL.
+ * Test accessors: lt_mlp_trainer_grads -- the LAST step's gradients before weight decay (depth 1: dW1 = dW, db1 = db, the other
+ * two not written); lt_mlp_trainer_logits -- its train-mode logits [rows of that step, ldz], rows in batch order;
+ * lt_mlp_trainer_counts -- steps and epochs run and the last step's row count (any may be NULL); lt_mlp_trainer_order -- the
+ * last Philox order, int32 [n] (LT_ERR_INVALID before any epoch ran under it).
+ * lt_mlp_forward: eval-mode logits Z [m, ldz] of rows[0 .. m) of any X2 [n2, ldx2] (rows == NULL: all n2 rows, m not read),
+ * through the trainer's forward kernels with the mask off: with p = 0 a step's logits are these bits.  Row ids are checked
+ * as above.  workspace: device, 16-byte aligned, lt_mlp_forward_workspace_bytes(rows scored, F, depth, H, C) bytes (0 for
+ * unsupported values), else LT_ERR_WORKSPACE. */
+typedef struct lt_mlp_trainer lt_mlp_trainer;
+int lt_mlp_trainer_create(const float *X, int64_t ldx, int32_t n, int32_t F, const void *labels, int64_t ldy, int32_t loss_kind,
+                          int32_t depth, int32_t H, int32_t C, float *W1, float *b1, float *W2, float *b2, int32_t batch_size,
+                          double lr, double weight_decay, double dropout, uint64_t seed, void *stream, lt_mlp_trainer **out);
+int lt_mlp_trainer_run(lt_mlp_trainer *t, int32_t n_epochs, const int32_t *order, float *record, void *stream);
+int lt_mlp_trainer_step(lt_mlp_trainer *t, const int32_t *rows, int32_t b, float *record, void *stream);
+int lt_mlp_trainer_grads(const lt_mlp_trainer *t, float *dW1, float *db1, float *dW2, float *db2, void *stream);
+int lt_mlp_trainer_logits(const lt_mlp_trainer *t, float *Z, int64_t ldz, void *stream);
+int lt_mlp_trainer_counts(const lt_mlp_trainer *t, int64_t *steps, int64_t *epochs, int32_t *last_rows);
+int lt_mlp_trainer_order(const lt_mlp_trainer *t, int32_t *order, void *stream);
+int lt_mlp_trainer_destroy(lt_mlp_trainer *t);
+size_t lt_mlp_forward_workspace_bytes(int32_t m, int32_t F, int32_t depth, int32_t H, int32_t C);
+int lt_mlp_forward(const float *X2, int64_t ldx2, int32_t n2, int32_t F, int32_t depth, int32_t H, int32_t C, const float *W1,
+                   const float *b1, const float *W2, const float *b2, const int32_t *rows, int32_t m, float *Z, int64_t ldz,
+                   void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- per-kernel timing (used by bench.py for the roofline object) --------------------------
  * lt_profile_enable(mask): bit k of mask set = launches of kernel class k are bracketed by a pair of

@@ -230,6 +230,20 @@ SIGNATURES = {
     "lt_gcn3_trainer_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lt_gcn3_trainer_attach_validation_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                                          C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "lt_mlp_trainer_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
+                                        C.c_double, C.c_double, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lt_mlp_trainer_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_mlp_trainer_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lt_mlp_trainer_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_mlp_trainer_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "lt_mlp_trainer_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "lt_mlp_trainer_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_mlp_trainer_destroy": (C.c_int, [C.c_void_p]),
+    "lt_mlp_forward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "lt_mlp_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
     "lt_profile_enable": (C.c_int, [C.c_int]),
     "lt_profile_reset": (C.c_int, []),
     "lt_profile_summary": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -40,6 +40,7 @@
 
 #include "lt_philox.hip.h"
 #include "lt_rows.hip.h"
+#include "lt_train_common.hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
@@ -47,48 +48,8 @@ typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 #define TR_BLOCK 256
 #define TR_ROWS_PER_BLOCK 32   // k_tr_bwd_rows: rows summed by one block (its partial is one slab of the column sums)
 
-// --------------------------------------------------------------------------------------------
-// The dropout mask: Philox4x32-10 (lt_philox.hip.h)
-// --------------------------------------------------------------------------------------------
-// word (i & 3) of Philox(counter (q lo, q hi, epoch, layer), key (seed lo, seed hi)), q = i >> 2
-__device__ __forceinline__ uint4 lt_drop_block(uint64_t q, uint32_t epoch, uint64_t seed, uint32_t layer) {
-    return lt_philox4x32_10(make_uint4((uint32_t)q, (uint32_t)(q >> 32), epoch, layer),
-                            make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
-}
-
-struct lt_drop_args {
-    int on;              // 0: p == 0, no RNG call
-    uint64_t thresh;     // keep iff u >= thresh = floor(p * 2^32)  (2^32 for p == 1: nothing is kept)
-    float scale;         // 1 / (1 - p), rounded once from double
-    uint32_t epoch;
-    uint64_t seed;
-    uint32_t layer = 0;  // counter word 3: the hidden layer the mask belongs to (the 2-layer trainer has one: 0)
-};
-
-// columns coff .. coff + 3 of row r of a [n, H] hidden layer (h >= 0 already): kept elements scaled, the others and the
-// pad columns zero
-__device__ __forceinline__ f32x4 lt_drop4(f32x4 h, int r, int coff, int H, const lt_drop_args &d) {
-    const uint64_t i0 = (uint64_t)r * H + coff;
-    uint32_t u[4];
-    if ((H & 3) == 0) {    // the 4 columns are the 4 words of one Philox block
-        const uint4 w = lt_drop_block(i0 >> 2, d.epoch, d.seed, d.layer);
-        u[0] = w.x; u[1] = w.y; u[2] = w.z; u[3] = w.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint64_t i = i0 + j;
-            const uint4 w = lt_drop_block(i >> 2, d.epoch, d.seed, d.layer);
-            const uint32_t sel = (uint32_t)(i & 3);
-            u[j] = sel == 0 ? w.x : sel == 1 ? w.y : sel == 2 ? w.z : w.w;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const bool keep = coff + j < H && (uint64_t)u[j] >= d.thresh;
-        h[j] = keep ? h[j] * d.scale : 0.f;
-    }
-    return h;
-}
+// (the dropout mask -- lt_drop_block, lt_drop_args, lt_drop4 -- and Adam's element update live in lt_train_common.hip.h, which
+// the minibatch MLP trainer shares)
 
 // --------------------------------------------------------------------------------------------
 // H1d = dropout(relu(Z1)) and S2 = H1d W2 (lane layout and summation order of k_layer1: with p = 0 these are its S2 bits)
@@ -430,37 +391,7 @@ __global__ __launch_bounds__(256) void k_gemm_tn_mfma(const float *__restrict__ 
 //   g = fma(p, wd, g);  m = fma(w1, g - m, m)  (lerp_, weight w1 = 1 - beta1 < 0.5);  v = v * beta2;  v = fma(w2 * g, g, v)
 //   denom = sqrt(v) / bc2_sqrt + eps;  p = p + (neg_step * m) / denom
 // --------------------------------------------------------------------------------------------
-struct lt_adam_scalars {
-    float wd, w1, beta2, w2, bc2_sqrt, eps, neg_step;
-    int decay;
-};
-
-static lt_adam_scalars adam_scalars(int64_t step, double lr, double beta1, double beta2, double eps, double wd) {
-    lt_adam_scalars s;
-    const double bc1 = 1.0 - pow(beta1, (double)step);
-    const double bc2 = 1.0 - pow(beta2, (double)step);
-    s.wd = (float)wd;
-    s.decay = wd != 0.0;
-    s.w1 = (float)(1.0 - beta1);
-    s.beta2 = (float)beta2;
-    s.w2 = (float)(1.0 - beta2);
-    s.bc2_sqrt = (float)pow(bc2, 0.5);   // Python's bc2 ** 0.5 is pow(), which may differ from sqrt() in the last bit
-    s.eps = (float)eps;
-    s.neg_step = (float)(-(lr / bc1));
-    return s;
-}
-
-__device__ __forceinline__ float adam_elem(float p, float g, float &m, float &v, const lt_adam_scalars &s) {
-    if (s.decay) g = fmaf(p, s.wd, g);
-    const float d = __fsub_rn(g, m);
-    m = s.w1 < 0.5f ? fmaf(s.w1, d, m) : fmaf(__fsub_rn(s.w1, 1.f), d, g);
-    v = __fmul_rn(v, s.beta2);
-    v = fmaf(__fmul_rn(s.w2, g), g, v);
-    // sqrtf and '/' are correctly rounded in fp32 (hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt); the header's
-    // __fsqrt_rn is the native approximation unless OCML_BASIC_ROUNDED_OPERATIONS is defined
-    const float denom = __fadd_rn(sqrtf(v) / s.bc2_sqrt, s.eps);
-    return __fadd_rn(p, (__fmul_rn(s.neg_step, m)) / denom);
-}
+// (lt_adam_scalars, adam_scalars and adam_elem: lt_train_common.hip.h)
 
 __global__ void k_adam(int64_t n, float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                        float *__restrict__ v, lt_adam_scalars s) {

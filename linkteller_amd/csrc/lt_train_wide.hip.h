@@ -11,7 +11,7 @@
 // k_trw_finish (one block) adds the blocks' partials: the losses by a fixed tree, the counts as integers.  No float atomics:
 // every sum has a fixed order.
 //
-// Row arithmetic, fp32, -ffp-contract=off:
+// Row arithmetic, fp32, -ffp-contract=off (the per-element functions live in lt_train_common.hip.h, shared with lt_mlp.hip):
 //   CE   mx = max_c z_c (first argmax: ties go to the lower column), e_c = expf(z_c - mx), s = sum e_c (a lane's four in column
 //        order, then the group butterfly), loss = (mx + logf(s)) - z_y, dZ = (e_c / s - [c == y]) / n.  k_tr_ce's operations; the
 //        sum's association differs from its one-thread chain, so the two heads agree to rounding, not bit for bit.  A label
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(TR_BLOCK) void k_trw_head(lt_trw_args a) {
                 for (int m = LPR / 2; m >= 1; m >>= 1) {
                     const float omx = __shfl_xor(mx, m, 64);
                     const int oarg = __shfl_xor(arg, m, 64);
-                    if (omx > mx || (omx == mx && oarg < arg)) { mx = omx; arg = oarg; }
+                    lt_argmax_merge(mx, arg, omx, oarg);
                 }
                 float e[4], s = 0.f, zy = 0.f;
 #pragma unroll
@@ -107,11 +107,11 @@ __global__ __launch_bounds__(TR_BLOCK) void k_trw_head(lt_trw_args a) {
                 }
                 s = group_sum<LPR>(s);
                 zy = group_sum<LPR>(zy);      // one lane holds z_y, the others 0
-                l = (mx + logf(s)) - zy;
+                l = lt_ce_row_loss(mx, s, zy);
                 if constexpr (GRAD) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        if (coff + j < C) dz[j] = (e[j] / s - (coff + j == y ? 1.f : 0.f)) * a.inv;
+                        if (coff + j < C) dz[j] = lt_ce_grad(e[j], s, coff + j == y, a.inv);
                 }
                 if (gl == 0 && (unsigned)y < (unsigned)C) {      // integer LDS atomics: the counts do not depend on order
                     if (arg == y) {
@@ -128,13 +128,9 @@ __global__ __launch_bounds__(TR_BLOCK) void k_trw_head(lt_trw_args a) {
                     if (coff + j < C) {
                         const float zj = z[j];
                         const bool yb = yr[j] != 0;
-                        const float y = yb ? 1.f : 0.f;
-                        const float ez = expf(-fabsf(zj));
-                        l += (fmaxf(zj, 0.f) - zj * y) + log1pf(ez);
-                        if constexpr (GRAD) {
-                            const float sig = zj >= 0.f ? 1.f / (1.f + ez) : ez / (1.f + ez);
-                            dz[j] = (sig - y) * a.inv;
-                        }
+                        float sig;
+                        l += lt_bce_elem(zj, yb, sig);
+                        if constexpr (GRAD) dz[j] = (sig - (yb ? 1.f : 0.f)) * a.inv;
                         const bool pred = zj > 0.f;
                         if (pred || yb) atomicAdd(&sc[3 * (coff + j) + (pred ? (yb ? 0 : 1) : 2)], 1);
                     }

@@ -1799,3 +1799,189 @@ def _as_nodes(nodes, n, device, name) -> torch.Tensor:
     if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
         raise IndexError(f"{name} out of range [0, {n})")
     return t.to(torch.int32).to(device)
+
+
+def torch_epoch_orders(n: int, n_epochs: int) -> torch.Tensor:
+    """int64 [n_epochs, n]: the row orders ``DataLoader(dataset of n rows, shuffle=True)`` walks in its next ``n_epochs``
+    epochs under torch's global CPU generator, which it advances exactly as those epochs would: per epoch the loader's
+    iterator first draws its base seed, then its ``RandomSampler`` draws the seed of the epoch's permutation."""
+    from torch.utils.data import RandomSampler
+    sampler = RandomSampler(range(int(n)))
+    out = torch.empty((max(int(n_epochs), 0), int(n)), dtype=torch.int64)
+    for e in range(out.shape[0]):
+        torch.empty((), dtype=torch.int64).random_()      # _BaseDataLoaderIter's base seed
+        out[e] = torch.tensor(list(sampler), dtype=torch.int64)
+    return out
+
+
+def _mlp_params(params, depth, f):
+    """The parameter tensors of an MLP baseline, checked: (W1 [F, H], b1 [H], W2 [H, C], b2 [C]) or (W [F, C], b [C])."""
+    if depth not in (1, 2):
+        raise ValueError(f"depth must be 1 or 2, got {depth!r}")
+    names = ("W1", "b1", "W2", "b2") if depth == 2 else ("W", "b")
+    if len(params) != len(names):
+        raise ValueError(f"depth {depth} takes the parameters {names}, got {len(params)} tensors")
+    ps = [_f32(t, n) for t, n in zip(params, names)]
+    dims = [f] + [w.shape[1] if w.dim() == 2 else -1 for w in ps[0::2]]
+    if any(w.dim() != 2 or tuple(w.shape) != (dims[l], dims[l + 1]) or tuple(b.shape) != (dims[l + 1],)
+           for l, (w, b) in enumerate(zip(ps[0::2], ps[1::2]))):
+        raise ValueError("inconsistent MLP shapes")
+    return ps, names, dims
+
+
+class MLPTrainer:
+    """Minibatch training of the feature-only baselines on the GPU (lt_mlp_trainer_*): the reference's ``MLPTrainer`` loop
+    (mlp_trainer.py) over ``SingleHiddenLayerMLP`` (``depth=2``: parameters w1, b1, w2, b2) or ``OneLayerMLP`` (``depth=1``:
+    w, b), in the project's [in, out] layout.  One epoch is ``ceil(n / batch_size)`` Adam steps over the epoch's row order; a
+    whole ``run`` is enqueued by one library call.  The parameters are updated IN PLACE; the trainer owns the Adam moments.
+    Dropout and the default shuffle are Philox4x32-10 streams keyed by ``seed`` (include/linkteller_hip.h), not torch's
+    generator.  Limits: hidden width <= 256, classes <= 256."""
+
+    _LOSSES = {"ce": 0, "bce": 1}
+
+    def __init__(self, x, labels, *params, depth, batch_size, lr, weight_decay, dropout=0.0, seed=0, loss="ce"):
+        if loss not in self._LOSSES:
+            raise ValueError(f"loss must be 'ce' or 'bce', got {loss!r}")
+        if not 0.0 <= float(dropout) <= 1.0:
+            raise ValueError(f"dropout probability has to be between 0 and 1, but got {dropout}")
+        if int(batch_size) < 1:
+            raise ValueError(f"batch_size must be at least 1, got {batch_size}")
+        self.x = _f32(x, "x")
+        n, f = self.x.shape
+        self.params, self._names, dims = _mlp_params(params, depth, f)
+        for t, src in zip(self.params, params):
+            if t.data_ptr() != src.data_ptr():
+                raise ValueError("the parameters are updated in place: pass contiguous float32 device tensors")
+        self.n, self.f, self.c, self.depth, self.loss = n, f, dims[-1], int(depth), loss
+        self.h = dims[1] if depth == 2 else 0
+        self.batch_size = int(batch_size)
+        self.steps_per_epoch = -(-n // self.batch_size)
+        _require_finite(features=self.x, **dict(zip(self._names, self.params)))
+        if not isinstance(labels, torch.Tensor):
+            labels = torch.as_tensor(labels)
+        if loss == "bce":
+            if tuple(labels.shape) != (n, self.c):
+                raise ValueError(f"labels must be [{n}, {self.c}] for loss='bce', got {tuple(labels.shape)}")
+            if labels.is_floating_point() or labels.is_complex():
+                raise ValueError(f"labels must have an integer or bool dtype, got {labels.dtype}")
+            if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) > 1):
+                raise ValueError("labels must hold 0 / 1")
+            self.labels = labels.to(device=self.x.device, dtype=torch.uint8).contiguous()
+        else:
+            labels = labels.reshape(-1)
+            if labels.numel() != n:
+                raise ValueError(f"labels: {labels.numel()} entries for {n} rows")
+            if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= self.c):
+                raise ValueError(f"labels outside [0, {self.c})")
+            self.labels = labels.to(device=self.x.device, dtype=torch.int32).contiguous()
+        ptrs = [t.data_ptr() for t in self.params] + [None] * (4 - len(self.params))
+        h = C.c_void_p()
+        _lib.check(_lib.lib().lt_mlp_trainer_create(self.x.data_ptr(), f, n, f, self.labels.data_ptr(), self.c,
+                                                    self._LOSSES[loss], self.depth, self.h, self.c, *ptrs, self.batch_size,
+                                                    float(lr), float(weight_decay), float(dropout), int(seed) & (2**64 - 1),
+                                                    _stream(), C.byref(h)), "lt_mlp_trainer_create")
+        self._h = h
+        self._finalizer = weakref.finalize(self, _lib.lib().lt_mlp_trainer_destroy, h)
+
+    def _order(self, epochs, order):
+        """``order`` of ``run`` as the int32 device tensor [epochs, n] the library reads (None: the Philox shuffle)."""
+        if order is None:
+            return None
+        if isinstance(order, str):
+            if order != "torch":
+                raise ValueError(f"order must be None, a tensor or 'torch', got {order!r}")
+            order = torch_epoch_orders(self.n, epochs)
+        t = order if isinstance(order, torch.Tensor) else torch.as_tensor(order)
+        if t.dtype.is_floating_point or t.dtype == torch.bool or t.is_complex():
+            raise TypeError(f"order must hold integer row ids, got {t.dtype}")
+        if tuple(t.shape) != (epochs, self.n):
+            raise ValueError(f"order must be [{epochs}, {self.n}], got {tuple(t.shape)}")
+        if t.is_cuda and t.dtype == torch.int32:
+            return t.contiguous()      # ids checked on the device (engine.node_check)
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= self.n):
+            raise IndexError(f"order out of range [0, {self.n})")
+        return t.to(device=self.x.device, dtype=torch.int32).contiguous()
+
+    def run_async(self, epochs: int, order=None) -> torch.Tensor:
+        """Enqueue ``epochs`` epochs; returns the device record [epochs * steps_per_epoch, 2] (loss, tp count) without syncing."""
+        epochs = max(int(epochs), 0)
+        dev_order = self._order(epochs, order)
+        record = torch.empty((epochs * self.steps_per_epoch, 2), dtype=torch.float32, device=self.x.device)
+        _lib.check(_lib.lib().lt_mlp_trainer_run(self._h, epochs, None if dev_order is None else dev_order.data_ptr(),
+                                                 record.data_ptr(), _stream()), "lt_mlp_trainer_run")
+        if dev_order is not None:
+            dev_order.record_stream(torch.cuda.current_stream())
+        for p in self.params:
+            torch.autograd.graph.increment_version(p)
+        return record
+
+    def run(self, epochs: int, order=None):
+        """Run ``epochs`` epochs; returns (loss [steps] float32, count [steps] int64) per optimiser step as CPU arrays (one
+        read at the end).  ``order``: None -- the documented Philox shuffle; an integer tensor [epochs, n] of row ids, one
+        permutation per epoch; ``"torch"`` -- each epoch's permutation drawn on the host as ``DataLoader(shuffle=True)`` draws
+        it under torch's global seed (``torch_epoch_orders``) and uploaded before the run: the reference's batch composition."""
+        rec = self.run_async(epochs, order).cpu().numpy()
+        return rec[:, 0].copy(), rec[:, 1].astype("int64")
+
+    def step_async(self, rows) -> torch.Tensor:
+        """Enqueue ONE optimiser step over the batch ``rows`` (at most ``min(batch_size, n)`` row ids): the step ``run`` takes
+        for that batch, bit for bit.  Returns the device record [2] (loss, tp count) without syncing."""
+        r = _as_nodes(rows, self.n, self.x.device, "rows")
+        record = torch.empty((2,), dtype=torch.float32, device=self.x.device)
+        _lib.check(_lib.lib().lt_mlp_trainer_step(self._h, r.data_ptr(), int(r.numel()), record.data_ptr(), _stream()),
+                   "lt_mlp_trainer_step")
+        r.record_stream(torch.cuda.current_stream())
+        for p in self.params:
+            torch.autograd.graph.increment_version(p)
+        return record
+
+    def _counts(self):
+        s, e, b = C.c_int64(), C.c_int64(), C.c_int32()
+        _lib.check(_lib.lib().lt_mlp_trainer_counts(self._h, C.byref(s), C.byref(e), C.byref(b)), "lt_mlp_trainer_counts")
+        return s.value, e.value, b.value
+
+    @property
+    def step(self) -> int:
+        return self._counts()[0]
+
+    @property
+    def epoch(self) -> int:
+        return self._counts()[1]
+
+    def grads(self):
+        """The last step's gradients (before weight decay), one per parameter in the constructor's order."""
+        out = [torch.empty_like(p) for p in self.params]
+        ptrs = [t.data_ptr() for t in out] + [None] * (4 - len(out))
+        _lib.check(_lib.lib().lt_mlp_trainer_grads(self._h, *ptrs, _stream()), "lt_mlp_trainer_grads")
+        return tuple(out)
+
+    def logits(self) -> torch.Tensor:
+        """The last step's train-mode logits [rows of that batch, C], rows in batch order (before that step's update)."""
+        out = torch.empty((self._counts()[2], self.c), dtype=torch.float32, device=self.x.device)
+        _lib.check(_lib.lib().lt_mlp_trainer_logits(self._h, out.data_ptr(), self.c, _stream()), "lt_mlp_trainer_logits")
+        return out
+
+    def last_order(self) -> torch.Tensor:
+        """The row order of the last epoch run under the Philox shuffle, int32 [n]."""
+        out = torch.empty((self.n,), dtype=torch.int32, device=self.x.device)
+        _lib.check(_lib.lib().lt_mlp_trainer_order(self._h, out.data_ptr(), _stream()), "lt_mlp_trainer_order")
+        return out
+
+
+def mlp_forward(x, *params, depth, rows=None) -> torch.Tensor:
+    """Eval-mode logits of an MLP baseline (lt_mlp_forward) for all rows of ``x`` or the listed ones: [rows, C] float32."""
+    x = _f32(x, "x")
+    n, f = x.shape
+    ps, _, dims = _mlp_params(params, depth, f)
+    r = None if rows is None else _as_nodes(rows, n, x.device, "rows")
+    m = n if r is None else int(r.numel())
+    c, h = dims[-1], dims[1] if depth == 2 else 0
+    out = torch.empty((m, c), dtype=torch.float32, device=x.device)
+    if m == 0:
+        return out
+    lib = _lib.lib()
+    ws = _workspace(lib.lt_mlp_forward_workspace_bytes(m, f, depth, h, c), x.device)
+    ptrs = [t.data_ptr() for t in ps] + [None] * (4 - len(ps))
+    _lib.check(lib.lt_mlp_forward(x.data_ptr(), f, n, f, depth, h, c, *ptrs, None if r is None else r.data_ptr(), m,
+                                  out.data_ptr(), c, ws.data_ptr(), ws.numel(), _stream()), "lt_mlp_forward")
+    return out

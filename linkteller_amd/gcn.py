@@ -91,3 +91,58 @@ class GCN3(nn.Module):
         h = self.gc1(x, adj, relu=True)
         h = self.gc2(h, adj, relu=True)
         return self.gc3(h, adj)
+
+
+class _MLPBase(nn.Module):
+    """What the two feature-only baselines share: inference through the library (``engine.mlp_forward``), autograd refused.
+    The layers are ``nn.Linear`` ([out, in] weights, the reference's key names); the kernels read the project's [in, out]
+    layout, so a forward transposes the weights once per call."""
+
+    _LAYERS = ()
+
+    def project_params(self):
+        """The trained layers' parameters in the project's layout: [in, out] weight, bias, per layer in order (fresh
+        contiguous tensors on the parameters' device)."""
+        out = []
+        for name in self._LAYERS:
+            layer = getattr(self, name)
+            out += [layer.weight.detach().t().contiguous(), layer.bias.detach().clone()]
+        return out
+
+    def load_project_params(self, params):
+        """The inverse of ``project_params``: copy [in, out] weights and biases into the ``nn.Linear`` layers."""
+        with torch.no_grad():
+            for k, name in enumerate(self._LAYERS):
+                layer = getattr(self, name)
+                layer.weight.copy_(params[2 * k].t())
+                layer.bias.copy_(params[2 * k + 1])
+
+    def forward(self, x, rows=None):
+        _refuse_training(self)
+        return engine.mlp_forward(x, *self.project_params(), depth=len(self._LAYERS), rows=rows)
+
+
+class SingleHiddenLayerMLP(_MLPBase):
+    """W2(dropout(relu(W1 x))), raw logits (reference gcn/models.py:91-107).  Created by ``nn.Linear``'s own init in the
+    reference's construction order -- W1, W2, then the reference's unused ``W`` layer, which the state_dict carries and
+    Adam never touches (it has no gradient) -- so a seed gives the reference's initial parameters and a saved ``model.pt``
+    loads into the reference's class and back."""
+
+    _LAYERS = ("W1", "W2")
+
+    def __init__(self, nfeat, nhid, nclass, dropout):
+        super().__init__()
+        self.W1 = nn.Linear(nfeat, nhid)
+        self.W2 = nn.Linear(nhid, nclass)
+        self.dropout = dropout
+        self.W = nn.Linear(nfeat, nclass)
+
+
+class OneLayerMLP(_MLPBase):
+    """W x, raw logits (reference gcn/models.py:110-120): logistic regression on the node features."""
+
+    _LAYERS = ("W",)
+
+    def __init__(self, nfeat, nclass):
+        super().__init__()
+        self.W = nn.Linear(nfeat, nclass)

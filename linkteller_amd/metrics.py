@@ -52,3 +52,28 @@ def curves_from_counts(thresholds, tps, fps) -> dict:
     return {"auc": {"fpr": fpr, "tpr": tpr, "thresholds": r_thr},
             "pr": {"precision": precision, "recall": recall, "thresholds": thr[::-1]},
             "auc_value": auc_value, "ap_value": ap_value}
+
+
+def rare_class_f1(output, labels, bare_zero=True):
+    """F1 / precision / recall / AP of the minority class of a two-class problem (reference gcn_trainer.py:262-284,
+    mlp_trainer.py:181-202): ``output`` [n, 2] logits, ``labels`` [n] of 0 / 1.  The rare class is 1 unless there are more
+    ones than zeros; AP scores the confidence of the predicted class against "is the rare class", as the reference does.
+    When no row is predicted as the rare class the reference returns a bare 0: so does ``bare_zero=True``; otherwise
+    (0.0, 0.0, 0.0, AP).  When rows are predicted rare and none of them is (precision = recall = 0, where the reference
+    divides by zero) F1 is 0.0."""
+    import torch
+    import torch.nn.functional as F
+    from sklearn.metrics import average_precision_score
+    ind = [torch.where(labels == 0)[0], torch.where(labels == 1)[0]]
+    rare = int(len(ind[0]) > len(ind[1]))
+    conf, pred = F.softmax(output, dim=1).max(1)
+    ap = average_precision_score(labels.cpu() if rare == 1 else 1 - labels.cpu(), conf.detach().cpu())
+    pred = pred.type_as(labels)
+    tp = torch.sum(pred[ind[rare]] == rare).item()
+    t, p = len(ind[rare]), torch.sum(pred == rare).item()
+    if p == 0:
+        return 0 if bare_zero else (0.0, 0.0, 0.0, ap)
+    precision, recall = tp / p, tp / t
+    if tp == 0:
+        return 0.0, precision, recall, ap
+    return 2 * precision * recall / (precision + recall), precision, recall, ap

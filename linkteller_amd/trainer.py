@@ -13,7 +13,6 @@ import time
 
 import torch
 import torch.nn.functional as F
-from sklearn.metrics import average_precision_score
 
 from .attacker import Attacker
 from .gcn import GCN, GCN3
@@ -217,18 +216,9 @@ class GCNTrainer:
         self.split_results = {"loss_valid": loss_valid, "f1_valid": acc_valid, "loss_test": loss_test, "f1_test": acc_test}
 
     def rare_class_f1(self, output, labels):
-        """gcn_trainer.py:262-284: F1 / precision / recall / AP of the minority class."""
-        ind = [torch.where(labels == 0)[0], torch.where(labels == 1)[0]]
-        rare = int(len(ind[0]) > len(ind[1]))
-        conf, pred = F.softmax(output, dim=1).max(1)
-        ap = average_precision_score(labels.cpu() if rare == 1 else 1 - labels.cpu(), conf.detach().cpu())
-        pred = pred.type_as(labels)
-        tp = torch.sum(pred[ind[rare]] == rare).item()
-        t, p = len(ind[rare]), torch.sum(pred == rare).item()
-        if p == 0:
-            return 0
-        precision, recall = tp / p, tp / t
-        return 2 * precision * recall / (precision + recall), precision, recall, ap
+        """gcn_trainer.py:262-284: F1 / precision / recall / AP of the minority class (``metrics.rare_class_f1``)."""
+        from .metrics import rare_class_f1
+        return rare_class_f1(output, labels)
 
     def _recover_whole_graph(self):
         """addition: ``--recover --recover-nodes all`` -- the attacked graph itself instead of a sample (``Attacker.recover_graph``)."""

@@ -55,11 +55,24 @@ def read_musae_edges(folder: str, code: str, n_nodes: int):
 GRAPHSAINT = ("reddit", "flickr", "ppi", "ppi-large")      # reference utils/load.py:115
 
 
-def read_graphsaint(folder: str):
+def is_transfer(dataset: str) -> bool:
+    """The reference's transfer rule (gcn_trainer.py:54-56, mlp_trainer.py:39-41): two graphs, train on one, test on the other."""
+    return (dataset.startswith("twitch") and not dataset.startswith("twitch-train")) \
+        or dataset.startswith("wikipedia") or dataset.startswith("deezer")
+
+
+def is_served(dataset: str) -> bool:
+    """The datasets this package reads: ``twitch/<A>/<B>`` and the GraphSAINT family."""
+    return dataset in GRAPHSAINT or (dataset.startswith("twitch") and not dataset.startswith("twitch-train")
+                                     and len(dataset.split("/")) == 3)
+
+
+def read_graphsaint(folder: str, with_adj: bool = True):
     """``role.json`` / ``feats.npy`` / ``class_map.json`` / ``adj_full.npz`` of a GraphSAINT dataset -> (features, features_train,
     labels, idx_train, idx_val, idx_test, adj_full) as reference utils/load.py:115-148, 209-216, 485-488 forms them: sorted
     index arrays, features standardised in float64 with the training rows' statistics and then narrowed to float32, labels a
-    LongTensor [n, multi_label] (``multi_label`` = the length of the first value of the class map, 1 for a plain int)."""
+    LongTensor [n, multi_label] (``multi_label`` = the length of the first value of the class map, 1 for a plain int).
+    ``with_adj=False`` leaves ``adj_full.npz`` unread and returns None in its place (the feature-only baselines)."""
     from sklearn.preprocessing import StandardScaler
     with open(os.path.join(folder, "role.json")) as fh:
         role = json.load(fh)
@@ -80,6 +93,8 @@ def read_graphsaint(folder: str):
     for key, value in class_map.items():
         labels[int(key)] = value
     labels = torch.LongTensor(labels)
+    if not with_adj:
+        return features, features_train, labels, idx_train, idx_val, idx_test, None
     adj = np.load(os.path.join(folder, "adj_full.npz"))
     n, m = adj["shape"]
     adj_full = sp.csr_matrix((adj["data"], adj["indices"], adj["indptr"]), (n, m))
@@ -92,8 +107,7 @@ class Worker:
         self.dataset = dataset
         self.mode = mode
         self.data_root = data_root
-        self.transfer = (dataset.startswith("twitch") and not dataset.startswith("twitch-train")) \
-            or dataset.startswith("wikipedia") or dataset.startswith("deezer")
+        self.transfer = is_transfer(dataset)
         self.load_data()
 
     def load_data(self):
@@ -200,3 +214,36 @@ class Worker:
         print("Normalizing Adj done!")
         self.features_1, self.features_2 = self.features_1.cuda(), self.features_2.cuda()
         self.labels_1, self.labels_2 = self.labels_1.cuda(), self.labels_2.cuda()
+
+
+class FeatureData:
+    """The graph-free view of a dataset for the feature-only baselines (``main_simple``): what ``Worker`` exposes of it,
+    without reading, perturbing or normalising an adjacency (no edge file is opened for either dataset family).  Transfer datasets (``twitch/<A>/<B>``):
+    ``features_1 / labels_1`` (training graph's nodes), ``features_2 / labels_2``.  The GraphSAINT family: ``features``,
+    ``labels`` [n, multi_label], ``idx_train / idx_val / idx_test``."""
+
+    def __init__(self, dataset, mode="mlp", data_root="./data"):
+        self.dataset, self.mode, self.data_root = dataset, mode, data_root
+        self.transfer = is_transfer(dataset)
+        dev = "cuda" if torch.cuda.is_available() else "cpu"
+        if dataset in GRAPHSAINT:
+            (features, _, labels, self.idx_train, self.idx_val, self.idx_test, _) = \
+                read_graphsaint(os.path.join(data_root, dataset), with_adj=False)
+            self.features, self.labels = features.to(dev), labels.to(dev)
+            self.n_nodes, self.n_features = len(labels), features.shape[1]
+            self.multi_label = labels.shape[1]
+            self.n_classes = labels.max().item() + 1 if self.multi_label == 1 else self.multi_label
+            return
+        if not (dataset.startswith("twitch") and not dataset.startswith("twitch-train")):
+            raise NotImplementedError(f"dataset = {dataset} not implemented! (served: twitch/<A>/<B>, {' / '.join(GRAPHSAINT)})")
+        family, code_1, code_2 = dataset.split("/")
+        f1, labels_1 = read_musae_features(os.path.join(data_root, family, code_1), code_1)
+        f2, labels_2 = read_musae_features(os.path.join(data_root, family, code_2), code_2)
+        from sklearn.preprocessing import StandardScaler
+        scaler = StandardScaler().fit(f1)                         # worker.py:486-490
+        self.features_1 = torch.FloatTensor(scaler.transform(f1)).to(dev)
+        self.features_2 = torch.FloatTensor(scaler.transform(f2)).to(dev)
+        self.labels_1, self.labels_2 = labels_1.to(dev), labels_2.to(dev)
+        self.n_nodes_1, self.n_nodes_2 = len(labels_1), len(labels_2)
+        self.n_nodes = self.n_nodes_2
+        self.n_features, self.multi_label, self.n_classes = TWITCH_N_FEATURES, 1, 2
