@@ -1005,19 +1005,107 @@ extern "C" size_t lt_influence3_workspace_bytes(const lt_baseline3 *b, int32_t n
     return carve3(nullptr, b, n_probe, n_obs).bytes;
 }
 
-// The probe chunks of a wide handle (LT_MODE_DELTA; the lists are the checked ones, the fp64 pre-activations are fresh): level 1
-// as for a narrow handle, then the wide forms of the last two steps (k3w_rank2 ... k3dw_stageC above).  Enqueue only.
-// The caller's pair list (lt_influence3_pairs).  A call with one has no observe list (n_obs = 0): observe_nodes is the checked pair_obs,
-// and only the last step of a chunk -- the observed rows -- reads it.
-struct lt_pairs3_job {
-    const int64_t *ptr;      // HOST [n_probe + 1], validated by the caller
-    const int32_t *obs;      // device [n_pairs]
-    int64_t n_pairs;
-};
+// ---- what the rows and pairs calls of lt_baseline3 and lt_baseline2w share (influence3_impl, influence3_wide_chunks, influence2w_impl) ----
+// The front of a call: everything that refuses it before its first launch.  fn: the entry point that was called; serves(): the handle's
+// own word on a known mode (a return code).  A pair list (pj; lt_internal.h) brings the observed ids of the call.  *go = false with
+// LT_OK: an empty list, nothing to do.
+template <class Serves>
+static int probe_front(const char *fn, int32_t n, int32_t mode, Serves serves, const int32_t *probe_nodes, int32_t n_probe,
+                       const int32_t **observe_nodes, int32_t n_obs, float delta, const float *out, int64_t ldo, const void *workspace,
+                       size_t workspace_bytes, size_t need, const lt_pairs_job *pj, bool *go) {
+    *go = false;
+    LT_REQUIRE(mode == LT_MODE_SPARSE || mode == LT_MODE_FULL || mode == LT_MODE_DELTA, "%s: unknown mode %d", fn, mode);
+    { const int rc = serves(); if (rc) return rc; }
+    LT_REQUIRE(n_probe >= 0 && n_obs >= 0, "%s: negative count", fn);
+    LT_REQUIRE(delta != 0.f && delta == delta, "%s: delta must be a non-zero number", fn);
+    if (n_probe == 0 || (pj ? pj->n_pairs == 0 : n_obs == 0)) return LT_OK;
+    if (pj) *observe_nodes = pj->obs;
+    LT_REQUIRE(probe_nodes && *observe_nodes && out, "%s: NULL pointer", fn);
+    LT_REQUIRE(pj || ldo >= n_obs, "%s: ldo=%lld < n_obs=%d", fn, (long long)ldo, n_obs);
+    LT_REQUIRE(n > 0, "%s: empty graph", fn);
+    { const int rc = lt_node_err_pending(); if (rc) return rc; }     // an earlier call's list held an id out of range
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 256))
+        return lt_set_error(LT_ERR_WORKSPACE, "%s: workspace needs %zu bytes, 256-byte aligned", fn, need);
+    *go = true;
+    return LT_OK;
+}
 
+// Every chunk's grid limits, before anything is enqueued: the lane groups of the chunk's last launch (`lanes` per cell) and the launches
+// over the chunk's items (at most rows_max per probe; 0: the carve keeps that product an int).  A chunk of a pair list whose probes own
+// no pair launches nothing.
+static int probe_chunk_limits(const char *fn, int n_probe, int chunk, int n_obs, const lt_pairs_job *pj, int lanes, long rows_max) {
+    for (int p0 = 0; p0 < n_probe; p0 += chunk) {
+        const int nb = (n_probe - p0) < chunk ? (n_probe - p0) : chunk;
+        const long cells = pj ? (long)(pj->ptr[p0 + nb] - pj->ptr[p0]) : (long)nb * n_obs;
+        if (pj && cells == 0) continue;
+        LT_REQUIRE((cells * lanes + LT_BLOCK - 1) / LT_BLOCK < 2147483647L, "%s: %ld cells per chunk of %d probes exceed the grid limit",
+                   fn, cells, nb);
+        LT_REQUIRE((long)nb * rows_max < 2147483647L, "%s: %d probes x %ld rows per chunk exceed the grid limit", fn, nb, rows_max);
+    }
+    return LT_OK;
+}
+
+// Node ids: both lists checked into the workspace, which the call reads from then on (the first reader is a GEMM that gathers
+// X[probes]).  A pair list: pair_obs is the observed list of the check -- LT_PAIRS_MAX keeps the two counts' sum an int -- and the
+// offsets go to the device behind it by one stream-ordered copy.
+static int probe_check_nodes(int n, const int32_t **probe_nodes, int n_probe, const int32_t **observe_nodes, int n_obs,
+                             const lt_pairs_job *pj, int32_t *probes_s, int32_t *obs_s, int64_t *pair_ptr_dev, hipStream_t st) {
+    const long n_list = pj ? (long)pj->n_pairs : (long)n_obs, tot = (long)n_probe + n_list;
+    hipLaunchKernelGGL(k_check_nodes, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, *probe_nodes, n_probe, *observe_nodes,
+                       (int)n_list, n, probes_s, obs_s, lt_node_err_dev());
+    LT_CHECK_LAUNCH();
+    *probe_nodes = probes_s;
+    *observe_nodes = obs_s;
+    if (pj) LT_HIP(hipMemcpyAsync(pair_ptr_dev, pj->ptr, ((size_t)n_probe + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    return LT_OK;
+}
+
+// Level 1 of the exact chain for a chunk's probes, over the inner baseline l1 of (X, W1, b1): the probes' own product rows in fp64
+// (dS1[v] = d * S1[v]) -- read off the inner baseline's product where it holds one (formed for every row: the 2-layer stage A reads a
+// probe's row the same way; X[probes] W1 over again on the f64 cores was 0.40 of the 0.87 ms this build took at twitch size, round 6),
+// formed here on the aggregate-first route --, the level-1 bitmap with positions (bits1, off) and dH1x on the fp64 pre-activation.
+static int exact_level1(const lt_graph *g, const lt_baseline *l1, const float *X, int64_t ldx, const float *W1, int F, int H, int Hp,
+                        int lpr1, const int32_t *probes, int nb, int words, double *Spd, uint2 *bits1, int32_t *off, float delta,
+                        float *dH1x, hipStream_t st) {
+    int rc = lt_tune().gcn3_product_gather != 0 ? lt_fp64_product_rows_gather(l1, probes, nb, Spd, (long)Hp, st) : 1;
+    if (rc == 1) {
+        if (Hp != H) LT_HIP(hipMemsetAsync(Spd, 0, (size_t)nb * Hp * sizeof(double), st));
+        rc = lt_launch_gemm_f64_gather(X, (long)ldx, probes, nb, W1, (long)H, H, F, Spd, (long)Hp, st);
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_item_bits, dim3(nb), dim3(256), 0, st, g->tptr, g->trow, probes, nb, words, bits1, off, (int2 *)nullptr, (uint2 *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
+    LT_CHECK_LAUNCH();
+    LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k3d_items1<LPR_>), dim3(LT3_GRID), dim3(LT_BLOCK), 0, st, g->tptr, g->trow, g->tval, probes,
+                                             nb, off, Spd, l1->Z1d, Hp, delta, dH1x));
+    LT_CHECK_LAUNCH();
+    return LT_OK;
+}
+
+// The last launch of a wide chunk, the observed rows: the cells of probes [p0, p0 + nb) x the observed list into the rectangle, or the
+// chunk's pairs [k0, k1) into out[k], over the tables (dSx, rank, off) of the level in front (k3dw_stageC / k3dw_stageC_pairs).
+static int wide_observed_rows(const lt_graph *g, int C, int Cp, int lprc, int p0, int nb, const float *dSx, const uint2 *rank, int words,
+                              const int32_t *off, const lt_pairs_job *pj, const int64_t *pair_ptr_dev, long k0, long k1,
+                              const int32_t *observe_nodes, int n_obs, float delta, float *out, int64_t ldo, hipStream_t st) {
+    const long cells = pj ? k1 - k0 : (long)nb * n_obs;
+    const unsigned gridC = (unsigned)((cells * lprc + LT_BLOCK - 1) / LT_BLOCK);
+    if (pj) {
+        LT_DISPATCH_LPR(lprc, hipLaunchKernelGGL((k3dw_stageC_pairs<LPR_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col,
+                                                 g->val, C, Cp, nb, dSx, rank, words, off, pair_ptr_dev + p0, k0, k1, observe_nodes,
+                                                 delta, out));
+    } else {
+        LT_DISPATCH_LPR(lprc, hipLaunchKernelGGL((k3dw_stageC<LPR_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
+                                                 C, Cp, nb, dSx, rank, words, off, observe_nodes, n_obs, delta,
+                                                 out + (int64_t)p0 * ldo, (long)ldo));
+    }
+    LT_CHECK_LAUNCH();
+    return LT_OK;
+}
+
+// The probe chunks of a wide handle (LT_MODE_DELTA; the lists are the checked ones, the fp64 pre-activations are fresh, the grid limits
+// hold): level 1 as for a narrow handle, then the wide forms of the last two steps (k3w_rank2 ... k3dw_stageC above).  Enqueue only.
 static int influence3_wide_chunks(const lt_baseline3 *b, const infl3_ws &w, const int32_t *probe_nodes, int n_probe,
                                   const int32_t *observe_nodes, int n_obs, float delta, float *out, int64_t ldo, hipStream_t st,
-                                  const lt_pairs3_job *pj) {
+                                  const lt_pairs_job *pj) {
     const lt_graph *g = b->g;
     const int n = b->n, C = b->C, Cp = b->Cp, Hp1 = b->Hp1, Hp2 = b->Hp2;
     const int lpr1 = lt_lpr_for(Hp1), lpr2 = lt_lpr_for(Hp2), lprc = lt_lpr_for(Cp);
@@ -1026,30 +1114,13 @@ static int influence3_wide_chunks(const lt_baseline3 *b, const infl3_ws &w, cons
     for (int p0 = 0; p0 < n_probe; p0 += w.chunk) {
         const int nb = (n_probe - p0) < w.chunk ? (n_probe - p0) : w.chunk;
         const int32_t *probes = probe_nodes + p0;
-        float *orow = out + (int64_t)p0 * ldo;
         // (a pair list: the chunk's pairs by value; a chunk whose probes own none is skipped whole, levels 1 and 2 included)
         const long k0 = pj ? (long)pj->ptr[p0] : 0L, k1 = pj ? (long)pj->ptr[p0 + nb] : 0L;
         if (pj && k0 == k1) continue;
-        const long cells = pj ? k1 - k0 : (long)nb * n_obs;
-        if (pj) LT_REQUIRE((cells * lprc + LT_BLOCK - 1) / LT_BLOCK < 2147483647L,
-                           "lt_influence3_pairs: %ld pairs per chunk of %d probes exceed the grid limit", cells, nb);
-        else LT_REQUIRE((cells * lprc + LT_BLOCK - 1) / LT_BLOCK < 2147483647L,
-                        "lt_influence3_rows: %d probes x %d observed nodes per chunk exceed the grid limit", nb, n_obs);
         const long m_bound = (long)nb * maxc, m2_bound = (long)nb * n;
-        LT_REQUIRE(m_bound < 2147483647L && m2_bound < 2147483647L,
-                   "lt_influence3_rows: %d probes x %ld rows per chunk exceed the grid limit", nb, maxc > n ? maxc : (long)n);
-        // level 1 (the narrow chain's): the probes' product rows in fp64, the items, dH1 on the fp64 pre-activation, dS2x = dH1x W2
-        int rc = lt_tune().gcn3_product_gather != 0 ? lt_fp64_product_rows_gather(b->l1, probes, nb, w.Spd, (long)Hp1, st) : 1;
-        if (rc == 1) {
-            if (Hp1 != b->H1) LT_HIP(hipMemsetAsync(w.Spd, 0, (size_t)nb * Hp1 * sizeof(double), st));
-            rc = lt_launch_gemm_f64_gather(b->X, (long)b->ldx, probes, nb, b->W1, (long)b->H1, b->H1, b->F, w.Spd, (long)Hp1, st);
-        }
+        // level 1 (the narrow chain's), then dS2x = dH1x W2
+        int rc = exact_level1(g, b->l1, b->X, b->ldx, b->W1, b->F, b->H1, Hp1, lpr1, probes, nb, words, w.Spd, w.bits1, w.off, delta, w.H1x, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_item_bits, dim3(nb), dim3(256), 0, st, g->tptr, g->trow, probes, nb, words, w.bits1, w.off, (int2 *)nullptr, (uint2 *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
-        LT_CHECK_LAUNCH();
-        LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k3d_items1<LPR_>), dim3(LT3_GRID), dim3(LT_BLOCK), 0, st, g->tptr, g->trow,
-                                                 g->tval, probes, nb, w.off, w.Spd, b->l1->Z1d, Hp1, delta, w.H1x));
-        LT_CHECK_LAUNCH();
         if (Hp2 != b->H2) LT_HIP(hipMemsetAsync(w.S2x, 0, (size_t)m_bound * Hp2 * sizeof(float), st));
         rc = lt_launch_gemm_mdev(w.H1x, Hp1, b->W2, b->H2, w.S2x, Hp2, (int)m_bound, w.off + nb, b->H2, b->H1, st);
         if (rc) return rc;
@@ -1070,17 +1141,9 @@ static int influence3_wide_chunks(const lt_baseline3 *b, const infl3_ws &w, cons
         rc = lt_launch_gemm_mdev(w.dH2x, Hp2, b->W3, C, w.S3x, Cp, (int)m2_bound, w.off2 + nb, C, b->H2, st);
         if (rc) return rc;
         // level 3: the observed rows
-        const unsigned gridC = (unsigned)((cells * lprc + LT_BLOCK - 1) / LT_BLOCK);
-        if (pj) {
-            LT_DISPATCH_LPR(lprc, hipLaunchKernelGGL((k3dw_stageC_pairs<LPR_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col,
-                                                     g->val, C, Cp, nb, w.S3x, w.rank2, words, w.off2, w.pair_ptr + p0, k0, k1,
-                                                     observe_nodes, delta, out));
-        } else {
-            LT_DISPATCH_LPR(lprc, hipLaunchKernelGGL((k3dw_stageC<LPR_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
-                                                     C, Cp, nb, w.S3x, w.rank2, words, w.off2, observe_nodes, n_obs, delta, orow,
-                                                     (long)ldo));
-        }
-        LT_CHECK_LAUNCH();
+        rc = wide_observed_rows(g, C, Cp, lprc, p0, nb, w.S3x, w.rank2, words, w.off2, pj, w.pair_ptr, k0, k1, observe_nodes, n_obs, delta, out,
+                                ldo, st);
+        if (rc) return rc;
     }
     return LT_OK;
 }
@@ -1094,7 +1157,7 @@ extern "C" int lt_influence3_rows(const lt_baseline3 *b, const int32_t *probe_no
 
 static int influence3_impl(const lt_baseline3 *b, const int32_t *probe_nodes, int32_t n_probe, const int32_t *observe_nodes,
                            int32_t n_obs, float delta, int32_t mode, float *out, int64_t ldo, void *workspace, size_t workspace_bytes,
-                           void *stream, const lt_pairs3_job *pj);
+                           void *stream, const lt_pairs_job *pj);
 
 extern "C" int lt_influence3_rows_mode(const lt_baseline3 *b, const int32_t *probe_nodes, int32_t n_probe,
                                        const int32_t *observe_nodes, int32_t n_obs, float delta, int32_t mode, float *out,
@@ -1112,67 +1175,44 @@ extern "C" int lt_influence3_pairs(const lt_baseline3 *b, const int32_t *probe_n
                                    const int32_t *pair_obs, int64_t n_pairs, float delta, int32_t mode, float *out,
                                    void *workspace, size_t workspace_bytes, void *stream) {
     LT_REQUIRE(b != nullptr, "lt_influence3_pairs: baseline is NULL");
-    LT_REQUIRE(n_probe >= 0 && n_pairs >= 0, "lt_influence3_pairs: negative count");
-    LT_REQUIRE(n_pairs <= LT_PAIRS_MAX, "lt_influence3_pairs: %lld pairs (at most %lld per call)", (long long)n_pairs, (long long)LT_PAIRS_MAX);
-    // the offsets, on the host, before anything is launched
-    LT_REQUIRE(pair_ptr != nullptr || n_pairs == 0, "lt_influence3_pairs: pair_ptr is NULL");
-    if (pair_ptr) {
-        LT_REQUIRE(pair_ptr[0] == 0, "lt_influence3_pairs: pair_ptr[0] = %lld, not 0", (long long)pair_ptr[0]);
-        for (int32_t i = 0; i < n_probe; ++i)
-            LT_REQUIRE(pair_ptr[i + 1] >= pair_ptr[i], "lt_influence3_pairs: pair_ptr decreases at probe %d", i);
-        LT_REQUIRE(pair_ptr[n_probe] == n_pairs, "lt_influence3_pairs: pair_ptr[n_probe] = %lld, n_pairs = %lld",
-                   (long long)pair_ptr[n_probe], (long long)n_pairs);
-    }
+    { const int rc = lt_pairs_check("lt_influence3_pairs", n_probe, pair_ptr, n_pairs); if (rc) return rc; }
     // (FULL names the quantity SPARSE computes for this model: lt_influence3_rows_mode evaluates both by the same launches)
-    const lt_pairs3_job pj = {pair_ptr, pair_obs, n_pairs};
+    const lt_pairs_job pj = {pair_ptr, pair_obs, n_pairs};
     return influence3_impl(b, probe_nodes, n_probe, nullptr, 0, delta, mode, out, 0, workspace, workspace_bytes, stream, &pj);
 }
 
 static int influence3_impl(const lt_baseline3 *b, const int32_t *probe_nodes, int32_t n_probe, const int32_t *observe_nodes,
                            int32_t n_obs, float delta, int32_t mode, float *out, int64_t ldo, void *workspace, size_t workspace_bytes,
-                           void *stream, const lt_pairs3_job *pj) {
-    LT_REQUIRE(b != nullptr, "lt_influence3_rows: baseline is NULL");
+                           void *stream, const lt_pairs_job *pj) {
+    const char *fn = pj ? "lt_influence3_pairs" : "lt_influence3_rows";
+    LT_REQUIRE(b != nullptr, "%s: baseline is NULL", fn);
     lt_prof_call prof_call_;
-    LT_REQUIRE(mode == LT_MODE_SPARSE || mode == LT_MODE_FULL || mode == LT_MODE_DELTA, "lt_influence3_rows_mode: unknown mode %d", mode);
     const bool exact = mode == LT_MODE_DELTA;
-    if (b->wide && !exact)
-        return lt_set_error(LT_ERR_UNSUPPORTED, "lt_influence3_rows: a wide handle (lt_baseline3_create_wide, C=%d) serves LT_MODE_DELTA "
-                            "only; the fp32 finite difference of this shape is the caller's loop over the unfused layers", b->C);
-    LT_REQUIRE(!exact || b->Z2d != nullptr, "lt_influence3_rows_mode: LT_MODE_DELTA needs lt_baseline3_enable_fp64");
-    LT_REQUIRE(n_probe >= 0 && n_obs >= 0, "lt_influence3_rows: negative count");
-    LT_REQUIRE(delta != 0.f && delta == delta, "lt_influence3_rows: delta must be a non-zero number");
-    if (n_probe == 0 || (pj ? pj->n_pairs == 0 : n_obs == 0)) return LT_OK;
-    if (pj) {
-        LT_REQUIRE(probe_nodes && pj->obs && out, "lt_influence3_pairs: NULL pointer");
-        observe_nodes = pj->obs;
-    } else {
-        LT_REQUIRE(probe_nodes && observe_nodes && out, "lt_influence3_rows: NULL pointer");
-        LT_REQUIRE(ldo >= n_obs, "lt_influence3_rows: ldo=%lld < n_obs=%d", (long long)ldo, n_obs);
+    {
+        const size_t need = pj ? lt_influence3_pairs_workspace_bytes(b, n_probe, pj->n_pairs) : lt_influence3_workspace_bytes(b, n_probe, n_obs);
+        bool go;
+        const int rc = probe_front(fn, b->n, mode, [&]() {
+            if (b->wide && !exact)
+                return lt_set_error(LT_ERR_UNSUPPORTED, "%s: a wide handle (lt_baseline3_create_wide, C=%d) serves LT_MODE_DELTA only; the "
+                                    "fp32 finite difference of this shape is the caller's loop over the unfused layers", fn, b->C);
+            LT_REQUIRE(!exact || b->Z2d != nullptr, "%s: LT_MODE_DELTA needs lt_baseline3_enable_fp64", fn);
+            return (int)LT_OK;
+        }, probe_nodes, n_probe, &observe_nodes, n_obs, delta, out, ldo, workspace, workspace_bytes, need, pj, &go);
+        if (rc || !go) return rc;
     }
-    LT_REQUIRE(b->n > 0, "lt_influence3_rows: empty graph");
-    { const int rc = lt_node_err_pending(); if (rc) return rc; }     // an earlier call's list held an id out of range
-    const size_t need = pj ? lt_influence3_pairs_workspace_bytes(b, n_probe, pj->n_pairs) : lt_influence3_workspace_bytes(b, n_probe, n_obs);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 256))
-        return lt_set_error(LT_ERR_WORKSPACE, "%s: workspace needs %zu bytes, 256-byte aligned",
-                            pj ? "lt_influence3_pairs" : "lt_influence3_rows", need);
     hipStream_t st = (hipStream_t)stream;
     const lt_graph *g = b->g;
     const infl3_ws w = carve3(workspace, b, n_probe, n_obs, pj ? pj->n_pairs : (int64_t)-1);
     const int n = b->n, C = b->C, Hp1 = b->Hp1, Hp2 = b->Hp2, cp = lt_cp_for(C);
-    {   // node ids: both lists checked into the workspace (the first reader is a GEMM that gathers X[probes])
-        // (a pair list: pair_obs is the observed list of the check -- LT_PAIRS_MAX keeps the two counts' sum an int -- and the offsets go
-        // to the device behind it by one stream-ordered copy)
-        const long n_list = pj ? (long)pj->n_pairs : (long)n_obs, tot = (long)n_probe + n_list;
-        hipLaunchKernelGGL(k_check_nodes, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, probe_nodes, n_probe, observe_nodes,
-                           (int)n_list, n, w.probes_s, w.obs_s, lt_node_err_dev());
-        LT_CHECK_LAUNCH();
-        probe_nodes = w.probes_s;
-        observe_nodes = w.obs_s;
-        if (pj) LT_HIP(hipMemcpyAsync(w.pair_ptr, pj->ptr, ((size_t)n_probe + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    const long maxc = g->max_col_nnz > 0 ? g->max_col_nnz : 1;
+    {   // (a wide handle's level-2 tables run over up to n rows per probe)
+        const int rc = probe_chunk_limits(fn, n_probe, w.chunk, n_obs, pj, b->wide ? lt_lpr_for(b->Cp) : LT_L2_LANES,
+                                          b->wide && n > maxc ? (long)n : maxc);
+        if (rc) return rc;
     }
+    { const int rc = probe_check_nodes(n, &probe_nodes, n_probe, &observe_nodes, n_obs, pj, w.probes_s, w.obs_s, w.pair_ptr, st); if (rc) return rc; }
     const int lpr1 = lt_lpr_for(Hp1), lpr2 = lt_lpr_for(Hp2);
     const int words = (n + 31) / 32;
-    const long maxc = g->max_col_nnz > 0 ? g->max_col_nnz : 1;
     {   // the baseline the mode reads: the fp64 pre-activations of the first two layers, or the fp32 forward
         const int rc = exact ? ensure3_fp64(b, st) : ensure3_fp32(b, st);
         if (rc) return rc;
@@ -1186,44 +1226,27 @@ static int influence3_impl(const lt_baseline3 *b, const int32_t *probe_nodes, in
         const long k0 = pj ? (long)pj->ptr[p0] : 0L, k1 = pj ? (long)pj->ptr[p0 + nb] : 0L;
         if (pj && k0 == k1) continue;
         const long cells = pj ? k1 - k0 : (long)nb * n_obs;
-        if (pj) LT_REQUIRE((cells * LT_L2_LANES + LT_BLOCK - 1) / LT_BLOCK < 2147483647L,
-                           "lt_influence3_pairs: %ld pairs per chunk of %d probes exceed the grid limit", cells, nb);
-        else LT_REQUIRE((cells * LT_L2_LANES + LT_BLOCK - 1) / LT_BLOCK < 2147483647L,
-                        "lt_influence3_rows: %d probes x %d observed nodes per chunk exceed the grid limit", nb, n_obs);
         const long m_bound = (long)nb * maxc;
-        LT_REQUIRE(m_bound < 2147483647L, "lt_influence3_rows: %d probes x %ld rows per chunk exceed the grid limit", nb, maxc);
         int rc;
+        // level 1: H1x rows (sparse: recomputed with row v substituted; delta: the change dH1), then S2x = H1x W2 (M = number of
+        // items, only known on the device: the GEMM runs over the chunk's upper bound nb * max column length, the tiles
+        // past the count exit -- no read-back, no host synchronisation)
         if (!exact) {
             // perturbed rows: Sp = (X[v] + X[v] d) W1, the slicing of the baseline product          attacker.py:101-105
             if (Hp1 != b->H1) LT_HIP(hipMemsetAsync(w.Sp, 0, (size_t)nb * Hp1 * sizeof(float), st));
             rc = lt_launch_gemm_splitk(b->X, b->ldx, b->W1, b->H1, w.Sp, Hp1, nb, b->H1, b->F, probe_kslice3(b), w.slabs, st,
                                        probes, delta);
             if (rc) return rc;
-        } else {
-            // the probes' own product rows in fp64 (dS1[v] = d * S1[v]): read off the inner baseline's product where it holds one
-            // (ensure3_fp64 formed it for every row: the 2-layer stage A reads a probe's row the same way) -- X[probes] W1 over again
-            // on the f64 cores was 0.40 of the 0.87 ms this build took at twitch size (round 6); formed here on the aggregate-first route
-            rc = lt_tune().gcn3_product_gather != 0 ? lt_fp64_product_rows_gather(b->l1, probes, nb, w.Spd, (long)Hp1, st) : 1;
-            if (rc == 1) {
-                if (Hp1 != b->H1) LT_HIP(hipMemsetAsync(w.Spd, 0, (size_t)nb * Hp1 * sizeof(double), st));
-                rc = lt_launch_gemm_f64_gather(b->X, (long)b->ldx, probes, nb, b->W1, (long)b->H1, b->H1, b->F, w.Spd, (long)Hp1, st);
-            }
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL(k_item_bits, dim3(nb), dim3(256), 0, st, g->tptr, g->trow, probes, nb, words, w.bits1, w.off, (int2 *)nullptr, (uint2 *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
-        LT_CHECK_LAUNCH();
-        // level 1: H1x rows (sparse: recomputed with row v substituted; delta: the change dH1), then S2x = H1x W2 (M = number of
-        // items, only known on the device: the GEMM runs over the chunk's upper bound nb * max column length, the tiles
-        // past the count exit -- no read-back, no host synchronisation)
-        if (!exact) {
+            hipLaunchKernelGGL(k_item_bits, dim3(nb), dim3(256), 0, st, g->tptr, g->trow, probes, nb, words, w.bits1, w.off, (int2 *)nullptr, (uint2 *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
+            LT_CHECK_LAUNCH();
             LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k3_rows_relu<LPR_>), dim3(LT3_GRID), dim3(LT_BLOCK), 0, st, 0, g->rowptr,
                                                      g->col, g->val, b->S1, Hp1, b->b1p, w.H1x, g->tptr, g->trow, probes, nb, w.off,
                                                      w.Sp));
+            LT_CHECK_LAUNCH();
         } else {
-            LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k3d_items1<LPR_>), dim3(LT3_GRID), dim3(LT_BLOCK), 0, st, g->tptr, g->trow,
-                                                     g->tval, probes, nb, w.off, w.Spd, b->l1->Z1d, Hp1, delta, w.H1x));
+            rc = exact_level1(g, b->l1, b->X, b->ldx, b->W1, b->F, b->H1, Hp1, lpr1, probes, nb, words, w.Spd, w.bits1, w.off, delta, w.H1x, st);
+            if (rc) return rc;
         }
-        LT_CHECK_LAUNCH();
         if (Hp2 != b->H2) LT_HIP(hipMemsetAsync(w.S2x, 0, (size_t)m_bound * Hp2 * sizeof(float), st));
         rc = lt_launch_gemm_mdev(w.H1x, Hp1, b->W2, b->H2, w.S2x, Hp2, (int)m_bound, w.off + nb, b->H2, b->H1, st);
         if (rc) return rc;
@@ -1445,28 +1468,20 @@ extern "C" size_t lt_influence2w_pairs_workspace_bytes(const lt_baseline2w *b, i
 // rows (pj == NULL) and pairs: everything but the last launch of a chunk is the same
 static int influence2w_impl(const lt_baseline2w *b, const int32_t *probe_nodes, int32_t n_probe, const int32_t *observe_nodes, int32_t n_obs,
                             float delta, int32_t mode, float *out, int64_t ldo, void *workspace, size_t workspace_bytes, void *stream,
-                            const lt_pairs3_job *pj) {
+                            const lt_pairs_job *pj) {
     const char *fn = pj ? "lt_influence2w_pairs" : "lt_influence2w_rows";
     lt_prof_call prof_call_;
-    LT_REQUIRE(mode == LT_MODE_SPARSE || mode == LT_MODE_FULL || mode == LT_MODE_DELTA, "%s: unknown mode %d", fn, mode);
-    if (mode != LT_MODE_DELTA)
-        return lt_set_error(LT_ERR_UNSUPPORTED, "%s: a lt_baseline2w handle (C=%d) serves LT_MODE_DELTA only; the fp32 finite difference "
-                            "of this shape is lt_influence_rows_vec + lt_wide_combine over class slices", fn, b->C);
-    LT_REQUIRE(n_probe >= 0 && n_obs >= 0, "%s: negative count", fn);
-    LT_REQUIRE(delta != 0.f && delta == delta, "%s: delta must be a non-zero number", fn);
-    if (n_probe == 0 || (pj ? pj->n_pairs == 0 : n_obs == 0)) return LT_OK;
-    if (pj) {
-        LT_REQUIRE(probe_nodes && pj->obs && out, "%s: NULL pointer", fn);
-        observe_nodes = pj->obs;
-    } else {
-        LT_REQUIRE(probe_nodes && observe_nodes && out, "%s: NULL pointer", fn);
-        LT_REQUIRE(ldo >= n_obs, "%s: ldo=%lld < n_obs=%d", fn, (long long)ldo, n_obs);
+    {
+        const size_t need = pj ? lt_influence2w_pairs_workspace_bytes(b, n_probe, pj->n_pairs) : lt_influence2w_workspace_bytes(b, n_probe, n_obs);
+        bool go;
+        const int rc = probe_front(fn, b->n, mode, [&]() {
+            if (mode != LT_MODE_DELTA)
+                return lt_set_error(LT_ERR_UNSUPPORTED, "%s: a lt_baseline2w handle (C=%d) serves LT_MODE_DELTA only; the fp32 finite "
+                                    "difference of this shape is lt_influence_rows_vec + lt_wide_combine over class slices", fn, b->C);
+            return (int)LT_OK;
+        }, probe_nodes, n_probe, &observe_nodes, n_obs, delta, out, ldo, workspace, workspace_bytes, need, pj, &go);
+        if (rc || !go) return rc;
     }
-    LT_REQUIRE(b->n > 0, "%s: empty graph", fn);
-    { const int rc = lt_node_err_pending(); if (rc) return rc; }     // an earlier call's list held an id out of range
-    const size_t need = pj ? lt_influence2w_pairs_workspace_bytes(b, n_probe, pj->n_pairs) : lt_influence2w_workspace_bytes(b, n_probe, n_obs);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 256))
-        return lt_set_error(LT_ERR_WORKSPACE, "%s: workspace needs %zu bytes, 256-byte aligned", fn, need);
     hipStream_t st = (hipStream_t)stream;
     const lt_graph *g = b->g;
     const infl2w_ws w = carve2w(workspace, b, n_probe, n_obs, pj ? pj->n_pairs : (int64_t)-1);
@@ -1474,23 +1489,8 @@ static int influence2w_impl(const lt_baseline2w *b, const int32_t *probe_nodes, 
     const int lpr1 = lt_lpr_for(Hp), lprc = lt_lpr_for(Cp);
     const int words = (n + 31) / 32;
     const long maxc = g->max_col_nnz > 0 ? g->max_col_nnz : 1;
-    // the grid of every chunk's last launch, before anything is enqueued
-    for (int p0 = 0; p0 < n_probe; p0 += w.chunk) {
-        const int nb = (n_probe - p0) < w.chunk ? (n_probe - p0) : w.chunk;
-        const long cells = pj ? (long)(pj->ptr[p0 + nb] - pj->ptr[p0]) : (long)nb * n_obs;
-        LT_REQUIRE((cells * lprc + LT_BLOCK - 1) / LT_BLOCK < 2147483647L, "%s: %ld cells per chunk of %d probes exceed the grid limit",
-                   fn, cells, nb);
-    }
-    {   // node ids: both lists checked into the workspace (a pair list: pair_obs is the observed list of the check, and the offsets
-        // go to the device behind it by one stream-ordered copy)
-        const long n_list = pj ? (long)pj->n_pairs : (long)n_obs, tot = (long)n_probe + n_list;
-        hipLaunchKernelGGL(k_check_nodes, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, probe_nodes, n_probe, observe_nodes,
-                           (int)n_list, n, w.probes_s, w.obs_s, lt_node_err_dev());
-        LT_CHECK_LAUNCH();
-        probe_nodes = w.probes_s;
-        observe_nodes = w.obs_s;
-        if (pj) LT_HIP(hipMemcpyAsync(w.pair_ptr, pj->ptr, ((size_t)n_probe + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    }
+    { const int rc = probe_chunk_limits(fn, n_probe, w.chunk, n_obs, pj, lprc, 0); if (rc) return rc; }
+    { const int rc = probe_check_nodes(n, &probe_nodes, n_probe, &observe_nodes, n_obs, pj, w.probes_s, w.obs_s, w.pair_ptr, st); if (rc) return rc; }
     { const int rc = lt_fp64_form_all(b->l1, st); if (rc) return rc; }      // Z1d, every row (nothing when it is current)
     for (int p0 = 0; p0 < n_probe; p0 += w.chunk) {
         const int nb = (n_probe - p0) < w.chunk ? (n_probe - p0) : w.chunk;
@@ -1498,35 +1498,17 @@ static int influence2w_impl(const lt_baseline2w *b, const int32_t *probe_nodes, 
         // (a pair list: the chunk's pairs by value; a chunk whose probes own none launches nothing)
         const long k0 = pj ? (long)pj->ptr[p0] : 0L, k1 = pj ? (long)pj->ptr[p0 + nb] : 0L;
         if (pj && k0 == k1) continue;
-        const long cells = pj ? k1 - k0 : (long)nb * n_obs;
         const long m_bound = (long)nb * maxc;       // (< 2^31: carve2w)
-        int rc = lt_tune().gcn3_product_gather != 0 ? lt_fp64_product_rows_gather(b->l1, probes, nb, w.Spd, (long)Hp, st) : 1;
-        if (rc == 1) {
-            if (Hp != b->H) LT_HIP(hipMemsetAsync(w.Spd, 0, (size_t)nb * Hp * sizeof(double), st));
-            rc = lt_launch_gemm_f64_gather(b->X, (long)b->ldx, probes, nb, b->W1, (long)b->H, b->H, b->F, w.Spd, (long)Hp, st);
-        }
+        int rc = exact_level1(g, b->l1, b->X, b->ldx, b->W1, b->F, b->H, Hp, lpr1, probes, nb, words, w.Spd, w.bits1, w.off, delta, w.dH1x, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_item_bits, dim3(nb), dim3(256), 0, st, g->tptr, g->trow, probes, nb, words, w.bits1, w.off, (int2 *)nullptr, (uint2 *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
-        LT_CHECK_LAUNCH();
-        LT_DISPATCH_LPR(lpr1, hipLaunchKernelGGL((k3d_items1<LPR_>), dim3(LT3_GRID), dim3(LT_BLOCK), 0, st, g->tptr, g->trow, g->tval,
-                                                 probes, nb, w.off, w.Spd, b->l1->Z1d, Hp, delta, w.dH1x));
-        LT_CHECK_LAUNCH();
         // dS2x = dH1x W2 over the items; W2 as the caller holds it (K = H rows, N = C columns: the pad columns of both operands
         // are left alone)
         rc = lt_launch_gemm_mdev(w.dH1x, Hp, b->W2, C, w.dS2x, Cp, (int)m_bound, w.off + nb, C, b->H, st);
         if (rc) return rc;
         // the observed rows: the wide chain's cell over the level-1 tables
-        const unsigned gridC = (unsigned)((cells * lprc + LT_BLOCK - 1) / LT_BLOCK);
-        if (pj) {
-            LT_DISPATCH_LPR(lprc, hipLaunchKernelGGL((k3dw_stageC_pairs<LPR_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col,
-                                                     g->val, C, Cp, nb, w.dS2x, w.bits1, words, w.off, w.pair_ptr + p0, k0, k1,
-                                                     observe_nodes, delta, out));
-        } else {
-            LT_DISPATCH_LPR(lprc, hipLaunchKernelGGL((k3dw_stageC<LPR_>), dim3(gridC), dim3(LT_BLOCK), 0, st, g->rowptr, g->col, g->val,
-                                                     C, Cp, nb, w.dS2x, w.bits1, words, w.off, observe_nodes, n_obs, delta,
-                                                     out + (int64_t)p0 * ldo, (long)ldo));
-        }
-        LT_CHECK_LAUNCH();
+        rc = wide_observed_rows(g, C, Cp, lprc, p0, nb, w.dS2x, w.bits1, words, w.off, pj, w.pair_ptr, k0, k1, observe_nodes, n_obs, delta, out,
+                                ldo, st);
+        if (rc) return rc;
     }
     return LT_OK;
 }
@@ -1543,17 +1525,7 @@ extern "C" int lt_influence2w_pairs(const lt_baseline2w *b, const int32_t *probe
                                     const int32_t *pair_obs, int64_t n_pairs, float delta, int32_t mode, float *out, void *workspace,
                                     size_t workspace_bytes, void *stream) {
     LT_REQUIRE(b != nullptr, "lt_influence2w_pairs: baseline is NULL");
-    LT_REQUIRE(n_probe >= 0 && n_pairs >= 0, "lt_influence2w_pairs: negative count");
-    LT_REQUIRE(n_pairs <= LT_PAIRS_MAX, "lt_influence2w_pairs: %lld pairs (at most %lld per call)", (long long)n_pairs, (long long)LT_PAIRS_MAX);
-    // the offsets, on the host, before anything is launched
-    LT_REQUIRE(pair_ptr != nullptr || n_pairs == 0, "lt_influence2w_pairs: pair_ptr is NULL");
-    if (pair_ptr) {
-        LT_REQUIRE(pair_ptr[0] == 0, "lt_influence2w_pairs: pair_ptr[0] = %lld, not 0", (long long)pair_ptr[0]);
-        for (int32_t i = 0; i < n_probe; ++i)
-            LT_REQUIRE(pair_ptr[i + 1] >= pair_ptr[i], "lt_influence2w_pairs: pair_ptr decreases at probe %d", i);
-        LT_REQUIRE(pair_ptr[n_probe] == n_pairs, "lt_influence2w_pairs: pair_ptr[n_probe] = %lld, n_pairs = %lld",
-                   (long long)pair_ptr[n_probe], (long long)n_pairs);
-    }
-    const lt_pairs3_job pj = {pair_ptr, pair_obs, n_pairs};
+    { const int rc = lt_pairs_check("lt_influence2w_pairs", n_probe, pair_ptr, n_pairs); if (rc) return rc; }
+    const lt_pairs_job pj = {pair_ptr, pair_obs, n_pairs};
     return influence2w_impl(b, probe_nodes, n_probe, nullptr, 0, delta, mode, out, 0, workspace, workspace_bytes, stream, &pj);
 }

@@ -2489,12 +2489,7 @@ struct lt_compact_out {
 // lt_influence_pairs: the caller's pair list.  A call with one has no observe list (observe_nodes = NULL, n_obs = 0): stage A runs as
 // in every other call on the item route -- no fused records, no pair marks, no per-row stage B, no hub blocks, all of which are keyed
 // by an observe list -- and stage B is k_pair_stageB writing out[k].
-// (LT_PAIRS_MAX, lt_internal.h: the list's check shares a launch -- and its int counts -- with the probes')
-struct lt_pairs_job {
-    const int64_t *ptr;      // HOST [n_probe + 1], validated by the caller
-    const int32_t *obs;      // device [n_pairs]
-    int64_t n_pairs;
-};
+// (lt_pairs_job and LT_PAIRS_MAX, lt_internal.h: the list's check shares a launch -- and its int counts -- with the probes')
 // lt_influence_step_host: what the call does inside influence_rows_impl, at the one place where it is known that nothing refuses the
 // call any more and which route it takes -- dst resolved only where the GPU writes it, then the baseline marked stale
 struct lt_host_job {
@@ -2914,18 +2909,8 @@ extern "C" int lt_influence_pairs(const lt_baseline *b, const int32_t *probe_nod
                                   const int32_t *pair_obs, int64_t n_pairs, float delta, int32_t mode, float *out,
                                   void *workspace, size_t workspace_bytes, void *stream) {
     LT_REQUIRE(b != nullptr, "lt_influence_pairs: baseline is NULL");
-    LT_REQUIRE(n_probe >= 0 && n_pairs >= 0, "lt_influence_pairs: negative count");
-    LT_REQUIRE(n_pairs <= LT_PAIRS_MAX, "lt_influence_pairs: %lld pairs (at most %lld per call)", (long long)n_pairs, (long long)LT_PAIRS_MAX);
     LT_REQUIRE(mode >= LT_MODE_FULL && mode <= LT_MODE_DELTA, "lt_influence_pairs: unknown mode %d", mode);
-    // the offsets, on the host, before anything is launched
-    LT_REQUIRE(pair_ptr != nullptr || n_pairs == 0, "lt_influence_pairs: pair_ptr is NULL");
-    if (pair_ptr) {
-        LT_REQUIRE(pair_ptr[0] == 0, "lt_influence_pairs: pair_ptr[0] = %lld, not 0", (long long)pair_ptr[0]);
-        for (int32_t i = 0; i < n_probe; ++i)
-            LT_REQUIRE(pair_ptr[i + 1] >= pair_ptr[i], "lt_influence_pairs: pair_ptr decreases at probe %d", i);
-        LT_REQUIRE(pair_ptr[n_probe] == n_pairs, "lt_influence_pairs: pair_ptr[n_probe] = %lld, n_pairs = %lld",
-                   (long long)pair_ptr[n_probe], (long long)n_pairs);
-    }
+    { const int rc = lt_pairs_check("lt_influence_pairs", n_probe, pair_ptr, n_pairs); if (rc) return rc; }
     if (n_probe == 0 || n_pairs == 0) return LT_OK;
     // (FULL names the quantity SPARSE computes, bit for bit: nothing of a pair list needs the all-rows stage A)
     const lt_pairs_job pj = {pair_ptr, pair_obs, n_pairs};

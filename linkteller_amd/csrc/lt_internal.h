@@ -348,6 +348,26 @@ int32_t *lt_node_err_dev();
 int lt_node_err_pending();
 // lt_influence_pairs / lt_influence3_pairs: pairs per call
 #define LT_PAIRS_MAX ((int64_t)2147483647 - 65536)      // the list's check shares a launch (and its int counts) with the probes'
+// lt_influence_pairs / lt_influence3_pairs / lt_influence2w_pairs: the caller's pair list.  A call with one has no observe list
+// (n_obs = 0): the checked pair_obs stands in for it, and only the last step of a probe chunk -- the observed rows -- reads it.
+struct lt_pairs_job {
+    const int64_t *ptr;      // HOST [n_probe + 1], validated by lt_pairs_check
+    const int32_t *obs;      // device [n_pairs]
+    int64_t n_pairs;
+};
+// the counts and the offsets of a pair list, on the host, before anything is launched (fn: the entry point that was called)
+static inline int lt_pairs_check(const char *fn, int32_t n_probe, const int64_t *pair_ptr, int64_t n_pairs) {
+    LT_REQUIRE(n_probe >= 0 && n_pairs >= 0, "%s: negative count", fn);
+    LT_REQUIRE(n_pairs <= LT_PAIRS_MAX, "%s: %lld pairs (at most %lld per call)", fn, (long long)n_pairs, (long long)LT_PAIRS_MAX);
+    LT_REQUIRE(pair_ptr != nullptr || n_pairs == 0, "%s: pair_ptr is NULL", fn);
+    if (pair_ptr) {
+        LT_REQUIRE(pair_ptr[0] == 0, "%s: pair_ptr[0] = %lld, not 0", fn, (long long)pair_ptr[0]);
+        for (int32_t i = 0; i < n_probe; ++i) LT_REQUIRE(pair_ptr[i + 1] >= pair_ptr[i], "%s: pair_ptr decreases at probe %d", fn, i);
+        LT_REQUIRE(pair_ptr[n_probe] == n_pairs, "%s: pair_ptr[n_probe] = %lld, n_pairs = %lld", fn, (long long)pair_ptr[n_probe],
+                   (long long)n_pairs);
+    }
+    return LT_OK;
+}
 
 int lt_baseline_refresh_fp64(lt_baseline *b, hipStream_t st);
 // what a call needs of the baseline, recomputed here if lt_baseline_refresh marked it stale: need_fp32 = S1 and the

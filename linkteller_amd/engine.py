@@ -117,36 +117,162 @@ def _refresh_handle(owner, name, *args):
     announced with ``features_changed()``."""
     v = _x_version(owner.x)
     if v != owner._x_seen:
-        changed = ("lt_baseline3_features_changed" if isinstance(owner, Baseline3) else
-                   "lt_baseline2w_features_changed" if isinstance(owner, Baseline2W) else "lt_baseline_features_changed")
+        changed = owner._SYM["changed"]
         _lib.check(getattr(_lib.lib(), changed)(owner._h, _stream()), changed)
         owner._x_seen = v
     _lib.check(getattr(_lib.lib(), name)(owner._h, *args, _stream()), name)
 
 
-class Baseline:
-    """Unperturbed forward state (S1, Z1, S2, logits) for the probe loop; see lt_baseline_create."""
+def _symbols(handle, calls, rows=None):
+    """The library's names of a probe handle's calls: ``handle`` prefixes the handle's own, ``calls`` the probe primitive's."""
+    return {"destroy": handle + "_destroy", "changed": handle + "_features_changed", "logits": handle + "_logits",
+            "rows": rows or calls + "_rows", "rows_ws": calls + "_workspace_bytes", "pairs": calls + "_pairs",
+            "pairs_ws": calls + "_pairs_workspace_bytes"}
 
-    def __init__(self, adj, x, w1, b1, w2, b2):
+
+class _ProbeHandle:
+    """What the probe handles ``Baseline``, ``Baseline3`` and ``Baseline2W`` share: the borrowed inputs and their checks, the
+    handle with its finalizer, ``features_changed`` / ``logits``, the cached workspace, the operands of the rectangle and the
+    whole of ``influence_pairs``.  A class says which symbols it calls (``_SYM``), which mode ``None`` stands for
+    (``_DEFAULT_MODE``), which modes it serves (``_serves``), whether `delta` needs ``enable_fp64`` first (``_fp64`` is False
+    until then; a class whose fp64 parts exist from creation sets it True) and whether its workspace depends on the mode
+    (``_WS_MODE``)."""
+
+    _SYM = None
+    _DEFAULT_MODE = "delta"
+    _WS_MODE = False
+    _fp64 = False
+
+    def _take(self, adj, error, **tensors):
+        """The constructor's front: ``x`` and (W, b) per layer by name -> ``self.x``, ``self.w1``, ``self.b1`` ... as contiguous
+        fp32 CUDA tensors, checked for consistent shapes (``ValueError(error)``), one device and finite values.  Returns the
+        widths (n, F, then every layer's)."""
         self.graph: HipGraph = as_hip_graph(adj)
-        self.x, self.w1, self.b1, self.w2, self.b2 = (
-            _f32(t, n) for t, n in ((x, "x"), (w1, "W1"), (b1, "b1"), (w2, "W2"), (b2, "b2")))
-        n, f = self.x.shape
-        self.n, self.f, self.h, self.c = n, f, self.w1.shape[1], self.w2.shape[1]
-        if n != self.graph.n or self.w1.shape[0] != f or self.w2.shape[0] != self.h:
-            raise ValueError("inconsistent GCN shapes")
+        held = [_f32(t, name) for name, t in tensors.items()]
+        for name, t in zip(tensors, held):
+            setattr(self, name.lower(), t)
+        self.n, self.f = n, f = self.x.shape
+        widths, ok = [n, f], n == self.graph.n
+        for w, b in zip(held[1::2], held[2::2]):
+            ok = ok and w.shape[0] == widths[-1] and b.numel() == w.shape[1]
+            widths.append(w.shape[1])
+        if not ok:
+            raise ValueError(error)
         if self.graph.device_index != self.x.device.index:
             raise ValueError(f"the graph lives on cuda:{self.graph.device_index}, the features on {self.x.device}")
-        _require_finite(features=self.x, W1=self.w1, b1=self.b1, W2=self.w2, b2=self.b2)
+        _require_finite(**{"features" if name == "x" else name: t for name, t in zip(tensors, held)})
+        self._layers = [a for w, b in zip(held[1::2], held[2::2]) for a in (w.data_ptr(), b.data_ptr(), w.shape[1])]
+        return widths
+
+    def _open(self, create):
+        """lt_*_create over what ``_take`` holds: the handle, its finalizer, the features' version, the workspace cache."""
         h = C.c_void_p()
-        _lib.check(_lib.lib().lt_baseline_create(self.graph.handle, self.x.data_ptr(), f, f, self.w1.data_ptr(),
-                                                 self.b1.data_ptr(), self.h, self.w2.data_ptr(),
-                                                 self.b2.data_ptr(), self.c, _stream(), C.byref(h)),
-                   "lt_baseline_create")
+        _lib.check(getattr(_lib.lib(), create)(self.graph.handle, self.x.data_ptr(), self.f, self.f, *self._layers, _stream(),
+                                               C.byref(h)), create)
         self._h = h
         self._x_seen = _x_version(self.x)       # the features' version the baseline's difference lists (if any) were built from
-        self._finalizer = weakref.finalize(self, _lib.lib().lt_baseline_destroy, h)
+        self._finalizer = weakref.finalize(self, getattr(_lib.lib(), self._SYM["destroy"]), h)
         self._ws = {}
+
+    @property
+    def handle(self):
+        return self._h
+
+    def features_changed(self):
+        """The contents of the feature tensor changed in a way torch's version counter does not show (a write through the raw
+        pointer, by another library): the difference lists of the feature route are built again (lt_baseline_features_changed
+        and its twins; may synchronise) and everything ``refresh()`` marks stale is stale.  In-place torch edits need no call:
+        ``refresh()`` sees the version counter."""
+        changed = self._SYM["changed"]
+        _lib.check(getattr(_lib.lib(), changed)(self._h, _stream()), changed)
+        self._x_seen = _x_version(self.x)
+        return self
+
+    def logits(self) -> torch.Tensor:
+        out = torch.empty((self.n, self.c), dtype=torch.float32, device=self.x.device)
+        _lib.check(getattr(_lib.lib(), self._SYM["logits"])(self._h, out.data_ptr(), _stream()), self._SYM["logits"])
+        return out
+
+    def _serves(self, m):
+        """Raise ``NotImplementedError`` for a mode the handle does not serve (before the node lists are touched)."""
+
+    def _mode(self, mode) -> int:
+        m = _lib.MODES[mode or self._DEFAULT_MODE] if isinstance(mode, str) or mode is None else int(mode)
+        self._serves(m)
+        return m
+
+    def _workspace(self, key, need):
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _workspace(need, self.x.device)
+            self._ws = {key: ws}   # keep only the latest: sizes repeat across steps
+        return ws
+
+    def _operands(self, m, probe_nodes, listed_nodes, out, ptr=None):
+        """What a rows call, or with the offsets ``ptr`` a pairs call, hands the library: the two node lists (``_as_nodes``), ``out``
+        allocated or validated, the fp64 parts for `delta`, the cached workspace by the call's own query."""
+        dev = self.x.device
+        probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
+        listed = _as_nodes(listed_nodes, self.n, dev, "observe_nodes" if ptr is None else "pair_obs")
+        npb, nls = probes.numel(), listed.numel()
+        if ptr is not None and ptr.size != npb + 1:
+            raise ValueError(f"pair_ptr must hold n_probe + 1 = {npb + 1} offsets, got {ptr.size}")
+        shape = (npb, nls) if ptr is None else (nls,)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+        elif out.shape != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous float32 {'[n_probe, n_obs]' if ptr is None else '[n_pairs]'} tensor on the "
+                             "baseline's device")
+        if m == _lib.MODE_DELTA and not self._fp64:
+            # kink test on an fp64-accumulated pre-activation (one-off cost, kept fresh by refresh())
+            self.enable_fp64()
+        extra = (m,) if self._WS_MODE else ()
+        key = ((npb, nls) if ptr is None else ("pairs", npb, nls)) + extra
+        query = getattr(_lib.lib(), self._SYM["rows_ws" if ptr is None else "pairs_ws"])
+        return probes, listed, out, self._workspace(key, query(self._h, npb, nls, *extra))   # (host arithmetic; depends on the knobs too)
+
+    def _rows(self, probe_nodes, observe_nodes, delta, mode, out, name=None, host=None):
+        """The rectangle by the handle's rows call, or by ``name``, a call that takes a float64 matrix ``host`` behind ``out``."""
+        m = self._mode(mode)
+        probes, obs, out, ws = self._operands(m, probe_nodes, observe_nodes, out)
+        npb, nob = out.shape
+        name = name or self._SYM["rows"]
+        dst = () if host is None else (host.data_ptr(), max(nob, 1))
+        _lib.check(getattr(_lib.lib(), name)(self._h, probes.data_ptr(), npb, obs.data_ptr(), nob, float(delta), m, out.data_ptr(),
+                                             nob, *dst, ws.data_ptr(), ws.numel(), _stream()), name)
+        return out
+
+    def influence_pairs(self, probe_nodes, pair_ptr, pair_obs, delta: float, mode="delta", out=None) -> torch.Tensor:
+        """[n_pairs] fp32 on the device: the scores of a LIST of pairs grouped by probe (lt_influence_pairs, lt_influence3_pairs,
+        lt_influence2w_pairs).  Probe i = ``probe_nodes[i]`` owns ``pair_obs[pair_ptr[i]:pair_ptr[i + 1]]`` (``group_pairs`` builds
+        the three from two id arrays) and ``out[k]`` is what ``influence_rows`` writes at (that probe, ``pair_obs[k]``) for the
+        same mode, bit for bit -- without the rectangle: the output and the workspace are sized by the list.  ``pair_ptr`` is a
+        HOST array of n_probe + 1 int64 offsets (validated by the library before anything is launched); the node lists follow
+        ``influence_rows`` (int32 CUDA tensors are checked on the device: ``engine.node_check()`` after synchronising).  Modes as
+        in ``influence_rows``."""
+        import numpy as np
+        m = self._mode(mode)
+        if isinstance(pair_ptr, torch.Tensor):
+            pair_ptr = pair_ptr.cpu().numpy()
+        ptr = np.ascontiguousarray(np.asarray(pair_ptr).reshape(-1), dtype=np.int64)
+        probes, obs, out, ws = self._operands(m, probe_nodes, pair_obs, out, ptr)
+        pairs = self._SYM["pairs"]
+        _lib.check(getattr(_lib.lib(), pairs)(self._h, probes.data_ptr(), probes.numel(), ptr.ctypes.data, obs.data_ptr(),
+                                              obs.numel(), float(delta), m, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                   pairs)
+        return out
+
+
+class Baseline(_ProbeHandle):
+    """Unperturbed forward state (S1, Z1, S2, logits) for the probe loop; see lt_baseline_create."""
+
+    _SYM = _symbols("lt_baseline", "lt_influence")
+    _DEFAULT_MODE = "full"
+    _WS_MODE = True
+
+    def __init__(self, adj, x, w1, b1, w2, b2):
+        _, _, self.h, self.c = self._take(adj, "inconsistent GCN shapes", x=x, W1=w1, b1=b1, W2=w2, b2=b2)
+        self._open("lt_baseline_create")
         self._host_scratch = {}
         self._fp64 = False
         self._shard = None          # (row_begin, row_end, per) while the sharded refresh of the fp32 product is on
@@ -155,10 +281,6 @@ class Baseline:
         self._shard64 = None        # the same for the fp64 product of `delta` (lt_baseline_refresh_rows_fp64)
         self._s1d_full = None
         self._send64 = None
-
-    @property
-    def handle(self):
-        return self._h
 
     def refresh(self, mode=None):
         """The borrowed inputs changed: everything derived from them is recomputed by the next call that reads it.
@@ -180,15 +302,6 @@ class Baseline:
             b, e, _ = self._shard64
             _refresh_handle(self, "lt_baseline_refresh_rows_fp64", b, e, self._send64.data_ptr())
             lt_dist.all_gather_into(self._s1d_full, self._send64)
-
-    def features_changed(self):
-        """The contents of the feature tensor changed in a way torch's version counter does not show (a write through the raw
-        pointer, by another library): the difference lists of the feature route are built again (lt_baseline_features_changed;
-        may synchronise) and everything ``refresh()`` marks stale is stale.  In-place torch edits need no call: ``refresh()``
-        sees the version counter."""
-        _lib.check(_lib.lib().lt_baseline_features_changed(self._h, _stream()), "lt_baseline_features_changed")
-        self._x_seen = _x_version(self.x)
-        return self
 
     def enable_fp64(self):
         """The fp64-accumulated pre-activation `delta` evaluates its ReLU kink test on (lt_baseline_enable_fp64):
@@ -305,11 +418,6 @@ class Baseline:
         self._shard = (b, e, per)
         return self
 
-    def logits(self) -> torch.Tensor:
-        out = torch.empty((self.n, self.c), dtype=torch.float32, device=self.x.device)
-        _lib.check(_lib.lib().lt_baseline_logits(self._h, out.data_ptr(), _stream()), "lt_baseline_logits")
-        return out
-
     def influence_rows(self, probe_nodes, observe_nodes, delta: float, mode="full", out=None, host=None,
                        wait=False) -> torch.Tensor:
         """[n_probe, n_obs] fp32 on the device: ||(f(X + delta e_v x_v^T) - f(X))[u]||_2 / delta.  ``host``: a pinned (or
@@ -317,77 +425,14 @@ class Baseline:
         with ``wait``, a PINNED HOST tensor that holds it when the call returns: lt_influence_matrix_host).
         Node lists given as int32 CUDA tensors are checked on the device: call ``engine.node_check()`` after synchronising
         (see ``_as_nodes``)."""
-        dev = self.x.device
-        probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
-        obs = _as_nodes(observe_nodes, self.n, dev, "observe_nodes")
-        m = _lib.MODES[mode] if isinstance(mode, str) else int(mode)
-        if m == _lib.MODE_DELTA and not self._fp64:
-            # kink test on an fp64-accumulated pre-activation (one-off cost, kept fresh by refresh())
-            self.enable_fp64()
-        npb, nob = probes.numel(), obs.numel()
-        if out is None:
-            out = torch.empty((npb, nob), dtype=torch.float32, device=dev)
-        elif out.shape != (npb, nob) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 [n_probe, n_obs] tensor")
-        key = (npb, nob, m)
-        need = _lib.lib().lt_influence_workspace_bytes(self._h, npb, nob, m)   # host arithmetic; depends on the tuning knobs too
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = _workspace(need, dev)
-            self._ws = {key: ws}   # keep only the latest: sizes repeat across steps
-        if host is not None and wait:
-            # lt_influence_matrix_host: the same call, and the stream wait; on the fused `delta` route the matrix's zeros are
-            # written here on the host while the GPU computes, and only the touched values cross PCIe
-            _lib.check(_lib.lib().lt_influence_matrix_host(self._h, probes.data_ptr(), npb, obs.data_ptr(), nob, float(delta),
-                                                           m, out.data_ptr(), nob, host.data_ptr(), max(nob, 1), ws.data_ptr(),
-                                                           ws.numel(), _stream()), "lt_influence_matrix_host")
-            return out
-        if host is not None:
-            # lt_influence_rows_f64: the float64 matrix is written as part of the same call (the fused `delta` route's blocks
-            # export their own rows; other routes end with the export launch)
-            _lib.check(_lib.lib().lt_influence_rows_f64(self._h, probes.data_ptr(), npb, obs.data_ptr(), nob, float(delta), m,
-                                                        out.data_ptr(), nob, host.data_ptr(), max(nob, 1), ws.data_ptr(),
-                                                        ws.numel(), _stream()), "lt_influence_rows_f64")
-            return out
-        _lib.check(_lib.lib().lt_influence_rows(self._h, probes.data_ptr(), npb, obs.data_ptr(), nob,
-                                                float(delta), m, out.data_ptr(), nob, ws.data_ptr(),
-                                                ws.numel(), _stream()), "lt_influence_rows")
-        return out
-
-    def influence_pairs(self, probe_nodes, pair_ptr, pair_obs, delta: float, mode="delta", out=None) -> torch.Tensor:
-        """[n_pairs] fp32 on the device: the scores of a LIST of pairs grouped by probe (lt_influence_pairs).  Probe i =
-        ``probe_nodes[i]`` owns ``pair_obs[pair_ptr[i]:pair_ptr[i + 1]]`` (``group_pairs`` builds the three from two id arrays)
-        and ``out[k]`` is what ``influence_rows`` writes at (that probe, ``pair_obs[k]``) for the same mode, bit for bit --
-        without the rectangle: the output and the workspace are sized by the list.  ``pair_ptr`` is a HOST array of
-        n_probe + 1 int64 offsets (validated by the library before anything is launched); the node lists follow
-        ``influence_rows`` (int32 CUDA tensors are checked on the device: ``engine.node_check()`` after synchronising)."""
-        import numpy as np
-        dev = self.x.device
-        probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
-        obs = _as_nodes(pair_obs, self.n, dev, "pair_obs")
-        if isinstance(pair_ptr, torch.Tensor):
-            pair_ptr = pair_ptr.cpu().numpy()
-        ptr = np.ascontiguousarray(np.asarray(pair_ptr).reshape(-1), dtype=np.int64)
-        npb, npairs = probes.numel(), obs.numel()
-        if ptr.size != npb + 1:
-            raise ValueError(f"pair_ptr must hold n_probe + 1 = {npb + 1} offsets, got {ptr.size}")
-        m = _lib.MODES[mode] if isinstance(mode, str) else int(mode)
-        if m == _lib.MODE_DELTA and not self._fp64:
-            self.enable_fp64()
-        if out is None:
-            out = torch.empty((npairs,), dtype=torch.float32, device=dev)
-        elif out.shape != (npairs,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError("out must be a contiguous float32 [n_pairs] tensor on the baseline's device")
-        key = ("pairs", npb, npairs, m)
-        need = _lib.lib().lt_influence_pairs_workspace_bytes(self._h, npb, npairs, m)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = _workspace(need, dev)
-            self._ws = {key: ws}
-        _lib.check(_lib.lib().lt_influence_pairs(self._h, probes.data_ptr(), npb, ptr.ctypes.data, obs.data_ptr(), npairs,
-                                                 float(delta), m, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-                   "lt_influence_pairs")
-        return out
+        if host is None:
+            return self._rows(probe_nodes, observe_nodes, delta, mode, out)
+        # lt_influence_matrix_host (``wait``): the same call, and the stream wait; on the fused `delta` route the matrix's zeros
+        # are written here on the host while the GPU computes, and only the touched values cross PCIe.  lt_influence_rows_f64:
+        # the float64 matrix is written as part of the same call (the fused `delta` route's blocks export their own rows; other
+        # routes end with the export launch)
+        return self._rows(probe_nodes, observe_nodes, delta, mode, out, "lt_influence_matrix_host" if wait else "lt_influence_rows_f64",
+                          host)
 
     def influence_matrix_host(self, probe_nodes, observe_nodes, delta: float, mode="delta", refresh=False):
         """[n_probe, n_obs] float64 on the HOST (the reference's ``influence_val``, attacker.py:216-229) by ONE library call
@@ -470,12 +515,7 @@ class Baseline:
         npb, nob = probes.numel(), obs.numel()
         if vec.numel() < npb * nob * self.c or vec.dtype != torch.float32 or not vec.is_contiguous():
             raise ValueError("vec must be a contiguous float32 tensor of at least n_probe * n_obs * C elements")
-        key = (npb, nob, m)
-        need = _lib.lib().lt_influence_workspace_bytes(self._h, npb, nob, m)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = _workspace(need, self.x.device)
-            self._ws = {key: ws}
+        ws = self._workspace((npb, nob, m), _lib.lib().lt_influence_workspace_bytes(self._h, npb, nob, m))
         _lib.check(_lib.lib().lt_influence_rows_vec(self._h, probes.data_ptr(), npb, obs.data_ptr(), nob, float(delta), m,
                                                     out.data_ptr(), nob, vec.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
                    "lt_influence_rows_vec")
@@ -1090,53 +1130,24 @@ def baseline_for(adj, x, w1, b1, w2, b2):
     return (Baseline if fused_shapes(w1.shape[1], w2.shape[1]) else WideBaseline)(adj, x, w1, b1, w2, b2)
 
 
-class Baseline3:
+class Baseline3(_ProbeHandle):
     """Unperturbed forward state of the 3-layer model (reference gcn/models.py:28-46) + its probe primitive
     (lt_baseline3_create / lt_influence3_rows): the reference's fp32 finite difference, evaluated on the rows a
     probe reaches in 1 / 2 / 3 hops.  More than 8 classes (up to 256) make a WIDE handle (lt_baseline3_create_wide,
     ``wide = True``): it serves ``mode="delta"`` alone, the fp32 finite difference of such a model is the attacker's loop."""
 
     NARROW_MAX_C = 8
+    _SYM = _symbols("lt_baseline3", "lt_influence3", rows="lt_influence3_rows_mode")
+    _DEFAULT_MODE = "sparse"
 
     def __init__(self, adj, x, w1, b1, w2, b2, w3, b3):
-        self.graph: HipGraph = as_hip_graph(adj)
-        self.x, self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = (
-            _f32(t, n) for t, n in ((x, "x"), (w1, "W1"), (b1, "b1"), (w2, "W2"), (b2, "b2"), (w3, "W3"), (b3, "b3")))
-        n, f = self.x.shape
-        self.n, self.f = n, f
-        self.h1, self.h2, self.c = self.w1.shape[1], self.w2.shape[1], self.w3.shape[1]
-        if (n != self.graph.n or self.w1.shape[0] != f or self.w2.shape[0] != self.h1 or self.w3.shape[0] != self.h2
-                or self.b1.numel() != self.h1 or self.b2.numel() != self.h2 or self.b3.numel() != self.c):
-            raise ValueError("inconsistent GCN3 shapes")
-        if self.graph.device_index != self.x.device.index:
-            raise ValueError(f"the graph lives on cuda:{self.graph.device_index}, the features on {self.x.device}")
-        _require_finite(features=self.x, W1=self.w1, b1=self.b1, W2=self.w2, b2=self.b2, W3=self.w3, b3=self.b3)
-        h = C.c_void_p()
+        _, _, self.h1, self.h2, self.c = self._take(adj, "inconsistent GCN3 shapes", x=x, W1=w1, b1=b1, W2=w2, b2=b2, W3=w3, b3=b3)
         self.wide = self.c > self.NARROW_MAX_C
-        create = "lt_baseline3_create_wide" if self.wide else "lt_baseline3_create"
-        _lib.check(getattr(_lib.lib(), create)(self.graph.handle, self.x.data_ptr(), f, f, self.w1.data_ptr(),
-                                               self.b1.data_ptr(), self.h1, self.w2.data_ptr(), self.b2.data_ptr(),
-                                               self.h2, self.w3.data_ptr(), self.b3.data_ptr(), self.c, _stream(),
-                                               C.byref(h)), create)
-        self._h = h
-        self._x_seen = _x_version(self.x)
-        self._finalizer = weakref.finalize(self, _lib.lib().lt_baseline3_destroy, h)
-        self._ws = {}
+        self._open("lt_baseline3_create_wide" if self.wide else "lt_baseline3_create")
         self._fp64 = False
 
     def refresh(self):
         _refresh_handle(self, "lt_baseline3_refresh")
-
-    def features_changed(self):
-        """``Baseline.features_changed`` for the 3-layer model (lt_baseline3_features_changed)."""
-        _lib.check(_lib.lib().lt_baseline3_features_changed(self._h, _stream()), "lt_baseline3_features_changed")
-        self._x_seen = _x_version(self.x)
-        return self
-
-    def logits(self) -> torch.Tensor:
-        out = torch.empty((self.n, self.c), dtype=torch.float32, device=self.x.device)
-        _lib.check(_lib.lib().lt_baseline3_logits(self._h, out.data_ptr(), _stream()), "lt_baseline3_logits")
-        return out
 
     def enable_fp64(self):
         """fp64 pre-activations of the first two layers for the exact (`delta`) propagation (lt_baseline3_enable_fp64)."""
@@ -1146,70 +1157,16 @@ class Baseline3:
             self._fp64 = True
         return self
 
+    def _serves(self, m):
+        if self.wide and m != _lib.MODE_DELTA:
+            raise NotImplementedError(f"a GCN3 with {self.c} classes is served in mode 'delta' only (lt_baseline3_create_wide); "
+                                      "its fp32 finite difference is Attacker._rows_generic")
+
     def influence_rows(self, probe_nodes, observe_nodes, delta: float, mode="sparse", out=None) -> torch.Tensor:
         """`sparse` (= `full`): the reference's fp32 finite difference on the rows a probe reaches in 1 / 2 / 3 hops;
-        `delta`: the perturbation propagated exactly through the three layers (lt_influence3_rows_mode)."""
-        m = _lib.MODES[mode or "sparse"] if isinstance(mode, str) or mode is None else int(mode)
-        if self.wide and m != _lib.MODE_DELTA:
-            raise NotImplementedError(f"a GCN3 with {self.c} classes is served in mode 'delta' only (lt_baseline3_create_wide); "
-                                      "its fp32 finite difference is Attacker._rows_generic")
-        if m == _lib.MODE_DELTA:
-            self.enable_fp64()
-        dev = self.x.device
-        probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
-        obs = _as_nodes(observe_nodes, self.n, dev, "observe_nodes")
-        npb, nob = probes.numel(), obs.numel()
-        if out is None:
-            out = torch.empty((npb, nob), dtype=torch.float32, device=dev)
-        elif out.shape != (npb, nob) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 [n_probe, n_obs] tensor")
-        key = (npb, nob)
-        need = _lib.lib().lt_influence3_workspace_bytes(self._h, npb, nob)   # depends on the tuning knobs too
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = _workspace(need, dev)
-            self._ws = {key: ws}
-        _lib.check(_lib.lib().lt_influence3_rows_mode(self._h, probes.data_ptr(), npb, obs.data_ptr(), nob, float(delta), m,
-                                                      out.data_ptr(), nob, ws.data_ptr(), ws.numel(), _stream()),
-                   "lt_influence3_rows_mode")
-        return out
-
-    def influence_pairs(self, probe_nodes, pair_ptr, pair_obs, delta: float, mode="delta", out=None) -> torch.Tensor:
-        """[n_pairs] fp32 on the device: ``Baseline.influence_pairs`` for the 3-layer model (lt_influence3_pairs).  Probe i =
-        ``probe_nodes[i]`` owns ``pair_obs[pair_ptr[i]:pair_ptr[i + 1]]`` and ``out[k]`` is what ``influence_rows`` writes at
-        (that probe, ``pair_obs[k]``) for the same mode, bit for bit -- without the rectangle: the output and the workspace are
-        sized by the list.  ``pair_ptr`` is a HOST array of n_probe + 1 int64 offsets (validated by the library before anything
-        is launched).  Modes as in ``influence_rows``: a wide handle serves ``delta`` alone."""
-        import numpy as np
-        m = _lib.MODES[mode] if isinstance(mode, str) else int(mode)
-        if self.wide and m != _lib.MODE_DELTA:
-            raise NotImplementedError(f"a GCN3 with {self.c} classes is served in mode 'delta' only (lt_baseline3_create_wide); "
-                                      "its fp32 finite difference is Attacker._rows_generic")
-        dev = self.x.device
-        probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
-        obs = _as_nodes(pair_obs, self.n, dev, "pair_obs")
-        if isinstance(pair_ptr, torch.Tensor):
-            pair_ptr = pair_ptr.cpu().numpy()
-        ptr = np.ascontiguousarray(np.asarray(pair_ptr).reshape(-1), dtype=np.int64)
-        npb, npairs = probes.numel(), obs.numel()
-        if ptr.size != npb + 1:
-            raise ValueError(f"pair_ptr must hold n_probe + 1 = {npb + 1} offsets, got {ptr.size}")
-        if m == _lib.MODE_DELTA and not self._fp64:
-            self.enable_fp64()
-        if out is None:
-            out = torch.empty((npairs,), dtype=torch.float32, device=dev)
-        elif out.shape != (npairs,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError("out must be a contiguous float32 [n_pairs] tensor on the baseline's device")
-        key = ("pairs", npb, npairs)
-        need = _lib.lib().lt_influence3_pairs_workspace_bytes(self._h, npb, npairs)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = _workspace(need, dev)
-            self._ws = {key: ws}
-        _lib.check(_lib.lib().lt_influence3_pairs(self._h, probes.data_ptr(), npb, ptr.ctypes.data, obs.data_ptr(), npairs,
-                                                  float(delta), m, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-                   "lt_influence3_pairs")
-        return out
+        `delta`: the perturbation propagated exactly through the three layers (lt_influence3_rows_mode).  A wide handle
+        serves ``delta`` alone."""
+        return self._rows(probe_nodes, observe_nodes, delta, mode, out)
 
 
 def wide_class_shapes(h: int, c: int) -> bool:
@@ -1218,7 +1175,7 @@ def wide_class_shapes(h: int, c: int) -> bool:
     return h <= 256 and 9 <= c <= 256
 
 
-class Baseline2W:
+class Baseline2W(_ProbeHandle):
     """The probe primitive of a 2-layer model with up to 256 classes as ONE handle (lt_baseline2w_create; H <= 256): `delta`
     alone -- the wide GCN3 chain with one level removed, one MFMA product over a probe chunk's items and a lane group across
     the class columns per (probe, observed) cell -- as a rectangle (``influence_rows``) and as a pair list
@@ -1226,37 +1183,16 @@ class Baseline2W:
     of these shapes is ``WideBaseline``'s.  The fp64 parts belong to the handle from creation (``enable_fp64`` is a no-op)."""
 
     supports_sharding = False       # dist.choose_baseline_sharding: replicated on every rank, no timing loop
+    _SYM = _symbols("lt_baseline2w", "lt_influence2w")
+    _fp64 = True
 
     def __init__(self, adj, x, w1, b1, w2, b2):
-        self.graph: HipGraph = as_hip_graph(adj)
-        self.x, self.w1, self.b1, self.w2, self.b2 = (
-            _f32(t, n) for t, n in ((x, "x"), (w1, "W1"), (b1, "b1"), (w2, "W2"), (b2, "b2")))
-        n, f = self.x.shape
-        self.n, self.f, self.h, self.c = n, f, self.w1.shape[1], self.w2.shape[1]
-        if (n != self.graph.n or self.w1.shape[0] != f or self.w2.shape[0] != self.h or self.b1.numel() != self.h
-                or self.b2.numel() != self.c):
-            raise ValueError("inconsistent GCN shapes")
-        if self.graph.device_index != self.x.device.index:
-            raise ValueError(f"the graph lives on cuda:{self.graph.device_index}, the features on {self.x.device}")
-        _require_finite(features=self.x, W1=self.w1, b1=self.b1, W2=self.w2, b2=self.b2)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().lt_baseline2w_create(self.graph.handle, self.x.data_ptr(), f, f, self.w1.data_ptr(),
-                                                   self.b1.data_ptr(), self.h, self.w2.data_ptr(), self.b2.data_ptr(),
-                                                   self.c, _stream(), C.byref(h)), "lt_baseline2w_create")
-        self._h = h
-        self._x_seen = _x_version(self.x)
-        self._finalizer = weakref.finalize(self, _lib.lib().lt_baseline2w_destroy, h)
-        self._ws = {}
+        _, _, self.h, self.c = self._take(adj, "inconsistent GCN shapes", x=x, W1=w1, b1=b1, W2=w2, b2=b2)
+        self._open("lt_baseline2w_create")
 
     def refresh(self, mode=None):
         """The borrowed inputs changed: everything derived from them is re-formed by the next call that reads it."""
         _refresh_handle(self, "lt_baseline2w_refresh")
-
-    def features_changed(self):
-        """``Baseline.features_changed`` for this handle (lt_baseline2w_features_changed)."""
-        _lib.check(_lib.lib().lt_baseline2w_features_changed(self._h, _stream()), "lt_baseline2w_features_changed")
-        self._x_seen = _x_version(self.x)
-        return self
 
     def enable_fp64(self):
         return self
@@ -1269,67 +1205,14 @@ class Baseline2W:
 
     shard_refresh_fp64 = shard_refresh
 
-    def logits(self) -> torch.Tensor:
-        out = torch.empty((self.n, self.c), dtype=torch.float32, device=self.x.device)
-        _lib.check(_lib.lib().lt_baseline2w_logits(self._h, out.data_ptr(), _stream()), "lt_baseline2w_logits")
-        return out
-
-    def _delta(self, mode):
-        m = _lib.MODES[mode or "delta"] if isinstance(mode, str) or mode is None else int(mode)
+    def _serves(self, m):
         if m != _lib.MODE_DELTA:
             raise NotImplementedError(f"a 2-layer model with {self.c} classes is served through this handle in mode 'delta' only "
                                       "(lt_baseline2w_create); its fp32 finite difference is engine.WideBaseline")
-        return m
-
-    def _workspace(self, key, need):
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = _workspace(need, self.x.device)
-            self._ws = {key: ws}
-        return ws
 
     def influence_rows(self, probe_nodes, observe_nodes, delta: float, mode="delta", out=None) -> torch.Tensor:
         """[n_probe, n_obs] fp32 on the device (lt_influence2w_rows): the perturbation propagated exactly through the two layers."""
-        m = self._delta(mode)
-        dev = self.x.device
-        probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
-        obs = _as_nodes(observe_nodes, self.n, dev, "observe_nodes")
-        npb, nob = probes.numel(), obs.numel()
-        if out is None:
-            out = torch.empty((npb, nob), dtype=torch.float32, device=dev)
-        elif out.shape != (npb, nob) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 [n_probe, n_obs] tensor")
-        ws = self._workspace((npb, nob), _lib.lib().lt_influence2w_workspace_bytes(self._h, npb, nob))   # (depends on the knobs too)
-        _lib.check(_lib.lib().lt_influence2w_rows(self._h, probes.data_ptr(), npb, obs.data_ptr(), nob, float(delta), m,
-                                                  out.data_ptr(), nob, ws.data_ptr(), ws.numel(), _stream()),
-                   "lt_influence2w_rows")
-        return out
-
-    def influence_pairs(self, probe_nodes, pair_ptr, pair_obs, delta: float, mode="delta", out=None) -> torch.Tensor:
-        """[n_pairs] fp32 on the device: ``Baseline.influence_pairs`` for this handle (lt_influence2w_pairs).  Probe i =
-        ``probe_nodes[i]`` owns ``pair_obs[pair_ptr[i]:pair_ptr[i + 1]]`` and ``out[k]`` is what ``influence_rows`` writes at
-        (that probe, ``pair_obs[k]``), bit for bit; ``pair_ptr`` is a HOST array of n_probe + 1 int64 offsets (validated by the
-        library before anything is launched).  The output and the workspace are sized by the list."""
-        import numpy as np
-        m = self._delta(mode)
-        dev = self.x.device
-        probes = _as_nodes(probe_nodes, self.n, dev, "probe_nodes")
-        obs = _as_nodes(pair_obs, self.n, dev, "pair_obs")
-        if isinstance(pair_ptr, torch.Tensor):
-            pair_ptr = pair_ptr.cpu().numpy()
-        ptr = np.ascontiguousarray(np.asarray(pair_ptr).reshape(-1), dtype=np.int64)
-        npb, npairs = probes.numel(), obs.numel()
-        if ptr.size != npb + 1:
-            raise ValueError(f"pair_ptr must hold n_probe + 1 = {npb + 1} offsets, got {ptr.size}")
-        if out is None:
-            out = torch.empty((npairs,), dtype=torch.float32, device=dev)
-        elif out.shape != (npairs,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError("out must be a contiguous float32 [n_pairs] tensor on the baseline's device")
-        ws = self._workspace(("pairs", npb, npairs), _lib.lib().lt_influence2w_pairs_workspace_bytes(self._h, npb, npairs))
-        _lib.check(_lib.lib().lt_influence2w_pairs(self._h, probes.data_ptr(), npb, ptr.ctypes.data, obs.data_ptr(), npairs,
-                                                   float(delta), m, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-                   "lt_influence2w_pairs")
-        return out
+        return self._rows(probe_nodes, observe_nodes, delta, mode, out)
 
 
 def group_pairs(probe, observed):
