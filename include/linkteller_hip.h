@@ -57,7 +57,9 @@ extern "C" {
                             Additive within 5: the 2-layer model with a wide class layer through one handle (lt_baseline2w_*,
                             lt_influence2w_*); no entry point changed.
                             Additive within 5: minibatch training of the feature-only MLP baselines (lt_mlp_trainer_*,
-                            lt_mlp_forward, lt_mlp_forward_workspace_bytes); no entry point changed */
+                            lt_mlp_forward, lt_mlp_forward_workspace_bytes); no entry point changed.
+                            Additive within 5: row bands of the baseline attacks' square (lt_corr_rows_prepare, lt_corr_rows,
+                            lt_corr_rows_workspace_bytes); no entry point changed */
 
 typedef enum lt_status {
     LT_OK = 0,
@@ -975,6 +977,38 @@ int lt_corr_square(const float *V, int64_t ldv, int32_t n, int32_t D, const int3
                    int64_t *info, void *ws, size_t ws_bytes, void *stream);
 int lt_corr_pairs(const float *V, int64_t ldv, int32_t n, int32_t D, const int32_t *u, const int32_t *v, int64_t m, float *out,
                   int64_t *info, void *ws, size_t ws_bytes, void *stream);
+
+/* ---- row bands of lt_corr_square's square: the square is never formed, rows arrive a band at a time (edge recovery over a whole
+ * graph: lt_top_stream_push consumes them) ---------------------------------------------------------------------------------------
+ * lt_corr_rows_prepare leaves the column mean over the k listed rows and the norm of every listed row in the head of ws and
+ *   fills info exactly as lt_corr_square does ([0] zero-norm rows, [1] ids outside [0, n)): one four-word copy tells the caller
+ *   about NaN rows before any row is formed.  The layout inside ws is the library's own; the caller keeps ws, V and nodes
+ *   untouched until the last rows call.
+ * lt_corr_rows writes out[i * ldo + j] = corr(nodes[row_begin + i], nodes[j]) for i < n_rows, j < n_cols; words j >= n_cols of a
+ *   row are left alone.  n_cols < k asks for the lower trapezoid only (the stream reads columns 0 .. i - 1 of row i): 64-column
+ *   blocks wholly at or right of n_cols are not computed.
+ * Bit contract: every cell written has the bits lt_corr_square writes at that cell for the same (V, nodes), for any row_begin,
+ *   n_rows, n_cols (bands need not start on a multiple of 64): the same tile arithmetic on v_mfma_f64_16x16x4_f64, the K slice
+ *   plan of the WHOLE list (a function of (k, D)), slices added in slice order from 0.0, norms = square roots of the Gram's own
+ *   diagonal (prepare forms the k / 64 diagonal tiles only), one rounding.  The two divisions round separately and do not
+ *   commute: the square forms a cell in its lower position, g / n_row / n_col with row >= col, and mirrors the bits; so a cell
+ *   (i, j) is g / n_max(i,j) / n_min(i,j) of list positions, above the diagonal too.  No floating-point atomics.
+ * Workspace: 8 * (D' + (P D)' + k' + part) bytes, x' = x rounded up to even, P = ceil(k / max(32, ceil(k / 1024))) column-sum
+ *   partitions; part = S * ceil(max_rows / 64) * ceil(k / 64) * 4096 words of per-slice partial tiles when the slice plan has
+ *   S > 1 slices (k below about 2000), 0 when it has one (the finish is then the Gram kernel's epilogue).  At least 16 bytes;
+ *   nothing grows with k^2.  lt_corr_rows_prepare needs the head (max_rows = 0).  Returns 0 for invalid arguments (n < 1, D < 1,
+ *   k < 0, max_rows < 0).
+ * Both calls enqueue only.  LT_ERR_INVALID before any device call: NULL pointers, n < 1, D < 1, k < 0, ldv < D, ldo < n_cols,
+ * row_begin < 0, n_rows < 0, row_begin + n_rows > k, n_cols outside [0, k], n_rows > 4 194 240 (65 535 row blocks of 64: one
+ * launch's grid; a longer band is several calls), a workspace smaller than
+ * lt_corr_rows_workspace_bytes(n, D, k, n_rows) -- that is n_rows above the max_rows it was sized for, where the size depends on
+ * it -- or not 8-byte aligned.  n_rows == 0 or n_cols == 0: a successful no-op.  A bad node id is never an address; its cells are
+ * NaN.  Additive in ABI 5. */
+size_t lt_corr_rows_workspace_bytes(int32_t n, int32_t D, int32_t k, int32_t max_rows);
+int lt_corr_rows_prepare(const float *V, int64_t ldv, int32_t n, int32_t D, const int32_t *nodes, int32_t k, int64_t *info, void *ws,
+                         size_t ws_bytes, void *stream);
+int lt_corr_rows(const float *V, int64_t ldv, int32_t n, int32_t D, const int32_t *nodes, int32_t k, int32_t row_begin,
+                 int32_t n_rows, int32_t n_cols, float *out, int64_t ldo, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- training of the 2-layer GCN (reference gcn_trainer.py:144-170 train_one_epoch + optim.Adam) ----
  * lt_gcn2_trainer_create borrows the graph, X [n, ldx], labels (int32 [n], device, each in [0, C)) and the four parameter

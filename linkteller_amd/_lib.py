@@ -138,6 +138,11 @@ SIGNATURES = {
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "lt_corr_pairs": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lt_corr_rows_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "lt_corr_rows_prepare": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
+    "lt_corr_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                               C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "lt_sample_square_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lt_sample_square_labels": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

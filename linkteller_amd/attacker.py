@@ -25,6 +25,11 @@ from . import engine
 from ._lib import LinkTellerHipError
 from .sampling import construct_balanced_edge_sets, construct_edge_sets_from_random_subgraph
 
+# args.baseline_scores / --baseline-scores: the values that form the baseline attacks' scores on the GPU, and those of them that
+# also admit the chunked recovery from the command line (main.check_*, GCNTrainer and Attacker._baseline_route all read these)
+DEVICE_BASELINE_SCORES = ("device", "stream")
+STREAM_BASELINE_SCORES = ("stream",)
+
 
 class Attacker:
     def __init__(self, args, model, worker):
@@ -599,29 +604,68 @@ class Attacker:
     # both forms; NOTES.md (2026-10-20) records what was measured and the decision
     recover_triangular = False
 
-    def _stream_top_pairs(self, probes, observed, m, chunk, mode=None):
-        """``engine.top_pairs_lower`` of the len(probes) x len(observed) influence rows without forming them at once: ``chunk``
-        probes at a time through an ``engine.TopPairsStream`` -> the same ``(idx, score, info)``.  Leaves the handle's counters in
-        ``self.recover_stream_stats`` (device bytes, pushes; with ``self.recover_keep_stats`` set, the compaction counts too)."""
-        n, chunk = int(observed.numel()), int(chunk)
+    # the baselines' streamed rows: chunk e's band formed over columns [0, e - 1) only (the square is symmetric, so the trapezoid is
+    # half the products).  tools/corr_stream_time.py times both forms
+    corr_trapezoid = True
+
+    def _influence_row_source(self, probes, observed, mode=None):
+        """The efficient attack's row source for ``_stream_top_pairs``: rows [b, e) of the influence matrix through ``_rows``."""
+        def source(b, e, n_cols):
+            obs = observed[:e] if (self.recover_triangular and e > 1) else observed
+            return self._rows(probes[b:e], obs, mode)
+        return source
+
+    def _corr_row_source(self, observed, chunk):
+        """The baseline attacks' row source for ``_stream_top_pairs`` over the listed nodes ``observed`` (int32, device) ->
+        ``(source, handle)``.  A zero-norm row raises the one-shot route's ``ValueError`` here, before any row is formed."""
+        vec = self._baseline_vectors_device()
+        handle = engine.CorrRows(vec, observed, min(int(chunk), int(observed.numel())))
+        handle.info.check(nan_ok=False)     # (a zero-norm row makes whole rows NaN: the selection's set would be unspecified)
+
+        def source(b, e, n_cols):
+            return handle.rows(b, e - b, n_cols if self.corr_trapezoid else None)
+        return source, handle
+
+    def _stream_top_pairs(self, source, n, m, chunk, device, extra_bytes=0):
+        """``engine.top_pairs_lower`` of an n x n score matrix without forming it at once: ``source(b, e, n_cols)`` returns rows
+        [b, e) -- of which columns [0, n_cols), n_cols = max(e - 1, 1), are read -- ``chunk`` rows at a time, consumed by an
+        ``engine.TopPairsStream`` -> the same ``(idx, score, info)``.  Leaves the handle's counters in
+        ``self.recover_stream_stats`` (device bytes, pushes; with ``self.recover_keep_stats`` set, the compaction counts too;
+        ``rows_device_bytes``: ``extra_bytes``, what the row source's own handle holds)."""
+        n, chunk = int(n), int(chunk)
         if chunk < 1:
             raise ValueError(f"chunk = {chunk}: at least 1")
         chunk = min(chunk, n)
-        sel = engine.TopPairsStream(n, m, chunk, device=observed.device)
+        sel = engine.TopPairsStream(n, m, chunk, device=device)
         try:
             pushes = 0
             for b in range(0, n, chunk):
                 e = min(b + chunk, n)
-                obs = observed[:e] if (self.recover_triangular and e > 1) else observed
-                sel.push(self._rows(probes[b:e], obs, mode), b)
+                sel.push(source(b, e, max(e - 1, 1)), b)
                 pushes += 1
             out = sel.finish()
             self.recover_stream_stats = {"device_bytes": sel.device_bytes, "pushes": pushes, "chunk": chunk}
+            if extra_bytes:
+                self.recover_stream_stats["rows_device_bytes"] = int(extra_bytes)
             if getattr(self, "recover_keep_stats", False):      # (a copy of the handle's counters: one wait)
                 self.recover_stream_stats.update(sel.stats())
         finally:
             sel.close()
         return out
+
+    def _stream_scores(self, probes, observed, m, chunk, mode=None):
+        """``_stream_top_pairs`` over the rows of the attack mode at hand: influence rows (efficient), or bands of the correlation
+        square of the listed nodes (baseline / baseline-feat on a device route; the host route forms its square in one piece)."""
+        n, dev = int(observed.numel()), observed.device
+        if int(chunk) < 1:
+            raise ValueError(f"chunk = {chunk}: at least 1")
+        if str(getattr(self.args, "attack_mode", "efficient")) in ("baseline", "baseline-feat"):
+            if self._baseline_route() != "device":
+                raise NotImplementedError("chunked recovery of the baseline attacks needs baseline_scores = 'device' or 'stream': "
+                                          "the host route forms its correlation square in one piece")
+            source, handle = self._corr_row_source(observed, chunk)
+            return self._stream_top_pairs(source, n, m, chunk, dev, handle.device_bytes)
+        return self._stream_top_pairs(self._influence_row_source(probes, observed, mode), n, m, chunk, dev)
 
     def recover_graph(self, beliefs=None, mode=None, chunk=1024, nodes=None) -> dict:
         """``recover_edges`` for the attacked graph itself: the node set is every node (or ``nodes``), each is perturbed, every
@@ -631,7 +675,9 @@ class Attacker:
         ``sampling.upper_edge_count`` on the device (a given ``nodes`` list: counted on the HOST in the scipy pattern restricted to
         the list, one pass over the stored entries -- the whole graph is the case the device count serves), ``is_edge`` from
         ``engine.pairs_present`` for the selected pairs only.  Returns and stores the ``recovered`` dict of ``recover_edges``, key
-        for key.  Serves every model kind ``_rows`` serves; with several ranks every rank forms everything itself."""
+        for key.  Serves every model kind ``_rows`` serves; with several ranks every rank forms everything itself.  With
+        ``attack_mode`` baseline / baseline-feat on a device route the rows are bands of the correlation square of the listed
+        nodes (``engine.CorrRows`` over ``_baseline_vectors_device()``, the mean over the listed nodes)."""
         from . import recover, sampling
         n_graph = int(self.features.shape[0])
         nodes = np.arange(n_graph, dtype=np.int64) if nodes is None else np.asarray(nodes, dtype=np.int64).reshape(-1)
@@ -655,7 +701,7 @@ class Attacker:
         beliefs = recover.density_ladder(n_edges, n) if beliefs is None else [float(b) for b in beliefs]
         counts = recover.belief_counts(beliefs, n_total)
         m = int(counts.max())
-        idx_d, val_d, info = self._stream_top_pairs(probes, observed, m, chunk, mode)
+        idx_d, val_d, info = self._stream_scores(probes, observed, m, chunk, mode)
         # cell (i, j), j < i: the pair (nodes[j], nodes[i]) scored by perturbing nodes[i]
         obs64 = observed.to(torch.int64)
         present_d = engine.pairs_present(csr, obs64[idx_d % n], obs64[idx_d // n])
@@ -693,7 +739,9 @@ class Attacker:
         ``unbalanced*`` sample type.  With several ranks every rank forms all rows itself: no collective of its own to mismatch.
         For ``attack_mode`` baseline / baseline-feat with ``args.baseline_scores == "device"`` the rows are the correlation square
         of ``engine.corr_square`` (symmetric) instead of influence rows; a sampled node whose centred vector is zero makes its
-        row NaN and raises ``ValueError`` (a ranking over NaNs is undefined)."""
+        row NaN and raises ``ValueError`` (a ranking over NaNs is undefined).  ``chunk=K`` forms the rows K at a time
+        (``_stream_scores``: influence rows, or bands of the correlation square through ``engine.CorrRows``, whose cells are the
+        square's bit for bit) and returns the same dict, array for array."""
         from . import recover
         st = str(self.args.sample_type)
         if not st.startswith("unbalanced"):
@@ -719,9 +767,8 @@ class Attacker:
         cinfo = None
         if chunk is not None:
             # addition: the rows chunk by chunk through engine.TopPairsStream -- the same triple, no n x n matrix
-            if str(getattr(self.args, "attack_mode", "efficient")) in ("baseline", "baseline-feat"):
-                raise NotImplementedError("recover_edges(chunk=...): the baseline attacks' correlation square is formed in one piece")
-            idx_d, val_d, info = self._stream_top_pairs(probes, observed, m, chunk, mode)
+            # (the baseline attacks on a device route: bands of their correlation square, engine.CorrRows)
+            idx_d, val_d, info = self._stream_scores(probes, observed, m, chunk, mode)
         elif str(getattr(self.args, "attack_mode", "efficient")) in ("baseline", "baseline-feat") and self._baseline_route() == "device":
             rows, cinfo = self._baseline_square_device()     # (addition: the baseline attacks' correlation square, symmetric)
             idx_d, val_d, info = engine.top_pairs_lower(rows, m)
@@ -934,9 +981,10 @@ class Attacker:
     # ---- baseline_scores = device (an addition) -----------------------------------------------------------
     def _baseline_route(self):
         route = getattr(self.args, "baseline_scores", "host")
-        if route not in ("host", "device"):
-            raise ValueError(f"baseline_scores = {route!r}: 'host' or 'device'")
-        return route
+        if route != "host" and route not in DEVICE_BASELINE_SCORES:
+            raise ValueError(f"baseline_scores = {route!r}: 'host', 'device' or 'stream'")
+        # 'stream' is the device route; it differs on the command line only, where it also admits the chunked recovery
+        return "device" if route in DEVICE_BASELINE_SCORES else route
 
     def _baseline_vectors_device(self):
         """The vectors of ``_baseline_vectors``, left on the device: softmax (sigmoid for ppi) of the model's output, or the

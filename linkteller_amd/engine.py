@@ -1632,6 +1632,58 @@ def corr_pairs(vectors: torch.Tensor, u: torch.Tensor, v: torch.Tensor):
     return out, CorrInfo(raw, "corr_pairs", n)
 
 
+class CorrRows:
+    """``corr_square``'s square a band of rows at a time (lt_corr_rows_prepare / lt_corr_rows): the k x k matrix is never formed.
+    The constructor enqueues the mean and the norms of the k listed rows into a workspace of its own and leaves ``info`` (a
+    ``CorrInfo``): ``info.check(nan_ok=False)`` -- one copy of four words -- tells about NaN rows before any row is formed.
+    ``rows(row_begin, n_rows, n_cols=None)`` returns fp32 [n_rows, k] on the device whose columns [0, n_cols) (default: all k) hold
+    ``corr_square``'s cells bit for bit, whatever the cut into bands; columns at or right of ``n_cols`` hold whatever an earlier
+    call left.  The buffer is REUSED by the next call.  ``vectors`` / ``nodes`` as for ``corr_square``; both are kept alive and
+    must not be written while the handle is in use.  At most ``max_rows`` rows a call (``.max_rows``: clipped to k and to the 4 194 240 rows one
+    library call takes).  ``device_bytes``: workspace plus buffer."""
+
+    def __init__(self, vectors: torch.Tensor, nodes: torch.Tensor, max_rows: int):
+        n, d, ldv, (nodes,) = _corr_operands(vectors, (("nodes", nodes),), "CorrRows")
+        max_rows = int(max_rows)
+        if max_rows < 1:
+            raise ValueError(f"max_rows={max_rows} < 1")
+        k, dev = int(nodes.numel()), vectors.device
+        if k < 1:
+            raise ValueError("CorrRows: no node listed")
+        self.n, self.d, self.ldv, self.k, self.device = n, d, ldv, k, dev
+        self.max_rows = min(max_rows, k, 65535 * 64)      # (one launch's grid: 65 535 row blocks of 64)
+        self._vectors, self._nodes = vectors, nodes
+        need = _lib.lib().lt_corr_rows_workspace_bytes(n, d, k, self.max_rows)
+        if need == 0:
+            raise ValueError(f"CorrRows: n={n}, D={d}, k={k}, max_rows={self.max_rows} are outside what the library serves")
+        self._ws = _workspace(need, dev)
+        self._out = torch.empty((self.max_rows, k), dtype=torch.float32, device=dev)
+        self.device_bytes = int(self._ws.numel()) * self._ws.element_size() + int(self._out.numel()) * 4
+        raw = torch.zeros(4, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().lt_corr_rows_prepare(vectors.data_ptr(), ldv, n, d, nodes.data_ptr(), k, raw.data_ptr(),
+                                                       self._ws.data_ptr(), self._ws.numel(), _stream()), "lt_corr_rows_prepare")
+        self.info = CorrInfo(raw, "CorrRows", n)
+
+    def rows(self, row_begin: int, n_rows: int, n_cols: int = None) -> torch.Tensor:
+        row_begin, n_rows = int(row_begin), int(n_rows)
+        n_cols = self.k if n_cols is None else int(n_cols)
+        if row_begin < 0 or n_rows < 0 or row_begin + n_rows > self.k:
+            raise ValueError(f"rows [{row_begin}, {row_begin + n_rows}) outside the {self.k} listed")
+        if n_rows > self.max_rows:
+            raise ValueError(f"{n_rows} rows a call, the handle was made for {self.max_rows}")
+        if not 0 <= n_cols <= self.k:
+            raise ValueError(f"n_cols={n_cols} outside [0, {self.k}]")
+        out = self._out[:n_rows, :self.k]
+        if n_rows == 0 or n_cols == 0:
+            return out
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().lt_corr_rows(self._vectors.data_ptr(), self.ldv, self.n, self.d, self._nodes.data_ptr(), self.k,
+                                               row_begin, n_rows, n_cols, out.data_ptr(), int(self._out.stride(0)),
+                                               self._ws.data_ptr(), self._ws.numel(), _stream()), "lt_corr_rows")
+        return out
+
+
 def export_rows_f64(rows: torch.Tensor):
     """The finished rows as a float64 numpy array on the host (the reference's ``influence_val = np.zeros(...)`` filled by
     n_test**2 ``.item()`` round trips, attacker.py:216-229) -- ONE launch that widens on the device and writes straight into

@@ -69,8 +69,9 @@ _OPTIONS = {
     "sample-rng": (str, "numpy", ["numpy", "philox"]),
     # addition: where the baseline attacks (--attack-mode baseline / baseline-feat) score their pairs.  'host' is the reference's
     # fp32 torch arithmetic on the CPU; 'device' forms the correlations on the GPU in fp64 (lt_corr_square / lt_corr_pairs), writes
-    # the same result file, and lets --metrics-only and --recover serve the baseline attacks
-    "baseline-scores": (str, "host", ["host", "device"]),
+    # the same result file, and lets --metrics-only and --recover serve the baseline attacks; 'stream' is 'device' and also admits
+    # --recover-chunk / --recover-nodes all: bands of the correlation square (lt_corr_rows) instead of the one-piece square
+    "baseline-scores": (str, "host", ["host", "device", "stream"]),
     # addition: with --train, validate on the held-out graph (features_2, adj_2, labels_2) after every epoch, on the GPU
     # (gcn_trainer.py:167-174).  'log': loss_val / acc_val in every epoch's log tuple; 'best': as log, and the model of the best
     # validation loss is restored and saved; 'early': as best, and the run stops after --patience epochs without improvement
@@ -163,6 +164,12 @@ def init_distributed():
     return True
 
 
+def _baseline_score_routes():
+    """(device routes, of them the ones that admit the chunked recovery): one definition, shared with the trainer and the Attacker."""
+    from .attacker import DEVICE_BASELINE_SCORES, STREAM_BASELINE_SCORES
+    return DEVICE_BASELINE_SCORES, STREAM_BASELINE_SCORES
+
+
 def check_recover(args):
     """``--recover`` is served after ``--attack --attack-mode efficient`` on an ``unbalanced*`` sample only (with
     ``--baseline-scores device`` also after the baseline attacks, whose square then lives on the device); anything else is
@@ -170,7 +177,8 @@ def check_recover(args):
     if not getattr(args, "recover", False):
         return
     # (--baseline-scores device: the baseline attacks' square is on the device too and is ranked like the efficient attack's)
-    served = ("efficient", "baseline", "baseline-feat") if getattr(args, "baseline_scores", "host") == "device" else ("efficient",)
+    served = (("efficient", "baseline", "baseline-feat") if getattr(args, "baseline_scores", "host") in _baseline_score_routes()[0]
+              else ("efficient",))
     if not (args.attack and args.attack_mode in served and str(args.sample_type).startswith("unbalanced")):
         raise NotImplementedError("--recover needs --attack --attack-mode efficient and --sample-type unbalanced / unbalanced-lo / "
                                   f"unbalanced-hi (got attack={args.attack}, attack-mode={args.attack_mode}, "
@@ -181,8 +189,8 @@ def check_recover(args):
 
 def check_recover_stream(args):
     """``--recover-chunk K`` / ``--recover-nodes all`` shape what ``--recover`` does: without it they are refused here, before a
-    Worker is built or the GPU is touched; so are a negative K and, with the baseline attacks (whose correlation square is formed
-    in one piece), anything but the defaults."""
+    Worker is built or the GPU is touched; so are a negative K and, with the baseline attacks, anything but the defaults --
+    unless ``--baseline-scores stream`` asks for their correlation square in bands of rows (``device`` forms it in one piece)."""
     chunk, nodes = int(getattr(args, "recover_chunk", 0)), getattr(args, "recover_nodes", "sample")
     if chunk == 0 and nodes == "sample":
         return
@@ -190,9 +198,11 @@ def check_recover_stream(args):
         raise ValueError(f"--recover-chunk {chunk}: the probes per chunk, > 0 (0 = the one-shot matrix)")
     if not getattr(args, "recover", False):
         raise NotImplementedError(f"--recover-chunk {chunk} / --recover-nodes {nodes} need --recover (they shape the edge recovery)")
+    if args.attack_mode in ("baseline", "baseline-feat") and getattr(args, "baseline_scores", "host") in _baseline_score_routes()[1]:
+        return
     if args.attack_mode != "efficient":
         raise NotImplementedError(f"--recover-chunk / --recover-nodes all need --attack-mode efficient (got {args.attack_mode}: "
-                                  "the baseline attacks' correlation square is formed in one piece)")
+                                  "the baseline attacks' correlation square is formed in one piece unless --baseline-scores stream)")
 
 
 def check_metrics_only(args):
@@ -201,18 +211,19 @@ def check_metrics_only(args):
     ``--baseline-scores device`` forms them on the device too."""
     if not getattr(args, "metrics_only", False):
         return
-    if args.attack_mode in ("baseline", "baseline-feat") and getattr(args, "baseline_scores", "host") != "device":
+    if args.attack_mode in ("baseline", "baseline-feat") and getattr(args, "baseline_scores", "host") not in _baseline_score_routes()[0]:
         raise NotImplementedError(f"--metrics-only needs --attack-mode efficient or naive (got attack-mode={args.attack_mode}: "
                                   "the baseline attacks score their pairs on the host)")
 
 
 def check_baseline_scores(args):
-    """``--baseline-scores device`` moves the baseline attacks' scores to the GPU: it is refused here, before a Worker is built or
+    """``--baseline-scores device`` / ``stream`` moves the baseline attacks' scores to the GPU: it is refused here, before a Worker is built or
     the GPU is touched, unless ``--attack --attack-mode baseline`` / ``baseline-feat`` asks for such scores."""
-    if getattr(args, "baseline_scores", "host") != "device":
+    route = getattr(args, "baseline_scores", "host")
+    if route not in _baseline_score_routes()[0]:
         return
     if not (args.attack and args.attack_mode in ("baseline", "baseline-feat")):
-        raise NotImplementedError("--baseline-scores device needs --attack and --attack-mode baseline / baseline-feat "
+        raise NotImplementedError(f"--baseline-scores {route} needs --attack and --attack-mode baseline / baseline-feat "
                                   f"(got attack={args.attack}, attack-mode={args.attack_mode})")
 
 

@@ -14,7 +14,7 @@ import time
 import torch
 import torch.nn.functional as F
 
-from .attacker import Attacker
+from .attacker import Attacker, DEVICE_BASELINE_SCORES, STREAM_BASELINE_SCORES
 from .gcn import GCN, GCN3
 
 
@@ -223,7 +223,9 @@ class GCNTrainer:
     def _recover_whole_graph(self):
         """addition: ``--recover --recover-nodes all`` -- the attacked graph itself instead of a sample (``Attacker.recover_graph``)."""
         a = self.args
-        if not (a.attack_mode == "efficient" and str(a.sample_type).startswith("unbalanced")):
+        # (baseline_scores = stream: the baseline attacks' correlation square arrives in bands of rows and is ranked the same way)
+        served = ("efficient", "baseline", "baseline-feat") if getattr(a, "baseline_scores", "host") in STREAM_BASELINE_SCORES else ("efficient",)
+        if not (a.attack_mode in served and str(a.sample_type).startswith("unbalanced")):
             raise NotImplementedError("recover: served after the efficient attack on an unbalanced* sample only")
         self.attacker = Attacker(args=a, model=self.model, worker=self.worker)
         print("recover-nodes = all: the sampled AUC attack is skipped, every node is perturbed and every pair ranked")
@@ -239,7 +241,8 @@ class GCNTrainer:
             self._recover_whole_graph()
         elif a.attack:
             # (addition: with baseline_scores = device the baseline attacks' square lives on the device and is ranked there too)
-            served = ("efficient", "baseline", "baseline-feat") if getattr(a, "baseline_scores", "host") == "device" else ("efficient",)
+            served = (("efficient", "baseline", "baseline-feat") if getattr(a, "baseline_scores", "host") in DEVICE_BASELINE_SCORES
+                      else ("efficient",))
             if getattr(a, "recover", False) and not (a.attack_mode in served and str(a.sample_type).startswith("unbalanced")):
                 raise NotImplementedError("recover: served after the efficient attack on an unbalanced* sample only")
             self.attacker = Attacker(args=a, model=self.model, worker=self.worker)
