@@ -1238,6 +1238,26 @@ int lt_gcn3_trainer_attach_validation_wide(lt_gcn3_trainer *t, const lt_graph *g
                                            const void *labels2, int64_t ldy2, int32_t keep_best, int32_t patience,
                                            const int32_t *rows, int32_t m, void *stream);
 
+/* ---- training on a listed subset of the rows: transductive training.  Additive within ABI 5. ----
+ * The reference's loss on the datasets whose adj_train is the whole graph (gcn_trainer.py:150-156:
+ * model(features_train, adj_train)[idx_train] against labels_train[idx_train]): the whole graph is forwarded, the loss is taken
+ * over m listed rows.  rows: HOST int32 [m], distinct ids in [0, n), any order; the library checks the list, copies it to the
+ * device and owns the copy (the caller's array is its own again when the call returns).  m = 0 (rows NULL or not) restores
+ * "all rows".  May be called between runs on either head, before or after attach_validation*; it waits for `stream` (a setup
+ * call, like lt_graph_create) and zeroes the trainer's dZc on it: pass the stream the trainer's runs use, or call it when the
+ * last run has completed (the zeroing must not overtake an epoch in flight).  Replacing or clearing a list waits for the
+ * whole device before the old copy is freed.  LT_ERR_INVALID with a message naming the position and the
+ * value, the trainer unchanged: an id outside [0, n), a repeated id, m < 0, m > n, rows NULL with m > 0.
+ * With a list set: loss = the mean over the listed rows (CE: / m, BCE: / (m C)); record[1] and lt_gcn*_trainer_counts count
+ * the listed rows only; dZc has the all-rows formula with m in place of n on the listed rows and is +0 on every other row;
+ * the class-bias gradient is the sum of dZc over the list in list order (thread t of the narrow head's reduce takes positions
+ * t, t + 256, ...; the wide head's blocks take their tiles of positions in order).  Everything behind dZc -- A^T dZc, the
+ * hidden layers' backward, the TN products, Adam, the mirrors -- is the unchanged chain over all n rows, and validation,
+ * snapshots and early stopping do not see the list.  The per-row arithmetic is the all-rows head's, operation for
+ * operation: the list 0 .. n - 1 trains the bits of a trainer without a list.  The head costs O(m) per epoch. */
+int lt_gcn2_trainer_set_train_rows(lt_gcn2_trainer *t, const int32_t *rows, int32_t m, void *stream);
+int lt_gcn3_trainer_set_train_rows(lt_gcn3_trainer *t, const int32_t *rows, int32_t m, void *stream);
+
 /* ---- the feature-only baselines, trained in minibatches.  Additive within ABI 5. ----
  * The reference's OneLayerMLP / SingleHiddenLayerMLP (gcn/models.py:91-120) under MLPTrainer (mlp_trainer.py): no graph.
  *   depth 2: Z1 = X_b W1 + b1, H1d = dropout_p(relu(Z1)), Z2 = H1d W2 + b2      (W1 [F, H], b1 [H], W2 [H, C], b2 [C])

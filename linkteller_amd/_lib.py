@@ -235,6 +235,8 @@ SIGNATURES = {
     "lt_gcn3_trainer_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lt_gcn3_trainer_attach_validation_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                                          C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "lt_gcn2_trainer_set_train_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "lt_gcn3_trainer_set_train_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "lt_mlp_trainer_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
                                         C.c_double, C.c_double, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]),

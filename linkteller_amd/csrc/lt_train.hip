@@ -89,14 +89,19 @@ __global__ __launch_bounds__(TR_BLOCK) void k_tr_dropout(int n, const float *__r
 // --------------------------------------------------------------------------------------------
 // softmax cross-entropy head, one thread per row: loss_r = logsumexp(z) - z[y], dZ2 = (softmax(z) - onehot(y)) / n,
 // correct = (first argmax == y)
+// LIST (lt_gcn*_trainer_set_train_rows): one thread per list POSITION k < n, row r = rows[k] (the library checked the list:
+// distinct ids inside the graph); loss_r / corr_r are indexed by k, dZ2 is written at row r and nowhere else -- the other
+// rows keep the zeros they got when the list was set -- and inv_n = 1 / (the list's length).  The same operations in the same
+// order: the list 0 .. n - 1 leaves the bits of the launch without one.  Without LIST rows is not read.
 // --------------------------------------------------------------------------------------------
-template <int CP>
-__global__ __launch_bounds__(TR_BLOCK) void k_tr_ce(int n, const float *__restrict__ Z2, int C,
+template <int CP, bool LIST>
+__global__ __launch_bounds__(TR_BLOCK) void k_tr_ce(int n, const int32_t *__restrict__ rows, const float *__restrict__ Z2, int C,
                                                     const int32_t *__restrict__ labels, float inv_n,
                                                     float *__restrict__ loss_r, int32_t *__restrict__ corr_r,
                                                     float *__restrict__ dZ2) {
-    const int r = blockIdx.x * TR_BLOCK + threadIdx.x;
-    if (r >= n) return;
+    const int k = blockIdx.x * TR_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    const int r = LIST ? rows[k] : k;
     const int y = labels[r];
     float z[CP];
 #pragma unroll
@@ -113,17 +118,19 @@ __global__ __launch_bounds__(TR_BLOCK) void k_tr_ce(int n, const float *__restri
         s += e[c];
         if (c == y) zy = z[c];
     }
-    loss_r[r] = (mx + logf(s)) - zy;
-    corr_r[r] = arg == y ? 1 : 0;
+    loss_r[k] = (mx + logf(s)) - zy;
+    corr_r[k] = arg == y ? 1 : 0;
 #pragma unroll
     for (int c = 0; c < CP; ++c)
         if (c < C) dZ2[(size_t)r * C + c] = (e[c] / s - (c == y ? 1.f : 0.f)) * inv_n;
 }
 
 // One block: mean loss and correct count into the epoch's record, db2 = sum_r dZ2 -- thread t sums rows t, t + 256, ...
-// in row order, then a fixed tree over the threads.
-template <int CP>
-__global__ __launch_bounds__(TR_BLOCK) void k_tr_ce_reduce(int n, int C, const float *__restrict__ loss_r,
+// in row order, then a fixed tree over the threads.  LIST: positions t, t + 256, ... of the n listed rows, dZ2 read through
+// the list.
+template <int CP, bool LIST>
+__global__ __launch_bounds__(TR_BLOCK) void k_tr_ce_reduce(int n, const int32_t *__restrict__ rows, int C,
+                                                           const float *__restrict__ loss_r,
                                                            const int32_t *__restrict__ corr_r,
                                                            const float *__restrict__ dZ2, float *__restrict__ record,
                                                            float *__restrict__ db2) {
@@ -135,9 +142,10 @@ __global__ __launch_bounds__(TR_BLOCK) void k_tr_ce_reduce(int n, int C, const f
     int k = 0;
 #pragma unroll
     for (int c = 0; c < CP; ++c) d[c] = 0.f;
-    for (int r = t; r < n; r += TR_BLOCK) {
-        l += loss_r[r];
-        k += corr_r[r];
+    for (int i = t; i < n; i += TR_BLOCK) {
+        const int r = LIST ? rows[i] : i;
+        l += loss_r[i];
+        k += corr_r[i];
 #pragma unroll
         for (int c = 0; c < CP; ++c)
             if (c < C) d[c] += dZ2[(size_t)r * C + c];
@@ -1012,6 +1020,11 @@ struct lt_trainer {
     int32_t wide = 0, loss_kind = 0, Cp = 0;
     int64_t ldy = 0;
     float *whead = nullptr;       // the head's partials (trw_part_bytes) and, behind them, the last epoch's counts [C, 3]
+    // lt_gcn*_trainer_set_train_rows (owned, NULL / 0 without a list): the m listed row ids on the device and, for the wide
+    // head, its partials at the list's length (trw_part_bytes(m): a shorter list can be cut into MORE blocks than n rows are)
+    int32_t *train_rows = nullptr;
+    int32_t n_train = 0;
+    float *lhead = nullptr;
 };
 // widest padded row a segment scratch holds: the hidden widths and, for the wide head, the class layer's Cp
 static inline int trainer_hpm(const lt_trainer *t) {
@@ -1019,8 +1032,12 @@ static inline int trainer_hpm(const lt_trainer *t) {
     return t->wide && t->Cp > h ? t->Cp : h;
 }
 static inline int trainer_ldc(const lt_trainer *t) { return t->wide ? t->Cp : t->C; }      // leading dimension of the [n, C] buffers
-static inline int32_t *trainer_counts(const lt_trainer *t) {      // behind the training head's partials
+static inline int32_t *trainer_counts(const lt_trainer *t) {      // behind the all-rows head's partials, with a list too
     return (int32_t *)((char *)t->whead + trw_parts(t->whead, t->n, t->C, true).bytes);
+}
+// the training head's partials: over all n rows, or over the list
+static inline lt_trw_parts trainer_head_parts(const lt_trainer *t) {
+    return t->train_rows ? trw_parts(t->lhead, t->n_train, t->C, true) : trw_parts(t->whead, t->n, t->C, true);
 }
 struct lt_gcn2_trainer : lt_trainer {};
 struct lt_gcn3_trainer : lt_trainer {};
@@ -1074,6 +1091,8 @@ static void free_trainer(lt_trainer *t) {
     lt_buf b[TR_MAX_BUFS];
     const int nb = trainer_bufs(t, b);
     for (int k = 0; k < nb; ++k) (void)hipFree(*b[k].slot);
+    (void)hipFree(t->train_rows);
+    (void)hipFree(t->lhead);
     if (t->layers == 3) delete static_cast<lt_gcn3_trainer *>(t);
     else delete static_cast<lt_gcn2_trainer *>(t);
 }
@@ -1240,7 +1259,7 @@ static int launch_wide_backward(const lt_trainer *t, float scale, hipStream_t st
     const lt_graph *g = t->g;
     const int top = t->layers - 2, n = t->n, H = t->H[top], Hp = t->Hp[top], C = t->C, Cp = t->Cp;
     float *bslabs = top ? t->part2 : t->part1;
-    const lt_trw_parts parts = trw_parts(t->whead, n, C, true);
+    const lt_trw_parts parts = trainer_head_parts(t);
     hipLaunchKernelGGL(k_tr_colsum, dim3((unsigned)((C + 63) / 64)), dim3(TR_BLOCK), 0, st, parts.db, parts.n_blk, C,
                        t->grad + t->off[2 * top + 2]);                                            // dbc
     LT_CHECK_LAUNCH();
@@ -1280,14 +1299,15 @@ static int launch_top_forward(const lt_trainer *t, const lt_graph *g, const floa
     return lt_launch_layer2(g, Sc, C, t->P[2 * top + 3], Zc, st);
 }
 
-// loss head: the epoch's record, dZc and dbc
+// loss head: the epoch's record, dZc and dbc; with a list of training rows (LIST), over its positions
+template <bool LIST>
 static int launch_loss_head(const lt_trainer *t, float *record, hipStream_t st) {
-    const int n = t->n, C = t->C, cp = lt_cp_for(C);
-    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_ce<CP_>), dim3(rows_grid(n, TR_BLOCK)), dim3(TR_BLOCK), 0, st, n, t->Zc, C,
-                                          t->labels, 1.0f / (float)n, t->loss_r, t->corr_r, t->dZc));
+    const int C = t->C, cp = lt_cp_for(C), cnt = LIST ? t->n_train : t->n;
+    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_ce<CP_, LIST>), dim3(rows_grid(cnt, TR_BLOCK)), dim3(TR_BLOCK), 0, st, cnt,
+                                          t->train_rows, t->Zc, C, t->labels, 1.0f / (float)cnt, t->loss_r, t->corr_r, t->dZc));
     LT_CHECK_LAUNCH();
-    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_ce_reduce<CP_>), dim3(1), dim3(TR_BLOCK), 0, st, n, C, t->loss_r, t->corr_r,
-                                          t->dZc, record, t->grad + t->off[2 * (t->layers - 2) + 2]));
+    LT_DISPATCH_CP(cp, hipLaunchKernelGGL((k_tr_ce_reduce<CP_, LIST>), dim3(1), dim3(TR_BLOCK), 0, st, cnt, t->train_rows, C,
+                                          t->loss_r, t->corr_r, t->dZc, record, t->grad + t->off[2 * (t->layers - 2) + 2]));
     LT_CHECK_LAUNCH();
     return LT_OK;
 }
@@ -1350,15 +1370,16 @@ static int run_epoch(lt_trainer *t, float *record, hipStream_t st) {
     if (t->wide) {      // the class layer as matrix products, the wide head, and their backward
         rc = launch_wide_forward(t, g, t->S, d, t->Hd, t->Sc, t->Zc, t->seg_part, st);
         if (rc) return rc;
-        rc = launch_trw_head(t->loss_kind, t->Zc, (long)t->Cp, t->labels, (long)t->ldy, n, t->C, nullptr, 0, t->dZc, t->whead,
-                             record, record + 1, trainer_counts(t), nullptr, nullptr, 0, 0, st);
+        rc = launch_trw_head(t->loss_kind, t->Zc, (long)t->Cp, t->labels, (long)t->ldy, n, t->C, t->train_rows, t->n_train, t->dZc,
+                             t->train_rows ? t->lhead : t->whead, record, record + 1, trainer_counts(t), nullptr, nullptr, 0, 0,
+                             st);
         if (rc) return rc;
         rc = launch_wide_backward(t, scale, st);
         if (rc) return rc;
     } else {
         rc = launch_top_forward(t, g, t->S, t->Z, &d, t->Hd, t->Sc, t->Zc, t->seg_part, st);
         if (rc) return rc;
-        rc = launch_loss_head(t, record, st);
+        rc = t->train_rows ? launch_loss_head<true>(t, record, st) : launch_loss_head<false>(t, record, st);
         if (rc) return rc;
         // backward
         rc = launch_top_backward(t, scale, st);
@@ -1723,7 +1744,58 @@ static int trainer_val_logits(const char *who, const lt_trainer *t, float *Z, in
     return copy_rows(Z, ldz, t->val->Zc, trainer_ldc(t), t->C, t->val->n, stream);
 }
 
+// lt_gcn*_trainer_set_train_rows.  Everything that can refuse comes first -- the checks of the host list, the allocations, the
+// copy -- so a refused call leaves the trainer as it was.  Then dZc is zeroed (the listed head writes listed rows only, and
+// the backward reads every row) and the new list replaces the old one.
+static int trainer_set_train_rows(const char *who, lt_trainer *t, const int32_t *rows, int32_t m, void *stream) {
+    LT_REQUIRE(t != nullptr, "%s: trainer is NULL", who);
+    LT_REQUIRE(m >= 0, "%s: m=%d, must be >= 0 (0: all rows)", who, m);
+    LT_REQUIRE(m <= t->n, "%s: m=%d ids, the graph has n=%d rows", who, m, t->n);
+    hipStream_t st = (hipStream_t)stream;
+    // an old list may still be read by epochs in flight on any stream: wait for the device before it is replaced and freed
+    // (before anything is allocated, so a failure here leaves nothing behind)
+    if (t->train_rows) LT_HIP(hipDeviceSynchronize());
+    int32_t *drows = nullptr;
+    float *lhead = nullptr;
+    if (m > 0) {
+        LT_REQUIRE(rows != nullptr, "%s: rows is NULL with m=%d", who, m);
+        const int n = t->n;
+        uint8_t *seen = new (std::nothrow) uint8_t[(size_t)n]();
+        if (!seen) return lt_set_error(LT_ERR_NOMEM, "%s: out of host memory", who);
+        int bad = -1, rep = -1;
+        for (int i = 0; i < m && bad < 0 && rep < 0; ++i) {
+            const int32_t r = rows[i];
+            if (r < 0 || r >= n) bad = i;
+            else if (seen[r]) rep = i;
+            else seen[r] = 1;
+        }
+        delete[] seen;
+        LT_REQUIRE(bad < 0, "%s: rows[%d]=%d outside [0, %d)", who, bad, bad >= 0 ? rows[bad] : 0, n);
+        LT_REQUIRE(rep < 0, "%s: rows[%d]=%d repeats an earlier id", who, rep, rep >= 0 ? rows[rep] : 0);
+        hipError_t e = hipMalloc((void **)&drows, (size_t)m * sizeof(int32_t));
+        if (e == hipSuccess && t->wide) e = hipMalloc((void **)&lhead, trw_part_bytes(m, t->C, true));
+        if (e == hipSuccess) e = hipMemcpyAsync(drows, rows, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);      // the caller's array is its own again when this returns
+        if (e == hipSuccess) e = hipMemsetAsync(t->dZc, 0, (size_t)n * trainer_ldc(t) * sizeof(float), st);
+        if (e != hipSuccess) {
+            (void)hipFree(drows);
+            (void)hipFree(lhead);
+            return lt_set_error(LT_ERR_HIP, "%s: setting up the list failed: %s", who, hipGetErrorString(e));
+        }
+    }
+    (void)hipFree(t->train_rows);
+    (void)hipFree(t->lhead);
+    t->train_rows = drows;
+    t->lhead = lhead;
+    t->n_train = m;
+    return LT_OK;
+}
+
 // ---- the 2-layer trainer ----
+extern "C" int lt_gcn2_trainer_set_train_rows(lt_gcn2_trainer *t, const int32_t *rows, int32_t m, void *stream) {
+    return trainer_set_train_rows("lt_gcn2_trainer_set_train_rows", t, rows, m, stream);
+}
+
 extern "C" int lt_gcn2_trainer_create(const lt_graph *g, const float *X, int64_t ldx, int32_t F, const int32_t *labels,
                                       int32_t H, int32_t C, float *W1, float *b1, float *W2, float *b2, double lr,
                                       double weight_decay, double dropout, uint64_t seed, void *stream,
@@ -1929,6 +2001,10 @@ extern "C" int lt_gcn3_trainer_attach_validation_wide(lt_gcn3_trainer *t, const 
                                                       int32_t patience, const int32_t *rows, int32_t m, void *stream) {
     return val_attach("lt_gcn3_trainer_attach_validation_wide", t, g2, X2, ldx2, n2, static_cast<const int32_t *>(labels2),
                       keep_best, patience, stream, rows != nullptr, rows, m, 1, ldy2);
+}
+
+extern "C" int lt_gcn3_trainer_set_train_rows(lt_gcn3_trainer *t, const int32_t *rows, int32_t m, void *stream) {
+    return trainer_set_train_rows("lt_gcn3_trainer_set_train_rows", t, rows, m, stream);
 }
 
 extern "C" int lt_gcn3_trainer_destroy(lt_gcn3_trainer *t) {

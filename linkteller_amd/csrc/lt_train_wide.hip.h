@@ -34,7 +34,7 @@ struct lt_trw_args {
     int C, Cp;
     const void *labels;        // CE: int32 [n]; BCE: uint8 [n, ldy]
     long ldy;
-    float inv;                 // GRAD: 1 / n (CE), 1 / (n C) (BCE)
+    float inv;                 // GRAD: 1 / cnt (CE), 1 / (cnt C) (BCE)
     float *dZ;                 // GRAD: [n, Cp]
     float *part_loss;          // [blocks]
     int32_t *part_cnt;         // [blocks, C, 3]
@@ -251,7 +251,9 @@ static size_t trw_part_bytes(int cnt, int C, bool grad) { return trw_parts(nullp
     }
 
 // The head over all n rows (rows == NULL) or the m listed ones, then the finish stage.  dZ != NULL: the training head, with
-// the gradient and its column-sum slabs.  `part` holds trw_part_bytes(cnt, C, dZ != NULL).
+// the gradient and its column-sum slabs; with a list it writes the listed rows of dZ only (the trainer zeroed the others
+// when the list was set), inv and the divisor from m, and the list 0 .. n - 1 leaves the bits of the launch without one.
+// `part` holds trw_part_bytes(cnt, C, dZ != NULL).
 static int launch_trw_head(int loss_kind, const float *Z, long ldz, const void *labels, long ldy, int n, int C,
                            const int32_t *rows, int m, float *dZ, float *part, float *loss_out, float *tp_out, int32_t *counts,
                            int32_t *n_bad, int32_t *state, int patience, int epoch, hipStream_t st) {
@@ -270,7 +272,8 @@ static int launch_trw_head(int loss_kind, const float *Z, long ldz, const void *
     a.n_bad = n_bad;
     a.tiles_per_block = p.tpb;
     const dim3 grid((unsigned)p.n_blk), block(TR_BLOCK);
-    if (dZ) TRW_DISPATCH(loss_kind, p.lpr, hipLaunchKernelGGL((k_trw_head<LOSS_, LPR_, true, false>), grid, block, 0, st, a));
+    if (dZ && rows) TRW_DISPATCH(loss_kind, p.lpr, hipLaunchKernelGGL((k_trw_head<LOSS_, LPR_, true, true>), grid, block, 0, st, a));
+    else if (dZ) TRW_DISPATCH(loss_kind, p.lpr, hipLaunchKernelGGL((k_trw_head<LOSS_, LPR_, true, false>), grid, block, 0, st, a));
     else if (rows) TRW_DISPATCH(loss_kind, p.lpr, hipLaunchKernelGGL((k_trw_head<LOSS_, LPR_, false, true>), grid, block, 0, st, a));
     else TRW_DISPATCH(loss_kind, p.lpr, hipLaunchKernelGGL((k_trw_head<LOSS_, LPR_, false, false>), grid, block, 0, st, a));
     LT_CHECK_LAUNCH();

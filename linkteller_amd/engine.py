@@ -972,7 +972,7 @@ class _GCNTrainer(_ValidationMixin):
             raise ValueError("the narrow head has the cross-entropy loss only: pass head='wide' for loss='bce'")
         self._WIDE, self.head, self.loss = head == "wide", head, loss
 
-    def __init__(self, adj, x, labels, params, *, lr, weight_decay, dropout, seed):
+    def __init__(self, adj, x, labels, params, *, lr, weight_decay, dropout, seed, train_rows=None):
         if not 0.0 <= float(dropout) <= 1.0:      # F.dropout's message
             raise ValueError(f"dropout probability has to be between 0 and 1, but got {dropout}")
         self.graph: HipGraph = as_hip_graph(adj)
@@ -1000,6 +1000,39 @@ class _GCNTrainer(_ValidationMixin):
                                            float(dropout), int(seed) & (2**64 - 1), _stream(), C.byref(h)), fn)
         self._h = h
         self._finalizer = weakref.finalize(self, getattr(_lib.lib(), f"{self._PREFIX}_destroy"), h)
+        self.n_train = n
+        if train_rows is not None:
+            self.set_train_rows(train_rows)
+
+    def set_train_rows(self, rows):
+        """Train on the listed rows only (lt_gcn*_trainer_set_train_rows; the reference's transductive loss,
+        ``model(features, adj)[idx_train]``, gcn_trainer.py:150-156): the whole graph is forwarded, the loss is the mean over
+        the listed rows, every other row's gradient of the logits is zero, and ``run``'s second value and ``counts()`` count
+        the listed rows.  ``rows``: a 1-d list, array or tensor of any integer dtype, distinct ids in [0, n), any order; ``None``
+        restores all rows.  Checked here, before the library is called: ``IndexError`` for ids outside the graph, ``ValueError``
+        for repeated ids, a float dtype, another dimension or an empty list; the trainer is then as it was.  May be called
+        between runs, before or after ``attach_validation``; validation does not see the list.  Waits for the stream."""
+        if rows is None:
+            self._call("set_train_rows", None, 0, _stream())
+            self.n_train = self.n
+            return
+        t = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(rows)
+        if t.numel() == 0:      # (before the dtype: an empty Python list arrives as float32)
+            raise ValueError("train_rows is empty: a loss over no row is undefined (None trains on all rows)")
+        if t.dtype.is_floating_point or t.dtype == torch.bool or t.is_complex():
+            raise ValueError(f"train_rows must hold integer ids, got {t.dtype}")
+        if t.dim() != 1:
+            raise ValueError(f"train_rows must be 1-d, got {tuple(t.shape)}")
+        t = t.detach().to(device="cpu", dtype=torch.int64)
+        outside = int(((t < 0) | (t >= self.n)).sum())
+        if outside:
+            raise IndexError(f"train_rows: {outside} ids outside the graph [0, {self.n})")
+        repeated = t.numel() - int(torch.unique(t).numel())
+        if repeated:
+            raise ValueError(f"train_rows: {repeated} ids repeat an earlier one")
+        host = t.to(torch.int32).contiguous()      # the library copies it before the call returns
+        self._call("set_train_rows", host.data_ptr(), host.numel(), _stream())
+        self.n_train = host.numel()
 
     def _prepare_labels(self, labels, n, name):
         """One class id per node as the int32 device tensor the library borrows; for the wide head with ``loss="bce"`` the
@@ -1050,7 +1083,8 @@ class _GCNTrainer(_ValidationMixin):
         return record
 
     def run(self, epochs: int):
-        """Run ``epochs`` epochs; returns (loss [epochs] float32, correct [epochs] int64) as CPU arrays (one read at the end)."""
+        """Run ``epochs`` epochs; returns (loss [epochs] float32, correct [epochs] int64) as CPU arrays (one read at the end);
+        with ``train_rows`` set both are over the listed rows."""
         rec = self.run_async(epochs).cpu().numpy()
         return rec[:, 0].copy(), rec[:, 1].astype("int64")
 
@@ -1076,14 +1110,17 @@ class GCN2Trainer(_GCNTrainer):
 
     _PREFIX, _NAMES, _MODEL = "lt_gcn2_trainer", ("W1", "b1", "W2", "b2"), "GCN"
 
-    def __init__(self, adj, x, labels, w1, b1, w2, b2, *, lr, weight_decay, dropout, seed, head="narrow", loss="ce"):
-        """``head="wide"`` (lt_gcn2_trainer_create_wide): up to 256 classes, the class layer as matrix products and the wide loss
+    def __init__(self, adj, x, labels, w1, b1, w2, b2, *, lr, weight_decay, dropout, seed, head="narrow", loss="ce",
+                 train_rows=None):
+        """``train_rows``: ``set_train_rows`` at creation (``n_train`` = their number, or n).
+        ``head="wide"`` (lt_gcn2_trainer_create_wide): up to 256 classes, the class layer as matrix products and the wide loss
         head; ``loss="ce"`` takes ``labels`` [n] (mean cross-entropy), ``loss="bce"`` takes ``labels`` [n, C] of 0 / 1 in any
         integer or bool dtype (mean binary cross-entropy with logits over all n C elements; kept as uint8 on the device).
         ``run`` then returns (loss, sum over the classes of tp): the correct count for ce.  ``head="narrow"`` (default) is the
         fused class layer for at most 8 classes with cross-entropy."""
         self._set_head(head, loss)
-        super().__init__(adj, x, labels, (w1, b1, w2, b2), lr=lr, weight_decay=weight_decay, dropout=dropout, seed=seed)
+        super().__init__(adj, x, labels, (w1, b1, w2, b2), lr=lr, weight_decay=weight_decay, dropout=dropout, seed=seed,
+                         train_rows=train_rows)
         self.h = self.w1.shape[1]
 
     def hidden(self) -> torch.Tensor:
@@ -1101,12 +1138,14 @@ class GCN3Trainer(_GCNTrainer):
 
     _PREFIX, _NAMES, _MODEL = "lt_gcn3_trainer", ("W1", "b1", "W2", "b2", "W3", "b3"), "GCN3"
 
-    def __init__(self, adj, x, labels, w1, b1, w2, b2, w3, b3, *, lr, weight_decay, dropout, seed, head="narrow", loss="ce"):
-        """``head`` and ``loss`` as for ``GCN2Trainer``: ``head="wide"`` (lt_gcn3_trainer_create_wide) puts the wide class layer
-        and loss head, up to 256 classes with ``loss="ce"`` or ``"bce"``, behind the two hidden layers; both heads draw the
-        same two dropout masks from one seed.  ``counts()`` and the [C, 3] ``val_counts`` follow."""
+    def __init__(self, adj, x, labels, w1, b1, w2, b2, w3, b3, *, lr, weight_decay, dropout, seed, head="narrow", loss="ce",
+                 train_rows=None):
+        """``train_rows``, ``head`` and ``loss`` as for ``GCN2Trainer``: ``head="wide"`` (lt_gcn3_trainer_create_wide) puts the
+        wide class layer and loss head, up to 256 classes with ``loss="ce"`` or ``"bce"``, behind the two hidden layers; both
+        heads draw the same two dropout masks from one seed.  ``counts()`` and the [C, 3] ``val_counts`` follow."""
         self._set_head(head, loss)
-        super().__init__(adj, x, labels, (w1, b1, w2, b2, w3, b3), lr=lr, weight_decay=weight_decay, dropout=dropout, seed=seed)
+        super().__init__(adj, x, labels, (w1, b1, w2, b2, w3, b3), lr=lr, weight_decay=weight_decay, dropout=dropout, seed=seed,
+                         train_rows=train_rows)
         self.h1, self.h2 = self.w1.shape[1], self.w2.shape[1]
 
     def hidden(self, layer: int) -> torch.Tensor:

@@ -17,6 +17,8 @@ Without either switch the run is refused (a default run does not start a 500-epo
 without improvement.  ``--dataset flickr`` (one graph with a train / validation / test split of its nodes; ``reddit``,
 ``ppi``, ``ppi-large`` with ``--train-head wide``) trains on the induced training subgraph, is validated on ``idx_val`` of the full graph
 after every epoch -- ``--early`` stops it as in the reference -- and is tested on ``idx_test`` with micro / macro / weighted F1.
+``--train-setting transductive`` (an addition) trains such a dataset as the reference trains the datasets whose ``adj_train``
+is the whole graph: the full graph is forwarded and the loss is taken over the rows ``idx_train`` only.
 """
 from __future__ import annotations
 
@@ -81,6 +83,11 @@ _OPTIONS = {
     # at most 8 classes, every check and every bit as before the flag existed; 'wide': up to 256 classes with cross-entropy or,
     # for a multi-label dataset, binary cross-entropy with logits (engine.GCN2Trainer(head="wide")): reddit, ppi, ppi-large
     "train-head": (str, "narrow", ["narrow", "wide"]),
+    # addition: what --train forwards on a dataset with one graph and a split of its nodes.  'inductive' (default): the
+    # subgraph induced by idx_train, every check and every bit as before the flag existed; 'transductive': the full graph, with
+    # the loss over the rows idx_train only (gcn_trainer.py:150-156 where adj_train is the full graph;
+    # engine.GCN2Trainer(train_rows=))
+    "train-setting": (str, "inductive", ["inductive", "transductive"]),
     # additions: with --recover, form the score rows K probes at a time and select through engine.TopPairsStream instead of the
     # one-shot n x n matrix (0 = one shot: the same edge list either way); and which nodes are ranked -- 'sample', the sampled
     # subgraph as before, or 'all': every node of the attacked graph (Attacker.recover_graph; the sampled AUC attack is skipped,
@@ -94,6 +101,8 @@ _HELP = {
     "patience": "epochs without improvement before --validate early stops (default 10)",
     "train-head": "with --train: narrow (default) trains a single label with at most 8 classes; wide trains up to 256 classes, "
                   "single- or multi-label (reddit, ppi, ppi-large), with the 2-layer GCN.",
+    "train-setting": "with --train on flickr (reddit / ppi / ppi-large with --train-head wide): inductive (default) trains on the "
+                     "subgraph induced by idx_train; transductive forwards the full graph and takes the loss over idx_train only.",
     "early": "with --train on flickr / reddit / ppi / ppi-large (one graph with a split of its nodes): stop after --patience "
              "epochs without improvement of the validation loss over idx_val and save the best model, as the reference does; a "
              "run that never stops saves the last model.  On transfer datasets (twitch/<A>/<B>) accepted and inert, as in the "
@@ -298,10 +307,30 @@ def check_train_head(args):
         raise NotImplementedError(f"--train-head wide is implemented for the 2-layer GCN only (got --n-layer {args.n_layer})")
 
 
+def check_train_setting(args):
+    """``--train-setting transductive`` forwards the full graph and lists the training rows: it is refused here, before a Worker
+    is built or the GPU is touched, without a training run and on a dataset that has no split to list (a transfer dataset
+    trains on one whole graph and tests on another).  ``main`` keeps its ``--n-layer 3`` refusal: GCN3 takes the setting
+    through the in-process ``GCNTrainer`` sequence of README."""
+    setting = getattr(args, "train_setting", "inductive")
+    if setting == "inductive":
+        return
+    if setting != "transductive":
+        raise ValueError(f"--train-setting {setting}: inductive or transductive")
+    if not args.train or args.test:
+        raise NotImplementedError("--train-setting transductive needs --train without --test (it selects the rows a training run "
+                                  "takes its loss over)")
+    if args.dataset not in _SPLIT_DATASETS:
+        raise NotImplementedError(f"--train-setting transductive needs a dataset with one graph and a split of its nodes "
+                                  f"({' / '.join(_SPLIT_DATASETS)}; got --dataset {args.dataset}: a transfer dataset trains on every "
+                                  "node of its first graph, there is nothing to list)")
+
+
 def main(argv=None):
     args = get_arguments(argv)
     check_validate(args)
     check_train_head(args)
+    check_train_setting(args)
     check_split_dataset(args)
     check_baseline_scores(args)
     check_recover(args)

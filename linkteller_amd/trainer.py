@@ -66,11 +66,18 @@ class GCNTrainer:
                         f"dataset = {self.dataset}: training is implemented for a single label and at most 8 classes (got "
                         f"multi_label = {w.multi_label}, n_classes = {w.n_classes}); load a trained model with --test --model-path")
                 train_on = (w.adj_train, w.features_train, w.labels[torch.as_tensor(w.idx_train, device=w.labels.device)])
+            rows = {}
+            if getattr(a, "train_setting", "inductive") == "transductive":      # addition: --train-setting
+                if w.transfer:
+                    raise NotImplementedError(f"dataset = {self.dataset}: train_setting = transductive needs one graph with a "
+                                              "split of its nodes (a transfer dataset has nothing to list)")
+                # gcn_trainer.py:150-156 where adj_train is the full graph: forward everything, the loss over idx_train
+                train_on, rows = (w.adj_full, w.features, w.labels), dict(train_rows=w.idx_train)
             layers = [self.model.gc1, self.model.gc2] + ([self.model.gc3] if a.n_layer == 3 else [])
             params = [t.detach() for g in layers for t in (g.weight, g.bias)]
             head = dict(head="wide", loss="bce" if getattr(w, "multi_label", 1) > 1 else "ce") if wide else {}
             self.gpu_trainer = (GCN3Trainer if a.n_layer == 3 else GCN2Trainer)(
-                *train_on, *params, lr=a.lr, weight_decay=a.weight_decay, dropout=a.dropout, seed=a.seed, **head)
+                *train_on, *params, lr=a.lr, weight_decay=a.weight_decay, dropout=a.dropout, seed=a.seed, **head, **rows)
 
     def train(self):
         """gcn_trainer.py:200-243 on a transfer dataset: ``num_epochs`` epochs on (features_1, adj_1, labels_1), the
@@ -125,7 +132,8 @@ class GCNTrainer:
         # the record's second word is the sum of tp over the classes: the correct rows of a single-label trainer; of a multi-label
         # one the (node, label) pairs that are true positives, printed as their share of all n C pairs (never above 1; the
         # training rows' (fp, fn) are kept for the last epoch only, so a per-epoch F1 as acc_val's cannot be formed)
-        train_terms = tr.n * (tr.c if getattr(tr, "loss", "ce") == "bce" else 1)
+        # (--train-setting transductive: over the listed training rows, n_train of the n forwarded)
+        train_terms = getattr(tr, "n_train", tr.n) * (tr.c if getattr(tr, "loss", "ce") == "bce" else 1)
         for epoch in range(done):
             logging.info("[epoch {}]".format(epoch))
             output_info = "Epoch: {:04d}".format(epoch + 1), \
